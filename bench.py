@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- region-grounded output tokens/sec of the MI355X path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 works both ways: under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` (the
   ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env) and as a plain `python bench.py --gpus N`, which forks its
   own N ranks -- one process per GPU, like the reference's launcher (scripts/srgpt/eval/srgpt_bench.sh:23-34) -- over RCCL.
@@ -14,8 +14,13 @@ Weights: seeded random weights of the VILA1.5-8B (Llama-3-8B + SigLIP-so400m) ar
 the device; inputs are resident in HBM before the timed region.  Weak scaling: every rank serves its own
 request stream (data parallel); the only exchange is an all-gather of the new ids.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the decode weight-streaming GEMV) and, at
-N = 1, `cpu_baseline` (the oracle = CPU restatement of the reference, timed on a bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; `roofline` and
+`cpu_baseline` are null.  `--full` adds the legs that cost runs of their own: `roofline` (dominant kernel = the decode
+weight-streaming GEMV, the whole decode phase and the request prefix, timed after the steps) and, at N = 1, `cpu_baseline`
+(the oracle = CPU restatement of the reference, timed on a bounded sample).
+`--dump-outputs DIR` writes what the last timed step returned -- the generated ids of every request, gathered over the
+ranks, as float64 (exact for ids) -- to DIR/output_ids.npy, so two builds can be compared output for output on the same
+seeded inputs.
 """
 from __future__ import annotations
 
@@ -37,8 +42,12 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before the timed ones (>= 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline leg and (N = 1) the CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (generated ids, float64) to DIR/output_ids.npy")
     ap.add_argument("--model", default="vila15_8b", choices=["vila15_8b", "vila15_8b_clip336", "llama2_7b", "sheared_3b", "tiny"])
     ap.add_argument("--regions", type=int, default=8)
     ap.add_argument("--prompt-len", type=int, default=64)
@@ -63,6 +72,8 @@ def parse():
     ap.add_argument("--cpu-decode-steps", type=int, default=12, help="decode steps the CPU baseline measures (full depth)")
     ap.add_argument("--no-cpu-fp32", action="store_true", help="skip the float32 leg of the CPU baseline (BASELINE.md asks for fp32 and bf16)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.preset == "config2":
         a.batch = 4
     elif a.preset == "config3":
@@ -307,7 +318,7 @@ def main():
     sd = synth_state_dict(cfg, seed=0, dtype=dtype, device=device)
     # CPU baseline runs the SAME weights at full depth: copy them to the host before the engine consumes them
     sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sd_cpu = {k: v.cpu() for k, v in sd.items()}
     # RoPE table: the request's positions (spliced prompt + new tokens), at least the 1024 every earlier round's line used
     rope_positions = max(1024, (spliced_len(cfg, args.prompt_len) + G + 127) // 128 * 128)
@@ -360,12 +371,18 @@ def main():
         dist_info.update(backend=("rccl (torch backend 'nccl')" if dist.get_backend() == "nccl" else dist.get_backend()),
                          per_rank_tokens_per_s=[round(float(t[0]), 2) for t in allr], rank_devices=[int(t[1]) for t in allr],
                          devices_visible=ndev, ranks_share_devices=bool(shared))
+    if args.dump_outputs and rank == 0:
+        # copied to the host now: the --full legs below run the model again
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "output_ids.npy"), out.cpu().numpy().astype(np.float64))
 
     # ---------------- roofline of the dominant kernel: decode weight-streaming GEMV (gate/up + SwiGLU) --------
     # measured live with events on the launch stream, cycling over all layers' matrices (7.5 GB >> 256 MB L3)
     eng = model.engine
     roof = None
-    if rank == 0:
+    if args.full and rank == 0:
         # the product as the timed workload launches it: one activation row per request of the batch (one row: the VALU GEMV,
         # 2+ rows: the MFMA skinny kernel)
         rows = args.batch

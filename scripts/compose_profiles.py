@@ -11,7 +11,7 @@ ks = open(g + "_kernel_stats.txt").read()
 m = re.search(r"^\s*\d+\s+[\d.]+\s+([\d.]+)\s+[\d.]+\s+[\d.]+\s+[\d.]+\s+gemv_kernel<.*?, true, 2(?:, \d+)?>", ks, re.M)
 trace_us = float(m.group(1)) if m else float("nan")
 r = d["roofline"]
-hdr = f"""# {tag}: rocprofv3 --kernel-trace -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline   (scripts/profile_round.sh)
+hdr = f"""# {tag}: rocprofv3 --kernel-trace -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline   (scripts/profile_round.sh)
 # 1x MI355X, VILA1.5-8B geometry, bs=1, 128 new tokens; 3 generate() calls + the roofline leg in the trace.
 # un-profiled default bench of the same build ({p}_bench.json): {d['value']} tok/s, {d['ms_per_step']} ms/request,
 #   decode {r['decode_ms_per_token']} ms/token; bench.py's event timing of the gate/up GEMV: {r['avg_launch_ms'] * 1e3:.1f} us/launch

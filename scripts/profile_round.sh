@@ -2,16 +2,17 @@
 # Round profile: kernel trace of the bench command + two separate PMC passes (counters never share a run with trace domains).
 # Usage (on the GPU box, from the repo root): bash scripts/profile_round.sh <tag>   -> gpurun_out/<tag>_*.txt
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=${1:-r05_final}
 OUT=$PWD/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline"
+CMD="python $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"
 rm -rf /tmp/prof_kt /tmp/prof_f /tmp/prof_m
 # 1. kernel trace (+ the un-profiled bench line of the same build for reference)
 $CMD > $OUT/${TAG}_bench_line.json 2>/dev/null
-python $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 > $OUT/${TAG}_bench_default.json 2>$OUT/${TAG}_bench_default.err
+python $ROOT/bench.py --full --steps 5 --warmup 2 > $OUT/${TAG}_bench_default.json 2>$OUT/${TAG}_bench_default.err
 rocprofv3 --kernel-trace -d /tmp/prof_kt -o run -- $CMD > /tmp/kt.log 2>&1
 DB=$(find /tmp/prof_kt -name "*.db" | head -1)
 python $GRAFT_REPO_ROOT/scripts/prof_summary.py $DB 40 > $OUT/${TAG}_kernel_stats.txt

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT; OUT=$PWD/gpurun_out; mkdir -p $OUT; F=$OUT/r05_longctx_perf
 echo "# long-context performance, VILA1.5-8B geometry, bf16, bs 1, one box (scripts/r05_longctx.sh)"
 echo "# --- whole requests: python bench.py --prompt-len P (T = P - 1 + 196), 128 greedy tokens"
 for P in 64 829 1853 3805; do
-  timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --prompt-len $P 2>/dev/null | python -c "
+  timeout 900 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --prompt-len $P 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

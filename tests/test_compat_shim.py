@@ -1,6 +1,7 @@
 """CPU: `PYTHONPATH=compat` resolves the import lines of the reference's callers (eval_spatial.py:17-21, eval_region_cls.py:16-20,
 model_vqa.py:13-17, demo/gradio_web_server_multi.py:23-26) to this package, with the callers byte-unchanged; with a reference
-checkout named by SRGPT_REFERENCE_ROOT the out-of-scope host modules (conversation templates, llava.utils) load from it."""
+checkout named by SRGPT_REFERENCE_ROOT the out-of-scope host modules (conversation templates, llava.utils) load from it (a stand-in
+checkout with the reference's layout, written by the test)."""
 import os
 import subprocess
 import sys
@@ -34,12 +35,25 @@ def test_caller_import_lines_resolve_to_this_package():
     assert r.returncode == 0 and "SHIM_OK" in r.stdout, r.stderr[-2000:]
 
 
-def test_out_of_scope_host_modules_load_from_a_reference_checkout():
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "llava")):  # the build container has it, the GPU box does not
-        import pytest
+def _stand_in_checkout(root):
+    """A checkout with the reference's layout: host modules the shim leaves to it (llava.conversation, llava.utils), and
+    modules the shim owns that must never load from it."""
+    llava = os.path.join(root, "llava")
+    os.makedirs(os.path.join(llava, "utils"))
+    os.makedirs(os.path.join(llava, "model"))
+    files = {"conversation.py": "import enum\n\n\nclass SeparatorStyle(enum.Enum):\n    PLAIN = enum.auto()\n\n\n"
+                                "conv_templates = {'llama_3': None, 'vicuna_v1': None, 'plain': None, 'v1': None}\n",
+             os.path.join("utils", "__init__.py"): "def disable_torch_init():\n    pass\n"}
+    for shadowed in ("constants.py", "mm_utils.py", os.path.join("model", "__init__.py"), os.path.join("model", "builder.py")):
+        files[shadowed] = "raise ImportError('loaded from the checkout instead of the shim')\n"
+    for name, text in files.items():
+        with open(os.path.join(llava, name), "w") as f:
+            f.write(text)
+    return root
 
-        pytest.skip("no reference checkout on this machine")
+
+def test_out_of_scope_host_modules_load_from_a_reference_checkout(tmp_path):
+    ref = _stand_in_checkout(str(tmp_path / "reference"))
     code = CALLER_IMPORTS + """
 from llava.conversation import SeparatorStyle, conv_templates
 from llava.utils import disable_torch_init

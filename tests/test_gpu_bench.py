@@ -1,10 +1,12 @@
-"""bench.py end to end on the tiny plumbing model: the driver's contract (one JSON line, the required keys, `roofline` measured at
-the workload's row count, `cpu_baseline` at N = 1) is exercised by the GPU suite, so a broken bench line cannot ship unnoticed."""
+"""bench.py end to end on the tiny plumbing model: the driver's contract (one JSON line, the required keys; with --full `roofline`
+measured at the workload's row count and `cpu_baseline` at N = 1; a plain run without them, --dump-outputs) is exercised by the GPU
+suite, so a broken bench line cannot ship unnoticed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +29,7 @@ def _run(*extra):
                                             (("--weights", "fp8", "--batch", "3", "--no-cpu-baseline"), 3, False),
                                             (("--no-graph", "--no-cpu-baseline"), 1, False)])
 def test_bench_line_contract(extra, rows, cpu):
-    d = _run(*extra)
+    d = _run("--full", *extra)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -47,7 +49,19 @@ def test_bench_line_contract(extra, rows, cpu):
 
 def test_bench_self_launch_two_ranks_on_one_device():
     """`python bench.py --gpus 2` forks its own ranks (one device here -> the ranks share it and rendezvous over gloo)."""
-    d = _run("--gpus", "2", "--no-cpu-baseline")
+    d = _run("--full", "--gpus", "2", "--no-cpu-baseline")
     assert d["n_gpus"] == 2 and d["config"]["dist"]["world_size_seen"] == 2
     assert len(d["config"]["dist"]["per_rank_tokens_per_s"]) == 2
     assert d["config"]["parallelism"] == "dp2"
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline figures only; --dump-outputs writes the last timed step's ids (float64)."""
+    d = _run("--batch", "2", "--dump-outputs", str(tmp_path))
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["value"] > 0 and abs(d["value"] - 2 * 6 * 2 / (d["ms_per_step"] * 2e-3)) < 0.01 * d["value"]
+    ids = np.load(tmp_path / "output_ids.npy")
+    assert ids.dtype == np.float64 and ids.shape == (2, 6)
+    assert np.array_equal(ids, np.round(ids)) and ids.min() >= 0 and ids.max() < 128  # token ids of the tiny model's vocabulary

@@ -219,6 +219,12 @@ def test_bench_presets_map_to_baseline_configs(monkeypatch):
 
     a, name = wl([])
     assert a.gpus == 1 and a.batch == 1 and "BASELINE configs[1]" in name and "T=259" in name
+    assert not a.full and a.dump_outputs is None  # a plain run times the steps only
+    a, _ = wl(["--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "0"])
+    assert a.full and a.dump_outputs == "out" and a.steps == 7 and a.warmup == 0
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            wl(bad)
     a, name = wl(["--preset", "config2"])
     assert a.batch == 4 and "configs[2]" in name
     a, name = wl(["--preset", "config3"])

@@ -323,8 +323,10 @@ int srgpt_cross_entropy(const float* logits, const int64_t* labels, float* row_l
  * llava/eval/model_vqa.py:66-80): scores = logits / temperature -> TopKLogitsWarper (everything below the k-th largest score is
  * removed, ties at it kept) -> TopPLogitsWarper (ascending cumulative softmax; entries whose cumulative mass is <= 1 - top_p are
  * removed, never the largest) -> one categorical draw from the softmax of what is left.
- *   top_k 1 .. 64; top_k = 0: no top-k filter -- then top_p must be >= 1 (pure temperature sampling, drawn by Gumbel-max over the
- *   whole vocabulary).  Other settings (top_k > 64; top_p < 1 without top_k) are not served on the device.
+ *   Two samplers read this block.  SRGPT_SAMPLER_TOPK64 (srgpt_sample, the decode step's default): top_k 1 .. 64 with any top_p;
+ *   top_k = 0: no top-k filter -- then top_p must be >= 1 (pure temperature sampling, drawn by Gumbel-max over the whole
+ *   vocabulary).  SRGPT_SAMPLER_FULL (ABI 9 additions: srgpt_sample_full and the _ex entry points): EVERY setting -- top_k 0 (off)
+ *   or 1 .. any (clamped to the vocabulary), top_p in [0, 1] -- over the whole vocabulary (V <= 262144).
  *   Randomness: Philox4x32-10, key = seed, counter = (counter, sequence, ...); every step advances `counter` by one. */
 typedef struct {
   float temperature;   /* > 0 */
@@ -347,6 +349,19 @@ int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void
  * srgpt_sample call on that workspace only: check after each draw whose settings may be out of range.  Inside the decode step the
  * word is the state's own and is never cleared once raised (sticky); srgpt_llm_decode_sync_state reports it. */
 int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream);
+/* The full sampler (additions under ABI 9).  Two launches, capturable: (1) one 1024-thread block per sequence writes the
+ * order-preserving integer keys of logits / T (a true division) to the workspace and finds the row's kept set as ONE threshold pair
+ * -- the kept set is a suffix of the order (score asc, index asc): top-k by a radix select over the keys (ties at the k-th score
+ * kept), top-p by the same digit walk over 64-bit fixed-point softmax mass of the top-k survivors (exact integer sums: a fixed
+ * result on every replay), the lowest indices of a tie group cut by top-p removed first (CPU torch.sort's order; top_p = 0 keeps the
+ * highest index among the tied maxima); (2) a masked Gumbel-max over 128 vocabulary slices (Philox addressed by (seed, counter,
+ * sequence, vocabulary index)), the slices' maxima merged like the greedy argmax.  Every setting is served: no error bit.
+ * ws = srgpt_sample_full_ws_bytes(B, V) = B * (4 V + 16 + 128 * 8) bytes.  kept_mask (optional, may be NULL): uint32
+ * [B][ceil(V / 32)], bit i % 32 of word i / 32 set <=> entry i is kept (the parity hook).  tok_out[b] = the drawn id; advances
+ * sp->counter.  V > 262144: SRGPT_ERR_UNSUPPORTED. */
+int64_t srgpt_sample_full_ws_bytes(int B, int V);
+int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
+                      srgpt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Composite: vision tower (VisionTower.forward, multimodal_encoder/vision_encoder.py:115-132 over HF
@@ -503,6 +518,15 @@ int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgp
 typedef struct srgpt_graph srgpt_graph;
 int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream,
                                   srgpt_graph** out);
+/* Sampler kinds of the _ex forms (additions under ABI 9): which device sampler draws when st->sampling is set (greedy otherwise,
+ * whatever the kind).  The forms without _ex are the SRGPT_SAMPLER_TOPK64 case.  An unknown kind is SRGPT_ERR_ARG; the full sampler
+ * over a vocabulary above 262144 is SRGPT_ERR_UNSUPPORTED -- both before any launch.  A graph captured with one kind replays that
+ * kind; the parameter block still says which setting. */
+enum { SRGPT_SAMPLER_TOPK64 = 0, SRGPT_SAMPLER_FULL = 1 };
+int srgpt_llm_sample_first_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream);
+int srgpt_llm_decode_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream);
+int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
+                                     srgpt_graph** out);
 int srgpt_graph_launch(srgpt_graph* g, int times, srgpt_stream_t stream);
 int srgpt_graph_destroy(srgpt_graph* g);
 

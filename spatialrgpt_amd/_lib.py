@@ -68,6 +68,7 @@ class Sampling(C.Structure):
 SAMPLING_TOP_K_MAX = 64        # sample.hip SMP_K
 SAMPLING_KEPT_MAX = 256        # sample.hip SMP_LIST
 SAMPLING_VOCAB_MAX = 128 * 2048
+SAMPLER_TOPK64, SAMPLER_FULL = 0, 1  # SRGPT_SAMPLER_*: which device sampler the _ex entry points run
 
 NORM_RMS, NORM_LAYER = 1, 2  # srgpt_gemm_norm
 SPLICE_STATS = 8             # SRGPT_SPLICE_STATS: ints per prompt the splice plan reports
@@ -119,6 +120,8 @@ _SIGNATURES = {
     "srgpt_sample_ws_bytes": (i64, [i32]),
     "srgpt_sample": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "srgpt_sample_status": (i32, [vp, i32, vp]),
+    "srgpt_sample_full_ws_bytes": (i64, [i32, i32]),
+    "srgpt_sample_full": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
     "srgpt_image_resize_normalize": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, i32, i32, vp]),
     "srgpt_mask_resize_nearest": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "srgpt_mask_pad_resize": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
@@ -132,6 +135,9 @@ _SIGNATURES = {
     "srgpt_llm_sample_first": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp]),
     "srgpt_llm_decode_sync_state": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp]),
     "srgpt_llm_decode_graph_create": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp, C.POINTER(vp)]),
+    "srgpt_llm_sample_first_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp]),
+    "srgpt_llm_decode_step_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp]),
+    "srgpt_llm_decode_graph_create_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, C.POINTER(vp)]),
     "srgpt_graph_launch": (i32, [vp, i32, vp]),
     "srgpt_graph_destroy": (i32, [vp]),
 }

@@ -12,6 +12,8 @@ void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* byte
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s);  // sample.hip
 extern "C" __attribute__((visibility("hidden"))) int srgpt_sample_slices(void);  // sample.hip (internal: not part of the C ABI)
+int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
+                             int V, hipStream_t s);  // sample.hip
 namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -59,6 +61,7 @@ struct LlmWs {
   int* amax_i;    // [batch, ARGMAX_BLOCKS] their indices
   int64_t* tok_emb;  // [batch] the token whose embedding row currently sits in xd (-1: none)
   void* smp;         // sampling: the slices' top-k candidates (srgpt_sample_ws_bytes)
+  void* smpf;        // full sampler: the row's keys and threshold pair (the head of srgpt_sample_full_ws_bytes)
   int* err;          // sticky error word of the decode step (bit 0: a caller-written st->tok outside the table), read by srgpt_llm_decode_sync_state
   float* rowss;   // decode, 2+ rows: two row-statistics tables [batch][SRGPT_ROWSS_STRIDE] (o_proj's and down_proj's output rows)
   void* a8;       // fp8_act: the e4m3 bytes of the current GEMM input [rows, max K]
@@ -91,6 +94,7 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
   l.tok_emb = reinterpret_cast<int64_t*>(c.take((size_t)batch * 8));
   l.err = reinterpret_cast<int*>(c.take(sizeof(int)));
   l.smp = c.take((size_t)srgpt_sample_ws_bytes(batch));
+  l.smpf = c.take((size_t)batch * ((size_t)4 * w->vocab + 16));
   l.rowss = reinterpret_cast<float*>(c.take((size_t)2 * batch * SRGPT_ROWSS_STRIDE * sizeof(float)));
   l.a8 = nullptr;
   l.a8s = nullptr;
@@ -159,13 +163,13 @@ constexpr int ADVANCE_MAXB = 256;
 __global__ __launch_bounds__(1024) void advance_kernel(const float* __restrict__ pv, const int* __restrict__ pi, int nb, int64_t* tok,
                                int64_t* out_ids, int* pos, int* step, int B, int max_new, int bump_pos,
                                const unsigned char* __restrict__ embed, unsigned char* __restrict__ xd, int row_bytes,
-                               int64_t* __restrict__ tok_emb, srgpt_sampling* __restrict__ sp) {
+                               int64_t* __restrict__ tok_emb, srgpt_sampling* __restrict__ sp, int select_drew) {
   __shared__ int picked[ADVANCE_MAXB];
   const int s = *step;
   const int lane = threadIdx.x & 63;
-  // sampling with a top-k filter: sample_select_kernel already drew tok[b]; greedy and Gumbel-max sampling (top_k = 0): the slices'
-  // maxima are merged here
-  const bool drawn = sp != nullptr && sp->top_k > 0;
+  // sampling with a top-k filter: sample_select_kernel already drew tok[b]; greedy, Gumbel-max sampling (top_k = 0) and the full
+  // sampler (select_drew = 0): the slices' maxima are merged here
+  const bool drawn = sp != nullptr && select_drew && sp->top_k > 0;
   for (int b = threadIdx.x >> 6; b < B; b += blockDim.x >> 6) {
     float best = -INFINITY;
     int bi = drawn ? (int)tok[b] : 0x7fffffff;
@@ -263,19 +267,24 @@ static inline bool advance_embeds(const srgpt_llm_weights* w, const srgpt_llm_st
   return st->batch <= ADVANCE_MAXB && ((size_t)w->hidden * dtype_size(w->dtype)) % 16 == 0;
 }
 
-// the next token of every sequence from st->logits: argmax (st->sampling == NULL) or a draw (sample.hip), then the bookkeeping
-static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, hipStream_t s) {
+// the next token of every sequence from st->logits: argmax (st->sampling == NULL) or a draw by the sampler `sampler` (sample.hip),
+// then the bookkeeping
+static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, int sampler, hipStream_t s) {
   const int B = st->batch;
   const bool emb = advance_embeds(w, st);
   if (st->sampling) {
     SRGPT_CHECK(srgpt_sample_slices() == ARGMAX_BLOCKS, SRGPT_ERR_STATE, "sampling: slice count differs from the argmax merge's");
-    SRGPT_TRY(srgpt_sample_launch(st->logits, st->sampling, st->tok, d.smp, d.amax_v, d.amax_i, d.err, B, w->vocab, s));
+    if (sampler == SRGPT_SAMPLER_FULL)
+      SRGPT_TRY(srgpt_sample_full_launch(st->logits, st->sampling, d.smpf, d.amax_v, d.amax_i, nullptr, B, w->vocab, s));
+    else
+      SRGPT_TRY(srgpt_sample_launch(st->logits, st->sampling, st->tok, d.smp, d.amax_v, d.amax_i, d.err, B, w->vocab, s));
   } else {
     hipLaunchKernelGGL(argmax_partial_kernel, dim3(ARGMAX_BLOCKS, B), dim3(256), 0, s, st->logits, d.amax_v, d.amax_i, w->vocab);
   }
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(B > 4 ? 1024 : 256), 0, s, d.amax_v, d.amax_i, ARGMAX_BLOCKS, st->tok, st->out_ids,
                      st->pos, st->step, B, st->max_new, bump_pos, emb ? reinterpret_cast<const unsigned char*>(w->embed) : nullptr,
-                     reinterpret_cast<unsigned char*>(d.xd), (int)((size_t)w->hidden * dtype_size(w->dtype)), d.tok_emb, st->sampling);
+                     reinterpret_cast<unsigned char*>(d.xd), (int)((size_t)w->hidden * dtype_size(w->dtype)), d.tok_emb, st->sampling,
+                     sampler == SRGPT_SAMPLER_TOPK64 ? 1 : 0);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -532,17 +541,31 @@ extern "C" int srgpt_llm_prefill_ragged(const srgpt_llm_weights* w, srgpt_llm_st
   return prefill_impl(w, st, inputs_embeds, T, lens, all_logits, hidden_out, stream);
 }
 
-extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
+// the _ex entry points: a known sampler kind, a valid state, and (full sampler, sampling on) a vocabulary it can hold -- all on the
+// host, before any launch
+static int check_sampler(const srgpt_llm_weights* w, const srgpt_llm_state* st, int sampler, const char* fn) {
+  SRGPT_CHECK(sampler == SRGPT_SAMPLER_TOPK64 || sampler == SRGPT_SAMPLER_FULL, SRGPT_ERR_ARG, "%s: unknown sampler kind %d", fn, sampler);
   SRGPT_TRY(check_llm(w, st));
+  SRGPT_CHECK(!(st->sampling && sampler == SRGPT_SAMPLER_FULL) || w->vocab <= ARGMAX_BLOCKS * 2048, SRGPT_ERR_UNSUPPORTED,
+              "%s: vocabulary %d exceeds the full sampler's %d", fn, w->vocab, ARGMAX_BLOCKS * 2048);
+  return SRGPT_OK;
+}
+
+extern "C" int srgpt_llm_sample_first_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
+  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_sample_first_ex"));
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, s, st->step, 1, 0);
   const LlmWs d = carve_llm(w, st->batch, st->ws_tokens, st->ws);
-  return greedy_pick(w, st, d, 0, s);
+  return greedy_pick(w, st, d, 0, sampler, s);
+}
+
+extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
+  return srgpt_llm_sample_first_ex(w, st, SRGPT_SAMPLER_TOPK64, stream);
 }
 
 // embed_first = false: the residual-stream buffer already holds the embeddings of st->tok (written by the advance_kernel of the
 // step before: the graph-captured greedy loop); the public entry always embeds (st->tok may have been set by the caller)
-static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first) {
+static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, int sampler) {
   SRGPT_TRY(check_llm(w, st));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
   const int B = st->batch, QW = (Hq + 2 * Hkv) * D;
@@ -602,11 +625,16 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
   }
   SRGPT_TRY(mv(d.xd, w->lm_head, w->lm_head8, w->lm_head_scale, w->final_norm, nullptr, st->logits, w->vocab, Hd, 0, 1,
                w->layers > 0 ? ss_mlp : nullptr, nullptr));
-  return greedy_pick(w, st, d, 1, s);
+  return greedy_pick(w, st, d, 1, sampler, s);
+}
+
+extern "C" int srgpt_llm_decode_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
+  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_step_ex"));
+  return decode_step_impl(w, st, stream, true, sampler);
 }
 
 extern "C" int srgpt_llm_decode_step(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
-  return decode_step_impl(w, st, stream, true);
+  return decode_step_impl(w, st, stream, true, SRGPT_SAMPLER_TOPK64);
 }
 
 // Health of the decode steps since the last prefill (synchronises `stream` ONCE: both read-backs are queued, then one wait):
@@ -639,10 +667,10 @@ extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srg
 // ================================================================================================
 // hipGraph of one decode step
 // ================================================================================================
-extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream,
-                                             srgpt_graph** out) {
+extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
+                                                srgpt_graph** out) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_decode_graph_create: null out");
-  SRGPT_TRY(check_llm(w, st));
+  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_graph_create_ex"));
   hipStream_t s = as_stream(stream);
   (void)srgpt_device_cus();  // make sure no device query happens inside the capture
   hipGraph_t graph = nullptr;
@@ -651,7 +679,7 @@ extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_l
     return SRGPT_ERR_STATE;
   }
   // replays continue from the token the previous step (or srgpt_llm_sample_first) picked: its embedding is already in place
-  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st));
+  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), sampler);
   const hipError_t ee = hipStreamEndCapture(s, &graph);
   if (rc != SRGPT_OK) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -670,6 +698,11 @@ extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_l
   }
   *out = new srgpt_graph{graph, exec};
   return SRGPT_OK;
+}
+
+extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream,
+                                             srgpt_graph** out) {
+  return srgpt_llm_decode_graph_create_ex(w, st, SRGPT_SAMPLER_TOPK64, stream, out);
 }
 
 extern "C" int srgpt_graph_launch(srgpt_graph* g, int times, srgpt_stream_t stream) {

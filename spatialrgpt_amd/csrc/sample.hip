@@ -15,6 +15,14 @@
 //             <= 256 entries: top-p exactly as TopPLogitsWarper (ascending cumulative softmax, remove <= 1 - top_p, never the
 //             largest), and the draw by inverse CDF on one Philox4x32-10 uniform.
 //   launch 3  advance_kernel (model.hip) books the token like the greedy path and advances the Philox counter.
+// That sampler serves top_k 1 .. 64 (any top_p) and pure temperature sampling.  The FULL sampler below (srgpt_sample_full, the
+// decode step's SRGPT_SAMPLER_FULL) serves every setting over the whole vocabulary:
+//   launch 1  sample_full_threshold_kernel  one 1024-thread block per sequence: keys of logits / T to the workspace; the kept set as
+//             ONE (key, index) threshold pair -- top-k by a 12 + 10 + 10-bit radix select of counts, top-p by the same digit walk
+//             over 64-bit fixed-point softmax mass (integer sums: bit-stable replays), a tie group cut by top-p losing its lowest
+//             indices first (CPU torch.sort's ascending order).
+//   launch 2  sample_full_draw_kernel       grid (128 slices, batch): masked Gumbel-max, per-slice (value, index) for the greedy
+//             merge (advance_kernel), Philox addressed like the top_k = 0 path.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (step counter, sequence, vocabulary index | ~0): reproducible for
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
 // on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
@@ -318,6 +326,300 @@ __global__ void sample_bump_kernel(srgpt_sampling* sp, const float* __restrict__
   if (threadIdx.x == 0) sp->counter += 1;
 }
 
+// ================================================================================================
+// The full sampler: every temperature / top_k / top_p over the whole vocabulary.  The kept set is always a SUFFIX of the row in
+// the order (score asc, index asc): top-k removes every key below the k-th largest (ties kept), top-p then removes a prefix of that
+// order (HF's ascending sort; CPU torch.sort puts the lower index of equal scores first).  So one (key, index) pair per row says
+// everything: kept <=> key > tkey || (key == tkey && index >= tidx).
+// ================================================================================================
+constexpr int SFU_THREADS = 1024;
+constexpr int SFU_BINS = 4096;  // digits of a 32-bit key: 12 + 10 + 10 bits
+constexpr float SFU_FIX = 35184372088832.0f;  // 2^45: mass exp(s - max) in (0, 1] as 64-bit fixed point; V <= 2^18 entries sum < 2^63
+
+struct FullLds {
+  unsigned long long hist[SFU_BINS];
+  unsigned long long part[SFU_THREADS / 64];
+  unsigned long long below, in_bin;
+  unsigned bin, maxkey;
+};
+
+__device__ __forceinline__ unsigned long long mass_of(unsigned key, float m) { return __float2ull_rn(expf(score_of(key) - m) * SFU_FIX); }
+
+// digit `level` of a key: bits 31..20, 19..10, 9..0; the bits above it must equal the prefix found so far
+__device__ __forceinline__ int digit_shift(int level) { return level == 0 ? 20 : (level == 1 ? 10 : 0); }
+__device__ __forceinline__ unsigned digit_bins(int level) { return level == 0 ? 4096u : 1024u; }
+__device__ __forceinline__ unsigned above_mask(int level) { return level == 0 ? 0u : (level == 1 ? 0xFFF00000u : 0xFFFFFC00u); }
+
+// f(key, i) for every entry of the row, thread tid taking i = tid + j * 1024 (the entries it wrote in pass 0); 8 independent loads in
+// flight per thread (one at a time, a pass over 128k L2-resident keys was ~40 us of load latency)
+constexpr int SFU_UNROLL = 8;
+template <class F>
+__device__ __forceinline__ void for_keys(const unsigned* __restrict__ keys, int V, F f) {
+  for (int i0 = threadIdx.x; i0 < V; i0 += SFU_THREADS * SFU_UNROLL) {
+    unsigned k[SFU_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SFU_UNROLL; ++u) k[u] = keys[min(i0 + u * SFU_THREADS, V - 1)];
+#pragma unroll
+    for (int u = 0; u < SFU_UNROLL; ++u)
+      if (i0 + u * SFU_THREADS < V) f(k[u], i0 + u * SFU_THREADS);
+  }
+}
+
+__device__ void clear_hist(FullLds& L, int nbins) {
+  for (int i = threadIdx.x; i < nbins; i += SFU_THREADS) L.hist[i] = 0;
+  __syncthreads();
+}
+
+// the smallest bin d whose inclusive prefix P(d) over hist[0 .. nbins) exceeds X (the total must exceed X): L.bin = d,
+// L.below = P(d - 1), L.in_bin = hist[d].  Integer sums in a fixed order: the same answer on every replay.
+__device__ void find_bin(FullLds& L, int nbins, unsigned long long X) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, per = nbins / SFU_THREADS;
+  unsigned long long s = 0;
+  for (int j = 0; j < per; ++j) s += L.hist[tid * per + j];
+  unsigned long long v = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  if (lane == 63) L.part[wv] = v;
+  __syncthreads();
+  unsigned long long run = v - s;
+  for (int w = 0; w < wv; ++w) run += L.part[w];
+  for (int j = 0; j < per; ++j) {
+    const unsigned long long h = L.hist[tid * per + j];
+    if (run <= X && X < run + h) {
+      L.bin = tid * per + j;
+      L.below = run;
+      L.in_bin = h;
+    }
+    run += h;
+  }
+  __syncthreads();
+}
+
+__device__ unsigned long long hist_total(FullLds& L, int nbins) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  unsigned long long s = 0;
+  for (int i = tid; i < nbins; i += SFU_THREADS) s += L.hist[i];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) L.part[wv] = s;
+  __syncthreads();
+  unsigned long long t = 0;
+  for (int w = 0; w < SFU_THREADS / 64; ++w) t += L.part[w];
+  __syncthreads();
+  return t;
+}
+
+// launch 1 of the full sampler: one block per sequence finds the row's threshold pair (tkey, tidx).  Pass 0 writes the order-preserving
+// keys of logits / T to the workspace (each thread later re-reads only the entries it wrote) and takes the maximum; top-k is a 3-digit
+// radix select by counts, top-p the same digit walk by fixed-point softmax mass over the top-k survivors, and where the top-p cut runs
+// through a group of equal scores a 2-digit select over their indices says how many of them (lowest indices first) go.
+__global__ __launch_bounds__(SFU_THREADS) void sample_full_threshold_kernel(const float* __restrict__ logits,
+                                                                          const srgpt_sampling* __restrict__ sp,
+                                                                          unsigned* __restrict__ keys_ws, unsigned* __restrict__ thr,
+                                                                          int V) {
+  __shared__ FullLds L;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const float* row = logits + (size_t)b * V;
+  unsigned* keys = keys_ws + (size_t)b * V;
+  const float T = sp->temperature;
+  const int top_k = sp->top_k;
+  const bool p_on = sp->top_p < 1.0f;
+  const int k = top_k != 0 ? min(max(top_k, 1), V) : V;  // TopKLogitsWarper: min(max(top_k, min_tokens_to_keep), V)
+  const bool k_on = k < V;
+  if (tid == 0) L.maxkey = 0;
+  clear_hist(L, SFU_BINS);
+  unsigned mx = 0;
+  for (int i0 = tid; i0 < V; i0 += SFU_THREADS * SFU_UNROLL) {
+    float x[SFU_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SFU_UNROLL; ++u) x[u] = row[min(i0 + u * SFU_THREADS, V - 1)];
+#pragma unroll
+    for (int u = 0; u < SFU_UNROLL; ++u) {
+      const int i = i0 + u * SFU_THREADS;
+      if (i < V) {
+        const unsigned key = key_of(x[u] / T);  // a true division, as HF's TemperatureLogitsWarper
+        keys[i] = key;
+        mx = max(mx, key);
+        if (k_on) atomicAdd(&L.hist[key >> 20], 1ull);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor(mx, o));
+  if (lane == 0) atomicMax(&L.maxkey, mx);
+  __syncthreads();
+  const unsigned maxkey = L.maxkey;
+
+  // ---- top-k: the k-th largest key = the smallest key t with #(keys <= t) > V - k ----
+  unsigned kthr = 0;
+  if (k_on) {
+    unsigned prefix = 0;
+    unsigned long long X = (unsigned long long)(V - k);
+#pragma unroll 1
+    for (int level = 0; level < 3; ++level) {
+      const int sh = digit_shift(level);
+      const unsigned nb = digit_bins(level), am = above_mask(level);
+      if (level > 0) {
+        clear_hist(L, SFU_THREADS);
+        for_keys(keys, V, [&](unsigned key, int) {
+          if ((key & am) == prefix) atomicAdd(&L.hist[(key >> sh) & (nb - 1)], 1ull);
+        });
+        __syncthreads();
+      }
+      find_bin(L, (int)max(nb, (unsigned)SFU_THREADS), X);
+      prefix |= L.bin << sh;
+      X -= L.below;
+      __syncthreads();
+    }
+    kthr = prefix;
+  }
+
+  unsigned tkey = kthr, tidx = 0;
+  if (p_on) {
+    // ---- top-p over the survivors (key >= kthr): cumulative mass in (score asc, index asc) order; an entry goes while its
+    // cumulative mass S <= top_p_rm * Z.  The first survivor is the smallest key t with S(keys <= t) > R = floor(top_p_rm * Z),
+    // R clamped below Z: the largest entry always stays (top_p = 0 keeps exactly one) ----
+    const float m = score_of(maxkey);
+    unsigned prefix = 0;
+    unsigned long long X = 0, R = 0;
+#pragma unroll 1
+    for (int level = 0; level < 3; ++level) {
+      const int sh = digit_shift(level);
+      const unsigned nb = digit_bins(level), am = above_mask(level);
+      clear_hist(L, (int)nb);
+      for_keys(keys, V, [&](unsigned key, int) {
+        if (key >= kthr && (key & am) == prefix) atomicAdd(&L.hist[(key >> sh) & (nb - 1)], mass_of(key, m));
+      });
+      __syncthreads();
+      if (level == 0) {
+        const unsigned long long Z = hist_total(L, SFU_BINS);
+        R = (unsigned long long)((double)Z * (double)sp->top_p_rm);
+        if (R >= Z) R = Z - 1;
+        X = R;
+      }
+      find_bin(L, (int)max(nb, (unsigned)SFU_THREADS), X);
+      prefix |= L.bin << sh;
+      X -= L.below;
+      __syncthreads();
+    }
+    tkey = prefix;
+    // every entry of key tkey carries the same mass q: the j-th of them (ascending index) has S = S(keys < tkey) + j q, so the
+    // r = X / q lowest indices go
+    const unsigned long long q = mass_of(tkey, m);
+    const unsigned long long r = X / q;
+    if (r > 0) {
+      // the (r + 1)-th smallest index among the entries of key tkey: V <= 2^18, digits idx >> 8 (<= 1024 bins) and idx & 255
+      unsigned ip = 0;
+      unsigned long long Xi = r;
+#pragma unroll 1
+      for (int level = 0; level < 2; ++level) {
+        clear_hist(L, SFU_THREADS);
+        for_keys(keys, V, [&](unsigned key, int i) {
+          if (key == tkey && (level == 0 || (unsigned)(i >> 8) == ip)) atomicAdd(&L.hist[level == 0 ? (i >> 8) : (i & 255)], 1ull);
+        });
+        __syncthreads();
+        find_bin(L, SFU_THREADS, Xi);
+        ip = level == 0 ? L.bin : ((ip << 8) | L.bin);
+        Xi -= L.below;
+        __syncthreads();
+      }
+      tidx = ip;
+    }
+  }
+  if (tid == 0) {
+    thr[(size_t)b * 4] = tkey;
+    thr[(size_t)b * 4 + 1] = tidx;
+  }
+}
+
+// launch 2: masked Gumbel-max per vocabulary slice, grid (ARGMAX_BLOCKS slices, batch) -> the per-slice (value, index) pairs the
+// greedy merge (advance_kernel, or sample_full_merge_kernel for the stand-alone op) consumes.  Same Philox addressing as the top_k = 0
+// path of sample_partial_kernel.  kept_mask (optional): bit i % 32 of word i / 32 of the row = entry i kept.
+__global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ keys_ws,
+                                                              const unsigned* __restrict__ thr, float* __restrict__ pv,
+                                                              int* __restrict__ pi, unsigned* __restrict__ kept_mask, int V) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int b = blockIdx.y, nb = gridDim.x, blk = blockIdx.x, tid = threadIdx.x;
+  const int per = (V + nb - 1) / nb;
+  const int lo = blk * per, hi = min(lo + per, V);
+  const unsigned* keys = keys_ws + (size_t)b * V;
+  const unsigned tkey = thr[(size_t)b * 4], tidx = thr[(size_t)b * 4 + 1];
+  const unsigned long long ctr = sp->counter, seed = sp->seed;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = lo + tid; i < hi; i += 256) {
+    const unsigned key = keys[i];
+    if (key < tkey || (key == tkey && (unsigned)i < tidx)) continue;
+    const U4 r = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)b, (unsigned)i}, (unsigned)seed, (unsigned)(seed >> 32));
+    const float u = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
+    const float v = score_of(key) - logf(-logf(u));
+    if (v > best) {
+      best = v;
+      bi = i;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o);
+    const int oi = __shfl_xor(bi, o);
+    if (ov > best || (ov == best && oi < bi)) {
+      best = ov;
+      bi = oi;
+    }
+  }
+  if ((tid & 63) == 0) {
+    sv[tid >> 6] = best;
+    si[tid >> 6] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < 4; ++i)
+      if (sv[i] > best || (sv[i] == best && si[i] < bi)) {
+        best = sv[i];
+        bi = si[i];
+      }
+    pv[(size_t)b * nb + blk] = best;
+    pi[(size_t)b * nb + blk] = bi;
+  }
+  if (kept_mask) {
+    const int nw = (V + 31) / 32;
+    for (int w = blk * 256 + tid; w < nw; w += nb * 256) {
+      unsigned bits = 0;
+      for (int j = 0; j < 32; ++j) {
+        const int i = w * 32 + j;
+        if (i >= V) break;
+        const unsigned key = keys[i];
+        if (key > tkey || (key == tkey && (unsigned)i >= tidx)) bits |= 1u << j;
+      }
+      kept_mask[(size_t)b * nw + w] = bits;
+    }
+  }
+}
+
+// stand-alone op only (the decode step's advance_kernel does both): merge the slices' maxima, advance the counter
+__global__ void sample_full_merge_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int nb,
+                                         int64_t* __restrict__ tok, int B) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = 0; i < nb; ++i) {
+      const float v = pv[(size_t)b * nb + i];
+      const int ix = pi[(size_t)b * nb + i];
+      if (v > best || (v == best && ix < bi)) {
+        best = v;
+        bi = ix;
+      }
+    }
+    tok[b] = bi == 0x7fffffff ? 0 : bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) sp->counter += 1;
+}
+
 }  // namespace
 
 // workspace: candidates (key + index) of every slice, then the Gumbel-mode slice maxima
@@ -369,3 +671,40 @@ extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream)
 }
 
 extern "C" __attribute__((visibility("hidden"))) int srgpt_sample_slices(void) { return SMP_NB; }  // cross-file helper, not exported
+
+// ---- the full sampler ----
+// workspace: keys u32 [B][V] | thresholds u32 [B][4] | slice maxima f32 [B][128] | their indices i32 [B][128]
+extern "C" int64_t srgpt_sample_full_ws_bytes(int B, int V) {
+  if (B <= 0 || V <= 0) return -1;
+  return (int64_t)B * ((int64_t)4 * V + 16 + (int64_t)SMP_NB * 8);
+}
+
+// internal (model.hip): launches 1 and 2 into the caller's slice maxima pv / pi ([B][128]); the caller merges, books the token and
+// advances the counter.  keys_thr = the first B * (4 V + 16) bytes of a srgpt_sample_full_ws_bytes workspace.
+int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
+                             int V, hipStream_t s) {
+  SRGPT_CHECK(logits && sp && keys_thr && pv && pi, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
+  SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
+  SRGPT_CHECK(V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample_full: vocabulary %d exceeds %d", V, SMP_NB * SMP_SLICE_MAX);
+  unsigned* keys = reinterpret_cast<unsigned*>(keys_thr);
+  unsigned* thr = keys + (size_t)B * V;
+  hipLaunchKernelGGL(sample_full_threshold_kernel, dim3(B), dim3(SFU_THREADS), 0, s, logits, sp, keys, thr, V);
+  hipLaunchKernelGGL(sample_full_draw_kernel, dim3(SMP_NB, B), dim3(256), 0, s, sp, keys, thr, pv, pi, kept_mask, V);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+extern "C" int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
+                                 srgpt_stream_t stream) {
+  SRGPT_CHECK(logits && sp && tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
+  SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
+  SRGPT_CHECK(V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample_full: vocabulary %d exceeds %d", V, SMP_NB * SMP_SLICE_MAX);
+  char* tail = reinterpret_cast<char*>(ws) + (size_t)B * ((size_t)4 * V + 16);
+  float* pv = reinterpret_cast<float*>(tail);
+  int* pi = reinterpret_cast<int*>(tail + (size_t)B * SMP_NB * 4);
+  hipStream_t s = as_stream(stream);
+  SRGPT_TRY(srgpt_sample_full_launch(logits, sp, ws, pv, pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
+  hipLaunchKernelGGL(sample_full_merge_kernel, dim3(1), dim3(256), 0, s, sp, pv, pi, SMP_NB, tok_out, B);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}

@@ -51,7 +51,8 @@ class DecodeState:
         st.sampling = None
         self.c = st
         self.host_len = [0] * batch  # cached positions per row as known on the host (prefill lengths + steps taken)
-        self.graphs = {}             # "greedy" / "sample" -> captured decode step (the pick kernels differ)
+        self.graphs = {}             # "greedy" / "sample" / "sample_full" -> captured decode step (the pick kernels differ)
+        self.sampler = L.SAMPLER_TOPK64  # which device sampler draws while c.sampling is set (SRGPT_SAMPLER_*)
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
         self._eng = eng
 
@@ -60,21 +61,25 @@ class DecodeState:
         return max(self.host_len)
 
     def set_sampling(self, sampling: Optional[dict]):
-        """None: the step picks argmax.  dict(temperature, top_k, top_p, seed): the step DRAWS (sample.hip); the parameters go to
-        the state's device block (one small H2D copy), so the graph captured for sampling serves every setting."""
+        """None: the step picks argmax.  dict(temperature, top_k, top_p, seed[, sampler]): the step DRAWS (sample.hip) with the
+        sampler kind `sampler` (default: the top-k-64 sampler); the parameters go to the state's device block (one small H2D copy),
+        so the graph captured for a sampler kind serves every setting."""
         if sampling is None:
             self.c.sampling = None
+            self.sampler = L.SAMPLER_TOPK64
             return
+        self.sampler = int(sampling.get("sampler", L.SAMPLER_TOPK64))
         if self.sampling is None:
             self.sampling = ops.SamplingParams(self._eng.device, self.batch)
         self.sampling.set(sampling["temperature"], sampling.get("top_k"), sampling.get("top_p"), sampling.get("seed", 0))
         self.c.sampling = self.sampling.ptr()
 
     def ensure_graph(self):
-        key = "greedy" if not self.c.sampling else "sample"
+        key = "greedy" if not self.c.sampling else ("sample_full" if self.sampler == L.SAMPLER_FULL else "sample")
         if key not in self.graphs:
             g = L.vp()
-            L.check(L.load().srgpt_llm_decode_graph_create(C.byref(self._eng.w.llm), C.byref(self.c), ops._stream(), C.byref(g)))
+            L.check(L.load().srgpt_llm_decode_graph_create_ex(C.byref(self._eng.w.llm), C.byref(self.c), self.sampler, ops._stream(),
+                                                              C.byref(g)))
             self.graphs[key] = g
         return self.graphs[key]
 
@@ -464,8 +469,9 @@ class SrgptEngine:
     def greedy_decode(self, st: DecodeState, max_new_tokens: int, eos_token_id=None, pad_token_id=None,
                       stopping_criteria=None, sampling: Optional[dict] = None) -> torch.Tensor:
         """HF generation-loop semantics (new ids only, finished rows padded), device-side steps via hipGraph.
-        sampling = None: greedy.  sampling = dict(temperature, top_k, top_p, seed): every step DRAWS its token on the device
-        (temperature -> top-k -> top-p -> categorical, sample.hip) -- same loop, same graph mechanism, no per-token host work."""
+        sampling = None: greedy.  sampling = dict(temperature, top_k, top_p, seed[, sampler]): every step DRAWS its token on the
+        device (temperature -> top-k -> top-p -> categorical, sample.hip; `sampler` = L.SAMPLER_FULL for the settings the top-k-64
+        sampler does not serve) -- same loop, same graph mechanism, no per-token host work."""
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
@@ -474,6 +480,7 @@ class SrgptEngine:
                 n_keep, eos = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
             finally:
                 st.c.sampling = None
+                st.sampler = L.SAMPLER_TOPK64
         cur.wait_stream(self.stream)
         # the decode attention hands partials between workgroups inside a launch (arrival tickets): a ticket left non-zero means a
         # launch merged nothing and later steps used stale attention output -- fail loudly, never return such ids
@@ -490,7 +497,7 @@ class SrgptEngine:
     def _decode_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria):
         lib = L.load()
         stream = ops._stream()
-        L.check(lib.srgpt_llm_sample_first(C.byref(self.w.llm), C.byref(st.c), stream))
+        L.check(lib.srgpt_llm_sample_first_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
         eos = None  # ordered list of EOS ids (HF accepts an int or a list; Llama-3 checkpoints list two)
         if eos_token_id is not None:
             eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
@@ -505,7 +512,7 @@ class SrgptEngine:
                 L.check(lib.srgpt_graph_launch(graph, n, stream))
             else:
                 for _ in range(n):
-                    L.check(lib.srgpt_llm_decode_step(C.byref(self.w.llm), C.byref(st.c), stream))
+                    L.check(lib.srgpt_llm_decode_step_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
 
         def judge(ids, lo, hi):
             """host-side EOS / stopping-criteria scan of steps [lo, hi) of `ids` (CPU int64 [B, >= hi]); -> stop step or None."""

@@ -513,8 +513,9 @@ def cross_entropy(shift_logits: torch.Tensor, shift_labels: torch.Tensor, ignore
 
 class SamplingParams:
     """The device-resident parameter block of the device-side draw (srgpt_sampling, include/srgpt.h): temperature -> top-k ->
-    top-p -> categorical, HF GenerationMixin.sample's warper chain.  `supported()` says whether a setting is served on the device
-    (top_k 1..64 with any top_p; or no top-k and no top-p: pure temperature sampling by Gumbel-max)."""
+    top-p -> categorical, HF GenerationMixin.sample's warper chain.  `supported()` says whether a setting is served by the top-k-64
+    sampler (top_k 1..64 with any top_p; or no top-k and no top-p: pure temperature sampling by Gumbel-max); `sampler()` says which
+    device sampler serves a setting at all (the full sampler takes every other one)."""
 
     def __init__(self, device, batch: int, keep_kept_sets: bool = False):
         self.device = torch.device(device)
@@ -532,11 +533,19 @@ class SamplingParams:
             return not p_on
         return 1 <= k <= L.SAMPLING_TOP_K_MAX
 
+    @staticmethod
+    def sampler(temperature, top_k, top_p, vocab: int) -> Optional[int]:
+        """L.SAMPLER_TOPK64 where `supported()`, else L.SAMPLER_FULL for any temperature > 0 over a vocabulary <= 262144; None:
+        no device sampler serves the setting."""
+        if temperature is None or not temperature > 0 or vocab > L.SAMPLING_VOCAB_MAX:
+            return None
+        return L.SAMPLER_TOPK64 if SamplingParams.supported(temperature, top_k, top_p, vocab) else L.SAMPLER_FULL
+
     def set(self, temperature: float, top_k, top_p, seed: int, counter: int = 0):
         """one small H2D copy on the current stream"""
         h = self.host
         h.temperature = float(temperature)
-        h.top_k = 0 if top_k is None else int(top_k)
+        h.top_k = 0 if top_k is None else min(int(top_k), 2 ** 31 - 1)  # any top_k >= V means V
         tp = 1.0 if top_p is None else float(top_p)
         h.top_p = tp
         h.top_p_rm = float(torch.tensor(1.0 - tp, dtype=torch.float64).to(torch.float32))  # HF compares against (1 - top_p) in fp32
@@ -564,3 +573,26 @@ def sample(logits: torch.Tensor, params: SamplingParams, check: bool = False) ->
     if check:  # settings the device sampler does not serve raise instead of drawing from a clamped distribution
         L.check(lib.srgpt_sample_status(_p(ws), B, _stream()))
     return out
+
+
+def sample_full(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = False):
+    """one draw per row of fp32 logits [B, V] with the full device sampler (every temperature / top_k / top_p); advances params'
+    counter.  -> int64 [B], or (ids, kept bool [B, V]) with kept_mask=True (the kept set, the parity hook)."""
+    _dev(logits)
+    if logits.dtype != torch.float32 or logits.ndim != 2:
+        raise ValueError("sample_full: logits must be fp32 [B, V]")
+    B, V = logits.shape
+    lib = L.load()
+    nbytes = lib.srgpt_sample_full_ws_bytes(B, V)
+    if nbytes < 0:
+        raise ValueError("sample_full: empty shape")
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
+    out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    nw = (V + 31) // 32
+    mask = torch.empty((B, nw), dtype=torch.int32, device=logits.device) if kept_mask else None
+    L.check(lib.srgpt_sample_full(_p(_c(logits)), params.ptr(), _p(out), _p(mask), _p(ws), B, V, _stream()))
+    if not kept_mask:
+        return out
+    bits = torch.arange(32, device=logits.device, dtype=torch.int32)
+    kept = ((mask[:, :, None] >> bits) & 1).bool().reshape(B, nw * 32)[:, :V]
+    return out, kept

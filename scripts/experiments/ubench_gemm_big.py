@@ -1,11 +1,7 @@
-"""GEMM at the shapes that fill the chip (batched ViT / batched prefill / large squares).  `--tuning` loads the A/B build
-(libsrgpt_hip_tuning.so, `make -C spatialrgpt_amd/csrc TUNING=1`) so that SRGPT_GEMM_FORCE_256=-1 / 1 selects the kernel."""
+"""GEMM at the shapes that fill the chip (batched ViT / batched prefill / large squares)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
-from spatialrgpt_amd import _lib
-if "--tuning" in sys.argv:
-    _lib.LIB_PATH = _lib.LIB_PATH.replace("libsrgpt_hip.so", "libsrgpt_hip_tuning.so")
 from spatialrgpt_amd import ops
 dev = "cuda"
 shapes = [("sq4096", 4096, 4096, 4096), ("sq8192", 8192, 8192, 8192),

@@ -16,4 +16,4 @@ for _ in range(5):
         e0.record(); ops.gemv(x,W,norm_w=g,eps=1e-5,out=out,out_f32=True); e1.record(); evs.append((e0,e1))
 torch.cuda.synchronize()
 ms=sorted(a.elapsed_time(b) for a,b in evs)
-print(os.environ.get("SRGPT_GEMV_BLOCKS_PER_CU"), f"median {ms[len(ms)//2]*1e3:.1f} us  {N*K*2/ms[len(ms)//2]/1e9:.2f} TB/s")
+print(f"median {ms[len(ms)//2]*1e3:.1f} us  {N*K*2/ms[len(ms)//2]/1e9:.2f} TB/s")

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from spatialrgpt_amd import _lib
-if os.environ.get("SRGPT_LIB"):  # a tuning build: the SRGPT_* knobs select kernel variants
+if os.environ.get("SRGPT_LIB"):  # another build of the library
     _lib.LIB_PATH = os.path.abspath(os.environ["SRGPT_LIB"])
 from spatialrgpt_amd.config import SrgptConfig
 from spatialrgpt_amd.model import LlavaLlamaModel

@@ -2,7 +2,7 @@
 //   ubench_decode_mv <libsrgpt_hip*.so> <batch> <bf16|fp8> [pub]
 // pub: through srgpt_gemv_rowss as the batched decode step calls them (the RMSNorm products read a published row-statistics table,
 // the residual products publish one)
-// The library is dlopen'ed so that one binary times every build variant (scripts/build_skinny_variants.sh).
+// The library is dlopen'ed so that one binary times every build of it (two trees of the project, each built with make).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <stdio.h>

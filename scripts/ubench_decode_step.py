@@ -1,8 +1,8 @@
 """decode ms/token of the whole graph-captured step for several (weights, batch) configurations in one process.
   SRGPT_LIB=<path of a libsrgpt_hip*.so build> python scripts/ubench_decode_step.py fp8:8 fp8:4 bf16:4 bf16:1:2048
 (weights:batch[:T] -- T = cached prompt positions, default 259)
-Knobs of the tuning builds (SRGPT_SKINNY_W8_MODE, SRGPT_DECODE_PREFETCH_ROUNDS, ...) are read from the environment once per
-process by the library itself; this script only reports them."""
+Every line echoes the run's SRGPT_* / UBENCH_* environment (UBENCH_DECODE_LAYOUT = packed / rowmajor: the fp8 decode copies).
+A kernel change is A/B'd by running this on two builds of the library (ab_libs_decode_step.sh)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

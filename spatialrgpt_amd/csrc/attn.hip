@@ -77,14 +77,6 @@ __global__ __launch_bounds__(64) void simple_attn_kernel(const T* __restrict__ q
 constexpr int DEC_CHUNK_MAX = 256;
 constexpr int DEC_SPLIT_MAX = 64;
 
-#ifdef SRGPT_TUNING_KNOBS
-// phase stamps of the decode attention kernel (tuning build only; scripts/experiments/ubench_decode_stamps.py): block 0 -> slots 0..15, the
-// block that merges (kv head 0, sequence 0) -> slots 16..31
-__device__ unsigned long long srgpt_dbg_stamps[32];
-#define DEC_STAMP(i) do { if (stamp_base >= 0 && threadIdx.x == 0) srgpt_dbg_stamps[stamp_base + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define DEC_STAMP(i) do { } while (0)
-#endif
 typedef SrgptPrefetch DecodePrefetch;  // common.h: L2 prefetch blocks appended to the launch (here: o_proj's weights)
 
 // splits per (sequence, kv head): enough blocks for ~2 per CU, capped at 16 for a single sequence (it needs them to spread its
@@ -92,12 +84,10 @@ typedef SrgptPrefetch DecodePrefetch;  // common.h: L2 prefetch blocks appended 
 // decode step at 4 sequences 3.44 ms with 8 splits vs 3.47 with 16, at 8 sequences 3.60 / 3.66, profiles/r02_decode_splits.txt),
 // never fewer than the score buffer requires (DEC_CHUNK_MAX keys per split)
 static inline int decode_nsplit(int max_pos, int B, int Hkv) {
-  const int force = SRGPT_KNOB("SRGPT_DECODE_MIN_SPLITS", 0);  // tuning build: fixed split count
   int want = cdiv(2 * srgpt_device_cus(), Hkv * B);
   const int cap = B == 1 ? 16 : 8;
   if (want > cap) want = cap;
   if (want < 1) want = 1;
-  if (force > 0) want = force;
   int n = cdiv(max_pos, DEC_CHUNK_MAX);
   if (n < want) n = want;
   if (n > DEC_SPLIT_MAX) n = DEC_SPLIT_MAX;
@@ -109,43 +99,30 @@ static inline int decode_nsplit(int max_pos, int B, int Hkv) {
 // (sequence, kv head) -- those past the sequence end leave at once and the merge skips them; beyond 64 splits the ranges grow in steps of 64 keys
 // and the waves loop
 static inline int decode_nsplit_mfma(int max_pos) {
-  const int force = SRGPT_KNOB("SRGPT_DECODE_MIN_SPLITS", 0);  // tuning build: fixed split count
   int n = cdiv(max_pos, 64);
   if (n < 1) n = 1;
-  if (force > 0) n = force;
   if (n > DEC_SPLIT_MAX) n = DEC_SPLIT_MAX;
   return n;
 }
 static inline bool decode_use_mfma(int dtype_is_bf16, int D, int G) {
-  return dtype_is_bf16 && D == 128 && (G == 1 || G == 2 || G == 4 || G == 8) && SRGPT_KNOB("SRGPT_DECODE_MFMA", 1);
+  return dtype_is_bf16 && D == 128 && (G == 1 || G == 2 || G == 4 || G == 8);
 }
 
 template <typename T, int D, int G, int SCLD>
 __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, int* __restrict__ ticket, int nsplit,
                                                     T* __restrict__ outp, float* __restrict__ sc, float* __restrict__ stat_m,
-                                                    float* __restrict__ stat_l, int tid, int lane, int wave, bool first_group,
-                                                    int stamp_base_in) {
-#ifdef SRGPT_TUNING_KNOBS
-  int stamp_base = stamp_base_in;
-#endif
+                                                    float* __restrict__ stat_l, int tid, int lane, int wave) {
   // ---- arrival ticket: every storing wave drains its write-through stores, one lane takes the ticket; the block that draws
   //      the last one merges the nsplit partials of its G query heads (fixed split order: the result does not depend on
   //      which block came last) and re-arms the ticket for the next launch on this stream ----
-  DEC_STAMP(7);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  DEC_STAMP(8);
   if (tid == 0) {
     const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     stat_l[0] = (t == nsplit - 1) ? 1.f : 0.f;  // stat_l is free again: broadcast "I am last" through the existing LDS
   }
   __syncthreads();
-  DEC_STAMP(9);
   if (stat_l[0] == 0.f) return;
-#ifdef SRGPT_TUNING_KNOBS
-  if (first_group) stamp_base = 16;
-#endif
-  DEC_STAMP(0);
   __syncthreads();
   // The first 16 splits' partials of this thread's pair of output dims AND the per-split statistics are requested back to
   // back: the merge pays one memory latency.  (G * D / 2 <= 256 * MAXW items; one or two per thread for the shipped shapes.)
@@ -178,7 +155,6 @@ __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, i
     sc[gq * SCLD + lane] = wv;
     if (lane == 0) stat_m[gq] = den > 0.f ? 1.f / den : 0.f;
   }
-  DEC_STAMP(1);
   __syncthreads();
 #pragma unroll
   for (int wi = 0; wi < MAXW; ++wi) {
@@ -213,7 +189,6 @@ __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, i
       op[1] = from_f<T>(n1 * stat_m[gq]);
     }
   }
-  DEC_STAMP(2);
   if (tid == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -242,10 +217,6 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
     return;
   }
   const int hk = (int)blockIdx.x % Hkv, split = ((int)blockIdx.x / Hkv) % nsplit, b = (int)blockIdx.x / (Hkv * nsplit);
-#ifdef SRGPT_TUNING_KNOBS
-  int stamp_base = blockIdx.x == 0 ? 0 : -1;
-#endif
-  DEC_STAMP(0);
   const int P = pos[b];
   const int total = P + 1;
   // the key ranges depend on the sequence length only (NOT on the cache capacity: fixed capacity-based ranges were measured --
@@ -269,7 +240,6 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
     }
   }
 
-  DEC_STAMP(1);
   // ---- rotate q (G heads) and the new k; stage v.  Every global load of this stage is issued before any of
   //      them is consumed (unrolled, index wrapped instead of branched): one L2 latency instead of three. ----
   {
@@ -305,9 +275,7 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
     }
     if (tid < D) vnew[tid] = vraw;
   }
-  DEC_STAMP(2);
   __syncthreads();
-  DEC_STAMP(3);
   if (split == 0) {  // exactly one block per (b, hk) appends; nobody reads position P from the cache
     for (int d = tid; d < D; d += 256) {
       kc[(size_t)P * D + d] = from_f<T>(knew[d]);
@@ -365,7 +333,6 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
     }
     score(key, kv);
   }
-  DEC_STAMP(4);
   __syncthreads();
   // ---- softmax statistics of the chunk, one wave per q head ----
   const int n = kend - kbeg;
@@ -385,7 +352,6 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
       stat_l[gq] = sum;
     }
   }
-  DEC_STAMP(5);
   __syncthreads();
   // ---- pass 2: O = P V ----
   float acc[G][VEC];
@@ -430,7 +396,6 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
       const float x = strided_sum<LPK>(acc[gq][i]);  // over the wave's KPW key sub-groups
       if (sub == 0) red[wave][gq][dl + i] = x;
     }
-  DEC_STAMP(6);
   __syncthreads();
   // 8-byte write-through stores (pairs of floats; rows of D + 2 floats are 8-byte aligned because D is even)
   for (int w = tid; w < G * (D / 2); w += 256) {
@@ -443,14 +408,7 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
   }  // !empty
 
   decode_ticket_merge<T, D, G, DEC_CHUNK_MAX>(wbase, tickets + (size_t)b * Hkv + hk, nsplit,
-                                              out + ((size_t)b * Hq + (size_t)hk * G) * D, &sc[0][0], stat_m, stat_l, tid, lane, wave,
-                                              hk == 0 && b == 0,
-#ifdef SRGPT_TUNING_KNOBS
-                                              stamp_base
-#else
-                                              -1
-#endif
-  );
+                                              out + ((size_t)b * Hq + (size_t)hk * G) * D, &sc[0][0], stat_m, stat_l, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -491,10 +449,6 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
     return;
   }
   const int hk = (int)blockIdx.x % Hkv, split = ((int)blockIdx.x / Hkv) % nsplit, b = (int)blockIdx.x / (Hkv * nsplit);
-#ifdef SRGPT_TUNING_KNOBS
-  int stamp_base = blockIdx.x == 0 ? 0 : -1;
-#endif
-  DEC_STAMP(0);
   const int P = pos[b];
   const int total = P + 1;
   // FIXED key ranges: block `split` owns keys [split * kpb, (split + 1) * kpb), kpb = 64 for caches up to 4096 positions -- the
@@ -528,7 +482,6 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
   int kb = kbeg + 16 * wave;
   fetch(kb);
 
-  DEC_STAMP(1);
   // ---- rotate q (G heads) and the new k; stage v.  Every global load of this stage is issued before any is consumed ----
   {
     constexpr int NITEM = (G + 1) * HALF;
@@ -568,9 +521,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
     }
     if (tid < D) vnew[tid] = vraw;
   }
-  DEC_STAMP(2);
   __syncthreads();
-  DEC_STAMP(3);
   if (split == 0) {  // exactly one block per (b, hk) appends; nobody reads position P from the cache
     if (tid < D / 2) {
       *reinterpret_cast<unsigned int*>(kc + (size_t)P * D + 2 * tid) = *reinterpret_cast<const unsigned int*>(knew + 2 * tid);
@@ -656,7 +607,6 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
     __builtin_amdgcn_wave_barrier();
     if (kb + 64 < kend) fetch(kb + 64);  // contexts beyond 64 keys per split (max_pos > 64 * DEC_SPLIT_MAX never; > 512 here)
   }
-  DEC_STAMP(4);
   // ---- the four waves meet: per-wave (m, l) and P.V through LDS ----
   if (lq < G && g4 == 0) {
     wm[wave][lq] = m_run;
@@ -664,9 +614,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
   }
 #pragma unroll
   for (int h = 0; h < G; ++h) *reinterpret_cast<f32x2*>(&accs[wave][h][2 * lane]) = f32x2{acc[h][0], acc[h][1]};
-  DEC_STAMP(5);
   __syncthreads();
-  DEC_STAMP(6);
   float* wbase = ws + (((size_t)b * Hkv + hk) * G) * (size_t)DEC_SPLIT_MAX * (D + 2);
   auto publish2 = [&](float* p, float a, float b2) {
     const unsigned long long u = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b2) << 32);
@@ -688,13 +636,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
     if (d == 0) publish2(wp + D, M, L);
   }
   decode_ticket_merge<T, D, G, 64>(wbase, tickets + (size_t)b * Hkv + hk, nlive, out + ((size_t)b * Hq + (size_t)hk * G) * D,
-                                   &sc[0][0], stat_m, stat_l, tid, lane, wave, hk == 0 && b == 0,
-#ifdef SRGPT_TUNING_KNOBS
-                                   stamp_base
-#else
-                                   -1
-#endif
-  );
+                                   &sc[0][0], stat_m, stat_l, tid, lane, wave);
 }
 
 template <typename T, int D>
@@ -763,12 +705,6 @@ int launch_decode(const void* qkv, void* kc, void* vc, const int* pos, const voi
 
 }  // namespace
 
-#ifdef SRGPT_TUNING_KNOBS
-extern "C" int srgpt_debug_stamps(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(srgpt_dbg_stamps), sizeof(unsigned long long) * (n < 32 ? n : 32));
-}
-#endif
-
 extern "C" int64_t srgpt_decode_attn_ws_floats(int B, int Hq, int D) {
   return (int64_t)B * Hq * DEC_SPLIT_MAX * (D + 2) + (int64_t)B * Hq;  // partials + arrival tickets (<= B * Hkv ints)
 }
@@ -777,20 +713,15 @@ extern "C" int64_t srgpt_decode_attn_ws_floats(int B, int Hq, int D) {
 // next_w = NULL -> no prefetch.  batch > 1 goes through the skinny kernel: no prefetch there (measured, common.h).
 int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
                               const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D, int max_pos, int dtype,
-                              const void* next_w, int next_n, int next_k, int next_fp8, int next_packed_rows, srgpt_stream_t stream) {
+                              const void* next_w, int next_n, int next_k, int next_fp8, int /*next_packed_rows: unused*/,
+                              srgpt_stream_t stream) {
   SRGPT_CHECK(qkv && kcache && vcache && pos && cos_tab && sin_tab && out && ws, SRGPT_ERR_ARG,
               "srgpt_decode_attention: null pointer");
   SRGPT_CHECK(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, SRGPT_ERR_ARG, "srgpt_decode_attention: bad heads");
-  // 0 = off; 2 = all of o_proj (measured 3.189 / 3.169 / 3.138 ms per token at 0 / 1 / 2 rounds)
-  const int pf_rounds = SRGPT_KNOB("SRGPT_DECODE_PREFETCH_ROUNDS", 2);
-  // batched decode on packed fp8 weights (round 6): o_proj's 16-row tiles are contiguous and tile p belongs to block p of the next
-  // launch -- the whole 16.8-MB matrix fits the 32 MB of L2; SRGPT_DECODE_PREFETCH_TILES = loads a prefetch wave keeps in flight (0: off)
-  const int pf_tiles = SRGPT_KNOB("SRGPT_DECODE_PREFETCH_TILES", 0);
-  const DecodePrefetch pf = dtype != SRGPT_BF16 ? srgpt_prefetch_for_gemv(nullptr, 0, 0, 0, 0, B, 0, 0)
-                            // (16 consecutive rows of a ROW-MAJOR matrix are one contiguous tile too: block p of the batched product
-                            //  streams rows 16 p .. 16 p + 15)
-                            : ((next_packed_rows == 16 || next_packed_rows == 0) && B > 1) ? srgpt_prefetch_for_packed_tiles(next_w, next_n, next_k, next_fp8 ? 1 : 2, pf_tiles)
-                                                                : srgpt_prefetch_for_gemv(next_w, next_n, next_k, 0, next_fp8, B, pf_rounds, 0);
+  // bf16 activations only; 2 rounds = all of o_proj (measured 3.189 / 3.169 / 3.138 ms per token at 0 / 1 / 2 rounds).  B > 1 gets no
+  // prefetch blocks (common.h); o_proj's packed tiles pulled by this launch were measured without gain
+  // (profiles/r06_decode_prefetch_tiles.txt)
+  const DecodePrefetch pf = srgpt_prefetch_for_gemv(dtype == SRGPT_BF16 ? next_w : nullptr, next_n, next_k, 0, next_fp8, B, 2, 0);
   if (dtype == SRGPT_BF16)
     return launch_decode<bf16_t>(qkv, kcache, vcache, pos, cos_tab, sin_tab, out, ws, B, Hq, Hkv, D, max_pos, pf,
                                  as_stream(stream));

@@ -57,16 +57,6 @@ void srgpt_set_error(const char* fmt, ...);
     if (rc__ != 0) return rc__; \
   } while (0)
 
-// Tuning knobs: the product library is built WITHOUT SRGPT_TUNING_KNOBS and every knob is its compile-time default (no
-// getenv, no globals).  `make TUNING=1` builds libsrgpt_hip_tuning.so for the A/B scripts under scripts/, where the same
-// sites read the environment once.
-#ifdef SRGPT_TUNING_KNOBS
-#include <stdlib.h>
-#define SRGPT_KNOB(name, dflt) ([]() -> int { static const int v__ = getenv(name) ? atoi(getenv(name)) : (dflt); return v__; }())
-#else
-#define SRGPT_KNOB(name, dflt) (dflt)
-#endif
-
 // Raise a kernel's dynamic-LDS limit once per (kernel, device).  hipFuncSetAttribute is per device, so the "done" state is a
 // per-device bit behind an atomic (thread-safe, idempotent): `done` is the call site's own function-local atomic.
 #include <atomic>
@@ -150,21 +140,8 @@ template <int N>
 __device__ __forceinline__ float lanes_max(float v) { return lanes_reduce<N>(v, [](float a, float b) { return fmaxf(a, b); }); }
 // whole-wave reductions (every lane gets the result): 4 DPP steps + 2 swaps, ~50 cycles -- the __shfl_xor butterfly they replace is
 // six dependent ds_bpermute round trips (~700 cycles), which in the GEMV sat between a row's last FMA and the next row's loads
-#ifndef SRGPT_WAVE_BPERMUTE  // (A/B builds only: the butterfly)
 __device__ __forceinline__ float wave_sum(float v) { return lanes_sum<64>(v); }
 __device__ __forceinline__ float wave_max(float v) { return lanes_max<64>(v); }
-#else
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-#endif
 // sum over the lanes l, l + S, l + 2S, ... of the wave (S = 1, 2, ..., 32 a power of two): rotations inside the 16-lane row, then
 // the row / half-wave swaps; every lane ends with the sum of its residue class mod S
 template <int S>
@@ -249,6 +226,7 @@ struct SrgptPrefetch {
                          // loads alone; 2 / 4 / 8: faster, at the price of queueing in front of them)
   int tile_bytes;        // > 0: TILE mode (round 6) -- the next launch is the batched MFMA product on a PACKED matrix whose block p
                          // streams the contiguous tile p (16 rows x K): prefetch block p pulls that tile, its waves interleaved
+                         // (measured without gain, profiles/r06_decode_prefetch_tiles.txt: no host path fills it)
 };
 
 template <int NB>
@@ -328,20 +306,6 @@ static inline SrgptPrefetch srgpt_prefetch_for_gemv(const void* W, int N, int K,
   pf.rounds = rounds;
   pf.nblocks = grid;
   pf.n_rows = swiglu ? 2 * N : N;
-  pf.batch = SRGPT_KNOB("SRGPT_DECODE_PREFETCH_BATCH", 2);  // measured 1 / 2 / 4 / 8: 3.016 / 2.948 / 2.986 / 3.000 ms per token (profiles/r03_decode_attention.txt)
-  return pf;
-}
-// descriptor for "the next launch is the batched MFMA product (skinny.hip) over a PACKED matrix of 16-row granules, one tile per block"
-// (o_proj / down_proj of the batched fp8 decode step): block p of that launch -- XCD p % 8, like prefetch block p -- streams tile p
-static inline SrgptPrefetch srgpt_prefetch_for_packed_tiles(const void* Wp, int N, int K, int elem_bytes, int batch_loads) {
-  SrgptPrefetch pf{nullptr, 0, 0, 0, 1, 1, 0, 1, 0, 0, 1, 1, 0};
-  const long long tile = 16LL * K * elem_bytes;
-  if (!Wp || batch_loads <= 0 || tile % 1024 != 0 || N % 16 != 0 || N / 16 > srgpt_device_cus()) return pf;
-  pf.base = reinterpret_cast<const char*>(Wp);
-  pf.tile_bytes = (int)tile;
-  pf.n_units = N / 16;
-  pf.gemv_grid = pf.nblocks = N / 16;
-  pf.rounds = 1;
-  pf.batch = batch_loads;
+  pf.batch = 2;  // measured 1 / 2 / 4 / 8: 3.016 / 2.948 / 2.986 / 3.000 ms per token (profiles/r03_decode_attention.txt)
   return pf;
 }

@@ -30,14 +30,6 @@ constexpr int QBLK = 64, KVBLK = 64;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-#ifdef SRGPT_TUNING_KNOBS
-// phase stamps of block (0, 0, 0), wave 0, key tile 5 (scripts/experiments/ubench_flash_stamps.py)
-__device__ unsigned long long srgpt_flash_stamps[16];
-#define FL_STAMP(i) do { if (stamp_on && t == 5 && threadIdx.x == 0) srgpt_flash_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define FL_STAMP(i) do { } while (0)
-#endif
-
 template <int HDP, bool CAUSAL>
 __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
   constexpr int NS = HDP / 8;                 // 16-byte slots per K / V row
@@ -128,18 +120,12 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
   float m = -INFINITY, l = 0.f;             // running maximum of the RAW products, running sum of exp(scale * (x - m))
   const float c2 = a.scale * 1.44269504088896340736f;
 
-#ifdef SRGPT_TUNING_KNOBS
-  const bool stamp_on = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0;
-#endif
   auto step = [&](auto CUR, int t) {
     constexpr int S = decltype(CUR)::value;
     const int k0 = t * KVBLK;
-    FL_STAMP(0);
     __syncthreads();  // tile t parked by every wave; every wave done with tile t - 1 (the other buffer)
-    FL_STAMP(1);
     if (t + 1 < ntiles) park(std::integral_constant<int, S ^ 1>{});
     fetch(std::integral_constant<int, S ^ 1>{}, t + 3);
-    FL_STAMP(2);
     const bf16_t* Kt = Ks[S];
     const bf16_t* Vt = Vs[S];
 
@@ -161,7 +147,6 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) p[s][r] = acc[r];
     }
-    FL_STAMP(3);
     bool edge = k0 + KVBLK > klen;
     if (CAUSAL) edge = edge || (k0 + KVBLK - 1 > q0 + wave * 16 + coff);  // the wave's FIRST query does not see the tile's last key
     if (edge) {
@@ -203,7 +188,6 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
     }
 
     // ---- O^T += V^T P^T ; contraction index 8g+i <-> key 32j + 4g + i (i<4), 32j + 16 + 4g + (i-4) ----
-    FL_STAMP(4);
     const bf16_t* vp = Vt + (4 * g + (lq >> 2)) * VLD + 4 * (lq & 3);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -222,7 +206,6 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
         o[ds] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), pf, o[ds], 0, 0, 0);
       }
     }
-    FL_STAMP(5);
   };
   for (int t = 0; t < ntiles; t += 2) {
     step(std::integral_constant<int, 0>{}, t);
@@ -267,9 +250,3 @@ void srgpt_flash_bf16_launch(const AttnArgs& a, int B, bool causal, hipStream_t 
   }
 #undef LF
 }
-
-#ifdef SRGPT_TUNING_KNOBS
-extern "C" int srgpt_flash_debug_stamps(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(srgpt_flash_stamps), sizeof(unsigned long long) * (n < 16 ? n : 16));
-}
-#endif

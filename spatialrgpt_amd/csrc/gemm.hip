@@ -1,7 +1,7 @@
 // GEMM family: C[M,N] = act(A[M,K] @ W[N,K]^T + bias) + residual      (see include/srgpt.h)
 //
-// bf16: LDS-tiled MFMA kernel (v_mfma_f32_32x32x16_bf16), 256 threads = 2x2 waves, BK = 64,
-//       register-staged double buffering, XOR-swizzled 16-byte LDS slots: slot ^ ((row >> 1) & 7) -- with 128-byte rows the
+// bf16: LDS-tiled MFMA kernel (v_mfma_f32_32x32x16_bf16), 256 threads = 4 waves, BK = 64,
+//       direct-to-LDS staging, XOR-swizzled 16-byte LDS slots: slot ^ ((row >> 1) & 7) -- with 128-byte rows the
 //       16 lanes of a ds_read_b128 pass (16 consecutive rows, one slot) then cover all 64 banks exactly once (the row's
 //       parity picks the 128-byte half, the swizzled slot the 16 bytes within it); slot ^ (row & 7) left rows r and r + 8
 //       on the same banks: SQ_LDS_BANK_CONFLICT was 50 % of SQ_LDS_IDX_ACTIVE, fused epilogue (bias / activation / residual / deconv pixel-shuffle / fp32 out).
@@ -17,139 +17,13 @@ int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Epi
 
 namespace {
 
-// ------------------------------------------------------------------------------------------------
-// bf16 MFMA kernel
-// ------------------------------------------------------------------------------------------------
 constexpr int BK = 64;  // bf16 elements per K tile = 8 slots of 16 B
-
-#ifdef SRGPT_TUNING_KNOBS  // register-staged predecessor: only in the A/B build (make TUNING=1, SRGPT_GEMM_GLDS=0)
-template <int BM, int BN>
-__global__ __launch_bounds__(256) void gemm_bf16_mfma(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
-                                                      int K, int lda, Epilogue e) {
-  constexpr int TM = BM / 64, TN = BN / 64;   // 32x32 MFMA tiles per wave per dim
-  constexpr int LA = BM / 32, LW = BN / 32;   // 16-byte slots each thread stages per tile
-  __shared__ __attribute__((aligned(16))) bf16_t lds[2 * (BM + BN) * BK];
-  bf16_t* As = lds;
-  bf16_t* Ws = lds + 2 * BM * BK;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-  const int sc = tid & 7, sr = tid >> 3;  // staging slot column / row
-
-  // two register sets: the global loads of K-tile t+2 are in flight while tile t is multiplied and tile t+1 sits
-  // in the other set waiting for its LDS slot (prefetch distance = 2 tiles; one tile cannot cover HBM/L2 latency)
-  u32x4 ra[2][LA], rw[2][LW];
-  auto gload = [&](int kt, u32x4 (&da)[LA], u32x4 (&dw)[LW]) {
-    const int k = kt * BK + sc * 8;
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int m = m0 + sr + 32 * i;
-      da[i] = (m < e.M && k < K) ? *reinterpret_cast<const u32x4*>(A + (size_t)m * lda + k) : u32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int i = 0; i < LW; ++i) {
-      const int n = n0 + sr + 32 * i;
-      dw[i] = (n < e.N && k < K) ? *reinterpret_cast<const u32x4*>(W + (size_t)n * K + k) : u32x4{0, 0, 0, 0};
-    }
-  };
-  auto lstore = [&](int buf, const u32x4 (&da)[LA], const u32x4 (&dw)[LW]) {
-#pragma unroll
-    for (int i = 0; i < LA; ++i) {
-      const int r = sr + 32 * i;
-      *reinterpret_cast<u32x4*>(As + (size_t)buf * BM * BK + r * BK + ((sc ^ ((r >> 1) & 7)) << 3)) = da[i];
-    }
-#pragma unroll
-    for (int i = 0; i < LW; ++i) {
-      const int r = sr + 32 * i;
-      *reinterpret_cast<u32x4*>(Ws + (size_t)buf * BN * BK + r * BK + ((sc ^ ((r >> 1) & 7)) << 3)) = dw[i];
-    }
-  };
-
-  f32x16 acc[TM][TN];
-  const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = zero16;
-
-  const int nk_all = (K + BK - 1) / BK;
-  const int kt0 = e.splits > 1 ? (int)blockIdx.z * e.tiles_per_split : 0;
-  const int nk = e.splits > 1 ? min(nk_all, kt0 + e.tiles_per_split) : nk_all;
-
-  auto compute = [&](int cur) {
-    const bf16_t* as = As + (size_t)cur * BM * BK;
-    const bf16_t* ws = Ws + (size_t)cur * BN * BK;
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      bf16x8 fa[TM], fw[TN];
-      const int slot = ks * 2 + (lane >> 5);
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int r = wm * (BM / 2) + i * 32 + (lane & 31);
-        fa[i] = *reinterpret_cast<const bf16x8*>(as + r * BK + ((slot ^ ((r >> 1) & 7)) << 3));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int r = wn * (BN / 2) + j * 32 + (lane & 31);
-        fw[j] = *reinterpret_cast<const bf16x8*>(ws + r * BK + ((slot ^ ((r >> 1) & 7)) << 3));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fw[j], acc[i][j], 0, 0, 0);
-    }
-  };
-
-  // tile t lives in register set (t - kt0) & 1 until it is written to LDS buffer (t - kt0) & 1
-  gload(kt0, ra[0], rw[0]);
-  if (kt0 + 1 < nk) gload(kt0 + 1, ra[1], rw[1]);
-  lstore(0, ra[0], rw[0]);
-  __syncthreads();
-  int kt = kt0;
-  for (; kt + 1 < nk; kt += 2) {
-    // even step: multiply LDS[0] (tile kt); set 0 is free -> fetch tile kt+2; stage tile kt+1 (set 1) into LDS[1]
-    if (kt + 2 < nk) gload(kt + 2, ra[0], rw[0]);
-    compute(0);
-    lstore(1, ra[1], rw[1]);
-    __syncthreads();
-    // odd step: multiply LDS[1] (tile kt+1); set 1 is free -> fetch tile kt+3; stage tile kt+2 (set 0) into LDS[0]
-    if (kt + 3 < nk) gload(kt + 3, ra[1], rw[1]);
-    compute(1);
-    if (kt + 2 < nk) lstore(0, ra[0], rw[0]);
-    __syncthreads();
-  }
-  if (kt < nk) compute(0);  // odd number of tiles: the last one is already staged in LDS[0]
-
-  // D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
-#pragma clang loop unroll(full)
-  for (int i = 0; i < TM; ++i)
-#pragma clang loop unroll(full)
-    for (int j = 0; j < TN; ++j) {
-      const f32x16 a = acc[i][j];
-      const int n = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
-      const int mb = m0 + wm * (BM / 2) + i * 32 + 4 * (lane >> 5);
-      if (e.splits > 1) {
-        float* slab = e.partial + (size_t)blockIdx.z * e.M * e.N;
-#pragma clang loop unroll(full)
-        for (int r = 0; r < 16; ++r) {
-          const int m = mb + (r & 3) + 8 * (r >> 2);
-          if (m < e.M && n < e.N) slab[(size_t)m * e.N + n] = a[r];
-        }
-      } else {
-        epilogue_tile32<bf16_t>(e, mb, n, a);
-      }
-    }
-}
-
-#endif  // SRGPT_TUNING_KNOBS
 
 // ------------------------------------------------------------------------------------------------
 // bf16 MFMA kernel, direct-to-LDS staging (global_load_lds_dwordx4): no staging VGPRs, no ds_write pass, single LDS
 // buffer (BM+BN) x 128 B -> 3 blocks per CU at 128x128, whose independent K loops overlap each other's barriers.
-// A wave-instruction moves 8 rows x 128 B into 1 KiB of LDS at (wave-uniform base + lane * 16); the XOR slot swizzle of
-// the register-staged kernel is kept by permuting WHICH 16-byte chunk of its row a lane fetches (chunk = slot ^ ((row >> 1) & 7)),
+// A wave-instruction moves 8 rows x 128 B into 1 KiB of LDS at (wave-uniform base + lane * 16); the XOR slot swizzle
+// (see the top of the file) is kept by permuting WHICH 16-byte chunk of its row a lane fetches (chunk = slot ^ ((row >> 1) & 7)),
 // so the fragment reads below are the same conflict-free ds_read_b128.  Rows past M / N re-read the last valid row
 // (their outputs are never stored); a ragged last K tile (K % 64 != 0) is staged through registers with zero fill.
 // ------------------------------------------------------------------------------------------------
@@ -704,28 +578,19 @@ static int gemm_impl(const void* A, const void* W, const void* bias, const void*
     const int cus = srgpt_device_cus();
     const int nk = K / 64;
     const int gx = cdiv(N, 128);
-    const int mode = SRGPT_KNOB("SRGPT_GEMM_288", 1);  // tuning build: 0 = never, 2 = for any M <= 272, > 2 = forced split count
     // measured at M = 259 (profiles/r04_gemm288.txt): gate/up 106.5 -> 84.2 us, down 64.8 -> 50.6, q/k/v 33.8 -> 32.0; o (27.5 vs
     // 27.9: 8 K tiles per block once K is split for 256 CUs, three of them pipeline fill) stays on the small tiles
-    const int anym = SRGPT_KNOB("SRGPT_GEMM_288_ANYM", 0);  // tuning build (round 5 probe): several 272-row tiles (grid.z) for M > 272
-    bool use288 = mode != 0 && K % 64 == 0 && nk >= 4 &&
-                  ((M > 224 && M <= 272 && (int64_t)N * K >= (int64_t)24 << 20) || (mode >= 2 && (M <= 272 || anym)));
+    bool use288 = K % 64 == 0 && nk >= 4 && M > 224 && M <= 272 && (int64_t)N * K >= (int64_t)24 << 20;
     int sp = 1;
-    if (use288) {
-      const int gz = cdiv(M, 272);
-      if (gx * gz < cus * 3 / 4 && ws) {
-        sp = (cus + gx * gz / 2) / (gx * gz);
+    if (use288) {  // one 272-row tile in M: the grid is gx column tiles x sp K splits
+      if (gx < cus * 3 / 4 && ws) {
+        sp = (cus + gx / 2) / gx;
         if (sp > nk / 8) sp = nk / 8;  // keep >= 8 K tiles per split: three of them are pipeline fill
         if (sp > 8) sp = 8;
         while (sp > 1 && (int64_t)sp * M * N * 4 > ws_bytes) --sp;
         if (sp < 1) sp = 1;
       }
-      if (mode > 2 && ws) {
-        sp = mode - 2;
-        if (sp > nk) sp = nk;
-        while (sp > 1 && (int64_t)sp * M * N * 4 > ws_bytes) --sp;
-      }
-      if ((long)gx * gz * sp < cus / 2) use288 = mode >= 2;  // too few blocks to fill the chip: the small tiles overlap better
+      if ((long)gx * sp < cus / 2) use288 = false;  // too few blocks to fill the chip: the small tiles overlap better
     }
     if (use288) {
       if (sp > 1) {
@@ -770,9 +635,6 @@ static int gemm_impl(const void* A, const void* W, const void* bias, const void*
         use256 = t256 * 100 >= rounds * cus * 88;
       }
     }
-    const int f256 = SRGPT_KNOB("SRGPT_GEMM_FORCE_256", 0);  // tuning build: 1 = whenever legal, -1 = never
-    if (f256 > 0) use256 = K % 64 == 0 && K >= 128, sp = 1;
-    if (f256 < 0) use256 = false;
     if (use256) {
       if (sp > 1) {
         e.partial = reinterpret_cast<float*>(ws);
@@ -815,54 +677,29 @@ static int gemm_impl(const void* A, const void* W, const void* bias, const void*
       if (splits < 1) splits = 1;
     }
   }
-  {  // tuning knobs (scripts/experiments/ubench_gemm.py sweeps them); unset in production
-    const int f_bm = SRGPT_KNOB("SRGPT_GEMM_FORCE_BM", 0);
-    const int f_sp = SRGPT_KNOB("SRGPT_GEMM_FORCE_SPLITS", 0);
-    if (f_bm == 64 || f_bm == 128 || f_bm == 96) bm = f_bm;
-    if (f_sp > 0 && ws) {
-      splits = f_sp;
-      if (splits > nk) splits = nk;
-      while (splits > 1 && (int64_t)splits * M * N * 4 > ws_bytes) --splits;
-    }
-    if (bm == 128) splits = 1;
-  }
   if (splits > 1) {
     e.partial = reinterpret_cast<float*>(ws);
     e.tiles_per_split = cdiv(nk, splits);
     splits = cdiv(nk, e.tiles_per_split);  // no empty split
     e.splits = splits;
   }
-  const int use_glds = SRGPT_KNOB("SRGPT_GEMM_GLDS", 1);  // A/B knob (tuning build only)
-  (void)use_glds;
   if (bm == 128) {
     dim3 grid(cdiv(N, 128), cdiv(M, 128), 1);
-#ifdef SRGPT_TUNING_KNOBS
-    if (!use_glds)
-      hipLaunchKernelGGL((gemm_bf16_mfma<128, 128>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-    else
-#endif
-      hipLaunchKernelGGL((gemm_bf16_glds<128, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
+    hipLaunchKernelGGL((gemm_bf16_glds<128, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
   } else if (bm == 96) {
     dim3 grid(cdiv(N, 128), cdiv(M, 96), e.splits);  // (96x256 tiles measured: slower on every shape)
-    const int f_nbuf = SRGPT_KNOB("SRGPT_GEMM_FORCE_NBUF", 0);
     const long blocks = (long)grid.x * grid.y * e.splits;
     // single buffer (5 blocks per CU overlap each other's K steps) only for un-split grids of >= 2 blocks per CU (gate/up 672,
     // ViT fc1 544 blocks: 106 vs 134 us, 25 vs 33 us); split-K and smaller grids double-buffer (q/k/v 34 vs 38 us)
-    const bool dbuf = f_nbuf ? f_nbuf == 2 : !(e.splits <= 1 && blocks >= 2L * srgpt_device_cus());
+    const bool dbuf = !(e.splits <= 1 && blocks >= 2L * srgpt_device_cus());
     if (dbuf)
       hipLaunchKernelGGL((gemm_bf16_glds<96, 128, 2>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
     else
       hipLaunchKernelGGL((gemm_bf16_glds<96, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
   } else {
     dim3 grid(cdiv(N, 128), cdiv(M, 64), e.splits);
-    const int f_nbuf = SRGPT_KNOB("SRGPT_GEMM_FORCE_NBUF", 0);
     const long blocks = tiles * e.splits;
-    const bool dbuf = f_nbuf ? f_nbuf == 2 : blocks < 3L * srgpt_device_cus();
-#ifdef SRGPT_TUNING_KNOBS
-    if (!use_glds)
-      hipLaunchKernelGGL((gemm_bf16_mfma<64, 128>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-    else
-#endif
+    const bool dbuf = blocks < 3L * srgpt_device_cus();
     if (dbuf)
       hipLaunchKernelGGL((gemm_bf16_glds<64, 128, 2>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
     else
@@ -937,8 +774,7 @@ extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int 
                                  int64_t ws_bytes, int dtype, srgpt_stream_t stream) {
   SRGPT_CHECK(A && Wgu && out, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: null pointer");
   SRGPT_CHECK(M > 0 && I > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: bad shape M=%d I=%d K=%d", M, I, K);
-  const int mode = SRGPT_KNOB("SRGPT_GEMM_SWIGLU", 1);  // tuning build: 0 = always the two launches
-  const bool fused = mode != 0 && dtype == SRGPT_BF16 && M > 224 && M <= 272 && K % 64 == 0 && K / 64 >= 4 && I % 64 == 0 &&
+  const bool fused = dtype == SRGPT_BF16 && M > 224 && M <= 272 && K % 64 == 0 && K / 64 >= 4 && I % 64 == 0 &&
                      I / 64 >= srgpt_device_cus() / 2 && ((uintptr_t)A % 16 == 0) && ((uintptr_t)Wgu % 16 == 0);
   if (fused) {
     Epilogue e{};

@@ -346,7 +346,7 @@ int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const Epi
   const bool w8 = e.wscale != nullptr;  // fp8 weight bytes + per-row scales
   // persistent form: more tiles than CUs and no split-K -- one block per CU (a multiple of 8: the XCD runs), each walks its tiles
   const int cus = srgpt_device_cus() & ~7;
-  const bool persist = e.splits <= 1 && gx * gy > cus && cus >= 8 && SRGPT_KNOB("SRGPT_GEMM_PERSIST", 1) != 0;
+  const bool persist = e.splits <= 1 && gx * gy > cus && cus >= 8;
 #define G_LAUNCH(W8V, PV)                                                                                                 \
   do {                                                                                                                    \
     static std::atomic<uint64_t> attr_done{0};                                                                            \

@@ -7,7 +7,7 @@
 // Work decomposition: a unit = one output row (plain) or one (gate row, up row) pair (SwiGLU); each wave owns
 // units grid-strided; per unit the K range is walked in batches of 8 row chunks: 8 independent 1-KiB loads are
 // issued back to back, then consumed in order with counted waits.  No cross-batch software pipeline: measured
-// (scripts/experiments/ubench_stream.hip, ubench_gemv_ts.hip) a 3-deep register pipeline with 16+ loads in flight per wave
+// (scripts/experiments/ubench_stream.hip and per-wave timestamps, round 2) a 3-deep register pipeline with 16+ loads in flight per wave
 // was 2-3 us SLOWER per launch -- 8 waves/CU x 8 KiB already saturate HBM, and the independent waves of a CU
 // drift apart so that some stream while others multiply.  Grid = 2 blocks per CU.
 //
@@ -19,22 +19,6 @@
 
 #include "common.h"
 
-// Optional per-wave timestamping (scripts/experiments/ubench_gemv_ts.hip builds this file with -DSRGPT_GEMV_TS)
-#ifdef SRGPT_GEMV_TS
-__device__ long long srgpt_gemv_ts[8 * 8192];
-extern "C" void* srgpt_gemv_ts_ptr() {
-  void* p = nullptr;
-  (void)hipGetSymbolAddress(&p, HIP_SYMBOL(srgpt_gemv_ts));
-  return p;
-}
-#define SRGPT_TS(slot)                                                                             \
-  do {                                                                                             \
-    if (lane == 0) srgpt_gemv_ts[((int)blockIdx.x * 4 + wave) * 8 + (slot)] = wall_clock64();     \
-  } while (0)
-#else
-#define SRGPT_TS(slot)
-#endif
-
 int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
                         int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
                         hipStream_t s);  // skinny.hip
@@ -42,18 +26,6 @@ int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, c
                            const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
                            const float* ss_in, float* ss_out, int packed, hipStream_t s);  // skinny.hip
 int srgpt_w8_valu_max_batch();  // skinny.hip
-
-// (compile-time variants: tuning / micro-benchmark builds only -- a product build that defines one is refused)
-#if !defined(SRGPT_TUNING_KNOBS) && (defined(SRGPT_GEMV_TS) || defined(SRGPT_GEMV_REG_PIPE) || defined(SRGPT_GEMV_PIPE))
-#error "gemv.hip: -DSRGPT_GEMV_* variants need -DSRGPT_TUNING_KNOBS (make TUNING=1, scripts/experiments/ubench_gemv_ts.hip)"
-#endif
-#ifndef SRGPT_GEMV_REG_PIPE
-#define SRGPT_GEMV_REG_PIPE 0  // the same for the register-resident variant (o_proj: its weights are L2-prefetched; measured
-                               // 3.036 vs 3.042 ms per token, o_proj 5.0 vs 5.45 us -- off)
-#endif
-#ifndef SRGPT_GEMV_PIPE
-#define SRGPT_GEMV_PIPE 1  // 0: issue -> consume per batch, nothing in flight across the prologue / reductions (A/B builds)
-#endif
 
 namespace {
 
@@ -98,7 +70,6 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = K / VEC;          // 16-byte chunks per row
   const int nit = (nchunks + 63) >> 6;  // chunk iterations per row (64 lanes each)
-  SRGPT_TS(0);
 
   // one batch = 8 independent 1-KiB wave loads (R rows x U chunks), issued back to back in consumption order, indices clamped,
   // never branched, so the compiler can place counted s_waitcnt vmcnt(N) in front of each consumer
@@ -142,13 +113,11 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
       xr[j] = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
       gr[j] = *reinterpret_cast<const Vec16<T>*>((do_norm ? norm_w : x) + (size_t)(c % nchunks) * VEC);
     }
-#if SRGPT_GEMV_PIPE
     // the wave's first weight batch goes out BEHIND the prologue's own loads (in-order return: the statistics below wait for the
     // activations only) and its HBM latency overlaps the RMSNorm, the LDS staging and the barrier
     __builtin_amdgcn_sched_barrier(0);
     issue(min((int)blockIdx.x * 4 + wave, N - 1), 0);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     float ss[B];
 #pragma unroll
     for (int b = 0; b < B; ++b) ss[b] = 0.f;
@@ -215,7 +184,6 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
     }
     __syncthreads();
   }
-  SRGPT_TS(2);
 
   int uk = 0;
   for (int unit = blockIdx.x * 4 + wave; unit < N; unit += gridDim.x * 4, ++uk) {
@@ -227,9 +195,6 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
 
     for (int it0 = 0; it0 < nit; it0 += U) {
       // Waves drift apart naturally, so some stream while others multiply; 8 waves/CU keep 64 KiB in flight.
-#if !SRGPT_GEMV_PIPE
-      issue(unit, it0);
-#endif
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         // branch-free: a chunk index past the row end is clamped for the loads and its weights are zeroed here.
@@ -257,14 +222,12 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
           }
         }
       }
-#if SRGPT_GEMV_PIPE
       // the registers are free again: the next batch of this wave's stream (the row's next chunks, or the first chunks of its
       // next unit; past the last unit a valid row is re-read and dropped) goes out before the reduction and the store
       {
         const bool more = it0 + U < nit;
         issue(more ? unit : min(unit + (int)gridDim.x * 4, N - 1), more ? it0 + U : 0);
       }
-#endif
     }
 
 #pragma unroll
@@ -287,7 +250,6 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
       }
     }
   }
-  SRGPT_TS(4);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -345,12 +307,6 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
       xp[j] = *reinterpret_cast<const u32x4*>(x + (size_t)c * VEC);
       if (NORM) gr[j] = *reinterpret_cast<const u32x4*>(norm_w + (size_t)c * VEC);
     }
-#if SRGPT_GEMV_REG_PIPE
-    // first weight batch behind the activation loads (see gemv_kernel): its latency overlaps theirs and the statistics
-    __builtin_amdgcn_sched_barrier(0);
-    issue(min((int)blockIdx.x * 4 + wave, N - 1), std::integral_constant<int, 0>{});
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     if (NORM) {
       float ss = 0.f;
 #pragma unroll
@@ -391,9 +347,9 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
     }
     auto batch = [&](auto it0_c) {
       constexpr int it0 = decltype(it0_c)::value;
-#if !SRGPT_GEMV_REG_PIPE
+      // issue -> consume per batch: the pipelined form of gemv_kernel was measured slower here (o_proj, whose weights are
+      // L2-prefetched: 3.036 vs 3.042 ms per token, o_proj 5.0 vs 5.45 us)
       issue(unit, it0_c);
-#endif
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         if (it0 + j < NIT) {  // static
@@ -410,11 +366,6 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
           }
         }
       }
-#if SRGPT_GEMV_REG_PIPE
-      // the next batch of the wave's stream goes out before the reduction and the store (past the last unit: a valid row, dropped)
-      if constexpr (it0 + U < NIT) issue(unit, std::integral_constant<int, it0 + U>{});
-      else issue(min(unit + (int)gridDim.x * 4, N - 1), std::integral_constant<int, 0>{});
-#endif
     };
     batch(std::integral_constant<int, 0>{});
     if constexpr (U < NIT) batch(std::integral_constant<int, U>{});
@@ -456,11 +407,6 @@ bool launch_gemv_reg(int nit, int grid, hipStream_t s, const void* x, const void
     SRGPT_REG_CASE(14);  // K = 6912
     default: break;
   }
-  if (!SWIGLU && !NORM && nit == 28 && SRGPT_KNOB("SRGPT_GEMV_REG_LONG", 0)) {  // K = 14336 (tuning builds): 112 VGPRs of activations, batches of 7
-    hipLaunchKernelGGL((gemv_reg_kernel<false, false, 28, 7>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)W,
-                       (const bf16_t*)norm_w, eps, (const bf16_t*)residual, out, N, K, out_f32);
-    return true;
-  }
   return false;  // longer rows (K = 11008, 14336: 88-112 VGPRs of activations, spills when unrolled) stay on the LDS kernel
 #undef SRGPT_REG_CASE
 }
@@ -471,17 +417,15 @@ int launch_gemv(const void* x, const void* W, const void* norm_w, float eps, con
   const size_t lds = (size_t)B * K * sizeof(T);
   SRGPT_CHECK(lds <= 150 * 1024, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv: batch*K too large for LDS (%zu bytes)", lds);
   const int cus = srgpt_device_cus();
-  const int env_per_cu = SRGPT_KNOB("SRGPT_GEMV_BLOCKS_PER_CU", 0);  // tuning knob
   // (round 5, measured and not kept: 3 / 4 / 5 blocks per CU for the short launches -- q/k/v, o_proj, where a wave owns only 2 - 3 rows,
   // i.e. 2 - 3 dependent memory round trips: 2.970 -> 2.998 / 3.009 / 3.017 ms per token; for all launches 3.037 / 3.049:
   // profiles/r05_decode_step_ab.txt)
-  const int per_cu = lds > 70 * 1024 ? 1 : (env_per_cu > 0 ? env_per_cu : 2);
+  const int per_cu = lds > 70 * 1024 ? 1 : 2;
   int grid = (N + 3) / 4;
   if (grid > cus * per_cu) grid = cus * per_cu;
   if (grid < 1) grid = 1;
   const int chunks = B * (K / WChunk<T>::VEC);
-  const int use_reg = SRGPT_KNOB("SRGPT_GEMV_REG", 1);  // A/B knob
-  if (B == 1 && sizeof(T) == 2 && use_reg) {
+  if (B == 1 && sizeof(T) == 2) {
     const int nit = (K / 8 + 63) / 64;
     // measured (scripts/experiments/ubench_gemv_c.hip): without the fused RMSNorm the register variant saves 0.6-0.8 us per launch
     // (o_proj 8.5 -> 7.9 us); with it every wave normalises the whole row redundantly and loses ~1 us -> LDS kernel
@@ -505,7 +449,7 @@ int launch_gemv(const void* x, const void* W, const void* norm_w, float eps, con
   const int nit = (K / WChunk<T>::VEC + 63) / 64;
   if (swiglu) {
     if (chunks <= 512) SRGPT_GEMV_LAUNCH(true, 2); else SRGPT_GEMV_LAUNCH(true, 8);
-  } else if (B == 1 && sizeof(T) == 2 && nit % 7 == 0 && nit % 8 != 0 && chunks > 512 && SRGPT_KNOB("SRGPT_GEMV_U7", 1)) {
+  } else if (B == 1 && sizeof(T) == 2 && nit % 7 == 0 && nit % 8 != 0 && chunks > 512) {
     SRGPT_GEMV_LAUNCH(false, 8, 7);
   } else {
     if (chunks <= 512) SRGPT_GEMV_LAUNCH(false, 2); else SRGPT_GEMV_LAUNCH(false, 8);
@@ -516,13 +460,12 @@ int launch_gemv(const void* x, const void* W, const void* norm_w, float eps, con
 }
 
 // bf16 rows >= this go to the MFMA kernel of skinny.hip
-inline int skinny_min_batch() { return SRGPT_KNOB("SRGPT_SKINNY_MIN_BATCH", 2); }  // measured (round 3, profiles/r03_skinny_min_batch.txt): VALU wins at 1 row, MFMA from 2
+constexpr int SKINNY_MIN_BATCH = 2;  // measured (round 3, profiles/r03_skinny_min_batch.txt): VALU wins at 1 row, MFMA from 2
 
 template <typename T>
 int dispatch_b(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
                int batch, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  const int skinny_min = skinny_min_batch();
-  if (batch > 4 || (sizeof(T) == 2 && batch >= skinny_min)) {
+  if (batch > 4 || (sizeof(T) == 2 && batch >= SKINNY_MIN_BATCH)) {
     // bf16: rows go through the MFMA skinny kernel 16 at a time (skinny.hip); fp32 (parity dtype of the tiny models):
     // 4 rows at a time through the VALU kernel.  Each chunk streams the weights once.
     const bool mfma = sizeof(T) == 2;
@@ -536,7 +479,7 @@ int dispatch_b(const void* x, const void* W, const void* norm_w, float eps, cons
       const void* rb = residual ? (const char*)residual + (size_t)b0 * N * sizeof(T) : nullptr;
       void* ob = (char*)out + (size_t)b0 * N * on;
       // (a single-row tail of a longer batch -- 17, 33 rows -- stays on the kernel its other rows took, as srgpt_gemv_rowss does)
-      if (mfma && (nb > 4 || nb >= skinny_min || b0 > 0))
+      if (mfma && (nb > 4 || nb >= SKINNY_MIN_BATCH || b0 > 0))
         SRGPT_TRY(srgpt_skinny_launch(xb, W, norm_w, eps, rb, ob, nb, N, K, swiglu, out_f32, nullptr, nullptr, 0, s));
       else
         SRGPT_TRY((dispatch_b<T>(xb, W, norm_w, eps, rb, ob, nb, N, K, swiglu, out_f32, s)));
@@ -577,7 +520,7 @@ extern "C" int srgpt_gemv(const void* x, const void* W, const void* norm_w, floa
 extern "C" int srgpt_gemv_rowss_supported(int batch, int dtype, int fp8) {
   if (dtype != SRGPT_BF16 || batch < 2) return 0;
   if (2 * srgpt_device_cus() > SRGPT_ROWSS_STRIDE) return 0;  // one slot per producer block (two 4-wave blocks per CU)
-  return fp8 ? (batch > srgpt_w8_valu_max_batch() ? 1 : 0) : (batch >= skinny_min_batch() ? 1 : 0);
+  return fp8 ? (batch > srgpt_w8_valu_max_batch() ? 1 : 0) : (batch >= SKINNY_MIN_BATCH ? 1 : 0);
 }
 
 extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,

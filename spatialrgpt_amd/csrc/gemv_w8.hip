@@ -1,4 +1,4 @@
-// Decode-path weight-streaming GEMV with fp8 weights for 1-2 batch rows (W8A16, BASELINE config 5):
+// Decode-path weight-streaming GEMV with fp8 weights for one batch row (W8A16, BASELINE config 5):
 //   out[b, n] = round_bf16( (sum_k x[b, k] * fp8(W8[n, k])) * wscale[n] )            (HBM-bound, half the bytes of bf16)
 //
 // Same structure as gemv.hip (wave per unit, 8 independent 1-KiB non-temporal wave loads per batch issued in consumption
@@ -10,7 +10,7 @@
 //   * weights are widened with v_cvt_pk_f32_fp8 (OCP e4m3fn on gfx950), 2 values per instruction; the two rows of a unit
 //     share the fp32 copies of x;
 //   * the per-row scale multiplies the reduced dot product.
-// More than 2 rows go through the MFMA skinny kernel (skinny.hip, W8 variant).
+// 2+ rows go through the MFMA skinny kernel (skinny.hip, W8 variant: srgpt_w8_valu_max_batch).
 #include <stdlib.h>
 
 #include "common.h"
@@ -279,9 +279,8 @@ int launch_gemv_w8(const void* x, const void* W, const float* wscale, const void
 
 }  // namespace
 
-// host entry used by srgpt_gemv_w8 (skinny.hip) for one row (two under the tuning knob); K must be a multiple of 16 here
+// host entry used by srgpt_gemv_w8 (skinny.hip) for one row (batch == 1); K must be a multiple of 16 here
 int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const void* norm_w, float eps,
                        const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  if (batch == 1) return launch_gemv_w8<1>(x, W8, wscale, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
-  return launch_gemv_w8<2>(x, W8, wscale, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
+  return launch_gemv_w8<1>(x, W8, wscale, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
 }

@@ -592,7 +592,7 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
   // 2+ bf16 rows (the MFMA kernel): o_proj / down_proj publish the sum of squares of the rows they write, the RMSNorm of the next
   // product reads 512 partial sums per row instead of re-reading every row in every block (skinny.hip; layer 0's q/k/v normalises
   // the embedding rows itself).  The per-op form of exactly this sequence is srgpt_gemv_rowss.
-  const bool pub = srgpt_gemv_rowss_supported(B, dt, w8 ? 1 : 0) != 0 && SRGPT_KNOB("SRGPT_DECODE_ROWSS", 1) != 0;
+  const bool pub = srgpt_gemv_rowss_supported(B, dt, w8 ? 1 : 0) != 0;
   float* const ss_attn = d.rowss;                                       // rows after the attention block's residual add
   float* const ss_mlp = d.rowss + (size_t)B * SRGPT_ROWSS_STRIDE;       // rows after the MLP block's
   // packed copy of layer i's matrix `which` (0 wqkv, 1 wo, 2 wgu, 3 wdown) for the MFMA kernel, or NULL: stream the row-major one
@@ -614,8 +614,7 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
     // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
     // (profiles/r03_fused_attention_oproj.txt)
     SRGPT_TRY(srgpt_decode_attention_pf(d.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, d.attnd, d.dws, B, Hq, Hkv, D,
-                                        st->max_pos, dt, pk(w->wo8p, i) ? pk(w->wo8p, i) : (w8 ? w->wo8[i] : w->wo[i]), Hd, Hq * D,
-                                        w8 ? 1 : 0, pk(w->wo8p, i) ? w->pk_rows_o : 0, stream));
+                                        st->max_pos, dt, w8 ? w->wo8[i] : w->wo[i], Hd, Hq * D, w8 ? 1 : 0, 0, stream));
     SRGPT_TRY(mv(d.attnd, w->wo[i], w8 ? w->wo8[i] : nullptr, w8 ? w->wo_scale[i] : nullptr, nullptr, d.xd, d.xd, Hd,
                  Hq * D, 0, 0, nullptr, ss_attn, pk(w->wo8p, i), w->pk_rows_o));
     SRGPT_TRY(mv(d.xd, w->wgu[i], w8 ? w->wgu8[i] : nullptr, w8 ? w->wgu_scale[i] : nullptr, w->mlp_norm[i], nullptr,

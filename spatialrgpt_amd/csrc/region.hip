@@ -80,14 +80,6 @@ __global__ __launch_bounds__(RP_POS) void region_resample_kernel(const MT* __res
   if (threadIdx.x == 0) psum[(size_t)m * gridDim.x + slab] = t;
 }
 
-#ifdef SRGPT_TUNING_KNOBS
-// phase stamps (tuning build; scripts/experiments/ubench_region_stamps.py): block (0, 0) -> slots 0..15, the last arriver of channel slab 0 -> 16..
-__device__ unsigned long long srgpt_region_stamps[32];
-#define RP_STAMP(i) do { if (stamp_base >= 0 && threadIdx.x == 0) srgpt_region_stamps[stamp_base + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define RP_STAMP(i) do { } while (0)
-#endif
-
 template <typename T, int MM>
 __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const T* __restrict__ feat, const float* __restrict__ v,
                                                           const float* __restrict__ psum, int n_psum,
@@ -117,10 +109,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
   const int cl = tid % RP_CL, rg = tid / RP_CL;
   const int chunk = cslab * RP_CL + cl;
   const bool active = rg < RP_RG && chunk * VEC < C;
-#ifdef SRGPT_TUNING_KNOBS
-  int stamp_base = (blockIdx.x == 0 && blockIdx.y == 0) ? 0 : -1;
-#endif
-  RP_STAMP(0);
   // ---- the feature rows of the first batch go out before the prologue touches anything else (row index clamped, never branched)
   const T* fbase = feat + (size_t)(active ? chunk : 0) * VEC;
   Vec16<T> f[RP_UN];
@@ -132,7 +120,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
     }
   };
   issue(0);
-  RP_STAMP(1);
   // ---- prologue: mask.sum() + 1e-8 in the feature dtype (fixed slab order), then the slab's normalised weights ----
   // (the resample launch's per-slab sums are fetched by 32 threads per mask at once and added in slab order from LDS: a chain of
   //  n_psum dependent loads in one thread was ~6 us of every block's prologue)
@@ -151,7 +138,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
   }
   if (tid < MM) den[tid] = rnd<T>(rnd<T>(sden) + 1e-8f);
   __syncthreads();
-  RP_STAMP(2);
   {  // mask / denorm in the feature dtype; the thread's v values are requested together (clamped, unconditional), then divided
     constexpr int NW = (MM * RP_ROWS + 255) / 256;
     float vv[NW];
@@ -171,7 +157,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
     }
   }
   __syncthreads();
-  RP_STAMP(3);
   float acc[MM][VEC];
 #pragma unroll
   for (int m = 0; m < MM; ++m)
@@ -191,7 +176,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
     }
     if (b + 1 < RP_NB) issue(b + 1);
   }
-  RP_STAMP(4);
   // ---- fixed-order reduce over the block's 30 row groups: the two row groups of a 16-lane row on the VALU (one DPP rotate), the
   //      16 (wave, row) partials through LDS in ONE round -- the staging array takes over the weights' LDS (dead by now).
   //      (The same sums as cross-lane v_permlane swaps took 12k cycles for 64 values; two masks per LDS round 6.4k.)
@@ -217,7 +201,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
     red[j / VEC][c8 * VEC + (j % VEC)] = t;
   }
   __syncthreads();
-  RP_STAMP(5);
   const int c0 = cslab * CW;
   // partials go out WRITE-THROUGH in 16-byte pieces (sc1 buffer stores: a 4-byte write-through store is one fabric write each,
   // ~6x the time per byte) -- whichever block of this channel slab arrives last reads every slab's partial with sc1 loads
@@ -234,21 +217,14 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
     }
   }
   // ---- arrival ticket of the channel slab; the last arriver sums the row slabs in slab order and stores ----
-  RP_STAMP(6);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  RP_STAMP(7);
   if (tid == 0) {
     const int t = __hip_atomic_fetch_add(tickets + cslab, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = (t == nslab - 1) ? 1 : 0;
   }
   __syncthreads();
-  RP_STAMP(8);
   if (!last) return;
-#ifdef SRGPT_TUNING_KNOBS
-  if (cslab == 0) stamp_base = 16;
-#endif
-  RP_STAMP(0);
   for (int j = tid; j < M * CW4; j += 256) {
     const int m = j / CW4, c = 4 * (j - m * CW4);
     if (c0 + c < C) {
@@ -271,7 +247,6 @@ __global__ __launch_bounds__(256, MM <= 8 ? 3 : 2) void region_pool_kernel(const
       for (int e = 0; e < 4; ++e) out[(size_t)m * C + c0 + c + e] = from_f<T>(t[e]);
     }
   }
-  RP_STAMP(1);
   if (tid == 0) __hip_atomic_store(tickets + cslab, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -313,10 +288,6 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
   const int slab = blockIdx.y, l0 = slab * ROWS, nslab = gridDim.y, cslab = blockIdx.x, c0 = cslab * CW;
   const int nrows = min(ROWS, L - l0);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef SRGPT_TUNING_KNOBS
-  int stamp_base = (blockIdx.x == 0 && blockIdx.y == 0) ? 0 : -1;
-#endif
-  RP_STAMP(0);
   // ---- requests in the order their consumers run: mask sums, the slab's resampled values, then every feature row of the wave.
   // Loads return in order, so the prologue waits only for the two small sets while the features stream in behind them.
   const int wm = tid >> 4, wr = tid & 15, wmc = min(wm, M - 1);  // weights: 16 threads per mask, positions wr + 16 j
@@ -334,7 +305,6 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
       const int r = min(l0 + (wave * CH + ch) * 32 + 8 * i + lrow, L - 1);
       f[ch][i] = *reinterpret_cast<const u32x4*>(feat + (size_t)r * C + cch);
     }
-  RP_STAMP(1);
   // ---- mask.sum() + 1e-8 in the feature dtype: the psum slabs in slab order (every thread of the mask's group, no exchange) ----
   float sden = 0.f;
 #pragma unroll
@@ -348,7 +318,6 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
       if (i0 + q < n_psum) sden += ps[q];
   }
   const float den = rnd<bf16_t>(rnd<bf16_t>(sden) + 1e-8f);
-  RP_STAMP(2);
   // ---- the slab's normalised weights rnd(v / denorm), bf16-exact; masks past M and rows past the slab weigh 0 ----
 #pragma unroll
   for (int j = 0; j < 8 * CH; ++j) {
@@ -356,7 +325,6 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
     wlds[wm * WLD + r] = (bf16_t)((wm < M && r < nrows) ? rnd<bf16_t>(vv[j] / den) : 0.f);
   }
   __syncthreads();
-  RP_STAMP(3);
   // ---- main: per chunk, park row-major, transpose-read the B fragments (ds_read_b64_tr_b16: a 16-lane group reads a
   // [4 positions][16 channels] block and every lane receives one channel's 4 positions), four MFMAs ----
   f32x4 acc[4];
@@ -380,14 +348,12 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
     }
     __builtin_amdgcn_wave_barrier();
   }
-  RP_STAMP(4);
   // ---- the four waves' partial sums, fixed wave order ----
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int q = 0; q < 4; ++q) red[wave][4 * g4 + q][16 * t + n16] = acc[t][q];
   __syncthreads();
-  RP_STAMP(5);
   const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(partial, 0, (int)((size_t)nslab * M * C * sizeof(float)), 0x00020000);
   {
     const int m = tid >> 4, c = 4 * (tid & 15);
@@ -398,22 +364,15 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
       __builtin_amdgcn_raw_buffer_store_b128(t, prs, (int)((((size_t)slab * M + m) * C + c0 + c) * sizeof(float)), 0, 16);
     }
   }
-  RP_STAMP(6);
   // ---- arrival ticket of the channel slab; the last arriver sums the row slabs in slab order and stores ----
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  RP_STAMP(7);
   if (tid == 0) {
     const int t = __hip_atomic_fetch_add(tickets + cslab, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     last = (t == nslab - 1) ? 1 : 0;
   }
   __syncthreads();
-  RP_STAMP(8);
   if (!last) return;
-#ifdef SRGPT_TUNING_KNOBS
-  if (cslab == 0) stamp_base = 16;
-#endif
-  RP_STAMP(0);
   {
     const int m = tid >> 4, c = 4 * (tid & 15);
     if (m < M && c0 + c < C) {
@@ -435,7 +394,6 @@ __global__ __launch_bounds__(256, 2) void region_pool_mfma_kernel(const bf16_t* 
       for (int e = 0; e < 4; ++e) out[(size_t)m * C + c0 + c + e] = (bf16_t)t[e];
     }
   }
-  RP_STAMP(1);
   if (tid == 0) __hip_atomic_store(tickets + cslab, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -549,12 +507,6 @@ static RegionWs region_ws(int M, int fw, int C) {
   return r;
 }
 
-#ifdef SRGPT_TUNING_KNOBS
-extern "C" int srgpt_region_debug_stamps(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(srgpt_region_stamps), sizeof(unsigned long long) * (n < 32 ? n : 32));
-}
-#endif
-
 extern "C" int64_t srgpt_region_pool_ws_floats(int M, int fw, int C) {
   if (M <= 0 || fw <= 0 || C <= 0) return -1;
   return (int64_t)region_ws(M, fw, C).total;
@@ -590,22 +542,13 @@ static int region_pool_impl(const void* feat, const void* masks, void* out, floa
     if (raw) RW(bf16_t, unsigned char, true);
     else if (mask_dtype == SRGPT_BF16) RW(bf16_t, bf16_t, false);
     else RW(bf16_t, float, false);
-    int ch = region_mfma_chunks((size_t)L);
-#ifdef SRGPT_TUNING_KNOBS  // A/B (scripts/experiments/ab_region_pool.sh): 0 = the VALU kernel on bf16 features, 1 / 2 / 4 = that many chunks per wave
-    const int mode = SRGPT_KNOB("SRGPT_REGION_MFMA", 3);
-    if ((mode == 1 || mode == 2 || mode == 4) && cdiv(L, 128 * mode) <= lay.nslab_cap) ch = mode;  // if the partials fit
-    if (mode == 0) {
-      if (M <= 8) RP(bf16_t, 8); else RP(bf16_t, 16);
-    } else
-#endif
-    {
-      const dim3 mgrid(ncslab, cdiv(L, 4 * ch * 32));
+    const int ch = region_mfma_chunks((size_t)L);
+    const dim3 mgrid(ncslab, cdiv(L, 4 * ch * 32));
 #define RPM(CHV)                                                                                                              \
   hipLaunchKernelGGL((region_pool_mfma_kernel<CHV>), mgrid, dim3(256), 0, s, (const bf16_t*)feat, v, psum, lay.n_psum, partial, \
                      tickets, (bf16_t*)out, M, L, C)
-      if (ch == 4) RPM(4); else if (ch == 2) RPM(2); else RPM(1);
+    if (ch == 4) RPM(4); else if (ch == 2) RPM(2); else RPM(1);
 #undef RPM
-    }
   } else {
     if (raw) RW(float, unsigned char, true);
     else if (mask_dtype == SRGPT_BF16) RW(float, bf16_t, false);

@@ -18,7 +18,7 @@
 // (6144 q/k/v columns = 24 per CU, 14336 gate/up pairs = 56 -- whole 16-column units left a quarter of the CUs with half the
 // work).  A tile is one sub-unit (SwiGLU: the 16 gate rows + the 16 matching up rows = 2 sub-units); up to 4 sub-units per
 // pass keep their 16x16 fp32 accumulators in registers (2 x 4 VGPRs each).  The waves of a block split K into one contiguous
-// range of 256-wide slices each (round 3; interleaved slices before: see SRGPT_SKINNY_CONTIG below), so every block uses all its
+// range of 256-wide slices each (round 3; interleaved slices before: see sl_of below), so every block uses all its
 // waves even when it owns a single tile (o_proj / down_proj); their partial sums are added in a fixed order through LDS at the end
 // of the pass (deterministic).
 //
@@ -37,48 +37,15 @@ int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const
 
 namespace {
 
-#ifdef SRGPT_TUNING_KNOBS
-// phase stamps of block 0 / wave 0 of the last skinny launch (tuning build only; scripts/ubench_skinny_stamps.py)
-__device__ unsigned long long srgpt_skinny_stamps[16];
-#define SK_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) srgpt_skinny_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define SK_STAMP(i) do { } while (0)
-#endif
-
-// Compile-time variants (-DSRGPT_SKINNY_*) and the timing probes below exist for the tuning build only: a product build that
-// defines one of them is refused (one stray flag must not ship a different -- or wrong -- product).
-#ifndef SRGPT_TUNING_KNOBS
-#if defined(SRGPT_SKINNY_DEPTH) || defined(SRGPT_SKINNY_DEPTH_W8) || defined(SRGPT_SKINNY_XREUSE) || defined(SRGPT_SKINNY_PRE) || \
-    defined(SRGPT_SKINNY_PRE_W8) || defined(SRGPT_SKINNY_FS) || defined(SRGPT_SKINNY_PROBE) || defined(SRGPT_SKINNY_CONTIG) || \
-    defined(SRGPT_SKINNY_PK_WPS) || defined(SRGPT_SKINNY_ONE_ACC) || defined(SRGPT_SKINNY_FIX_NSU)
-#error "skinny.hip: -DSRGPT_SKINNY_* variants need the tuning build (make TUNING=1)"
-#endif
-#endif
-
 constexpr int WROWB = 512 + 32;        // bytes per staged weight row: 136 dwords = 8 mod 64 banks -> the lane groups of ds_read_b128
                                        // (MI355X guide, LDS table) hit distinct banks; 528 measured 30 % conflict cycles
 constexpr int WSTAGEB = 16 * WROWB;    // weight stage per wave
 constexpr int MAXSU = 4;               // sub-units (16-row weight tiles) accumulated per pass (8 for one 8-wave SwiGLU block per CU that
                                        // walks K once: measured equal, profiles/r06_skinny_gateup_8wave.txt)
 
-#ifndef SRGPT_SKINNY_DEPTH
-#define SRGPT_SKINNY_DEPTH 2           // register ring depth of weight stages (tuning builds override)
-#endif
-#ifndef SRGPT_SKINNY_DEPTH_W8
-#define SRGPT_SKINNY_DEPTH_W8 2        // the same for fp8 weights (a stage is half the registers and half the bytes in flight)
-#endif
-#ifndef SRGPT_SKINNY_XREUSE
-#define SRGPT_SKINNY_XREUSE 1          // activation fragments of a slice kept in registers across its sub-units
-#endif
-#ifndef SRGPT_SKINNY_PRE
-#define SRGPT_SKINNY_PRE 1            // first weight stage of a block requested before its RMSNorm statistics are reduced
-#endif
-#ifndef SRGPT_SKINNY_PRE_W8
-#define SRGPT_SKINNY_PRE_W8 0         // the same with fp8 weights (measured slower in round 2; re-measured in round 3, see profiles/)
-#endif
-#ifndef SRGPT_SKINNY_FS
-#define SRGPT_SKINNY_FS 4              // MFMA k steps per fragment batch (8 LDS reads in flight per batch)
-#endif
+constexpr int DEPTH = 2;               // register ring depth of weight stages, bf16 and fp8 weights alike (an fp8 stage is half the
+                                       // registers and half the bytes in flight; 3 / 4: profiles/r06_skinny_inflight.txt)
+constexpr int FS_MAX = 4;              // MFMA k steps per fragment batch (8 LDS reads in flight per batch)
 
 // NI = x rows staged per wave / 2: 2 (batch <= 4), 4 (batch <= 8) or 8 (batch <= 16).  NW = waves per block (the K split): two 4-wave
 // blocks per CU, or one 8-wave block per CU (the launcher's rule, below).
@@ -105,10 +72,7 @@ constexpr int MAXSU = 4;               // sub-units (16-row weight tiles) accumu
 // slices.  4-row granules keep every column split of the row-major kernel (24 q/k/v columns or 28 gate / up pairs per block);
 // 16-row granules (1 KiB contiguous per instruction) stream the single-tile products faster (profiles/r06_skinny_packed.txt).
 template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK>
-#ifndef SRGPT_SKINNY_PK_WPS
-#define SRGPT_SKINNY_PK_WPS 2  // waves per SIMD the packed fp8 4-wave kernel is compiled for (tuning builds: 3 / 4 = 3 / 4 blocks per CU)
-#endif
-__global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS : 2) : 1) void skinny_kernel(const bf16_t* __restrict__ x, const void* __restrict__ Wv,
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const bf16_t* __restrict__ x, const void* __restrict__ Wv,
                                                                           const float* __restrict__ wscale,
                                                                           const bf16_t* __restrict__ norm_w, float norm_eps,
                                                                           const bf16_t* __restrict__ residual, void* __restrict__ out,
@@ -152,7 +116,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
   // j has been staged.  Vector loads return IN ORDER: with one slot, waiting for the next slice's activations also waits for every
   // weight stage requested before them -- a product whose slices are ONE weight stage (o_proj / down_proj: a single 16-column tile)
   // then never has more than one stage in flight whatever the weight ring's depth (round 6; run_pass picks XS per sub-unit count).
-  constexpr int DEPTH = W8 ? SRGPT_SKINNY_DEPTH_W8 : SRGPT_SKINNY_DEPTH;
   constexpr int XSMAX = DEPTH;
   u32x4 xr[XSMAX][XL];
   u32x4 gr[XSMAX];
@@ -268,10 +231,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
   // 8 fp8 -> 8 bf16 (every e4m3 value is exactly representable in bf16)
   auto widen = [&](const u32x2& r) -> u32x4 {
     u32x4 o;
-#if defined(SRGPT_SKINNY_PROBE) && SRGPT_SKINNY_PROBE == 1  // timing probe (WRONG results): what would the K loop cost without the fp8 -> bf16 conversions?
-    o[0] = r[0]; o[1] = r[1]; o[2] = r[0] ^ 0x3c003c00u; o[3] = r[1] ^ 0x3c003c00u;
-    return o;
-#endif
 #pragma unroll
     for (int h = 0; h < 2; ++h) {  // v_cvt_scalef32_pk_bf16_fp8 (gfx950): two fp8 -> packed bf16x2 in one instruction, scale 1
       o[2 * h] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r[h], 1.0f, false));
@@ -294,25 +253,17 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
   // A wave's K slices are ONE contiguous range of the rows (round 3): interleaved over the waves (wave, wave + NW, ...: the first
   // version) every 512-byte piece of a weight row was fetched by a different wave at a different time -- the same DRAM pages
   // opened again and again; contiguous ranges stream 5 - 6 % faster at 4 / 8 bf16 rows, 2.5 % at 8 fp8 rows
-  // (profiles/r03_skinny_contig.txt).  -DSRGPT_SKINNY_CONTIG=0 restores the interleaved split (tuning builds).
-#ifndef SRGPT_SKINNY_CONTIG
-#define SRGPT_SKINNY_CONTIG 1
-#endif
-#if SRGPT_SKINNY_CONTIG
+  // (profiles/r03_skinny_contig.txt).
   const int per_wave = (nsl + NW - 1) / NW, first_sl = wave * per_wave;
   const int cnt = max(0, min(per_wave, nsl - first_sl));  // slices of this wave: [first_sl, first_sl + cnt)
   auto sl_of = [&](int i) { return first_sl + i; };
-#else
-  const int cnt = wave < nsl ? (nsl - wave + NW - 1) / NW : 0;  // slices of this wave: wave, wave + NW, ...
-  auto sl_of = [&](int i) { return wave + NW * i; };
-#endif
-  SK_STAMP(0);
   load_x(std::integral_constant<int, 0>{}, sl_of(0));
   bool x0_ready = true;  // slot 0 holds (a request for) the first slice of the pass about to start
 
-  // measured per decode step (profiles/r02_skinny_ab.txt, section 6): 5-8 rows bf16 -1.8 %, 3-4 rows bf16 +-0, fp8 +0.8..1 % -> bf16 only;
+  // PRE: the block's first weight stage is requested before its RMSNorm statistics are reduced.  Measured per decode step
+  // (profiles/r02_skinny_ab.txt, section 6): 5-8 rows bf16 -1.8 %, 3-4 rows bf16 +-0, fp8 +0.8..1 % -> bf16 only;
   // 16 staged rows: the registers are not there
-  constexpr bool PRE = (W8 ? SRGPT_SKINNY_PRE_W8 != 0 : SRGPT_SKINNY_PRE != 0) && NI == 4;
+  constexpr bool PRE = !W8 && NI == 4;
 
   // ---- RMSNorm statistics of every batch row (LlamaRMSNorm: fp32 mean of squares over K) ----
   // `between` runs once, after the statistics' first batch of loads has been issued and before it is reduced
@@ -397,11 +348,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
   auto run_pass = [&](auto nsu_c, int pass, int nu) {
     constexpr int NSU = decltype(nsu_c)::value;
     constexpr int NS = SK / 32;           // MFMA k steps per stage
-    constexpr int FS = NI == 8 ? 2 : SRGPT_SKINNY_FS;  // k steps whose fragments are read together (16 staged rows: fewer, registers)
-#ifndef SRGPT_SKINNY_ONE_ACC
-#define SRGPT_SKINNY_ONE_ACC 0
-#endif
-    constexpr bool TWO_ACC = NI < 8 && !SRGPT_SKINNY_ONE_ACC;  // even / odd k steps on separate accumulators (16 staged rows: the registers are not there)
+    constexpr int FS = NI == 8 ? 2 : FS_MAX;  // k steps whose fragments are read together (16 staged rows: fewer, registers)
+    constexpr bool TWO_ACC = NI < 8;  // even / odd k steps on separate accumulators (16 staged rows: the registers are not there)
     // slots of the activation ring (see load_x): as many slices ahead as the weight ring reaches
     // (fp8 only: with bf16 weights a stage is twice the registers and the 8-row single-tile kernel spills under a second slot --
     //  o / down 9.2 / 22.6 -> 9.9 / 24.4 us at 8 bf16 rows, profiles/r06_skinny_norm_staging.txt)
@@ -460,11 +408,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
     __builtin_amdgcn_sched_barrier(0);
     load_epilogue_operands();
     __builtin_amdgcn_sched_barrier(0);
-    if (pass == 0) SK_STAMP(1);
     // one slice (h-th of the trip that starts at slice index i): NSU stages
     // activation fragments of a slice held across its sub-units where the registers are there (fp8 weights: the stage ring is
     // half as wide; bf16 weights: the 4-row variant only)
-    constexpr bool XREUSE = SRGPT_SKINNY_XREUSE != 0 && NSU >= 2 && (W8 ? NI <= 4 : NI == 2);
+    constexpr bool XREUSE = NSU >= 2 && (W8 ? NI <= 4 : NI == 2);
     auto slice = [&](int i, auto h_c) {
       constexpr int h = decltype(h_c)::value;
       const int sl = sl_of(i + h);
@@ -480,12 +427,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
               if constexpr (XS == 1) load_x(std::integral_constant<int, 0>{}, i + h + 1 < cnt ? sl_of(i + h + 1) : sl_of(0));  // next slice, or the first one of the next pass
               else load_x(std::integral_constant<int, h % XS>{}, sl_of(min(i + h + XS, cnt - 1)));  // XS slices ahead (past the end: a valid slice, never staged)
             }
-#if !(defined(SRGPT_SKINNY_PROBE) && SRGPT_SKINNY_PROBE == 2)
             if constexpr (!PK) {
 #pragma unroll
               for (int j = 0; j < 8; ++j) *reinterpret_cast<u32x4*>(wst + (2 * j + lrow) * WROWB + lchunk * 16) = staged(wb[cur][j]);
             }
-#endif
             __builtin_amdgcn_wave_barrier();
             // The fragment reads of FS k steps are issued together in front of their MFMAs, which alternate between two
             // accumulators.  Left to the compiler the unrolled loop became read -> wait -> MFMA per k step on ONE accumulator: a
@@ -507,25 +452,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
                 const int s = s0 + t;
                 if constexpr (XREUSE) xf[t] = xall[s];
                 else xf[t] = *reinterpret_cast<const bf16x8*>(xst + xrow * XROWB + (4 * s + (lane >> 4)) * 16);
-#if defined(SRGPT_SKINNY_PROBE) && SRGPT_SKINNY_PROBE == 2  // timing probe (WRONG results): weights never pass through LDS
-                wfr[t] = __builtin_bit_cast(bf16x8, staged(wb[cur][s & 7]));
-#else
                 if constexpr (PK) wfr[t] = pk_frag(wb[cur], s);
                 else wfr[t] = *reinterpret_cast<const bf16x8*>(wst + (lane & 15) * WROWB + (4 * s + (lane >> 4)) * 16);
-#endif
               }
               __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
               for (int t = 0; t < FS; ++t) {
                 const bf16x8 wf = wfr[t];
                 // D[batch row][weight row] += x[batch row][k] * W[weight row][k]
-#if defined(SRGPT_SKINNY_PROBE) && SRGPT_SKINNY_PROBE == 3  // timing probe (WRONG results): no matrix instructions
-                acc[su][0] += (float)xf[t][0] * (float)wf[0];
-                acc[su][1] += (float)xf[t][7] * (float)wf[7];
-#else
                 if (TWO_ACC && (t & 1)) acc2[TWO_ACC ? su : 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[t], wf, acc2[TWO_ACC ? su : 0], 0, 0, 0);
                 else acc[su] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[t], wf, acc[su], 0, 0, 0);
-#endif
               }
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -538,7 +474,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
     int i = 0;
     for (; i + DEPTH <= cnt; i += DEPTH) {
       slice(i, std::integral_constant<int, 0>{});
-      if (pass == 0 && i == 0) SK_STAMP(2);
       if constexpr (DEPTH > 1) slice(i, std::integral_constant<int, 1>{});
       if constexpr (DEPTH > 2) slice(i, std::integral_constant<int, 2>{});
       if constexpr (DEPTH > 3) slice(i, std::integral_constant<int, 3>{});
@@ -550,10 +485,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
       if (i + 2 < cnt) slice(i, std::integral_constant<int, 2>{});
     static_assert(DEPTH >= 2 && DEPTH <= 4, "ring depth");
 
-    if (pass == 0) SK_STAMP(3);
     // ---- cross-wave reduction (fixed order) + epilogue ----
     __syncthreads();
-    if (pass == 0) SK_STAMP(4);
     float* redf = reinterpret_cast<float*>(smem);  // [NW waves][MAXSU][64 lanes][4]
 #pragma unroll
     for (int su = 0; su < NSU; ++su) *reinterpret_cast<f32x4*>(redf + ((wave * MAXSU + su) * 64 + lane) * 4) = TWO_ACC ? acc[su] + acc2[TWO_ACC ? su : 0] : acc[su];
@@ -589,7 +522,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
         }
       }
     }
-    if (pass == 0) SK_STAMP(5);
     __syncthreads();  // the reduction buffer aliases the wave-private stages of the next pass
   };
 
@@ -602,10 +534,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (PK && W8 ? SRGPT_SKINNY_PK_WPS 
 #pragma unroll
     for (int u = 0; u < MAXU; ++u) nu += (pass * MAXU + u < ntile) ? 1 : 0;
     if (nu == 0) break;  // uniform per block; later passes are empty too
-#ifdef SRGPT_SKINNY_FIX_NSU  // register / occupancy probe (tuning builds): ONE sub-unit count compiled in -- only shapes with that count compute correctly
-    run_pass(std::integral_constant<int, SRGPT_SKINNY_FIX_NSU>{}, pass, nu);
-    continue;
-#endif
     switch (nu * R) {
       case 1: run_pass(std::integral_constant<int, 1>{}, pass, nu); break;
       case 2: run_pass(std::integral_constant<int, 2>{}, pass, nu); break;
@@ -663,13 +591,9 @@ int launch_skinny_nw(const void* x, const void* W, const float* wscale, const vo
   // would own few columns AND has the RMSNorm statistics to compute first (q/k/v: 24 columns per CU, 14.1 vs 14.3 us bf16,
   // 12.3 vs 13.7 fp8) -- there the prologue is shared by twice the threads.
   const int cus = srgpt_device_cus();
-  int waves = SRGPT_KNOB("SRGPT_SKINNY_WAVES", 0);
-  if (waves != 4 && waves != 8) {
-    const int ncol = (N + cus - 1) / cus;  // output columns per CU
-    waves = (norm_w != nullptr && ncol <= 32) ? 8 : 4;
-    if (norm_w == nullptr && ncol <= SRGPT_KNOB("SRGPT_SKINNY_W8_RES_COLS", 0)) waves = 8;
-  }
-  const int blocks = waves == 8 ? cus : SRGPT_KNOB("SRGPT_SKINNY_BPC", 2) * cus;
+  const int ncol = (N + cus - 1) / cus;  // output columns per CU
+  const int waves = (norm_w != nullptr && ncol <= 32) ? 8 : 4;
+  const int blocks = waves == 8 ? cus : 2 * cus;
   int cw = (N + blocks - 1) / blocks;
   if (cw < 16) cw = 16;
   const int gr_shift = packed == 16 ? 4 : packed == 8 ? 3 : 2;
@@ -677,25 +601,25 @@ int launch_skinny_nw(const void* x, const void* W, const float* wscale, const vo
   const int grid = (N + cw - 1) / cw;
   SRGPT_CHECK(!ss_out || grid <= SRGPT_ROWSS_STRIDE, SRGPT_ERR_UNSUPPORTED, "skinny: %d blocks do not fit the %d row-statistics slots",
               grid, SRGPT_ROWSS_STRIDE);
-#define SRGPT_SKINNY_GO(NWV, PUBV, PKV) \
+#define SKINNY_GO(NWV, PUBV, PKV) \
   return launch_skinny<SWIGLU, NI, NWV, W8, PUBV, PKV>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, grid, cw, ss_in, ss_out, gr_shift, s)
   if (packed) {
     SRGPT_CHECK(K % (W8 ? 64 : 32) == 0 && (!SWIGLU || N % packed == 0), SRGPT_ERR_UNSUPPORTED,
                 "skinny: the packed weight layout needs K %% %d == 0 (K = %d)%s", W8 ? 64 : 32, K, SWIGLU ? " and whole granules per half" : "");
     if (ss_in != nullptr) {
-      if (waves == 8) SRGPT_SKINNY_GO(8, true, true);
-      SRGPT_SKINNY_GO(4, true, true);
+      if (waves == 8) SKINNY_GO(8, true, true);
+      SKINNY_GO(4, true, true);
     }
-    if (waves == 8) SRGPT_SKINNY_GO(8, false, true);
-    SRGPT_SKINNY_GO(4, false, true);
+    if (waves == 8) SKINNY_GO(8, false, true);
+    SKINNY_GO(4, false, true);
   }
   if (ss_in != nullptr) {
-    if (waves == 8) SRGPT_SKINNY_GO(8, true, false);
-    SRGPT_SKINNY_GO(4, true, false);
+    if (waves == 8) SKINNY_GO(8, true, false);
+    SKINNY_GO(4, true, false);
   }
-  if (waves == 8) SRGPT_SKINNY_GO(8, false, false);
-  SRGPT_SKINNY_GO(4, false, false);
-#undef SRGPT_SKINNY_GO
+  if (waves == 8) SKINNY_GO(8, false, false);
+  SKINNY_GO(4, false, false);
+#undef SKINNY_GO
 }
 
 template <bool W8>
@@ -703,10 +627,6 @@ int skinny_dispatch(const void* x, const void* W, const float* wscale, const voi
                     void* out, int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
                     hipStream_t s) {
   // packed: 0 = row-major W [N][K]; 4 / 16 = the packed decode layout with granules of that many rows (srgpt_pack_decode_weights)
-  if (SRGPT_KNOB("SRGPT_SKINNY_PACKED_TIMING", 0)) {  // tuning build: fetch-pattern timing on row-major data (WRONG results)
-    const int ncol = (N + srgpt_device_cus() - 1) / srgpt_device_cus();
-    packed = ncol <= 16 ? SRGPT_KNOB("SRGPT_SKINNY_PACKED_T1", 16) : SRGPT_KNOB("SRGPT_SKINNY_PACKED_TN", 4);
-  }
   SRGPT_CHECK(packed == 0 || packed == 4 || packed == 8 || packed == 16, SRGPT_ERR_ARG, "skinny: packed layout granule %d (0, 4, 8 or 16)", packed);
   SRGPT_CHECK(batch >= 1 && batch <= 16, SRGPT_ERR_ARG, "skinny: batch %d outside 1..16", batch);
   SRGPT_CHECK(K % 8 == 0 && K >= 8, SRGPT_ERR_ARG, "skinny: K=%d must be a multiple of 8", K);
@@ -723,12 +643,6 @@ int skinny_dispatch(const void* x, const void* W, const float* wscale, const voi
 }
 
 }  // namespace
-
-#ifdef SRGPT_TUNING_KNOBS
-extern "C" int srgpt_skinny_debug_stamps(unsigned long long* host, int n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(srgpt_skinny_stamps), sizeof(unsigned long long) * (n < 16 ? n : 16));
-}
-#endif
 
 // host entry used by srgpt_gemv (gemv.hip) for batches of up to 16 rows, bf16 weights
 int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
@@ -753,7 +667,7 @@ int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, c
 }
 
 // rows at or below this count take the one-row VALU kernel of gemv_w8.hip (which neither reads nor publishes row statistics)
-int srgpt_w8_valu_max_batch() { return SRGPT_KNOB("SRGPT_W8_VALU_MAX_BATCH", 1); }  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
+int srgpt_w8_valu_max_batch() { return 1; }  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
 
 // Decode-path product with fp8 (OCP e4m3fn) weights and one fp32 scale per weight row, bf16 activations (W8A16):
 // out[b, n] = bf16( (sum_k x[b, k] * fp8(W8[n, k])) * wscale[n] ), same fusions as srgpt_gemv.  Any batch size
@@ -766,8 +680,7 @@ extern "C" int srgpt_gemv_w8(const void* x, const void* W8, const float* wscale,
   SRGPT_CHECK(K % 8 == 0, SRGPT_ERR_ARG, "srgpt_gemv_w8: K=%d must be a multiple of 8", K);
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_w8: swiglu excludes residual/out_f32");
   hipStream_t s = as_stream(stream);
-  const int valu_max = srgpt_w8_valu_max_batch();
-  if (batch <= valu_max && batch <= 2 && K % 16 == 0)  // one row: VALU kernel (gemv_w8.hip), like the bf16 path
+  if (batch <= srgpt_w8_valu_max_batch() && K % 16 == 0)  // one row: VALU kernel (gemv_w8.hip), like the bf16 path
     return srgpt_gemv_w8_valu(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, s);
   return srgpt_skinny_w8_launch(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, nullptr, nullptr, 0, s);
 }

@@ -29,8 +29,8 @@ def test_header_symbols_are_exported():
 
 def test_product_library_exports_nothing_but_the_header():
     """The product library carries no experiment residue: every exported `srgpt_*` C symbol is declared in include/srgpt.h (cross-file
-    helpers have hidden visibility), and nothing of the tuning build (debug stamps, environment knobs, the VALU pooling kernel's
-    bf16 instances) is in it."""
+    helpers have hidden visibility), and no experiment residue (debug stamps, environment knobs, the VALU pooling kernel's bf16
+    instances) is in it."""
     import subprocess
 
     from spatialrgpt_amd import _lib
@@ -42,6 +42,20 @@ def test_product_library_exports_nothing_but_the_header():
     for residue in (b"debug_stamps", b"SRGPT_GEMM_", b"SRGPT_REGION_", b"SRGPT_DECODE_", b"SRGPT_SKINNY_", b"SRGPT_GEMV_",
                     b"region_pool_kernelIDF16b"):
         assert residue not in blob, residue
+
+
+def test_kernel_sources_have_one_build():
+    """One compiled path per kernel: no source under spatialrgpt_amd/csrc reads the environment or carries the knob macros of the
+    removed tuning build, and the Makefile has no TUNING branch."""
+    csrc = os.path.join(ROOT, "spatialrgpt_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f == "Makefile" or f.endswith((".hip", ".h")))  # (not the build products)
+    assert "Makefile" in files and "common.h" in files and len(files) > 10
+    for name in files:
+        src = open(os.path.join(csrc, name)).read()
+        for word in ("SRGPT_KNOB", "SRGPT_TUNING_KNOBS", "getenv"):
+            assert word not in src, (name, word)
+    makefile = open(os.path.join(csrc, "Makefile")).read()
+    assert "TUNING" not in makefile and "tuning" not in makefile
 
 
 def test_struct_layouts_match_header():

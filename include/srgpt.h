@@ -173,7 +173,7 @@ int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* 
  * per instruction and wants lane (c = lane & 15, g = lane >> 4) to hold row c, k = 32 s + 8 g .. + 8 of the step.  A row-major
  * matrix delivers that through an LDS transpose per 8-KiB stage; the packed array stores the SAME bytes in operand order, so one
  * coalesced 16-byte load per lane is the fragment (fp8 weights, 8 rows per GPU: the four layer products 56 -> 52 us,
- * profiles/r06_skinny_packed.txt).  Layout, `rows` = 4, 8 or 16 rows per granule, e = bytes per element (1: fp8, 2: bf16),
+ * profiles/r06_skinny_packed_gr.txt).  Layout, `rows` = 4, 8 or 16 rows per granule, e = bytes per element (1: fp8, 2: bf16),
  * kb = 16 / e ... a k block is 64 k (fp8) or 32 k (bf16):
  *   out[ ((n / rows) * (K / kblock) + k / kblock) * rows * 64  +  ((k % 32) / 8 * rows + n % rows) * 16  +  byte ]
  *   byte = (k % 8) * 2 (bf16)   |   ((k % 64) / 32) * 8 + k % 8 (fp8: the lane's 8 k of two consecutive MFMA steps)

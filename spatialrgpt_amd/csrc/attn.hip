@@ -9,7 +9,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "flash.h"
+#include "internal.h"
 
 namespace {
 
@@ -713,8 +713,7 @@ extern "C" int64_t srgpt_decode_attn_ws_floats(int B, int Hq, int D) {
 // next_w = NULL -> no prefetch.  batch > 1 goes through the skinny kernel: no prefetch there (measured, common.h).
 int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
                               const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D, int max_pos, int dtype,
-                              const void* next_w, int next_n, int next_k, int next_fp8, int /*next_packed_rows: unused*/,
-                              srgpt_stream_t stream) {
+                              const void* next_w, int next_n, int next_k, int next_fp8, srgpt_stream_t stream) {
   SRGPT_CHECK(qkv && kcache && vcache && pos && cos_tab && sin_tab && out && ws, SRGPT_ERR_ARG,
               "srgpt_decode_attention: null pointer");
   SRGPT_CHECK(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, SRGPT_ERR_ARG, "srgpt_decode_attention: bad heads");
@@ -743,7 +742,7 @@ extern "C" int srgpt_decode_attention(const void* qkv, void* kcache, void* vcach
                                       const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D,
                                       int max_pos, int dtype, srgpt_stream_t stream) {
   return srgpt_decode_attention_pf(qkv, kcache, vcache, pos, cos_tab, sin_tab, out, ws, B, Hq, Hkv, D, max_pos, dtype, nullptr, 0,
-                                   0, 0, 0, stream);
+                                   0, 0, stream);
 }
 
 extern "C" int srgpt_attention(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq,

@@ -21,7 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "flash.h"
+#include "internal.h"
 
 namespace {
 

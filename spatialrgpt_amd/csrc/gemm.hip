@@ -11,9 +11,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
-
-int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const Epilogue& e, hipStream_t s);  // gemm256.hip
-int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Epilogue& e, hipStream_t s);  // gemm288.hip
+#include "internal.h"
 
 namespace {
 

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "internal.h"
 
 namespace {
 

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "internal.h"
 
 namespace {
 

@@ -18,8 +18,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
-
-int srgpt_splitk_reduce_bf16(const Epilogue& e, hipStream_t s);  // gemm.hip
+#include "internal.h"
 
 namespace {
 

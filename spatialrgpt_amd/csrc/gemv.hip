@@ -18,14 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
-
-int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
-                        int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
-                        hipStream_t s);  // skinny.hip
-int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
-                           const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
-                           const float* ss_in, float* ss_out, int packed, hipStream_t s);  // skinny.hip
-int srgpt_w8_valu_max_batch();  // skinny.hip
+#include "internal.h"
 
 namespace {
 
@@ -520,7 +513,7 @@ extern "C" int srgpt_gemv(const void* x, const void* W, const void* norm_w, floa
 extern "C" int srgpt_gemv_rowss_supported(int batch, int dtype, int fp8) {
   if (dtype != SRGPT_BF16 || batch < 2) return 0;
   if (2 * srgpt_device_cus() > SRGPT_ROWSS_STRIDE) return 0;  // one slot per producer block (two 4-wave blocks per CU)
-  return fp8 ? (batch > srgpt_w8_valu_max_batch() ? 1 : 0) : (batch >= SKINNY_MIN_BATCH ? 1 : 0);
+  return fp8 ? (batch > W8_VALU_MAX_BATCH ? 1 : 0) : (batch >= SKINNY_MIN_BATCH ? 1 : 0);
 }
 
 extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,

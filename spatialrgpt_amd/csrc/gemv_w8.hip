@@ -10,10 +10,11 @@
 //   * weights are widened with v_cvt_pk_f32_fp8 (OCP e4m3fn on gfx950), 2 values per instruction; the two rows of a unit
 //     share the fp32 copies of x;
 //   * the per-row scale multiplies the reduced dot product.
-// 2+ rows go through the MFMA skinny kernel (skinny.hip, W8 variant: srgpt_w8_valu_max_batch).
+// 2+ rows go through the MFMA skinny kernel (skinny.hip, W8 variant: W8_VALU_MAX_BATCH in internal.h).
 #include <stdlib.h>
 
 #include "common.h"
+#include "internal.h"
 
 namespace {
 

@@ -1,0 +1,55 @@
+// Every function that crosses translation units inside the library and is NOT part of the C ABI (include/srgpt.h) is declared
+// here, once: the file that defines it and every file that calls it include this header, so the compiler checks the definition
+// against the declaration.  These are C++ functions: exports.map keeps their (mangled) names out of the dynamic symbol table,
+// which holds what include/srgpt.h declares and nothing else (tests/test_capi_symbols.py).  (srgpt_set_error is in common.h,
+// beside the macros that call it.)
+#pragma once
+#include "common.h"
+
+struct SrgptGemmEpilogue;  // gemm_epilogue.h
+
+// ---- gemm256.hip / gemm288.hip: the 256 x 256 and the whole-M (up to 272 rows) bf16 MFMA tiles, dispatched by gemm.hip ----
+int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
+int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
+
+// ---- gemm.hip: the split-K slab reduction + epilogue for kernels in other files (gemm_f8.hip) ----
+int srgpt_splitk_reduce_bf16(const SrgptGemmEpilogue& e, hipStream_t s);
+
+// ---- skinny.hip: the MFMA decode products of 2+ rows, entered from srgpt_gemv / srgpt_gemv_rowss (gemv.hip) ----
+int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
+                        int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
+                        hipStream_t s);
+int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
+                           const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
+                           const float* ss_in, float* ss_out, int packed, hipStream_t s);
+// fp8 rows at or below this count take the one-row VALU kernel of gemv_w8.hip (which neither reads nor publishes row statistics)
+constexpr int W8_VALU_MAX_BATCH = 1;  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
+
+// ---- gemv_w8.hip: the one-row VALU kernel, entered from srgpt_gemv_w8 (skinny.hip) ----
+int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const void* norm_w, float eps,
+                       const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, hipStream_t s);
+
+// ---- attn.hip: the decode attention with the L2 prefetch of the next GEMV's weights, and its arrival tickets, for model.hip ----
+int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
+                              const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D, int max_pos, int dtype,
+                              const void* next_w, int next_n, int next_k, int next_fp8, srgpt_stream_t stream);
+void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* bytes);
+
+// ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping ----
+int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
+                        hipStream_t s);
+int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
+                             int V, hipStream_t s);
+int srgpt_sample_slices();  // slices per row of both samplers (the argmax merge of model.hip reads as many)
+
+// ---- flash.hip: the MFMA flash attention kernel's arguments and launcher, for srgpt_attention (attn.hip) ----
+struct AttnArgs {
+  const bf16_t *q, *k, *v;
+  bf16_t* o;
+  int Tq, Tk, Hq, Hkv, D;
+  int64_t q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs;
+  float scale;
+  const int* kv_len;
+};
+int64_t srgpt_flash_slice_span_limit();  // byte offsets inside a (batch, head) K / V slice are 32-bit in the kernel
+void srgpt_flash_bf16_launch(const AttnArgs& a, int B, bool causal, hipStream_t s);

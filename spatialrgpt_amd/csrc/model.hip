@@ -4,16 +4,8 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
-int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
-                              const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D, int max_pos, int dtype,
-                              const void* next_w, int next_n, int next_k, int next_fp8, int next_packed_rows, srgpt_stream_t stream);  // attn.hip
-void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* bytes);  // attn.hip
-int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
-                        hipStream_t s);  // sample.hip
-extern "C" __attribute__((visibility("hidden"))) int srgpt_sample_slices(void);  // sample.hip (internal: not part of the C ABI)
-int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
-                             int V, hipStream_t s);  // sample.hip
 namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -387,18 +379,172 @@ __global__ void gather_last_rows_kernel(const T* __restrict__ x, const int* __re
   if (threadIdx.x == 0) pos[b] = len;
 }
 
+namespace {
+
+// ---- weight formats ----
+// FMT_DTYPE: the dtype matrices (srgpt_gemm / srgpt_gemv).  fp8 copies present -> they are the weights and the dtype matrices are
+// not touched: FMT_W8A16 (srgpt_gemm_w8 / srgpt_gemv_w8; the decode step streams half the bytes per token), or with fp8_act
+// FMT_W8A8: the prefill's per-token e4m3 activations on the fp8 matrix pipe (include/srgpt.h).  The decode step and the
+// all-position lm_head (fp32 logits, parity hook) are W8A16 under both fp8 formats.
+enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8 };
+
+// the format of `w` and the check that fp8 weights are complete, on the host before any launch; `fn`: the entry point the message names
+int llm_format(const srgpt_llm_weights* w, const char* fn, LlmFormat* fmt) {
+  *fmt = FMT_DTYPE;
+  if (!w->wqkv8) return SRGPT_OK;
+  SRGPT_CHECK(w->dtype == SRGPT_BF16 && w->wo8 && w->wgu8 && w->wdown8 && w->lm_head8 && w->wqkv_scale && w->wo_scale &&
+                  w->wgu_scale && w->wdown_scale && w->lm_head_scale,
+              SRGPT_ERR_ARG, "%s: fp8 weights need bf16 activations and all five matrices + scales", fn);
+  *fmt = w->fp8_act != 0 ? FMT_W8A8 : FMT_W8A16;
+  return SRGPT_OK;
+}
+
+// one weight matrix in the forms the products take
+struct Mat {
+  const void* w;       // row-major, engine dtype
+  const void* w8;      // row-major fp8 bytes (NULL under FMT_DTYPE)
+  const float* scale;  // their row scales
+  const void* pk;      // packed copy of the fp8 bytes for the MFMA decode kernel, or NULL: stream the row-major ones
+  int pk_rows;         // its rows per granule
+};
+struct LayerMats {
+  Mat qkv, o, gu, down;
+};
+LayerMats layer_mats(const srgpt_llm_weights* w, LlmFormat fmt, int i) {
+  const bool fp8 = fmt != FMT_DTYPE;
+  auto mat = [&](const void* const* W, const void* const* W8, const float* const* sc, const void* const* pk, int pk_rows) {
+    return Mat{W[i], fp8 ? W8[i] : nullptr, fp8 ? sc[i] : nullptr, fp8 && pk != nullptr ? pk[i] : nullptr, pk_rows};
+  };
+  return LayerMats{mat(w->wqkv, w->wqkv8, w->wqkv_scale, w->wqkv8p, w->pk_rows_qkv), mat(w->wo, w->wo8, w->wo_scale, w->wo8p, w->pk_rows_o),
+                   mat(w->wgu, w->wgu8, w->wgu_scale, w->wgu8p, w->pk_rows_gu),
+                   mat(w->wdown, w->wdown8, w->wdown_scale, w->wdown8p, w->pk_rows_down)};
+}
+
+// ---- prefill ----
+// One prefill's shapes, workspace and stream; the launches its layers are made of; and, per weight format, the launch sequence of
+// layer i in order (layer_*).  Everything the formats share is in prefill_impl.
+struct Prefill {
+  const srgpt_llm_weights* w;
+  const srgpt_llm_state* st;
+  LlmWs l;
+  LlmFormat fmt;
+  int B, T, rows, Hd, I, HqD, QW, dt;
+  srgpt_stream_t stream;
+
+  int64_t gws_bytes() const { return (int64_t)l.gws_bytes; }
+  char* cache(void* base, int i) const {
+    return reinterpret_cast<char*>(base) + (size_t)i * B * w->kv_heads * st->max_pos * w->head_dim * dtype_size(dt);
+  }
+  // l.h = RMSNorm(l.x)
+  int norm(const void* norm_w) const { return srgpt_rmsnorm(l.x, norm_w, l.h, rows, Hd, w->rms_eps, dt, stream); }
+  int rope_append(int i) const {
+    return srgpt_rope_kv_append(l.qkv, cache(st->kcache, i), cache(st->vcache, i), nullptr, w->rope_cos, w->rope_sin, B, T, w->heads,
+                                w->kv_heads, w->head_dim, st->max_pos, dt, stream);
+  }
+  int attention(int i) const {
+    const int Hkv = w->kv_heads, D = w->head_dim;
+    return srgpt_attention(l.qkv, cache(st->kcache, i), cache(st->vcache, i), l.attn, B, T, T, w->heads, Hkv, D, (int64_t)T * QW, QW, D,
+                           (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D, (int64_t)Hkv * st->max_pos * D, D,
+                           (int64_t)st->max_pos * D, 1.0f / sqrtf((float)D), 1, nullptr, dt, stream);
+  }
+  // W8A16 product: out = a @ m^T (+ res)
+  int gemm_w8(const void* a, const Mat& m, const void* res, void* out, int N, int K) const {
+    return srgpt_gemm_w8(a, m.w8, m.scale, nullptr, res, out, rows, N, K, K, N, SRGPT_ACT_NONE, 0, l.gws, gws_bytes(), stream);
+  }
+  // W8A8: the rows of `a` -> e4m3 bytes + per-token scales (l.a8, l.a8s), and the product of the rows quantised last
+  int quant(const void* a, int K) const { return srgpt_quant_rows_e4m3(a, l.a8, l.a8s, rows, K, K, stream); }
+  int gemm_w8a8(const Mat& m, const void* res, void* out, int N, int K) const {
+    return srgpt_gemm_w8a8(l.a8, l.a8s, m.w8, m.scale, nullptr, res, out, rows, N, K, K, N, 0, l.gws, gws_bytes(), stream);
+  }
+
+  // dtype matrices: the RMSNorm that follows o_proj / down_proj rides in the product's split-K reduction (srgpt_gemm_norm:
+  // bit-identical to the two launches, one launch and one pass over the rows less per norm), so only layer 0 normalises l.x itself
+  int layer_dtype(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
+    // projection + RoPE + cache append: the rotation rides in the split-K reduction
+    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, m.qkv.w, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), nullptr,
+                                        w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim, st->max_pos, dt, stream));
+    SRGPT_TRY(attention(i));
+    SRGPT_TRY(srgpt_gemm_norm(l.attn, m.o.w, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
+                              l.h, w->rms_eps, dt, stream));
+    // gate / up + SiLU * up: the activation is the product's epilogue on the whole-M kernel
+    SRGPT_TRY(srgpt_gemm_swiglu(l.h, m.gu.w, l.act, rows, I, Hd, l.gu, l.gws, gws_bytes(), dt, stream));
+    if (i + 1 < w->layers)
+      return srgpt_gemm_norm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->attn_norm[i + 1],
+                             nullptr, l.h, w->rms_eps, dt, stream);
+    return srgpt_gemm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, I, Hd, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, l.gws,
+                      gws_bytes(), dt, stream);
+  }
+
+  int layer_w8a16(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(norm(w->attn_norm[i]));
+    SRGPT_TRY(gemm_w8(l.h, m.qkv, nullptr, l.qkv, QW, Hd));
+    SRGPT_TRY(rope_append(i));
+    SRGPT_TRY(attention(i));
+    SRGPT_TRY(gemm_w8(l.attn, m.o, l.x, l.x, Hd, HqD));
+    SRGPT_TRY(norm(w->mlp_norm[i]));
+    SRGPT_TRY(gemm_w8(l.h, m.gu, nullptr, l.gu, 2 * I, Hd));
+    SRGPT_TRY(srgpt_silu_mul(l.gu, l.act, rows, I, dt, stream));
+    return gemm_w8(l.act, m.down, l.x, l.x, Hd, I);
+  }
+
+  // W8A8, rows of up to 16384 columns: the producer of a GEMM's input rows (RMSNorm, SwiGLU) is fused into their per-token
+  // quantisation -- the bf16 intermediate is neither written nor read (bit-identical to the two launches: tests/test_gpu_fp8_mfma.py)
+  int layer_w8a8(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(srgpt_quant_rows_e4m3_rmsnorm(l.x, w->attn_norm[i], w->rms_eps, l.a8, l.a8s, rows, Hd, Hd, stream));
+    SRGPT_TRY(gemm_w8a8(m.qkv, nullptr, l.qkv, QW, Hd));
+    SRGPT_TRY(rope_append(i));
+    SRGPT_TRY(attention(i));
+    SRGPT_TRY(quant(l.attn, HqD));
+    SRGPT_TRY(gemm_w8a8(m.o, l.x, l.x, Hd, HqD));
+    SRGPT_TRY(srgpt_quant_rows_e4m3_rmsnorm(l.x, w->mlp_norm[i], w->rms_eps, l.a8, l.a8s, rows, Hd, Hd, stream));
+    SRGPT_TRY(gemm_w8a8(m.gu, nullptr, l.gu, 2 * I, Hd));
+    SRGPT_TRY(srgpt_quant_rows_e4m3_swiglu(l.gu, l.a8, l.a8s, rows, I, stream));
+    return gemm_w8a8(m.down, l.x, l.x, Hd, I);
+  }
+
+  // W8A8, wider rows (Llama-3-70B: inter 28672): the W8A16 sequence with every product's input quantised by a launch of its own
+  int layer_w8a8_wide(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(norm(w->attn_norm[i]));
+    SRGPT_TRY(quant(l.h, Hd));
+    SRGPT_TRY(gemm_w8a8(m.qkv, nullptr, l.qkv, QW, Hd));
+    SRGPT_TRY(rope_append(i));
+    SRGPT_TRY(attention(i));
+    SRGPT_TRY(quant(l.attn, HqD));
+    SRGPT_TRY(gemm_w8a8(m.o, l.x, l.x, Hd, HqD));
+    SRGPT_TRY(norm(w->mlp_norm[i]));
+    SRGPT_TRY(quant(l.h, Hd));
+    SRGPT_TRY(gemm_w8a8(m.gu, nullptr, l.gu, 2 * I, Hd));
+    SRGPT_TRY(srgpt_silu_mul(l.gu, l.act, rows, I, dt, stream));
+    SRGPT_TRY(quant(l.act, I));
+    return gemm_w8a8(m.down, l.x, l.x, Hd, I);
+  }
+};
+
+}  // namespace
+
 static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T, const int* lens,
                         float* all_logits, void* hidden_out, srgpt_stream_t stream) {
   SRGPT_TRY(check_llm(w, st));
   SRGPT_CHECK(inputs_embeds && T > 0 && T <= st->max_pos, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds max_pos=%d", T,
               st->max_pos);
-  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
-  const int B = st->batch, rows = B * T, QW = (Hq + 2 * Hkv) * D;
+  SRGPT_CHECK(T <= st->ws_tokens, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds ws_tokens=%d", T, st->ws_tokens);
+  LlmFormat fmt;
+  SRGPT_TRY(llm_format(w, "srgpt_llm_prefill", &fmt));
+  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, D = w->head_dim;
+  const int B = st->batch, rows = B * T;
+  if (fmt == FMT_W8A8)
+    SRGPT_CHECK(Hd % 128 == 0 && I % 128 == 0 && (Hq * D) % 128 == 0 && Hd >= 256 && I >= 256 && Hq * D >= 256,
+                SRGPT_ERR_UNSUPPORTED, "srgpt_llm_prefill: fp8_act needs hidden, inter and heads * head_dim to be multiples of 128");
+  const bool wide = Hd > 16384 || I > 16384;  // the fused quantisation kernels hold rows of up to 16384 columns
   const size_t es = dtype_size(dt);
   hipStream_t s = as_stream(stream);
-  SRGPT_CHECK(T <= st->ws_tokens, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds ws_tokens=%d", T, st->ws_tokens);
-  const LlmWs l = carve_llm(w, B, st->ws_tokens, st->ws);
-  const size_t layer_kv = (size_t)B * Hkv * st->max_pos * D * es;
+  const Prefill p{w, st, carve_llm(w, B, st->ws_tokens, st->ws), fmt, B, T, rows, Hd, I, Hq * D, (Hq + 2 * w->kv_heads) * D, dt, stream};
+  const LlmWs& l = p.l;
   const size_t hid_bytes = (size_t)rows * Hd * es;
   {  // the decode attention's arrival tickets / sync words must be zero before the first step: every prefill re-arms them, so a
      // caller-allocated (never zeroed) workspace or an aborted launch cannot leave the decode steps merging nothing
@@ -414,94 +560,25 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
     return SRGPT_ERR_LAUNCH;
   }
   if (hidden_out) SRGPT_HIP_TRY(hipMemcpyAsync(hidden_out, l.x, hid_bytes, hipMemcpyDeviceToDevice, s), "srgpt_llm_prefill: hidden-state copy");
-  const float scale = 1.0f / sqrtf((float)D);
-  // fp8 copies present -> they are the weights (srgpt_gemm_w8 / srgpt_gemv_w8); the dtype matrices are not touched
-  const bool w8 = w->wqkv8 != nullptr;
-  if (w8)
-    SRGPT_CHECK(dt == SRGPT_BF16 && w->wo8 && w->wgu8 && w->wdown8 && w->lm_head8 && w->wqkv_scale && w->wo_scale &&
-                    w->wgu_scale && w->wdown_scale && w->lm_head_scale,
-                SRGPT_ERR_ARG, "srgpt_llm_prefill: fp8 weights need bf16 activations and all five matrices + scales");
-  const bool a8 = w8 && w->fp8_act != 0;  // W8A8 prefill: per-token e4m3 activations on the fp8 matrix pipe (include/srgpt.h)
-  if (a8)
-    SRGPT_CHECK(Hd % 128 == 0 && I % 128 == 0 && (Hq * D) % 128 == 0 && Hd >= 256 && I >= 256 && Hq * D >= 256,
-                SRGPT_ERR_UNSUPPORTED, "srgpt_llm_prefill: fp8_act needs hidden, inter and heads * head_dim to be multiples of 128");
-  auto mm = [&](const void* a, const void* Wd, const void* W8p, const float* sc, const void* res, void* out, int N, int K,
-                int f32, void* gws, int64_t gws_bytes) -> int {
-    if (a8 && !f32) {  // the layers' four products; the all-position lm_head (fp32 logits, parity hook) stays W8A16
-      SRGPT_TRY(srgpt_quant_rows_e4m3(a, l.a8, l.a8s, rows, K, K, stream));
-      return srgpt_gemm_w8a8(l.a8, l.a8s, W8p, sc, nullptr, res, out, rows, N, K, K, N, 0, gws, gws_bytes, stream);
-    }
-    if (w8) return srgpt_gemm_w8(a, W8p, sc, nullptr, res, out, rows, N, K, K, N, SRGPT_ACT_NONE, f32, gws, gws_bytes, stream);
-    return srgpt_gemm(a, Wd, nullptr, res, out, rows, N, K, K, N, SRGPT_ACT_NONE, 0, 0, f32, SRGPT_OUT_PLAIN, 0, gws, gws_bytes, dt,
-                      stream);
-  };
-  // W8A8: the producer of a GEMM's input rows (RMSNorm, SwiGLU) is fused into their per-token quantisation -- the bf16
-  // intermediate is neither written nor read (bit-identical to the two launches: tests/test_gpu_fp8_mfma.py)
-  auto mm8 = [&](const void* W8p, const float* sc, const void* res, void* out, int N, int K) -> int {
-    return srgpt_gemm_w8a8(l.a8, l.a8s, W8p, sc, nullptr, res, out, rows, N, K, K, N, 0, l.gws, (int64_t)l.gws_bytes, stream);
-  };
-  const bool fuse8 = a8 && Hd <= 16384 && I <= 16384;
-  const bool plain = !w8;  // dtype matrices: srgpt_gemm
-  bool h_ready = false;   // l.h already holds RMSNorm(l.x) under the coming layer's attn_norm
   for (int i = 0; i < w->layers; ++i) {
-    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
-    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
-    if (fuse8) {
-      SRGPT_TRY(srgpt_quant_rows_e4m3_rmsnorm(l.x, w->attn_norm[i], w->rms_eps, l.a8, l.a8s, rows, Hd, Hd, stream));
-      SRGPT_TRY(mm8(w->wqkv8[i], w->wqkv_scale[i], nullptr, l.qkv, QW, Hd));
-    } else {
-      if (!h_ready) SRGPT_TRY(srgpt_rmsnorm(l.x, w->attn_norm[i], l.h, rows, Hd, w->rms_eps, dt, stream));
-      if (!plain)
-        SRGPT_TRY(mm(l.h, w->wqkv[i], w8 ? w->wqkv8[i] : nullptr, w8 ? w->wqkv_scale[i] : nullptr, nullptr, l.qkv, QW, Hd, 0, l.gws,
-                     (int64_t)l.gws_bytes));
-    }
-    if (plain && !fuse8)  // projection + RoPE + cache append: the rotation rides in the split-K reduction
-      SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, w->wqkv[i], l.qkv, Hd, l.gws, (int64_t)l.gws_bytes, kc, vc, nullptr, w->rope_cos,
-                                          w->rope_sin, B, T, Hq, Hkv, D, st->max_pos, dt, stream));
-    else
-      SRGPT_TRY(srgpt_rope_kv_append(l.qkv, kc, vc, nullptr, w->rope_cos, w->rope_sin, B, T, Hq, Hkv, D, st->max_pos, dt,
-                                     stream));
-    SRGPT_TRY(srgpt_attention(l.qkv, kc, vc, l.attn, B, T, T, Hq, Hkv, D, (int64_t)T * QW, QW, D,
-                              (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D,
-                              (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D, scale, 1, nullptr, dt, stream));
-    // plain weights: the RMSNorm that follows o_proj / down_proj rides in the product's split-K reduction (srgpt_gemm_norm:
-    // bit-identical to the two launches, one launch and one pass over the rows less per norm)
-    if (plain)
-      SRGPT_TRY(srgpt_gemm_norm(l.attn, w->wo[i], nullptr, l.x, l.x, (int)rows, Hd, Hq * D, l.gws, (int64_t)l.gws_bytes, SRGPT_NORM_RMS,
-                                w->mlp_norm[i], nullptr, l.h, w->rms_eps, dt, stream));
-    else
-      SRGPT_TRY(mm(l.attn, w->wo[i], w8 ? w->wo8[i] : nullptr, w8 ? w->wo_scale[i] : nullptr, l.x, l.x, Hd, Hq * D, 0, l.gws,
-                   (int64_t)l.gws_bytes));
-    if (fuse8) {
-      SRGPT_TRY(srgpt_quant_rows_e4m3_rmsnorm(l.x, w->mlp_norm[i], w->rms_eps, l.a8, l.a8s, rows, Hd, Hd, stream));
-      SRGPT_TRY(mm8(w->wgu8[i], w->wgu_scale[i], nullptr, l.gu, 2 * I, Hd));
-      SRGPT_TRY(srgpt_quant_rows_e4m3_swiglu(l.gu, l.a8, l.a8s, rows, I, stream));
-      SRGPT_TRY(mm8(w->wdown8[i], w->wdown_scale[i], l.x, l.x, Hd, I));
-    } else {
-      if (!plain) SRGPT_TRY(srgpt_rmsnorm(l.x, w->mlp_norm[i], l.h, rows, Hd, w->rms_eps, dt, stream));
-      if (plain) {  // gate / up + SiLU * up: the activation is the product's epilogue on the whole-M kernel
-        SRGPT_TRY(srgpt_gemm_swiglu(l.h, w->wgu[i], l.act, (int)rows, I, Hd, l.gu, l.gws, (int64_t)l.gws_bytes, dt, stream));
-      } else {
-        SRGPT_TRY(mm(l.h, w->wgu[i], w8 ? w->wgu8[i] : nullptr, w8 ? w->wgu_scale[i] : nullptr, nullptr, l.gu, 2 * I, Hd, 0, l.gws,
-                     (int64_t)l.gws_bytes));
-        SRGPT_TRY(srgpt_silu_mul(l.gu, l.act, rows, I, dt, stream));
-      }
-      h_ready = plain && i + 1 < w->layers;
-      if (h_ready)
-        SRGPT_TRY(srgpt_gemm_norm(l.act, w->wdown[i], nullptr, l.x, l.x, (int)rows, Hd, I, l.gws, (int64_t)l.gws_bytes, SRGPT_NORM_RMS,
-                                  w->attn_norm[i + 1], nullptr, l.h, w->rms_eps, dt, stream));
-      else
-        SRGPT_TRY(mm(l.act, w->wdown[i], w8 ? w->wdown8[i] : nullptr, w8 ? w->wdown_scale[i] : nullptr, l.x, l.x, Hd, I, 0, l.gws,
-                     (int64_t)l.gws_bytes));
+    switch (fmt) {
+      case FMT_DTYPE: SRGPT_TRY(p.layer_dtype(i)); break;
+      case FMT_W8A16: SRGPT_TRY(p.layer_w8a16(i)); break;
+      case FMT_W8A8: SRGPT_TRY(wide ? p.layer_w8a8_wide(i) : p.layer_w8a8(i)); break;
     }
     if (hidden_out)
       SRGPT_HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(hidden_out) + (size_t)(i + 1) * hid_bytes, l.x, hid_bytes,
                                    hipMemcpyDeviceToDevice, s),
                     "srgpt_llm_prefill: hidden-state copy");
   }
-  if (all_logits) {
-    SRGPT_TRY(srgpt_rmsnorm(l.x, w->final_norm, l.h, rows, Hd, w->rms_eps, dt, stream));
-    SRGPT_TRY(mm(l.h, w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, all_logits, w->vocab, Hd, 1, nullptr, 0));
+  if (all_logits) {  // no split-K workspace in any format
+    SRGPT_TRY(p.norm(w->final_norm));
+    if (fmt == FMT_DTYPE)
+      SRGPT_TRY(srgpt_gemm(l.h, w->lm_head, nullptr, nullptr, all_logits, rows, w->vocab, Hd, Hd, w->vocab, SRGPT_ACT_NONE, 0, 0, 1,
+                           SRGPT_OUT_PLAIN, 0, nullptr, 0, dt, stream));
+    else
+      SRGPT_TRY(srgpt_gemm_w8(l.h, w->lm_head8, w->lm_head_scale, nullptr, nullptr, all_logits, rows, w->vocab, Hd, Hd, w->vocab,
+                              SRGPT_ACT_NONE, 1, nullptr, 0, stream));
   }
   // last position of every sequence -> logits (final norm fused into the GEMV prologue)
   if (lens) {  // right-padded ragged batch: row b ends at lens[b] - 1 and decoding continues from position lens[b]
@@ -522,12 +599,10 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
     hipLaunchKernelGGL(set_int_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, st->pos, B, T);
     SRGPT_LAUNCH_CHECK();
   }
-  if (w8)
-    SRGPT_TRY(srgpt_gemv_w8(l.last, w->lm_head8, w->lm_head_scale, w->final_norm, w->rms_eps, nullptr, st->logits, B, w->vocab, Hd,
-                            0, 1, stream));
-  else
-    SRGPT_TRY(srgpt_gemv(l.last, w->lm_head, w->final_norm, w->rms_eps, nullptr, st->logits, B, w->vocab, Hd, 0, 1, dt, stream));
-  return SRGPT_OK;
+  if (fmt == FMT_DTYPE)
+    return srgpt_gemv(l.last, w->lm_head, w->final_norm, w->rms_eps, nullptr, st->logits, B, w->vocab, Hd, 0, 1, dt, stream);
+  return srgpt_gemv_w8(l.last, w->lm_head8, w->lm_head_scale, w->final_norm, w->rms_eps, nullptr, st->logits, B, w->vocab, Hd, 0, 1,
+                       stream);
 }
 
 extern "C" int srgpt_llm_prefill(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T,
@@ -563,10 +638,36 @@ extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_stat
   return srgpt_llm_sample_first_ex(w, st, SRGPT_SAMPLER_TOPK64, stream);
 }
 
+namespace {
+
+// ---- decode step ----
+// One product of the decode step, by the route the weights and the batch allow.  pub: 2+ bf16 rows (the MFMA kernel): o_proj /
+// down_proj publish the sum of squares of the rows they write (ss_out), the RMSNorm of the next product reads 512 partial sums per
+// row (ss_in) instead of re-reading every row in every block (skinny.hip).  The per-op form of exactly this is srgpt_gemv_rowss.
+struct DecodeStep {
+  const srgpt_llm_weights* w;
+  int B;
+  bool fp8, pub;
+  srgpt_stream_t stream;
+
+  int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
+           const float* ss_in, float* ss_out) const {
+    if (pub && m.pk != nullptr)  // the MFMA kernel reads the packed copy
+      return srgpt_gemv_rowss(x, nullptr, m.pk, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, m.pk_rows, stream);
+    if (pub) return srgpt_gemv_rowss(x, m.w, m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, 0, stream);
+    if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
+    return srgpt_gemv(x, m.w, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, w->dtype, stream);
+  }
+};
+
+}  // namespace
+
 // embed_first = false: the residual-stream buffer already holds the embeddings of st->tok (written by the advance_kernel of the
 // step before: the graph-captured greedy loop); the public entry always embeds (st->tok may have been set by the caller)
 static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, int sampler) {
   SRGPT_TRY(check_llm(w, st));
+  LlmFormat fmt;
+  SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
   const int B = st->batch, QW = (Hq + 2 * Hkv) * D;
   const size_t es = dtype_size(dt);
@@ -583,47 +684,27 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
                        (int64_t)w->vocab, d.err);
     SRGPT_LAUNCH_CHECK();
   }
-  // fp8 copies present -> the decode step streams them (W8A16, half the bytes per token)
-  const bool w8 = w->wqkv8 != nullptr;
-  if (w8)
-    SRGPT_CHECK(dt == SRGPT_BF16 && w->wo8 && w->wgu8 && w->wdown8 && w->lm_head8 && w->wqkv_scale && w->wo_scale &&
-                    w->wgu_scale && w->wdown_scale && w->lm_head_scale,
-                SRGPT_ERR_ARG, "srgpt_llm_decode_step: fp8 weights need bf16 activations and all five matrices + scales");
-  // 2+ bf16 rows (the MFMA kernel): o_proj / down_proj publish the sum of squares of the rows they write, the RMSNorm of the next
-  // product reads 512 partial sums per row instead of re-reading every row in every block (skinny.hip; layer 0's q/k/v normalises
-  // the embedding rows itself).  The per-op form of exactly this sequence is srgpt_gemv_rowss.
-  const bool pub = srgpt_gemv_rowss_supported(B, dt, w8 ? 1 : 0) != 0;
+  const bool fp8 = fmt != FMT_DTYPE;
+  const DecodeStep ds{w, B, fp8, srgpt_gemv_rowss_supported(B, dt, fp8 ? 1 : 0) != 0, stream};
+  // the row statistics (layer 0's q/k/v normalises the embedding rows itself)
   float* const ss_attn = d.rowss;                                       // rows after the attention block's residual add
   float* const ss_mlp = d.rowss + (size_t)B * SRGPT_ROWSS_STRIDE;       // rows after the MLP block's
-  // packed copy of layer i's matrix `which` (0 wqkv, 1 wo, 2 wgu, 3 wdown) for the MFMA kernel, or NULL: stream the row-major one
-  auto pk = [&](const void* const* arr, int i) -> const void* { return pub && w8 && arr != nullptr ? arr[i] : nullptr; };
-  auto mv = [&](const void* x, const void* Wd, const void* W8p, const float* sc, const void* norm, const void* res, void* out,
-                int N, int K, int swiglu, int f32, const float* ss_in, float* ss_out, const void* W8pk = nullptr, int pk_rows = 0) -> int {
-    if (pub && W8pk != nullptr)
-      return srgpt_gemv_rowss(x, nullptr, W8pk, sc, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, pk_rows, stream);
-    if (pub) return srgpt_gemv_rowss(x, Wd, W8p, sc, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, 0, stream);
-    if (w8) return srgpt_gemv_w8(x, W8p, sc, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
-    return srgpt_gemv(x, Wd, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, dt, stream);
-  };
   for (int i = 0; i < w->layers; ++i) {
     char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
     char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
-    SRGPT_TRY(mv(d.xd, w->wqkv[i], w8 ? w->wqkv8[i] : nullptr, w8 ? w->wqkv_scale[i] : nullptr, w->attn_norm[i], nullptr,
-                 d.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr, pk(w->wqkv8p, i), w->pk_rows_qkv));
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(ds.gemv(m.qkv, d.xd, w->attn_norm[i], nullptr, d.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
     // the attention launch also pulls o_proj's weights into L2 (HBM is idle while it runs).  Round 3 built the next step -- o_proj
     // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
     // (profiles/r03_fused_attention_oproj.txt)
     SRGPT_TRY(srgpt_decode_attention_pf(d.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, d.attnd, d.dws, B, Hq, Hkv, D,
-                                        st->max_pos, dt, w8 ? w->wo8[i] : w->wo[i], Hd, Hq * D, w8 ? 1 : 0, 0, stream));
-    SRGPT_TRY(mv(d.attnd, w->wo[i], w8 ? w->wo8[i] : nullptr, w8 ? w->wo_scale[i] : nullptr, nullptr, d.xd, d.xd, Hd,
-                 Hq * D, 0, 0, nullptr, ss_attn, pk(w->wo8p, i), w->pk_rows_o));
-    SRGPT_TRY(mv(d.xd, w->wgu[i], w8 ? w->wgu8[i] : nullptr, w8 ? w->wgu_scale[i] : nullptr, w->mlp_norm[i], nullptr,
-                 d.actd, I, Hd, 1, 0, ss_attn, nullptr, pk(w->wgu8p, i), w->pk_rows_gu));
-    SRGPT_TRY(mv(d.actd, w->wdown[i], w8 ? w->wdown8[i] : nullptr, w8 ? w->wdown_scale[i] : nullptr, nullptr, d.xd, d.xd,
-                 Hd, I, 0, 0, nullptr, ss_mlp, pk(w->wdown8p, i), w->pk_rows_down));
+                                        st->max_pos, dt, fp8 ? m.o.w8 : m.o.w, Hd, Hq * D, fp8 ? 1 : 0, stream));
+    SRGPT_TRY(ds.gemv(m.o, d.attnd, nullptr, d.xd, d.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
+    SRGPT_TRY(ds.gemv(m.gu, d.xd, w->mlp_norm[i], nullptr, d.actd, I, Hd, 1, 0, ss_attn, nullptr));
+    SRGPT_TRY(ds.gemv(m.down, d.actd, nullptr, d.xd, d.xd, Hd, I, 0, 0, nullptr, ss_mlp));
   }
-  SRGPT_TRY(mv(d.xd, w->lm_head, w->lm_head8, w->lm_head_scale, w->final_norm, nullptr, st->logits, w->vocab, Hd, 0, 1,
-               w->layers > 0 ? ss_mlp : nullptr, nullptr));
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
+                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
   return greedy_pick(w, st, d, 1, sampler, s);
 }
 
@@ -670,6 +751,8 @@ extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgp
                                                 srgpt_graph** out) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_decode_graph_create: null out");
   SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_graph_create_ex"));
+  LlmFormat fmt;  // incomplete fp8 weights never begin a capture (the step below resolves the format again)
+  SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
   hipStream_t s = as_stream(stream);
   (void)srgpt_device_cus();  // make sure no device query happens inside the capture
   hipGraph_t graph = nullptr;

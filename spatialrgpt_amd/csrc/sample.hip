@@ -27,6 +27,7 @@
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
 // on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
 #include "common.h"
+#include "internal.h"
 
 namespace {
 
@@ -670,7 +671,7 @@ extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream)
   return SRGPT_OK;
 }
 
-extern "C" __attribute__((visibility("hidden"))) int srgpt_sample_slices(void) { return SMP_NB; }  // cross-file helper, not exported
+int srgpt_sample_slices() { return SMP_NB; }
 
 // ---- the full sampler ----
 // workspace: keys u32 [B][V] | thresholds u32 [B][4] | slice maxima f32 [B][128] | their indices i32 [B][128]

@@ -31,9 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
-
-int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const void* norm_w, float eps,
-                       const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, hipStream_t s);  // gemv_w8.hip
+#include "internal.h"
 
 namespace {
 
@@ -70,7 +68,7 @@ constexpr int FS_MAX = 4;              // MFMA k steps per fragment batch (8 LDS
 // sequentially.  The weights then never touch LDS: no ds_write / wave barrier / fragment ds_read per stage (the timing probe of
 // round 5 priced them at 4 - 7 % of the fp8 layer, profiles/r05_skinny_probes.txt) and a block needs LDS only for its activation
 // slices.  4-row granules keep every column split of the row-major kernel (24 q/k/v columns or 28 gate / up pairs per block);
-// 16-row granules (1 KiB contiguous per instruction) stream the single-tile products faster (profiles/r06_skinny_packed.txt).
+// 16-row granules (1 KiB contiguous per instruction) stream the single-tile products faster (profiles/r06_skinny_packed_gr.txt).
 template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const bf16_t* __restrict__ x, const void* __restrict__ Wv,
                                                                           const float* __restrict__ wscale,
@@ -666,9 +664,6 @@ int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, c
   return SRGPT_OK;
 }
 
-// rows at or below this count take the one-row VALU kernel of gemv_w8.hip (which neither reads nor publishes row statistics)
-int srgpt_w8_valu_max_batch() { return 1; }  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
-
 // Decode-path product with fp8 (OCP e4m3fn) weights and one fp32 scale per weight row, bf16 activations (W8A16):
 // out[b, n] = bf16( (sum_k x[b, k] * fp8(W8[n, k])) * wscale[n] ), same fusions as srgpt_gemv.  Any batch size
 // (16 rows per weight pass).
@@ -680,7 +675,7 @@ extern "C" int srgpt_gemv_w8(const void* x, const void* W8, const float* wscale,
   SRGPT_CHECK(K % 8 == 0, SRGPT_ERR_ARG, "srgpt_gemv_w8: K=%d must be a multiple of 8", K);
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_w8: swiglu excludes residual/out_f32");
   hipStream_t s = as_stream(stream);
-  if (batch <= srgpt_w8_valu_max_batch() && K % 16 == 0)  // one row: VALU kernel (gemv_w8.hip), like the bf16 path
+  if (batch <= W8_VALU_MAX_BATCH && K % 16 == 0)  // one row: VALU kernel (gemv_w8.hip), like the bf16 path
     return srgpt_gemv_w8_valu(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, s);
   return srgpt_skinny_w8_launch(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, nullptr, nullptr, 0, s);
 }

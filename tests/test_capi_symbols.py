@@ -28,15 +28,15 @@ def test_header_symbols_are_exported():
 
 
 def test_product_library_exports_nothing_but_the_header():
-    """The product library carries no experiment residue: every exported `srgpt_*` C symbol is declared in include/srgpt.h (cross-file
-    helpers have hidden visibility), and no experiment residue (debug stamps, environment knobs, the VALU pooling kernel's bf16
-    instances) is in it."""
+    """The dynamic symbol table of the product library is the C ABI: every defined symbol is a name declared in include/srgpt.h, or one
+    of the toolchain's own `__hip_cuid_*` objects -- no cross-file helper (mangled or not), kernel handle or host stub.  And no
+    experiment residue (debug stamps, environment knobs, the VALU pooling kernel's bf16 instances) is in the library."""
     import subprocess
 
     from spatialrgpt_amd import _lib
 
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("srgpt_")}
+    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split() and not ln.split()[-1].startswith("__hip_cuid_")}
     assert exported == set(_declared()), exported ^ set(_declared())
     blob = open(_lib.LIB_PATH, "rb").read()
     for residue in (b"debug_stamps", b"SRGPT_GEMM_", b"SRGPT_REGION_", b"SRGPT_DECODE_", b"SRGPT_SKINNY_", b"SRGPT_GEMV_",

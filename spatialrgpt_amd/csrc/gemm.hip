@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_route.h"
 #include "internal.h"
 
 namespace {
@@ -393,40 +394,44 @@ __global__ __launch_bounds__(256) void splitk_reduce_rope_kernel(Epilogue e) {
   }
 }
 
-// launches the reduction that fits the epilogue (returns through SRGPT_LAUNCH_CHECK at the call site); true when the RMSNorm the
-// epilogue asks for went into it
+// launches the reduction that fits the epilogue (returns through SRGPT_LAUNCH_CHECK at the call site); true when the norm / RoPE
+// the epilogue asks for went into it
 template <typename T>
 static inline bool launch_splitk_reduce(const Epilogue& e, hipStream_t s) {
   const size_t total = (size_t)e.M * e.N;
   const bool vec4 = e.N % 4 == 0 && e.ldc % 4 == 0 && e.out_mode != SRGPT_OUT_DECONV2X && e.bias_mod <= 0 && e.res_mod <= 0 &&
                     e.splits <= 8 && ((uintptr_t)e.C % 16 == 0);
+// MAXS = the 4 or 8 slabs a thread of the vectorised kernels keeps in flight
+#define SRGPT_FOR_MAXS(LAUNCH)  \
+  do {                          \
+    if (e.splits <= 4) {        \
+      constexpr int MAXS = 4;   \
+      LAUNCH;                   \
+    } else {                    \
+      constexpr int MAXS = 8;   \
+      LAUNCH;                   \
+    }                           \
+  } while (0)
   if (e.rope_k && std::is_same<T, bf16_t>::value && vec4 && !e.out_f32 && !e.bias && !e.residual && !e.wscale &&
       e.act == SRGPT_ACT_NONE && e.N % 8 == 0 && e.ldc % 8 == 0 && e.N <= 24576) {
     const size_t lds = (size_t)e.N * sizeof(bf16_t);  // <= 48 KB
-    if (e.splits <= 4) hipLaunchKernelGGL((splitk_reduce_rope_kernel<4>), dim3(e.M), dim3(256), lds, s, e);
-    else hipLaunchKernelGGL((splitk_reduce_rope_kernel<8>), dim3(e.M), dim3(256), lds, s, e);
+    SRGPT_FOR_MAXS(hipLaunchKernelGGL((splitk_reduce_rope_kernel<MAXS>), dim3(e.M), dim3(256), lds, s, e));
     return true;
   }
   if (e.norm_y && std::is_same<T, bf16_t>::value && vec4 && !e.out_f32 && e.N % 8 == 0 && e.ldc % 8 == 0 && e.N <= 8192 &&
       ((uintptr_t)e.norm_y % 16 == 0) && ((uintptr_t)e.norm_w % 16 == 0) && (!e.norm_b || (uintptr_t)e.norm_b % 16 == 0) &&
       (!e.residual || (uintptr_t)e.residual % 16 == 0)) {
-    const bool wide = e.N > 4096;
-    if (e.splits <= 4) {
-      if (wide) hipLaunchKernelGGL((splitk_reduce_norm_kernel<4, 4>), dim3(e.M), dim3(256), 0, s, e);
-      else hipLaunchKernelGGL((splitk_reduce_norm_kernel<4, 2>), dim3(e.M), dim3(256), 0, s, e);
-    } else {
-      if (wide) hipLaunchKernelGGL((splitk_reduce_norm_kernel<8, 4>), dim3(e.M), dim3(256), 0, s, e);
-      else hipLaunchKernelGGL((splitk_reduce_norm_kernel<8, 2>), dim3(e.M), dim3(256), 0, s, e);
-    }
+    if (e.N > 4096) SRGPT_FOR_MAXS(hipLaunchKernelGGL((splitk_reduce_norm_kernel<MAXS, 4>), dim3(e.M), dim3(256), 0, s, e));
+    else SRGPT_FOR_MAXS(hipLaunchKernelGGL((splitk_reduce_norm_kernel<MAXS, 2>), dim3(e.M), dim3(256), 0, s, e));
     return true;
   }
   if (vec4) {
     int rgrid = (int)((total / 4 + 255) / 256);
     if (rgrid > 2048) rgrid = 2048;
-    if (e.splits <= 4) hipLaunchKernelGGL((splitk_reduce4_kernel<T, 4>), dim3(rgrid), dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((splitk_reduce4_kernel<T, 8>), dim3(rgrid), dim3(256), 0, s, e);
+    SRGPT_FOR_MAXS(hipLaunchKernelGGL((splitk_reduce4_kernel<T, MAXS>), dim3(rgrid), dim3(256), 0, s, e));
     return false;
   }
+#undef SRGPT_FOR_MAXS
   int rgrid = (int)((total + 255) / 256);
   if (rgrid > 2048) rgrid = 2048;
   hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3(rgrid), dim3(256), 0, s, e);
@@ -530,198 +535,86 @@ __global__ __launch_bounds__(256) void gemm_w8_simple(const bf16_t* __restrict__
 
 }  // namespace
 
-// the split-K slab reduction + epilogue for kernels in other files (gemm_f8.hip)
-int srgpt_splitk_reduce_bf16(const Epilogue& e, hipStream_t s) {
-  launch_splitk_reduce<bf16_t>(e, s);
+// ---- split-K on the host, for every product of this file and of gemm_f8.hip (internal.h): the route's split goes into the
+//      epilogue in front of the launch ...
+void srgpt_splitk_apply(Epilogue& e, const GemmRoute& r, void* ws) {
+  if (r.splits <= 1) return;
+  e.partial = reinterpret_cast<float*>(ws);
+  e.tiles_per_split = r.tiles_per_split;
+  e.splits = r.splits;
+}
+
+// ... and the slab reduction + epilogue follows it.  *fused (may be NULL): the norm / RoPE the epilogue asks for went into the
+// reduction; left alone when K was not split.
+int srgpt_splitk_finish(const Epilogue& e, hipStream_t s, bool* fused) {
+  if (e.splits <= 1) return SRGPT_OK;
+  const bool f = launch_splitk_reduce<bf16_t>(e, s);
+  if (fused) *fused = f;
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int64_t srgpt_gemm_ws_bytes(int M, int N) { return (int64_t)8 * M * N * 4; }
 
-// norm_w / norm_y / norm_eps: the RMSNorm of the output rows (srgpt_gemm_rmsnorm below); *norm_done = it went into the reduction
-static int gemm_impl(const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K, int lda,
-                     int ldc, int act, int bias_mod, int res_mod, int out_f32, int out_mode, int gw, void* ws, int64_t ws_bytes,
-                     int dtype, srgpt_stream_t stream, int norm_kind, const void* norm_w, const void* norm_b, void* norm_y, float norm_eps,
-                     bool* norm_done, const Epilogue* rope = nullptr) {
-  SRGPT_CHECK(A && W && C, SRGPT_ERR_ARG, "srgpt_gemm: null pointer");
+// a dense row-major product without bias, activation or residual; the entry points below assign what they add
+static Epilogue plain_epilogue(void* C, int M, int N, int ldc) {
+  Epilogue e{};
+  e.C = C, e.M = M, e.N = N, e.ldc = ldc, e.act = SRGPT_ACT_NONE, e.out_mode = SRGPT_OUT_PLAIN, e.splits = 1;
+  return e;
+}
+
+// C = epilogue(A W^T) for the entry points below: validate, pick the route (gemm_route.h), launch its kernel, reduce the slabs.
+// *fused: see srgpt_splitk_finish.
+static int gemm_run(const void* A, const void* W, int K, int lda, int dtype, void* ws, int64_t ws_bytes, Epilogue e,
+                    srgpt_stream_t stream, bool* fused) {
+  const int M = e.M, N = e.N;
+  SRGPT_CHECK(A && W && e.C, SRGPT_ERR_ARG, "srgpt_gemm: null pointer");
   SRGPT_CHECK(M > 0 && N > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm: bad shape M=%d N=%d K=%d", M, N, K);
   SRGPT_CHECK(dtype == SRGPT_F32 || dtype == SRGPT_BF16, SRGPT_ERR_ARG, "srgpt_gemm: bad dtype %d", dtype);
   const int vec = dtype == SRGPT_BF16 ? 8 : 4;
   SRGPT_CHECK(K % vec == 0 && lda % vec == 0, SRGPT_ERR_ARG,
               "srgpt_gemm: K=%d and lda=%d must be multiples of %d (16-byte rows)", K, lda, vec);
   SRGPT_CHECK(((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0), SRGPT_ERR_ARG, "srgpt_gemm: A/W must be 16-byte aligned");
-  if (out_mode == SRGPT_OUT_DECONV2X) {
-    SRGPT_CHECK(N % 4 == 0 && gw > 0 && M % (gw * gw) == 0, SRGPT_ERR_ARG, "srgpt_gemm: bad deconv geometry");
+  if (e.out_mode == SRGPT_OUT_DECONV2X) {
+    SRGPT_CHECK(N % 4 == 0 && e.gw > 0 && M % (e.gw * e.gw) == 0, SRGPT_ERR_ARG, "srgpt_gemm: bad deconv geometry");
   } else {
-    SRGPT_CHECK(out_mode == SRGPT_OUT_PLAIN, SRGPT_ERR_ARG, "srgpt_gemm: unknown out_mode %d", out_mode);
-    SRGPT_CHECK(ldc >= N, SRGPT_ERR_ARG, "srgpt_gemm: ldc < N");
-  }
-  Epilogue e{bias, residual, C, M, N, ldc, act, bias_mod, res_mod, out_f32, out_mode, gw, nullptr, 1, 0, nullptr, norm_w, norm_b, norm_y, norm_eps, norm_kind};
-  if (rope) {
-    e.rope_k = rope->rope_k, e.rope_v = rope->rope_v, e.rope_pos0 = rope->rope_pos0, e.rope_cos = rope->rope_cos;
-    e.rope_sin = rope->rope_sin, e.rope_T = rope->rope_T, e.rope_Hq = rope->rope_Hq, e.rope_Hkv = rope->rope_Hkv;
-    e.rope_D = rope->rope_D, e.rope_max_pos = rope->rope_max_pos;
+    SRGPT_CHECK(e.out_mode == SRGPT_OUT_PLAIN, SRGPT_ERR_ARG, "srgpt_gemm: unknown out_mode %d", e.out_mode);
+    SRGPT_CHECK(e.ldc >= N, SRGPT_ERR_ARG, "srgpt_gemm: ldc < N");
   }
   hipStream_t s = as_stream(stream);
-  if (dtype == SRGPT_F32) {
-    dim3 grid(cdiv(N, 64), cdiv(M, 64));
-    hipLaunchKernelGGL(gemm_f32_simple, grid, dim3(256), 0, s, (const float*)A, (const float*)W, K, lda, e);
-    SRGPT_LAUNCH_CHECK();
-    return SRGPT_OK;
-  }
-  // ---- 288 x 128 whole-M kernel (gemm288.hip) for the bs = 1 prefill products (224 < M <= 272): W crosses the global -> LDS path
-  //      once, requests three K tiles deep.  Column tiles x K splits should come to about one block per CU.
-  {
-    const int cus = srgpt_device_cus();
-    const int nk = K / 64;
-    const int gx = cdiv(N, 128);
-    // measured at M = 259 (profiles/r04_gemm288.txt): gate/up 106.5 -> 84.2 us, down 64.8 -> 50.6, q/k/v 33.8 -> 32.0; o (27.5 vs
-    // 27.9: 8 K tiles per block once K is split for 256 CUs, three of them pipeline fill) stays on the small tiles
-    bool use288 = K % 64 == 0 && nk >= 4 && M > 224 && M <= 272 && (int64_t)N * K >= (int64_t)24 << 20;
-    int sp = 1;
-    if (use288) {  // one 272-row tile in M: the grid is gx column tiles x sp K splits
-      if (gx < cus * 3 / 4 && ws) {
-        sp = (cus + gx / 2) / gx;
-        if (sp > nk / 8) sp = nk / 8;  // keep >= 8 K tiles per split: three of them are pipeline fill
-        if (sp > 8) sp = 8;
-        while (sp > 1 && (int64_t)sp * M * N * 4 > ws_bytes) --sp;
-        if (sp < 1) sp = 1;
-      }
-      if ((long)gx * sp < cus / 2) use288 = false;  // too few blocks to fill the chip: the small tiles overlap better
-    }
-    if (use288) {
-      if (sp > 1) {
-        e.partial = reinterpret_cast<float*>(ws);
-        e.tiles_per_split = cdiv(nk, sp);
-        e.splits = cdiv(nk, e.tiles_per_split);
-      }
-      SRGPT_TRY(srgpt_gemm288_launch(A, W, K, lda, e, s));
-      if (e.splits > 1) {
-        {
-          const bool fused = launch_splitk_reduce<bf16_t>(e, s);
-          if (norm_done) *norm_done = fused;
-        }
-        SRGPT_LAUNCH_CHECK();
-      }
-      return SRGPT_OK;
+  const GemmRoute r = dtype == SRGPT_F32 ? gemm_route_f32() : gemm_route(M, N, K, srgpt_device_cus(), ws != nullptr, ws_bytes);
+  srgpt_splitk_apply(e, r, ws);
+  switch (r.family) {
+    case GEMM_F32_SIMPLE:
+      hipLaunchKernelGGL(gemm_f32_simple, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, s, (const float*)A, (const float*)W, K, lda, e);
+      SRGPT_LAUNCH_CHECK();
+      break;
+    case GEMM_WHOLE_M_288: SRGPT_TRY(srgpt_gemm288_launch(A, W, K, lda, e, s)); break;
+    case GEMM_TILE_256: SRGPT_TRY(srgpt_gemm256_launch(A, W, K, lda, e, s)); break;
+    case GEMM_GLDS: {
+      const dim3 grid(cdiv(N, 128), cdiv(M, r.bm), e.splits);
+#define SRGPT_GLDS(BM, NBUF) \
+  hipLaunchKernelGGL((gemm_bf16_glds<BM, 128, NBUF>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e)
+      if (r.bm == 128) SRGPT_GLDS(128, 1);
+      else if (r.bm == 96 && r.nbuf == 2) SRGPT_GLDS(96, 2);
+      else if (r.bm == 96) SRGPT_GLDS(96, 1);
+      else if (r.nbuf == 2) SRGPT_GLDS(64, 2);
+      else SRGPT_GLDS(64, 1);
+#undef SRGPT_GLDS
+      SRGPT_LAUNCH_CHECK();
+      break;
     }
   }
-  // ---- 256 x 256 eight-wave kernel (gemm256.hip); rule calibrated on MI355X measurements (profiles/r02_gemm256_*.txt,
-  //      profiles/r02_gemm_final.txt: one block per CU, ~15 us of launch + prologue + epilogue per round of tiles) ----
-  //   K >= 2048: it wins or ties on every shape with M >= 384 (prefill b8 qkv 111 vs 172 us, down 334 vs 455, b4 down 140 vs 212);
-  //              an under-filled grid splits K (deterministic slabs) up to ~1.1 rounds of blocks
-  //   K <  2048: the fixed cost per round is a quarter of the tile time, so only when the last round is nearly full
-  //              (>= 88 %: ViT out-proj 50 vs 62 us; ViT qkv / fc1 at 84 / 76 % stay on the small-tile kernel: 131 vs 143 us)
-  {
-    const int cus = srgpt_device_cus();
-    const int nk256 = K / 64;
-    const long t256 = (long)cdiv(M, 256) * cdiv(N, 256);
-    // M >= 384 and at most 25 % of padded rows (M = 518 would fill 3 row tiles to 67 %)
-    bool use256 = K % 64 == 0 && K >= 256 && M >= 384 && (long)M * 4 >= (long)cdiv(M, 256) * 256 * 3;
-    int sp = 1;
-    if (use256) {
-      if (K >= 2048) {
-        if (t256 < cus && ws) {
-          sp = (int)((cus * 11 / 10 + t256 / 2) / t256);
-          if (sp < 1) sp = 1;
-          if (sp > 4) sp = 4;
-          while (sp > 1 && (nk256 / sp < 8 || (int64_t)sp * M * N * 4 > ws_bytes)) --sp;
-        }
-      } else {
-        const long rounds = (t256 + cus - 1) / cus;
-        use256 = t256 * 100 >= rounds * cus * 88;
-      }
-    }
-    if (use256) {
-      if (sp > 1) {
-        e.partial = reinterpret_cast<float*>(ws);
-        e.tiles_per_split = cdiv(nk256, sp);
-        e.splits = cdiv(nk256, e.tiles_per_split);
-      }
-      SRGPT_TRY(srgpt_gemm256_launch(A, W, K, lda, e, s));
-      if (e.splits > 1) {
-        {
-          const bool fused = launch_splitk_reduce<bf16_t>(e, s);
-          if (norm_done) *norm_done = fused;
-        }
-        SRGPT_LAUNCH_CHECK();
-      }
-      return SRGPT_OK;
-    }
-  }
-  // ---- tile / split-K selection: fill the 256 CUs with >= ~2 blocks each ----
-  const long t128 = (long)cdiv(M, 128) * cdiv(N, 128);
-  const long t64x128 = (long)cdiv(M, 64) * cdiv(N, 128);
-  const int nk = cdiv(K, BK);
-  int bm = 128, splits = 1;
-  long tiles = t128;
-  const bool pad_waste = (long)cdiv(M, 128) * 128 * 10 > (long)cdiv(M, 64) * 64 * 11;  // > 10 % fewer padded rows with BM = 64
-  // 128x128 only when it alone fills the chip at 4 blocks per CU; below that 64x128 has twice the blocks to overlap
-  // (measured with the direct-to-LDS kernel: M=1458 N=4304 K=1152: 32.5 us vs 46.1 us; equal at 4096^3)
-  if (t128 < 1024 || pad_waste) {
-    bm = 64;
-    tiles = t64x128;
-    // 96-row tiles (three 32-row MFMA tiles per wave, 1 x 4 waves) where they do not pad M by more than 8 % over 64-row tiles:
-    // this kernel is bound by the global -> LDS fill rate, and a 96x128 step moves 17.8 B/kFLOP against 23.4 (M = 259 pads to
-    // 288 instead of 320: gate/up 156 -> 106 us, ViT fc1 38 -> 25 us, profiles/r02_gemm_bm96.txt).  The split count keeps
-    // following the 64-row tile count (the measured configuration).
-    if (M > 64 && (long)cdiv(M, 96) * 96 * 100 <= (long)cdiv(M, 64) * 64 * 108) bm = 96;
-    if (tiles < 384 && ws) {
-      splits = (int)((512 + tiles - 1) / tiles);
-      if (splits > nk / 8) splits = nk / 8;  // keep >= 8 K-tiles (512 columns of K) per split
-      if (splits > 8) splits = 8;
-      while (splits > 1 && (int64_t)splits * M * N * 4 > ws_bytes) --splits;
-      if (splits < 1) splits = 1;
-    }
-  }
-  if (splits > 1) {
-    e.partial = reinterpret_cast<float*>(ws);
-    e.tiles_per_split = cdiv(nk, splits);
-    splits = cdiv(nk, e.tiles_per_split);  // no empty split
-    e.splits = splits;
-  }
-  if (bm == 128) {
-    dim3 grid(cdiv(N, 128), cdiv(M, 128), 1);
-    hipLaunchKernelGGL((gemm_bf16_glds<128, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-  } else if (bm == 96) {
-    dim3 grid(cdiv(N, 128), cdiv(M, 96), e.splits);  // (96x256 tiles measured: slower on every shape)
-    const long blocks = (long)grid.x * grid.y * e.splits;
-    // single buffer (5 blocks per CU overlap each other's K steps) only for un-split grids of >= 2 blocks per CU (gate/up 672,
-    // ViT fc1 544 blocks: 106 vs 134 us, 25 vs 33 us); split-K and smaller grids double-buffer (q/k/v 34 vs 38 us)
-    const bool dbuf = !(e.splits <= 1 && blocks >= 2L * srgpt_device_cus());
-    if (dbuf)
-      hipLaunchKernelGGL((gemm_bf16_glds<96, 128, 2>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-    else
-      hipLaunchKernelGGL((gemm_bf16_glds<96, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-  } else {
-    dim3 grid(cdiv(N, 128), cdiv(M, 64), e.splits);
-    const long blocks = tiles * e.splits;
-    const bool dbuf = blocks < 3L * srgpt_device_cus();
-    if (dbuf)
-      hipLaunchKernelGGL((gemm_bf16_glds<64, 128, 2>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-    else
-      hipLaunchKernelGGL((gemm_bf16_glds<64, 128, 1>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
-  }
-  SRGPT_LAUNCH_CHECK();
-  if (e.splits > 1) {
-    {
-          const bool fused = launch_splitk_reduce<bf16_t>(e, s);
-          if (norm_done) *norm_done = fused;
-        }
-    SRGPT_LAUNCH_CHECK();
-  }
-  return SRGPT_OK;
+  return srgpt_splitk_finish(e, s, fused);
 }
 
-// C = epilogue((A @ fp8(W8)^T) * wscale): bf16 activations, OCP e4m3fn weight bytes, one fp32 scale per weight row -- the
-// prefill-side companion of srgpt_gemv_w8 (BASELINE config 5).  Always the 256 x 256 kernel (W tile staged as bytes, widened
-// to bf16 between LDS and the MFMA operands); K splits (deterministic slabs) when the tiles do not fill the chip.
 extern "C" int srgpt_gemm(const void* A, const void* W, const void* bias, const void* residual, void* C, int M,
                           int N, int K, int lda, int ldc, int act, int bias_mod, int res_mod, int out_f32,
                           int out_mode, int gw, void* ws, int64_t ws_bytes, int dtype, srgpt_stream_t stream) {
-  return gemm_impl(A, W, bias, residual, C, M, N, K, lda, ldc, act, bias_mod, res_mod, out_f32, out_mode, gw, ws, ws_bytes, dtype,
-                   stream, 0, nullptr, nullptr, nullptr, 0.f, nullptr);
+  Epilogue e = plain_epilogue(C, M, N, ldc);
+  e.bias = bias, e.residual = residual, e.act = act, e.bias_mod = bias_mod, e.res_mod = res_mod;
+  e.out_f32 = out_f32, e.out_mode = out_mode, e.gw = gw;
+  return gemm_run(A, W, K, lda, dtype, ws, ws_bytes, e, stream, nullptr);
 }
 
 // C = A W^T + bias + residual (dense rows) and Y = norm(C) in one call (include/srgpt.h; the layer loops of model.hip).  The norm
@@ -734,9 +627,11 @@ extern "C" int srgpt_gemm_norm(const void* A, const void* W, const void* bias, c
               norm_kind);
   SRGPT_CHECK(norm_w && Y && (norm_kind == SRGPT_NORM_RMS || norm_b), SRGPT_ERR_ARG, "srgpt_gemm_norm: null pointer");
   SRGPT_CHECK(Y != C, SRGPT_ERR_ARG, "srgpt_gemm_norm: Y must not alias C");  // Y may be A: the norm runs after the product
+  Epilogue e = plain_epilogue(C, M, N, N);
+  e.bias = bias, e.residual = residual;
+  e.norm_w = norm_w, e.norm_b = norm_b, e.norm_y = Y, e.norm_eps = norm_eps, e.norm_kind = norm_kind;
   bool fused = false;
-  SRGPT_TRY(gemm_impl(A, W, bias, residual, C, M, N, K, K, N, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, ws, ws_bytes, dtype, stream,
-                      norm_kind, norm_w, norm_b, Y, norm_eps, &fused));
+  SRGPT_TRY(gemm_run(A, W, K, K, dtype, ws, ws_bytes, e, stream, &fused));
   if (!fused) {
     if (norm_kind == SRGPT_NORM_RMS) SRGPT_TRY(srgpt_rmsnorm(C, norm_w, Y, M, N, norm_eps, dtype, stream));
     else SRGPT_TRY(srgpt_layernorm(C, norm_w, norm_b, Y, M, N, norm_eps, SRGPT_ACT_NONE, dtype, stream));
@@ -754,12 +649,11 @@ extern "C" int srgpt_gemm_rope_kv_append(const void* A, const void* W, void* qkv
   SRGPT_CHECK(B > 0 && T_ > 0 && Hq > 0 && Hkv > 0 && D > 0 && (D & 1) == 0 && T_ <= max_pos, SRGPT_ERR_ARG,
               "srgpt_gemm_rope_kv_append: bad shape");
   const int M = B * T_, N = (Hq + 2 * Hkv) * D;
-  Epilogue r{};
-  r.rope_k = kcache, r.rope_v = vcache, r.rope_pos0 = pos0, r.rope_cos = cos_tab, r.rope_sin = sin_tab;
-  r.rope_T = T_, r.rope_Hq = Hq, r.rope_Hkv = Hkv, r.rope_D = D, r.rope_max_pos = max_pos;
+  Epilogue e = plain_epilogue(qkv, M, N, N);
+  e.rope_k = kcache, e.rope_v = vcache, e.rope_pos0 = pos0, e.rope_cos = cos_tab, e.rope_sin = sin_tab;
+  e.rope_T = T_, e.rope_Hq = Hq, e.rope_Hkv = Hkv, e.rope_D = D, e.rope_max_pos = max_pos;
   bool fused = false;
-  SRGPT_TRY(gemm_impl(A, W, nullptr, nullptr, qkv, M, N, K, K, N, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, ws, ws_bytes, dtype,
-                      stream, 0, nullptr, nullptr, nullptr, 0.f, &fused, &r));
+  SRGPT_TRY(gemm_run(A, W, K, K, dtype, ws, ws_bytes, e, stream, &fused));
   if (!fused) SRGPT_TRY(srgpt_rope_kv_append(qkv, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq, Hkv, D, max_pos, dtype, stream));
   return SRGPT_OK;
 }
@@ -772,11 +666,10 @@ extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int 
                                  int64_t ws_bytes, int dtype, srgpt_stream_t stream) {
   SRGPT_CHECK(A && Wgu && out, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: null pointer");
   SRGPT_CHECK(M > 0 && I > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: bad shape M=%d I=%d K=%d", M, I, K);
-  const bool fused = dtype == SRGPT_BF16 && M > 224 && M <= 272 && K % 64 == 0 && K / 64 >= 4 && I % 64 == 0 &&
-                     I / 64 >= srgpt_device_cus() / 2 && ((uintptr_t)A % 16 == 0) && ((uintptr_t)Wgu % 16 == 0);
-  if (fused) {
-    Epilogue e{};
-    e.C = out, e.M = M, e.N = I, e.ldc = I, e.act = SRGPT_ACT_NONE, e.splits = 1, e.swiglu_inter = I;
+  if (dtype == SRGPT_BF16 && gemm_swiglu_fused_shape(M, I, K, srgpt_device_cus()) && ((uintptr_t)A % 16 == 0) &&
+      ((uintptr_t)Wgu % 16 == 0)) {
+    Epilogue e = plain_epilogue(out, M, I, I);
+    e.swiglu_inter = I;
     SRGPT_TRY(srgpt_gemm288_launch(A, Wgu, K, K, e, as_stream(stream)));
     return SRGPT_OK;
   }
@@ -786,6 +679,9 @@ extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int 
   return srgpt_silu_mul(gu_scratch, out, M, I, dtype, stream);
 }
 
+// C = epilogue((A @ fp8(W8)^T) * wscale): bf16 activations, OCP e4m3fn weight bytes, one fp32 scale per weight row -- the
+// prefill-side companion of srgpt_gemv_w8 (BASELINE config 5).  Always the 256 x 256 kernel (W tile staged as bytes, widened
+// to bf16 between LDS and the MFMA operands); K splits (deterministic slabs) when the tiles do not fill the chip.
 extern "C" int srgpt_gemm_w8(const void* A, const void* W8, const float* wscale, const void* bias, const void* residual,
                              void* C, int M, int N, int K, int lda, int ldc, int act, int out_f32, void* ws,
                              int64_t ws_bytes, srgpt_stream_t stream) {
@@ -793,7 +689,8 @@ extern "C" int srgpt_gemm_w8(const void* A, const void* W8, const float* wscale,
   SRGPT_CHECK(M > 0 && N > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm_w8: bad shape M=%d N=%d K=%d", M, N, K);
   SRGPT_CHECK(lda >= K, SRGPT_ERR_ARG, "srgpt_gemm_w8: lda < K");
   SRGPT_CHECK(ldc >= N, SRGPT_ERR_ARG, "srgpt_gemm_w8: ldc < N");
-  Epilogue e{bias, residual, C, M, N, ldc, act, 0, 0, out_f32, SRGPT_OUT_PLAIN, 0, nullptr, 1, 0, wscale};
+  Epilogue e = plain_epilogue(C, M, N, ldc);
+  e.bias = bias, e.residual = residual, e.act = act, e.out_f32 = out_f32, e.wscale = wscale;
   hipStream_t s = as_stream(stream);
   if (K % 64 != 0 || lda % 8 != 0 || ((uintptr_t)A % 16) || ((uintptr_t)W8 % 16)) {  // odd geometries: the scalar kernel
     hipLaunchKernelGGL(gemm_w8_simple, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, s, (const bf16_t*)A,
@@ -801,24 +698,7 @@ extern "C" int srgpt_gemm_w8(const void* A, const void* W8, const float* wscale,
     SRGPT_LAUNCH_CHECK();
     return SRGPT_OK;
   }
-  const int cus = srgpt_device_cus();
-  const int nk = K / 64;
-  const long tiles = (long)cdiv(M, 256) * cdiv(N, 256);
-  int sp = 1;
-  if (tiles < cus && ws) {
-    sp = (int)(cus / tiles);
-    if (sp > 4) sp = 4;
-    while (sp > 1 && (nk / sp < 8 || (int64_t)sp * M * N * 4 > ws_bytes)) --sp;
-  }
-  if (sp > 1) {
-    e.partial = reinterpret_cast<float*>(ws);
-    e.tiles_per_split = cdiv(nk, sp);
-    e.splits = cdiv(nk, e.tiles_per_split);
-  }
+  srgpt_splitk_apply(e, gemm_route_fp8(M, N, K / 64, 8, srgpt_device_cus(), ws != nullptr, ws_bytes), ws);
   SRGPT_TRY(srgpt_gemm256_launch(A, W8, K, lda, e, s));
-  if (e.splits > 1) {
-    launch_splitk_reduce<bf16_t>(e, s);
-    SRGPT_LAUNCH_CHECK();
-  }
-  return SRGPT_OK;
+  return srgpt_splitk_finish(e, s, nullptr);
 }

@@ -340,8 +340,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_256_kernel(const bf16_t* __r
 
 }  // namespace
 
-// e.splits / e.tiles_per_split / e.partial are set by the caller (srgpt_gemm) when it wants split-K; the deterministic
-// slab reduction (splitk_reduce_kernel in gemm.hip) follows there.
+// e.splits / e.tiles_per_split / e.partial are set by the caller (srgpt_splitk_apply) when it wants split-K; the deterministic
+// slab reduction (srgpt_splitk_finish, gemm.hip) follows there.
 int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const Epilogue& e, hipStream_t s) {
   const int gx = cdiv(e.N, G_BN), gy = cdiv(e.M, G_BM);
   const bool w8 = e.wscale != nullptr;  // fp8 weight bytes + per-row scales

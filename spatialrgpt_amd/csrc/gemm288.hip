@@ -296,8 +296,8 @@ do {                                  \
 
 }  // namespace
 
-// e.splits / e.tiles_per_split / e.partial are set by the caller (srgpt_gemm) when it wants split-K; the deterministic slab
-// reduction (splitk_reduce_kernel in gemm.hip) follows there.
+// e.splits / e.tiles_per_split / e.partial are set by the caller (srgpt_splitk_apply) when it wants split-K; the deterministic slab
+// reduction (srgpt_splitk_finish, gemm.hip) follows there.
 int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Epilogue& e, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
   SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_bf16_288_kernel, T_LDS));

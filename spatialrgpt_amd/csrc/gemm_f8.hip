@@ -18,6 +18,7 @@
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_route.h"
 #include "internal.h"
 
 namespace {
@@ -463,8 +464,8 @@ int srgpt_quant_rows_e4m3_swiglu(const void* gate_up, void* q, float* scale, int
 }
 
 // C = ((A8 @ W8^T) * ascale[m] * wscale[n] + bias[n]) + residual in bf16 (or fp32 if out_f32), no activation (the LLM's Linears
-// have none); K splits (deterministic slabs) when the 256 x 256
-// tiles do not fill the chip -- the rule of srgpt_gemm_w8.
+// have none); K splits (deterministic slabs) when the 256 x 256 tiles do not fill the chip -- gemm_route_fp8 (gemm_route.h), the
+// rule of srgpt_gemm_w8 with 4 instead of 8 K tiles per split at least.
 int srgpt_gemm_w8a8(const void* A8, const float* ascale, const void* W8, const float* wscale, const void* bias,
                     const void* residual, void* C, int M, int N, int K, int lda, int ldc, int out_f32, void* ws,
                     int64_t ws_bytes, srgpt_stream_t stream) {
@@ -475,29 +476,17 @@ int srgpt_gemm_w8a8(const void* A8, const float* ascale, const void* W8, const f
   SRGPT_CHECK(K % F_BK == 0 && K >= 2 * F_BK && lda % 16 == 0 && ((uintptr_t)A8 % 16) == 0 && ((uintptr_t)W8 % 16) == 0,
               SRGPT_ERR_UNSUPPORTED, "srgpt_gemm_w8a8: K must be a multiple of 128 (>= 256) and the rows 16-byte aligned (K=%d lda=%d)",
               K, lda);
-  Epilogue e{bias, residual, C, M, N, ldc, SRGPT_ACT_NONE, 0, 0, out_f32, SRGPT_OUT_PLAIN, 0, nullptr, 1, 0, wscale};
+  Epilogue e{};
+  e.bias = bias, e.residual = residual, e.C = C, e.M = M, e.N = N, e.ldc = ldc, e.act = SRGPT_ACT_NONE, e.out_f32 = out_f32;
+  e.out_mode = SRGPT_OUT_PLAIN, e.splits = 1, e.wscale = wscale;
   hipStream_t s = as_stream(stream);
-  const int cus = srgpt_device_cus();
-  const int nk = K / F_BK;
   const int gx = cdiv(N, F_BN), gy = cdiv(M, F_BM);
-  const long tiles = (long)gx * gy;
-  int sp = 1;
-  if (tiles < cus && ws) {
-    sp = (int)(cus / tiles);
-    if (sp > 4) sp = 4;
-    while (sp > 1 && (nk / sp < 4 || (int64_t)sp * M * N * 4 > ws_bytes)) --sp;
-  }
-  if (sp > 1) {
-    e.partial = reinterpret_cast<float*>(ws);
-    e.tiles_per_split = cdiv(nk, sp);
-    e.splits = cdiv(nk, e.tiles_per_split);
-  }
+  srgpt_splitk_apply(e, gemm_route_fp8(M, N, K / F_BK, 4, srgpt_device_cus(), ws != nullptr, ws_bytes), ws);
   static std::atomic<uint64_t> attr_done{0};
   SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_f8_256_kernel, F_LDS));
   hipLaunchKernelGGL(gemm_f8_256_kernel, dim3(gx * gy, e.splits > 1 ? e.splits : 1), dim3(512), F_LDS, s,
                      (const unsigned char*)A8, (const unsigned char*)W8, ascale, K, lda, e, gx, gy);
   SRGPT_LAUNCH_CHECK();
-  if (e.splits > 1) SRGPT_TRY(srgpt_splitk_reduce_bf16(e, s));
-  return SRGPT_OK;
+  return srgpt_splitk_finish(e, s, nullptr);
 }
 }

@@ -7,13 +7,17 @@
 #include "common.h"
 
 struct SrgptGemmEpilogue;  // gemm_epilogue.h
+struct GemmRoute;          // gemm_route.h
 
 // ---- gemm256.hip / gemm288.hip: the 256 x 256 and the whole-M (up to 272 rows) bf16 MFMA tiles, dispatched by gemm.hip ----
 int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
 int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
 
-// ---- gemm.hip: the split-K slab reduction + epilogue for kernels in other files (gemm_f8.hip) ----
-int srgpt_splitk_reduce_bf16(const SrgptGemmEpilogue& e, hipStream_t s);
+// ---- gemm.hip: split-K around a product's launch, for every GEMM launcher (gemm.hip, gemm_f8.hip): the route's split into the
+//      epilogue in front of it, the slab reduction + epilogue (when K was split) behind it; *fused (may be NULL) = the norm / RoPE
+//      of the epilogue went into the reduction ----
+void srgpt_splitk_apply(SrgptGemmEpilogue& e, const GemmRoute& r, void* ws);
+int srgpt_splitk_finish(const SrgptGemmEpilogue& e, hipStream_t s, bool* fused);
 
 // ---- skinny.hip: the MFMA decode products of 2+ rows, entered from srgpt_gemv / srgpt_gemv_rowss (gemv.hip) ----
 int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,

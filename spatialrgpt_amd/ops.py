@@ -61,6 +61,15 @@ def _splitk_ws(device, M, N):
     return t
 
 
+def _ws_arg(device, M, N, enabled=True):
+    """(pointer, byte count) of the split-K workspace for an [M, N] product as the C ABI takes them; (None, 0) -- no split-K --
+    when the caller's condition is off or the slabs would be too large."""
+    if not (enabled and M * N <= (1 << 24)):
+        return None, 0
+    ws = _splitk_ws(device, M, N)
+    return ws.data_ptr(), ws.numel()
+
+
 def gemm(a, w, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False, bias_mod=0, res_mod=0,
          out_mode=L.OUT_PLAIN, gw=0, out_shape=None):
     """act(a @ w.T + bias) + residual.  a [M,K] (row stride may exceed K), w [N,K]."""
@@ -73,9 +82,9 @@ def gemm(a, w, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False
         shape = out_shape if out_shape is not None else (M, N)
         out = torch.empty(shape, device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
     ldc = N if out_mode != L.OUT_PLAIN else out.stride(0) if out.dim() == 2 else N
-    ws = _splitk_ws(a.device, M, N) if (a.dtype == torch.bfloat16 and M * N <= (1 << 24)) else None
+    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16)
     L.check(L.load().srgpt_gemm(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, a.stride(0), ldc, act,
-                                bias_mod, res_mod, int(out_f32), out_mode, gw, _p(ws), 0 if ws is None else ws.numel(),
+                                bias_mod, res_mod, int(out_f32), out_mode, gw, ws, ws_bytes,
                                 dt_code(a), _stream()))
     return out
 
@@ -93,9 +102,9 @@ def gemm_norm(a, w, residual, norm_w, eps, bias=None, norm_b=None, out=None, y=N
         out = torch.empty((M, N), device=a.device, dtype=a.dtype)
     if y is None:
         y = torch.empty((M, N), device=a.device, dtype=a.dtype)
-    ws = _splitk_ws(a.device, M, N) if (a.dtype == torch.bfloat16 and M * N <= (1 << 24)) else None
+    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16)
     kind = L.NORM_RMS if norm_b is None else L.NORM_LAYER
-    L.check(L.load().srgpt_gemm_norm(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, _p(ws), 0 if ws is None else ws.numel(),
+    L.check(L.load().srgpt_gemm_norm(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, ws, ws_bytes,
                                      kind, _p(norm_w), _p(norm_b), _p(y), float(eps), dt_code(a), _stream()))
     return out, y
 
@@ -218,9 +227,9 @@ def gemm_w8(a, w8, wscale, bias=None, residual=None, act=L.ACT_NONE, out=None, o
     assert w8.shape[1] == K and a.stride(1) == 1 and w8.is_contiguous() and wscale.numel() == N
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
-    ws = _splitk_ws(a.device, M, N) if M * N <= (1 << 24) else None
+    ws, ws_bytes = _ws_arg(a.device, M, N)
     L.check(L.load().srgpt_gemm_w8(_p(a), _p(w8), _p(wscale), _p(bias), _p(residual), _p(out), M, N, K, a.stride(0), out.stride(0),
-                                   act, int(out_f32), _p(ws), 0 if ws is None else ws.numel(), _stream()))
+                                   act, int(out_f32), ws, ws_bytes, _stream()))
     return out
 
 
@@ -275,9 +284,9 @@ def gemm_w8a8(a8, ascale, w8, wscale, bias=None, residual=None, out=None, out_f3
     assert w8.shape[1] == K and a8.stride(1) == 1 and w8.is_contiguous() and ascale.numel() == M and wscale.numel() == N
     if out is None:
         out = torch.empty((M, N), device=a8.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
-    ws = _splitk_ws(a8.device, M, N) if M * N <= (1 << 24) else None
+    ws, ws_bytes = _ws_arg(a8.device, M, N)
     L.check(L.load().srgpt_gemm_w8a8(_p(a8), _p(ascale), _p(w8), _p(wscale), _p(bias), _p(residual), _p(out), M, N, K,
-                                     a8.stride(0), out.stride(0), int(out_f32), _p(ws), 0 if ws is None else ws.numel(),
+                                     a8.stride(0), out.stride(0), int(out_f32), ws, ws_bytes,
                                      _stream()))
     return out
 
@@ -332,8 +341,8 @@ def gemm_swiglu(a, wgu, out=None):
     if out is None:
         out = torch.empty((M, I), device=a.device, dtype=a.dtype)
     scratch = torch.empty((M, 2 * I), device=a.device, dtype=a.dtype)
-    ws = _splitk_ws(a.device, M, 2 * I) if (a.dtype == torch.bfloat16 and M * 2 * I <= (1 << 24)) else None
-    L.check(L.load().srgpt_gemm_swiglu(_p(a), _p(wgu), _p(out), M, I, K, _p(scratch), _p(ws), 0 if ws is None else ws.numel(),
+    ws, ws_bytes = _ws_arg(a.device, M, 2 * I, a.dtype == torch.bfloat16)
+    L.check(L.load().srgpt_gemm_swiglu(_p(a), _p(wgu), _p(out), M, I, K, _p(scratch), ws, ws_bytes,
                                        dt_code(a), _stream()))
     return out
 
@@ -346,9 +355,9 @@ def gemm_rope_kv_append(a, w, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D
     assert M == B * T and w.shape == (N, K) and a.is_contiguous() and w.is_contiguous()
     if qkv is None:
         qkv = torch.empty((M, N), device=a.device, dtype=a.dtype)
-    ws = _splitk_ws(a.device, M, N) if (a.dtype == torch.bfloat16 and M * N <= (1 << 24)) else None
+    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16)
     max_pos = kcache.shape[-2]
-    L.check(L.load().srgpt_gemm_rope_kv_append(_p(a), _p(w), _p(qkv), K, _p(ws), 0 if ws is None else ws.numel(), _p(kcache),
+    L.check(L.load().srgpt_gemm_rope_kv_append(_p(a), _p(w), _p(qkv), K, ws, ws_bytes, _p(kcache),
                                                _p(vcache), _p(pos0), _p(cos_tab), _p(sin_tab), B, T, Hq, Hkv, D, max_pos,
                                                dt_code(a), _stream()))
     return qkv

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/srgpt.h"
 
 typedef __bf16 bf16_t;
@@ -73,6 +75,25 @@ static inline int srgpt_ensure_dyn_lds(std::atomic<uint64_t>& done, const void* 
   }
   done.fetch_or(bit, std::memory_order_release);
   return 0;
+}
+
+// "ensure dynamic LDS, launch" for a kernel whose dynamic LDS can exceed the default limit: raises the limit of `kfn` to
+// `lds_limit` bytes (once per device; the static below is the kernel's own) and launches it with `lds` bytes
+template <auto kfn, typename... Args>
+int srgpt_launch_dyn_lds(int lds_limit, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+  static std::atomic<uint64_t> attr_done{0};
+  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)kfn, lds_limit));
+  hipLaunchKernelGGL(kfn, grid, block, lds, s, args...);
+  return 0;
+}
+
+// A route's runtime value onto a template argument: f(std::integral_constant<.., V>{}) for the V of Vs that equals v
+template <auto... Vs, typename T, typename F>
+int srgpt_switch(T v, const char* what, F&& f) {
+  int rc = 0;
+  if (((v == Vs ? (rc = f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...)) return rc;
+  srgpt_set_error("no kernel instance for %s = %d", what, (int)v);
+  return SRGPT_ERR_UNSUPPORTED;
 }
 
 static inline hipStream_t as_stream(srgpt_stream_t s) { return reinterpret_cast<hipStream_t>(s); }

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemv_route.h"
 #include "internal.h"
 
 namespace {
@@ -386,111 +387,66 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
   }
 }
 
-template <bool SWIGLU, bool NORM>
-bool launch_gemv_reg(int nit, int grid, hipStream_t s, const void* x, const void* W, const void* norm_w, float eps,
-                     const void* residual, void* out, int N, int K, int out_f32) {
-#define SRGPT_REG_CASE(NITV)                                                                                                   \
-  case NITV:                                                                                                                   \
-    hipLaunchKernelGGL((gemv_reg_kernel<SWIGLU, NORM, NITV>), dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)W, \
-                       (const bf16_t*)norm_w, eps, (const bf16_t*)residual, out, N, K, out_f32);                               \
-    return true
-  switch (nit) {
-    SRGPT_REG_CASE(5);   // K = 2560
-    SRGPT_REG_CASE(8);   // K = 4096
-    SRGPT_REG_CASE(14);  // K = 6912
-    default: break;
-  }
-  return false;  // longer rows (K = 11008, 14336: 88-112 VGPRs of activations, spills when unrolled) stay on the LDS kernel
-#undef SRGPT_REG_CASE
-}
-
-template <typename T, int B>
-int launch_gemv(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out, int N,
-                int K, int swiglu, int out_f32, hipStream_t s) {
-  const size_t lds = (size_t)B * K * sizeof(T);
-  SRGPT_CHECK(lds <= 150 * 1024, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv: batch*K too large for LDS (%zu bytes)", lds);
-  const int cus = srgpt_device_cus();
-  // (round 5, measured and not kept: 3 / 4 / 5 blocks per CU for the short launches -- q/k/v, o_proj, where a wave owns only 2 - 3 rows,
-  // i.e. 2 - 3 dependent memory round trips: 2.970 -> 2.998 / 3.009 / 3.017 ms per token; for all launches 3.037 / 3.049:
-  // profiles/r05_decode_step_ab.txt)
-  const int per_cu = lds > 70 * 1024 ? 1 : 2;
-  int grid = (N + 3) / 4;
-  if (grid > cus * per_cu) grid = cus * per_cu;
-  if (grid < 1) grid = 1;
-  const int chunks = B * (K / WChunk<T>::VEC);
-  if (B == 1 && sizeof(T) == 2) {
-    const int nit = (K / 8 + 63) / 64;
-    // measured (scripts/experiments/ubench_gemv_c.hip): without the fused RMSNorm the register variant saves 0.6-0.8 us per launch
-    // (o_proj 8.5 -> 7.9 us); with it every wave normalises the whole row redundantly and loses ~1 us -> LDS kernel
-    bool ok = false;
-    if (!norm_w)
-      ok = swiglu ? launch_gemv_reg<true, false>(nit, grid, s, x, W, norm_w, eps, residual, out, N, K, out_f32)
-                  : launch_gemv_reg<false, false>(nit, grid, s, x, W, norm_w, eps, residual, out, N, K, out_f32);
-    if (ok) {
-      SRGPT_LAUNCH_CHECK();
-      return SRGPT_OK;
+// one launch of up to 4 rows on the route's VALU kernel (GEMV_LDS or GEMV_REG)
+template <typename T>
+int launch_gemv(GemvFamily family, const DecodeProduct& p, hipStream_t s) {
+  const GemvValuLaunch l = gemv_valu_launch(family, p.batch, p.N, p.K, sizeof(T) == 2, p.swiglu != 0, srgpt_device_cus());
+  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv: batch*K too large for LDS (%zu bytes)", (size_t)l.lds);
+  const T *x = (const T*)p.x, *W = (const T*)p.W, *norm_w = (const T*)p.norm_w, *residual = (const T*)p.residual;
+  SRGPT_TRY((srgpt_switch<false, true>(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
+    constexpr bool SW = decltype(sw_c)::value;
+    if constexpr (sizeof(T) == 2) {
+      if (family == GEMV_REG)
+        return srgpt_switch<5, 8, 14>(l.NIT, "NIT", [&](auto nit_c) {  // K = 2560, 4096, 6912
+          hipLaunchKernelGGL((gemv_reg_kernel<SW, false, decltype(nit_c)::value>), dim3(l.grid), dim3(256), 0, s, x, W, norm_w, p.eps,
+                             residual, p.out, p.N, p.K, p.out_f32);
+          return (int)SRGPT_OK;
+        });
     }
-  }
-#define SRGPT_GEMV_LAUNCH(SW, NXV, ...)                                                                         \
-  do {                                                                                                          \
-    auto kfn = gemv_kernel<T, B, SW, NXV, ##__VA_ARGS__>;                                                       \
-    static std::atomic<uint64_t> attr_done{0};                                                                  \
-    SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)kfn, lds > 48 * 1024 ? 150 * 1024 : 0));             \
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, s, (const T*)x, (const T*)W, (const T*)norm_w, eps,     \
-                       (const T*)residual, out, N, K, out_f32);                                                 \
-  } while (0)
-  const int nit = (K / WChunk<T>::VEC + 63) / 64;
-  if (swiglu) {
-    if (chunks <= 512) SRGPT_GEMV_LAUNCH(true, 2); else SRGPT_GEMV_LAUNCH(true, 8);
-  } else if (B == 1 && sizeof(T) == 2 && nit % 7 == 0 && nit % 8 != 0 && chunks > 512) {
-    SRGPT_GEMV_LAUNCH(false, 8, 7);
-  } else {
-    if (chunks <= 512) SRGPT_GEMV_LAUNCH(false, 2); else SRGPT_GEMV_LAUNCH(false, 8);
-  }
-#undef SRGPT_GEMV_LAUNCH
+    return srgpt_switch<1, 2, 3, 4>(l.B, "B", [&](auto b_c) {
+      return srgpt_switch<2, 8>(l.NX, "NX", [&](auto nx_c) {
+        constexpr int B = decltype(b_c)::value, NX = decltype(nx_c)::value;
+        const auto go = [&](auto ub_c) {
+          constexpr auto kfn = &gemv_kernel<T, B, SW, NX, decltype(ub_c)::value>;
+          return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, x, W, norm_w,
+                                           p.eps, residual, p.out, p.N, p.K, p.out_f32);
+        };
+        if constexpr (!SW && NX == 8) {  // the only instances with batches of 7 loads (scripts/compare_isa.py guards the instance set)
+          if (l.UB == 7) return go(std::integral_constant<int, 7>{});
+        }
+        return go(std::integral_constant<int, 8>{});
+      });
+    });
+  })));
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
-// bf16 rows >= this go to the MFMA kernel of skinny.hip
-constexpr int SKINNY_MIN_BATCH = 2;  // measured (round 3, profiles/r03_skinny_min_batch.txt): VALU wins at 1 row, MFMA from 2
-
-template <typename T>
-int dispatch_b(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
-               int batch, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  if (batch > 4 || (sizeof(T) == 2 && batch >= SKINNY_MIN_BATCH)) {
-    // bf16: rows go through the MFMA skinny kernel 16 at a time (skinny.hip); fp32 (parity dtype of the tiny models):
-    // 4 rows at a time through the VALU kernel.  Each chunk streams the weights once.
-    const bool mfma = sizeof(T) == 2;
-    int step = mfma ? 16 : 4;
-    if (!mfma)
-      while (step > 1 && (size_t)step * K * sizeof(T) > 150 * 1024) --step;
-    const size_t on = out_f32 ? sizeof(float) : sizeof(T);
-    for (int b0 = 0; b0 < batch; b0 += step) {
-      const int nb = batch - b0 < step ? batch - b0 : step;
-      const void* xb = (const char*)x + (size_t)b0 * K * sizeof(T);
-      const void* rb = residual ? (const char*)residual + (size_t)b0 * N * sizeof(T) : nullptr;
-      void* ob = (char*)out + (size_t)b0 * N * on;
-      // (a single-row tail of a longer batch -- 17, 33 rows -- stays on the kernel its other rows took, as srgpt_gemv_rowss does)
-      if (mfma && (nb > 4 || nb >= SKINNY_MIN_BATCH || b0 > 0))
-        SRGPT_TRY(srgpt_skinny_launch(xb, W, norm_w, eps, rb, ob, nb, N, K, swiglu, out_f32, nullptr, nullptr, 0, s));
-      else
-        SRGPT_TRY((dispatch_b<T>(xb, W, norm_w, eps, rb, ob, nb, N, K, swiglu, out_f32, s)));
-    }
-    return SRGPT_OK;
-  }
-  switch (batch) {
-    case 1: return launch_gemv<T, 1>(x, W, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
-    case 2: return launch_gemv<T, 2>(x, W, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
-    case 3: return launch_gemv<T, 3>(x, W, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
-    case 4: return launch_gemv<T, 4>(x, W, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
-    default:
-      srgpt_set_error("srgpt_gemv: batch %d not supported", batch);
-      return SRGPT_ERR_UNSUPPORTED;
-  }
-}
-
 }  // namespace
+
+// The decode products' one way in: srgpt_gemv, srgpt_gemv_w8 (skinny.hip) and srgpt_gemv_rowss validate and come here.  The route
+// (gemv_route.h) names the kernel family and the rows per weight pass; every pass takes its rows of x, residual, out and both
+// statistics tables.
+int srgpt_decode_product(const DecodeProduct& p, hipStream_t s) {
+  const bool bf16 = p.dtype == SRGPT_BF16;
+  const GemvRoute r = gemv_route(p.batch, p.K, bf16, p.fp8 != 0, p.norm_w != nullptr);
+  const size_t es = dtype_size(p.dtype), on = p.out_f32 ? sizeof(float) : es;
+  for (int b0 = 0; b0 < p.batch; b0 += r.chunk) {
+    DecodeProduct c = p;
+    c.batch = p.batch - b0 < r.chunk ? p.batch - b0 : r.chunk;
+    c.x = (const char*)p.x + (size_t)b0 * p.K * es;
+    if (p.residual) c.residual = (const char*)p.residual + (size_t)b0 * p.N * es;
+    c.out = (char*)p.out + (size_t)b0 * p.N * on;
+    if (p.ss_in) c.ss_in = p.ss_in + (size_t)b0 * SRGPT_ROWSS_STRIDE;
+    if (p.ss_out) c.ss_out = p.ss_out + (size_t)b0 * SRGPT_ROWSS_STRIDE;
+    switch (r.family) {
+      case GEMV_SKINNY: SRGPT_TRY(srgpt_skinny_launch(c, s)); break;
+      case GEMV_W8: SRGPT_TRY(srgpt_gemv_w8_valu(c, s)); break;
+      default: SRGPT_TRY(bf16 ? launch_gemv<bf16_t>(r.family, c, s) : launch_gemv<float>(r.family, c, s));
+    }
+  }
+  return SRGPT_OK;
+}
 
 extern "C" int srgpt_gemv(const void* x, const void* W, const void* norm_w, float norm_eps, const void* residual,
                           void* out, int batch, int N, int K, int swiglu, int out_f32, int dtype,
@@ -501,19 +457,17 @@ extern "C" int srgpt_gemv(const void* x, const void* W, const void* norm_w, floa
   const int vec = dtype == SRGPT_BF16 ? 8 : 4;
   SRGPT_CHECK(K % vec == 0, SRGPT_ERR_ARG, "srgpt_gemv: K=%d must be a multiple of %d", K, vec);
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv: swiglu excludes residual/out_f32");
-  hipStream_t s = as_stream(stream);
-  if (dtype == SRGPT_BF16)
-    return dispatch_b<bf16_t>(x, W, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, s);
-  return dispatch_b<float>(x, W, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, s);
+  return srgpt_decode_product(DecodeProduct{x, W, nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, dtype, 0,
+                                            nullptr, nullptr, 0},
+                              as_stream(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
 // The same products with the row-statistics hand-off of skinny.hip (ABI 8): bf16 activations, 2+ rows (the MFMA kernel).
 // ------------------------------------------------------------------------------------------------
+static_assert(GEMV_ROWSS_SLOTS == SRGPT_ROWSS_STRIDE, "gemv_route.h counts the slots of include/srgpt.h's tables");
 extern "C" int srgpt_gemv_rowss_supported(int batch, int dtype, int fp8) {
-  if (dtype != SRGPT_BF16 || batch < 2) return 0;
-  if (2 * srgpt_device_cus() > SRGPT_ROWSS_STRIDE) return 0;  // one slot per producer block (two 4-wave blocks per CU)
-  return fp8 ? (batch > W8_VALU_MAX_BATCH ? 1 : 0) : (batch >= SKINNY_MIN_BATCH ? 1 : 0);
+  return gemv_rowss_supported(batch, dtype == SRGPT_BF16, fp8 != 0, srgpt_device_cus()) ? 1 : 0;
 }
 
 extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,
@@ -529,15 +483,7 @@ extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, co
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_rowss: swiglu excludes residual/out_f32");
   SRGPT_CHECK(srgpt_gemv_rowss_supported(batch, SRGPT_BF16, W8 != nullptr), SRGPT_ERR_UNSUPPORTED,
               "srgpt_gemv_rowss: %d row(s) of %s weights take a kernel without the statistics hand-off", batch, W8 ? "fp8" : "bf16");
-  hipStream_t s = as_stream(stream);
-  if (W8) return srgpt_skinny_w8_launch(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, rowss_in, rowss_out, packed_rows, s);
-  const size_t on = out_f32 ? sizeof(float) : 2;
-  for (int b0 = 0; b0 < batch; b0 += 16) {
-    const int nb = batch - b0 < 16 ? batch - b0 : 16;
-    SRGPT_TRY(srgpt_skinny_launch((const char*)x + (size_t)b0 * K * 2, W, norm_w, norm_eps,
-                                  residual ? (const char*)residual + (size_t)b0 * N * 2 : nullptr, (char*)out + (size_t)b0 * N * on, nb,
-                                  N, K, swiglu, out_f32, rowss_in ? rowss_in + (size_t)b0 * SRGPT_ROWSS_STRIDE : nullptr,
-                                  rowss_out ? rowss_out + (size_t)b0 * SRGPT_ROWSS_STRIDE : nullptr, packed_rows, s));
-  }
-  return SRGPT_OK;
+  return srgpt_decode_product(DecodeProduct{x, W8 ? W8 : W, W8 ? wscale : nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu,
+                                            out_f32, SRGPT_BF16, W8 != nullptr, rowss_in, rowss_out, packed_rows},
+                              as_stream(stream));
 }

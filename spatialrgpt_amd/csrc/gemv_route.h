@@ -1,0 +1,159 @@
+// Which kernel a decode product runs on, with which template arguments and launch shape, and how a call of many rows is cut into
+// weight passes: the host-side selection of gemv.hip / gemv_w8.hip / skinny.hip as pure functions of the shape and the CU count.
+// Plain C++ (no HIP): tests/test_host_gemv_route.py compiles this header alone and pins the launch of every product of the decode
+// step (tests/golden/gemv_routes.json) -- every threshold below was calibrated on the MI355X, and all routes compute the same bits,
+// so nothing else notices a slipped comparison.
+#pragma once
+
+enum GemvFamily {
+  GEMV_LDS,     // gemv_kernel<T, B, SWIGLU, NX, UB> (gemv.hip): VALU, 1 - 4 rows staged in LDS
+  GEMV_REG,     // gemv_reg_kernel<SWIGLU, false, NIT> (gemv.hip): VALU, one bf16 row held in registers
+  GEMV_W8,      // gemv_w8_kernel<1, SWIGLU, NX> (gemv_w8.hip): VALU, one bf16 row, fp8 weights
+  GEMV_SKINNY,  // skinny_kernel<SWIGLU, NI, NW, W8, PUB, PK> (skinny.hip): MFMA, up to 16 bf16 rows
+};
+
+// How a call is cut: ceil(rows / chunk) launches of up to `chunk` rows, each streaming the weights once, ALL on `family` -- a
+// single-row tail of a longer call (17, 33 rows) stays on the kernel its other rows took
+struct GemvRoute {
+  GemvFamily family;
+  int chunk;
+};
+
+// VALU families (256 threads per block)
+struct GemvValuLaunch {
+  int B;          // rows (GEMV_LDS: the template argument)
+  int NX;         // activation chunks a thread of the prologue holds in registers (GEMV_LDS, GEMV_W8)
+  int UB;         // weight loads per batch (GEMV_LDS)
+  int NIT;        // 64-lane chunk iterations per row (GEMV_REG: the template argument)
+  int grid;
+  long long lds;  // dynamic LDS bytes: the activation rows (GEMV_REG: none); above GEMV_LDS_CAP the launch is refused
+  bool raise_lds_limit;  // more than the 48 KiB a kernel gets unasked: needs the GEMV_LDS_CAP attribute
+};
+
+// MFMA family (64 * NW threads per block)
+struct GemvSkinnyLaunch {
+  int NI;         // x rows staged per wave / 2
+  int NW;         // waves per block (the K split)
+  bool PUB, PK;   // statistics read from the producer's table; weights in the packed layout
+  int grid, cw;   // block b owns output columns [b cw, (b + 1) cw)
+  int gr_shift;   // log2 of the packed granule's rows (row-major: unused)
+  int lds;        // dynamic LDS bytes (above 48 KiB the launcher raises the kernel's limit to exactly this)
+};
+
+// bf16 rows >= this go to the MFMA kernel of skinny.hip
+constexpr int SKINNY_MIN_BATCH = 2;  // measured (round 3, profiles/r03_skinny_min_batch.txt): VALU wins at 1 row, MFMA from 2
+// fp8 rows at or below this count take the one-row VALU kernel of gemv_w8.hip (which neither reads nor publishes row statistics)
+constexpr int W8_VALU_MAX_BATCH = 1;  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
+constexpr int GEMV_LDS_CAP = 150 * 1024;  // dynamic LDS a VALU kernel may ask for
+constexpr int GEMV_ROWSS_SLOTS = 512;     // SRGPT_ROWSS_STRIDE (include/srgpt.h): one slot per producer block
+
+namespace gemv_route_detail {
+
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// 2+ bf16 rows on the MFMA kernel?  (the VALU kernels hold at most 4 rows)
+inline bool rows_take_mfma(int rows, bool fp8) { return fp8 ? rows > W8_VALU_MAX_BATCH : rows > 4 || rows >= SKINNY_MIN_BATCH; }
+
+// the register kernel's instances: K = 2560, 4096, 6912; longer rows (K = 11008, 14336: 88 - 112 VGPRs of activations, spills when
+// unrolled) stay on the LDS kernel
+inline bool reg_kernel_nit(int nit) { return nit == 5 || nit == 8 || nit == 14; }
+
+// The grid of the VALU kernels, a wave per unit and four waves per block: two blocks per CU, one where the rows fill over 70 KiB of
+// LDS.  (round 5, measured and not kept: 3 / 4 / 5 blocks per CU for the short launches -- q/k/v, o_proj, where a wave owns only
+// 2 - 3 rows, i.e. 2 - 3 dependent memory round trips: 2.970 -> 2.998 / 3.009 / 3.017 ms per token; for all launches 3.037 / 3.049:
+// profiles/r05_decode_step_ab.txt)
+inline int valu_grid(int units, long long lds, int cus) {
+  const int per_cu = lds > 70 * 1024 ? 1 : 2;
+  int grid = ceil_div(units, 4);
+  if (grid > cus * per_cu) grid = cus * per_cu;
+  return grid < 1 ? 1 : grid;
+}
+
+// NXMAX of the VALU prologues: 2 chunks of 16 activation bytes per thread cover 512, else 8 (past 2048 the kernel loops)
+inline int valu_nx(int chunks) { return chunks <= 512 ? 2 : 8; }
+
+}  // namespace gemv_route_detail
+
+// srgpt_gemv (bf16 / fp32), srgpt_gemv_w8 (fp8) and srgpt_gemv_rowss (bf16 or fp8, with the statistics hand-off): `rows` x K
+// activations, bf16 or fp32 (the parity dtype of the tiny models); fp8: OCP e4m3 weights, bf16 activations; norm: RMSNorm prologue
+inline GemvRoute gemv_route(int rows, int K, bool bf16, bool fp8, bool norm) {
+  using namespace gemv_route_detail;
+  if (fp8) {
+    // one row: VALU kernel, like the bf16 path (its 16-byte weight chunks need K % 16 == 0); else 16 rows per weight pass
+    if (!rows_take_mfma(rows, true) && K % 16 == 0) return GemvRoute{GEMV_W8, rows};
+    return GemvRoute{GEMV_SKINNY, 16};
+  }
+  if (bf16) {
+    if (rows_take_mfma(rows, false)) return GemvRoute{GEMV_SKINNY, 16};  // 16 rows = the M side of one MFMA tile
+    // measured (scripts/experiments/ubench_gemv_c.hip): without the fused RMSNorm the register variant saves 0.6-0.8 us per launch
+    // (o_proj 8.5 -> 7.9 us); with it every wave normalises the whole row redundantly and loses ~1 us -> LDS kernel
+    if (rows == 1 && !norm && reg_kernel_nit(ceil_div(K / 8, 64))) return GemvRoute{GEMV_REG, 1};
+    return GemvRoute{GEMV_LDS, rows};
+  }
+  // fp32: up to 4 rows per launch; a longer call takes 4 at a time, fewer where 4 rows of K do not fit the LDS cap
+  if (rows <= 4) return GemvRoute{GEMV_LDS, rows};
+  int step = 4;
+  while (step > 1 && (long long)step * K * 4 > GEMV_LDS_CAP) --step;
+  return GemvRoute{GEMV_LDS, step};
+}
+
+// Does (rows, dtype, fp8) take the kernel with the row-statistics hand-off (srgpt_gemv_rowss)?  The MFMA kernel, and a table with
+// one slot per producer block (two 4-wave blocks per CU).
+inline bool gemv_rowss_supported(int rows, bool bf16, bool fp8, int cus) {
+  return bf16 && rows >= 2 && 2 * cus <= GEMV_ROWSS_SLOTS && gemv_route_detail::rows_take_mfma(rows, fp8);
+}
+
+// one launch of a VALU family: B rows (one chunk of the route)
+inline GemvValuLaunch gemv_valu_launch(GemvFamily family, int B, int N, int K, bool bf16, bool swiglu, int cus) {
+  using namespace gemv_route_detail;
+  const int vec = bf16 ? 8 : 4;  // activation elements per 16-byte chunk
+  GemvValuLaunch l{B, 0, 8, 0, 0, (long long)B * K * (bf16 ? 2 : 4), false};
+  l.raise_lds_limit = l.lds > 48 * 1024;
+  l.NX = valu_nx(B * (K / vec));
+  if (family == GEMV_W8) {  // a unit is two output columns
+    l.grid = valu_grid((N + 1) / 2, l.lds, cus);
+    return l;
+  }
+  l.grid = valu_grid(N, l.lds, cus);
+  l.NIT = ceil_div(K / vec, 64);
+  if (family == GEMV_REG) {
+    l.lds = 0;
+    l.raise_lds_limit = false;
+    return l;
+  }
+  // batches of 7 loads for rows whose chunk iterations are a multiple of 7 and not of 8 (K = 14336, down_proj: 28 iterations are
+  // 4 batches of 7, where batches of 8 spent every row's fourth batch half on clamped re-reads of the row's last chunk)
+  if (!swiglu && B == 1 && bf16 && l.NIT % 7 == 0 && l.NIT % 8 != 0 && l.NX == 8) l.UB = 7;
+  return l;
+}
+
+// dynamic LDS of a skinny_kernel block: per wave an activation stage of 2 NI rows and (row-major weights) a 16-row weight stage,
+// rows padded to 544 bytes; reused for the cross-wave reduction of 4 sub-units x 64 lanes x 4 floats per wave
+constexpr int GEMV_SKINNY_ROW_BYTES = 512 + 32, GEMV_SKINNY_SUBUNITS = 4;
+constexpr int gemv_skinny_lds(int NI, int NW, bool PK) {
+  const int stages = NW * (2 * NI + (PK ? 0 : 16)) * GEMV_SKINNY_ROW_BYTES, reduction = NW * GEMV_SKINNY_SUBUNITS * 64 * 4 * 4;
+  return stages > reduction ? stages : reduction;
+}
+
+// one launch of the MFMA family: up to 16 rows (one chunk of the route)
+inline GemvSkinnyLaunch gemv_skinny_launch(int rows, int N, bool norm, bool ss_in, int packed, int cus) {
+  using namespace gemv_route_detail;
+  GemvSkinnyLaunch l{};
+  l.NI = rows <= 4 ? 2 : rows <= 8 ? 4 : 8;
+  // Two 4-wave blocks per CU, or one 8-wave block per CU; both split the columns evenly over their blocks.  Measured per decode
+  // step (profiles/r02_skinny_ab.txt): 4-wave blocks win (o_proj 8.8 vs 9.7 us, fp8 gate/up 27.4 vs 30.4) except where a block
+  // would own few columns AND has the RMSNorm statistics to compute first (q/k/v: 24 columns per CU, 14.1 vs 14.3 us bf16,
+  // 12.3 vs 13.7 fp8) -- there the prologue is shared by twice the threads.
+  const int ncol = ceil_div(N, cus);  // output columns per CU
+  l.NW = norm && ncol <= 32 ? 8 : 4;
+  const int blocks = l.NW == 8 ? cus : 2 * cus;
+  l.cw = ceil_div(N, blocks);
+  if (l.cw < 16) l.cw = 16;  // at least one whole 16-column tile
+  l.gr_shift = packed == 16 ? 4 : packed == 8 ? 3 : 2;
+  if (packed) l.cw = ceil_div(l.cw, packed) * packed;  // whole granules
+  l.grid = ceil_div(N, l.cw);
+  l.PUB = ss_in;
+  l.PK = packed != 0;
+  l.lds = gemv_skinny_lds(l.NI, l.NW, l.PK);
+  return l;
+}

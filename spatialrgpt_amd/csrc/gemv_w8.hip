@@ -10,10 +10,11 @@
 //   * weights are widened with v_cvt_pk_f32_fp8 (OCP e4m3fn on gfx950), 2 values per instruction; the two rows of a unit
 //     share the fp32 copies of x;
 //   * the per-row scale multiplies the reduced dot product.
-// 2+ rows go through the MFMA skinny kernel (skinny.hip, W8 variant: W8_VALU_MAX_BATCH in internal.h).
+// 2+ rows go through the MFMA skinny kernel (skinny.hip, W8 variant: W8_VALU_MAX_BATCH in gemv_route.h).
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemv_route.h"
 #include "internal.h"
 
 namespace {
@@ -248,40 +249,22 @@ __global__ __launch_bounds__(256, 2) void gemv_w8_kernel(const T* __restrict__ x
   }
 }
 
-template <int B>
-int launch_gemv_w8(const void* x, const void* W, const float* wscale, const void* norm_w, float eps, const void* residual,
-                   void* out, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  const size_t lds = (size_t)B * K * sizeof(T);
-  SRGPT_CHECK(lds <= 150 * 1024, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv_w8: batch*K too large for LDS (%zu bytes)", lds);
-  const int cus = srgpt_device_cus();
-  const int per_cu = lds > 70 * 1024 ? 1 : 2;
-  const int nunit = (N + 1) / 2;
-  int grid = (nunit + 3) / 4;
-  if (grid > cus * per_cu) grid = cus * per_cu;
-  if (grid < 1) grid = 1;
-  const int chunks = B * (K / 8);
-#define SRGPT_W8_LAUNCH(SW, NXV)                                                                               \
-  do {                                                                                                         \
-    auto kfn = gemv_w8_kernel<B, SW, NXV>;                                                                     \
-    static std::atomic<uint64_t> attr_done{0};                                                                 \
-    SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)kfn, lds > 48 * 1024 ? 150 * 1024 : 0));            \
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, s, (const T*)x, (const unsigned char*)W, wscale,       \
-                       (const T*)norm_w, eps, (const T*)residual, out, N, K, out_f32);                         \
-  } while (0)
-  if (swiglu) {
-    if (chunks <= 512) SRGPT_W8_LAUNCH(true, 2); else SRGPT_W8_LAUNCH(true, 8);
-  } else {
-    if (chunks <= 512) SRGPT_W8_LAUNCH(false, 2); else SRGPT_W8_LAUNCH(false, 8);
-  }
-#undef SRGPT_W8_LAUNCH
-  SRGPT_LAUNCH_CHECK();
-  return SRGPT_OK;
-}
-
 }  // namespace
 
-// host entry used by srgpt_gemv_w8 (skinny.hip) for one row (batch == 1); K must be a multiple of 16 here
-int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const void* norm_w, float eps,
-                       const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  return launch_gemv_w8<1>(x, W8, wscale, norm_w, eps, residual, out, N, K, swiglu, out_f32, s);
+// one row on the VALU kernel (GEMV_W8 of gemv_route.h), entered from srgpt_decode_product (gemv.hip)
+int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s) {
+  const GemvValuLaunch l = gemv_valu_launch(GEMV_W8, p.batch, p.N, p.K, true, p.swiglu != 0, srgpt_device_cus());
+  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv_w8: batch*K too large for LDS (%zu bytes)", (size_t)l.lds);
+  SRGPT_TRY((srgpt_switch<false, true>(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
+    return srgpt_switch<1>(l.B, "B", [&](auto b_c) {
+      return srgpt_switch<2, 8>(l.NX, "NX", [&](auto nx_c) {
+        constexpr auto kfn = &gemv_w8_kernel<decltype(b_c)::value, decltype(sw_c)::value, decltype(nx_c)::value>;
+        return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, (const T*)p.x,
+                                         (const unsigned char*)p.W, p.wscale, (const T*)p.norm_w, p.eps, (const T*)p.residual, p.out,
+                                         p.N, p.K, p.out_f32);
+      });
+    });
+  })));
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
 }

@@ -19,19 +19,26 @@ int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Srg
 void srgpt_splitk_apply(SrgptGemmEpilogue& e, const GemmRoute& r, void* ws);
 int srgpt_splitk_finish(const SrgptGemmEpilogue& e, hipStream_t s, bool* fused);
 
-// ---- skinny.hip: the MFMA decode products of 2+ rows, entered from srgpt_gemv / srgpt_gemv_rowss (gemv.hip) ----
-int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
-                        int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
-                        hipStream_t s);
-int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
-                           const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
-                           const float* ss_in, float* ss_out, int packed, hipStream_t s);
-// fp8 rows at or below this count take the one-row VALU kernel of gemv_w8.hip (which neither reads nor publishes row statistics)
-constexpr int W8_VALU_MAX_BATCH = 1;  // 2 rows: the MFMA kernel is 7 % faster per step (round 3)
-
-// ---- gemv_w8.hip: the one-row VALU kernel, entered from srgpt_gemv_w8 (skinny.hip) ----
-int srgpt_gemv_w8_valu(const void* x, const void* W8, const float* wscale, const void* norm_w, float eps,
-                       const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, hipStream_t s);
+// ---- the decode products (gemv.hip, gemv_w8.hip, skinny.hip) ----
+// One product as its entry point received it.  W: dtype weights, or (fp8) e4m3 bytes with wscale, row-major or packed (`packed` rows
+// per granule); ss_in / ss_out: the rows' statistics tables of srgpt_gemv_rowss, or NULL
+struct DecodeProduct {
+  const void *x, *W;
+  const float* wscale;
+  const void* norm_w;
+  float eps;
+  const void* residual;
+  void* out;
+  int batch, N, K, swiglu, out_f32, dtype, fp8;
+  const float* ss_in;
+  float* ss_out;
+  int packed;
+};
+// gemv.hip: the way in for the validated arguments of srgpt_gemv, srgpt_gemv_w8 and srgpt_gemv_rowss -- asks gemv_route.h for the
+// kernel family and the rows per weight pass, and hands every pass (`batch` = its rows) to that family's launcher:
+int srgpt_decode_product(const DecodeProduct& p, hipStream_t s);
+int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s);  // skinny.hip: MFMA, up to 16 bf16 rows, bf16 or fp8 weights
+int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s);   // gemv_w8.hip: VALU, one row, fp8 weights (K % 16 == 0)
 
 // ---- attn.hip: the decode attention with the L2 prefetch of the next GEMV's weights, and its arrival tickets, for model.hip ----
 int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemv_route.h"
 #include "internal.h"
 
 namespace {
@@ -641,9 +642,9 @@ extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_stat
 namespace {
 
 // ---- decode step ----
-// One product of the decode step, by the route the weights and the batch allow.  pub: 2+ bf16 rows (the MFMA kernel): o_proj /
-// down_proj publish the sum of squares of the rows they write (ss_out), the RMSNorm of the next product reads 512 partial sums per
-// row (ss_in) instead of re-reading every row in every block (skinny.hip).  The per-op form of exactly this is srgpt_gemv_rowss.
+// One product of the decode step, by the entry the step's route (gemv_route.h) and the weights allow.  pub: 2+ bf16 rows (the MFMA
+// kernel): o_proj / down_proj publish the sum of squares of the rows they write (ss_out), the RMSNorm of the next product reads 512
+// partial sums per row (ss_in) instead of re-reading every row in every block (skinny.hip): the per-op form is srgpt_gemv_rowss.
 struct DecodeStep {
   const srgpt_llm_weights* w;
   int B;
@@ -652,9 +653,9 @@ struct DecodeStep {
 
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
            const float* ss_in, float* ss_out) const {
-    if (pub && m.pk != nullptr)  // the MFMA kernel reads the packed copy
-      return srgpt_gemv_rowss(x, nullptr, m.pk, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, m.pk_rows, stream);
-    if (pub) return srgpt_gemv_rowss(x, m.w, m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out, 0, stream);
+    if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
+      return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out,
+                              m.pk ? m.pk_rows : 0, stream);
     if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
     return srgpt_gemv(x, m.w, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, w->dtype, stream);
   }
@@ -685,7 +686,7 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
     SRGPT_LAUNCH_CHECK();
   }
   const bool fp8 = fmt != FMT_DTYPE;
-  const DecodeStep ds{w, B, fp8, srgpt_gemv_rowss_supported(B, dt, fp8 ? 1 : 0) != 0, stream};
+  const DecodeStep ds{w, B, fp8, gemv_rowss_supported(B, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
   // the row statistics (layer 0's q/k/v normalises the embedding rows itself)
   float* const ss_attn = d.rowss;                                       // rows after the attention block's residual add
   float* const ss_mlp = d.rowss + (size_t)B * SRGPT_ROWSS_STRIDE;       // rows after the MLP block's

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gemv_route.h"
 #include "internal.h"
 
 namespace {
@@ -564,103 +565,48 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   }
 }
 
-template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK>
-int launch_skinny(const void* x, const void* W, const float* wscale, const void* norm_w, float eps, const void* residual,
-                  void* out, int batch, int N, int K, int out_f32, int grid, int cw, const float* ss_in, float* ss_out,
-                  int gr_shift, hipStream_t s) {
-  constexpr int lds_k = NW * (2 * NI * WROWB + (PK ? 0 : WSTAGEB)), lds_r = NW * MAXSU * 64 * 4 * 4;  // K loop stages | reduction buffer
-  constexpr int lds = lds_k > lds_r ? lds_k : lds_r;
-  static_assert(lds <= 160 * 1024, "LDS");
-  static_assert(NW == 8 || 2 * lds <= 160 * 1024, "two 4-wave blocks per CU");
-  auto kfn = skinny_kernel<SWIGLU, NI, NW, W8, PUB, PK>;
-  static std::atomic<uint64_t> attr_done{0};
-  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)kfn, lds));
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(64 * NW), lds, s, (const bf16_t*)x, W, wscale, (const bf16_t*)norm_w, eps,
-                     (const bf16_t*)residual, out, batch, N, K, out_f32, cw, ss_in, ss_out, gr_shift);
-  SRGPT_LAUNCH_CHECK();
-  return SRGPT_OK;
-}
-
-template <bool SWIGLU, int NI, bool W8>
-int launch_skinny_nw(const void* x, const void* W, const float* wscale, const void* norm_w, float eps, const void* residual,
-                     void* out, int batch, int N, int K, int out_f32, const float* ss_in, float* ss_out, int packed, hipStream_t s) {
-  // Two 4-wave blocks per CU, or one 8-wave block per CU; both split the columns evenly over their blocks.  Measured per decode
-  // step (profiles/r02_skinny_ab.txt): 4-wave blocks win (o_proj 8.8 vs 9.7 us, fp8 gate/up 27.4 vs 30.4) except where a block
-  // would own few columns AND has the RMSNorm statistics to compute first (q/k/v: 24 columns per CU, 14.1 vs 14.3 us bf16,
-  // 12.3 vs 13.7 fp8) -- there the prologue is shared by twice the threads.
-  const int cus = srgpt_device_cus();
-  const int ncol = (N + cus - 1) / cus;  // output columns per CU
-  const int waves = (norm_w != nullptr && ncol <= 32) ? 8 : 4;
-  const int blocks = waves == 8 ? cus : 2 * cus;
-  int cw = (N + blocks - 1) / blocks;
-  if (cw < 16) cw = 16;
-  const int gr_shift = packed == 16 ? 4 : packed == 8 ? 3 : 2;
-  if (packed) cw = ((cw + packed - 1) / packed) * packed;  // whole granules
-  const int grid = (N + cw - 1) / cw;
-  SRGPT_CHECK(!ss_out || grid <= SRGPT_ROWSS_STRIDE, SRGPT_ERR_UNSUPPORTED, "skinny: %d blocks do not fit the %d row-statistics slots",
-              grid, SRGPT_ROWSS_STRIDE);
-#define SKINNY_GO(NWV, PUBV, PKV) \
-  return launch_skinny<SWIGLU, NI, NWV, W8, PUBV, PKV>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, grid, cw, ss_in, ss_out, gr_shift, s)
-  if (packed) {
-    SRGPT_CHECK(K % (W8 ? 64 : 32) == 0 && (!SWIGLU || N % packed == 0), SRGPT_ERR_UNSUPPORTED,
-                "skinny: the packed weight layout needs K %% %d == 0 (K = %d)%s", W8 ? 64 : 32, K, SWIGLU ? " and whole granules per half" : "");
-    if (ss_in != nullptr) {
-      if (waves == 8) SKINNY_GO(8, true, true);
-      SKINNY_GO(4, true, true);
-    }
-    if (waves == 8) SKINNY_GO(8, false, true);
-    SKINNY_GO(4, false, true);
-  }
-  if (ss_in != nullptr) {
-    if (waves == 8) SKINNY_GO(8, true, false);
-    SKINNY_GO(4, true, false);
-  }
-  if (waves == 8) SKINNY_GO(8, false, false);
-  SKINNY_GO(4, false, false);
-#undef SKINNY_GO
-}
-
-template <bool W8>
-int skinny_dispatch(const void* x, const void* W, const float* wscale, const void* norm_w, float eps, const void* residual,
-                    void* out, int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed,
-                    hipStream_t s) {
-  // packed: 0 = row-major W [N][K]; 4 / 16 = the packed decode layout with granules of that many rows (srgpt_pack_decode_weights)
-  SRGPT_CHECK(packed == 0 || packed == 4 || packed == 8 || packed == 16, SRGPT_ERR_ARG, "skinny: packed layout granule %d (0, 4, 8 or 16)", packed);
-  SRGPT_CHECK(batch >= 1 && batch <= 16, SRGPT_ERR_ARG, "skinny: batch %d outside 1..16", batch);
-  SRGPT_CHECK(K % 8 == 0 && K >= 8, SRGPT_ERR_ARG, "skinny: K=%d must be a multiple of 8", K);
-  SRGPT_CHECK(!ss_in || norm_w, SRGPT_ERR_ARG, "skinny: published row statistics are the RMSNorm's input (norm_w is NULL)");
-  SRGPT_CHECK(!ss_out || (!swiglu && !out_f32), SRGPT_ERR_ARG, "skinny: row statistics are published for plain bf16 outputs only");
-  if (batch <= 4)
-    return swiglu ? launch_skinny_nw<true, 2, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, nullptr, packed, s)
-                  : launch_skinny_nw<false, 2, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, ss_out, packed, s);
-  if (batch <= 8)
-    return swiglu ? launch_skinny_nw<true, 4, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, nullptr, packed, s)
-                  : launch_skinny_nw<false, 4, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, ss_out, packed, s);
-  return swiglu ? launch_skinny_nw<true, 8, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, nullptr, packed, s)
-                : launch_skinny_nw<false, 8, W8>(x, W, wscale, norm_w, eps, residual, out, batch, N, K, out_f32, ss_in, ss_out, packed, s);
-}
+static_assert(GEMV_SKINNY_ROW_BYTES == WROWB && 16 * GEMV_SKINNY_ROW_BYTES == WSTAGEB && GEMV_SKINNY_SUBUNITS == MAXSU,
+              "gemv_route.h sizes the kernel's LDS: K loop stages | reduction buffer");
 
 }  // namespace
 
-// host entry used by srgpt_gemv (gemv.hip) for batches of up to 16 rows, bf16 weights
-int srgpt_skinny_launch(const void* x, const void* W, const void* norm_w, float eps, const void* residual, void* out,
-                        int batch, int N, int K, int swiglu, int out_f32, const float* ss_in, float* ss_out, int packed, hipStream_t s) {
-  return skinny_dispatch<false>(x, W, nullptr, norm_w, eps, residual, out, batch, N, K, swiglu, out_f32, ss_in, ss_out, packed, s);
-}
-
-// fp8 weights, any batch size (16 rows per weight pass); ss_in / ss_out: the rows' statistics tables (see skinny_kernel)
-int srgpt_skinny_w8_launch(const void* x, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
-                           const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
-                           const float* ss_in, float* ss_out, int packed, hipStream_t s) {
-  const size_t on = out_f32 ? sizeof(float) : 2;
-  for (int b0 = 0; b0 < batch; b0 += 16) {
-    const int nb = batch - b0 < 16 ? batch - b0 : 16;
-    SRGPT_TRY(skinny_dispatch<true>((const char*)x + (size_t)b0 * K * 2, W8, wscale, norm_w, norm_eps,
-                                    residual ? (const char*)residual + (size_t)b0 * N * 2 : nullptr,
-                                    (char*)out + (size_t)b0 * N * on, nb, N, K, swiglu, out_f32,
-                                    ss_in ? ss_in + (size_t)b0 * SRGPT_ROWSS_STRIDE : nullptr,
-                                    ss_out ? ss_out + (size_t)b0 * SRGPT_ROWSS_STRIDE : nullptr, packed, s));
-  }
+// One weight pass of up to 16 rows on the MFMA kernel (GEMV_SKINNY of gemv_route.h), entered from srgpt_decode_product (gemv.hip);
+// bf16 or fp8 weights.  packed: 0 = row-major W [N][K]; 4 / 8 / 16 = the packed decode layout with granules of that many rows
+// (srgpt_pack_decode_weights); ss_in / ss_out: the rows' statistics tables (see skinny_kernel)
+int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s) {
+  const int packed = p.packed, kblock = p.fp8 ? 64 : 32;
+  SRGPT_CHECK(packed == 0 || packed == 4 || packed == 8 || packed == 16, SRGPT_ERR_ARG, "skinny: packed layout granule %d (0, 4, 8 or 16)", packed);
+  SRGPT_CHECK(p.batch >= 1 && p.batch <= 16, SRGPT_ERR_ARG, "skinny: batch %d outside 1..16", p.batch);
+  SRGPT_CHECK(p.K % 8 == 0 && p.K >= 8, SRGPT_ERR_ARG, "skinny: K=%d must be a multiple of 8", p.K);
+  SRGPT_CHECK(!p.ss_in || p.norm_w, SRGPT_ERR_ARG, "skinny: published row statistics are the RMSNorm's input (norm_w is NULL)");
+  SRGPT_CHECK(!p.ss_out || (!p.swiglu && !p.out_f32), SRGPT_ERR_ARG, "skinny: row statistics are published for plain bf16 outputs only");
+  const GemvSkinnyLaunch l = gemv_skinny_launch(p.batch, p.N, p.norm_w != nullptr, p.ss_in != nullptr, packed, srgpt_device_cus());
+  SRGPT_CHECK(!p.ss_out || l.grid <= SRGPT_ROWSS_STRIDE, SRGPT_ERR_UNSUPPORTED, "skinny: %d blocks do not fit the %d row-statistics slots",
+              l.grid, SRGPT_ROWSS_STRIDE);
+  SRGPT_CHECK(!packed || (p.K % kblock == 0 && (!p.swiglu || p.N % packed == 0)), SRGPT_ERR_UNSUPPORTED,
+              "skinny: the packed weight layout needs K %% %d == 0 (K = %d)%s", kblock, p.K, p.swiglu ? " and whole granules per half" : "");
+  const auto flag = [](bool v, const char* what, auto&& f) { return srgpt_switch<false, true>(v, what, f); };
+  SRGPT_TRY((flag(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
+    return srgpt_switch<2, 4, 8>(l.NI, "NI", [&](auto ni_c) {
+      return srgpt_switch<4, 8>(l.NW, "NW", [&](auto nw_c) {
+        return flag(p.fp8 != 0, "W8", [&](auto w8_c) {
+          return flag(l.PUB, "PUB", [&](auto pub_c) {
+            return flag(l.PK, "PK", [&](auto pk_c) {
+              constexpr int NI = decltype(ni_c)::value, NW = decltype(nw_c)::value;
+              constexpr bool PK = decltype(pk_c)::value;
+              static_assert(gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "LDS");
+              static_assert(NW == 8 || 2 * gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "two 4-wave blocks per CU");
+              constexpr auto kfn = &skinny_kernel<decltype(sw_c)::value, NI, NW, decltype(w8_c)::value, decltype(pub_c)::value, PK>;
+              return srgpt_launch_dyn_lds<kfn>(l.lds, dim3(l.grid), dim3(64 * NW), (size_t)l.lds, s, (const bf16_t*)p.x, p.W, p.wscale,
+                                               (const bf16_t*)p.norm_w, p.eps, (const bf16_t*)p.residual, p.out, p.batch, p.N, p.K,
+                                               p.out_f32, l.cw, p.ss_in, p.ss_out, l.gr_shift);
+            });
+          });
+        });
+      });
+    });
+  })));
+  SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
@@ -674,10 +620,9 @@ extern "C" int srgpt_gemv_w8(const void* x, const void* W8, const float* wscale,
   SRGPT_CHECK(N > 0 && K > 0 && batch > 0, SRGPT_ERR_ARG, "srgpt_gemv_w8: bad shape");
   SRGPT_CHECK(K % 8 == 0, SRGPT_ERR_ARG, "srgpt_gemv_w8: K=%d must be a multiple of 8", K);
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_w8: swiglu excludes residual/out_f32");
-  hipStream_t s = as_stream(stream);
-  if (batch <= W8_VALU_MAX_BATCH && K % 16 == 0)  // one row: VALU kernel (gemv_w8.hip), like the bf16 path
-    return srgpt_gemv_w8_valu(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, s);
-  return srgpt_skinny_w8_launch(x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, nullptr, nullptr, 0, s);
+  return srgpt_decode_product(DecodeProduct{x, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, SRGPT_BF16, 1,
+                                            nullptr, nullptr, 0},
+                              as_stream(stream));
 }
 
 // ---- the packed decode layout (include/srgpt.h, ABI 9) ----

@@ -207,6 +207,8 @@ class PreparedWeights:
             # same fp8 bytes in MFMA-operand order.  The row-major copies stay: prefill (srgpt_gemm_w8 / _w8a8) and the one-row
             # decode kernel read those -- +6.5 GB of the 288 for an 8B model.  Granule rows per matrix from the measured table
             # (profiles/r06_skinny_packed_gr.txt): 16 (1 KiB per instruction) where a CU owns a single 16-column tile, else 4.
+            # (Load-time layout; what the kernel then does with a granule -- column width in whole granules, gr_shift -- is
+            # gemv_skinny_launch of csrc/gemv_route.h.)
             self.llm_pk, self.pk_rows = {}, {}
             if self.decode_layout == "packed":
                 n_cu = int(L.load().srgpt_device_cus())

@@ -363,6 +363,34 @@ int64_t srgpt_sample_full_ws_bytes(int B, int V);
 int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
                       srgpt_stream_t stream);
 
+/* Logits processors (additions under ABI 9): the part of HF's `LogitsProcessorList` that `generate(repetition_penalty=...,
+ * no_repeat_ngram_size=..., min_length=... / min_new_tokens=...)` builds, transformers 4.37.2 generation/logits_process.py, on the
+ * device.  The parameter block lives in DEVICE memory like srgpt_sampling: one captured graph serves every setting.
+ * srgpt_logits_process: scores fp32 [B, V], processed IN PLACE; ids int64 [B, ld], the first n entries of a row are that row's
+ *   history (n_dev != NULL: *n_dev, a device int, replaces n -- clamped to [0, ld]).  Per row, with s = the row's scores:
+ *   RepetitionPenaltyLogitsProcessor (repetition_penalty p != 1): for every DISTINCT id t of the history
+ *     s[t] = s[t] < 0 ? s[t] * p : s[t] / p -- once, however often t occurs, from the ORIGINAL s[t]; a true fp32 division (the
+ *     CPU's bits).
+ *   NoRepeatNGramLogitsProcessor (no_repeat_ngram g > 0): when n + 1 >= g, every id t that would complete a g-gram already in the
+ *     history -- some i has ids[i .. i + g - 2] equal to the last g - 1 ids and ids[i + g - 1] = t -- gets -inf (g = 1 bans every id
+ *     of the history).
+ *   MinLengthLogitsProcessor / MinNewTokensLengthLogitsProcessor: while n < min_new_tokens every eos[j], j < n_eos, gets -inf.  (A
+ *     generate() fed `inputs_embeds` starts from empty input_ids, so both classes count generated tokens: the host passes
+ *     max(min_length, min_new_tokens).)
+ *   A ban (-inf) wins over a penalty on the same entry; history ids and EOS ids outside [0, V) are skipped; the result does not
+ *   depend on scheduling (one block per row: every history entry reads its original score, barrier, the penalised values are
+ *   written -- duplicates write identical bits --, barrier, the -inf writes).  One launch.  ld <= 12288, else SRGPT_ERR_UNSUPPORTED.
+ *   NULL scores / lp / ids, B, V or ld <= 0, n outside [0, ld]: SRGPT_ERR_ARG, before any launch. */
+typedef struct {
+  float repetition_penalty;   /* > 0; 1.0: off */
+  int   no_repeat_ngram;      /* 0: off */
+  int   min_new_tokens;       /* 0: off; max(min_length, min_new_tokens) as resolved by the host */
+  int   n_eos;                /* 0 .. 8 ids in eos[] */
+  int64_t eos[8];
+} srgpt_logits_proc;
+int srgpt_logits_process(float* scores, const srgpt_logits_proc* lp, const int64_t* ids, int ld, int n, const int* n_dev, int B, int V,
+                         srgpt_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Composite: vision tower (VisionTower.forward, multimodal_encoder/vision_encoder.py:115-132 over HF
  * SiglipVisionModel; returns hidden_states[select_layer], i.e. runs `n_layers_run` encoder layers).
@@ -527,6 +555,18 @@ int srgpt_llm_sample_first_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, i
 int srgpt_llm_decode_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream);
 int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
                                      srgpt_graph** out);
+/* The _ex forms with logits processors (additions under ABI 9).  lp: DEVICE pointer to a srgpt_logits_proc block, or NULL = exactly
+ * the _ex form (same launches).  With lp set, srgpt_logits_process runs on st->logits between lm_head and the pick -- in front of the
+ * greedy argmax and of both samplers -- with ids = st->out_ids, ld = st->max_new and the count read from st->step on the device: the
+ * first token (srgpt_llm_sample_first_proc) sees 0 ids whatever *step held before, step t sees the t ids generated so far.
+ * st->logits holds the PROCESSED scores after such a step.  st->max_new > 12288 with lp set: SRGPT_ERR_UNSUPPORTED before any
+ * launch.  A graph captured with lp replays with that block's address; the block's contents may change between replays. */
+int srgpt_llm_sample_first_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                                srgpt_stream_t stream);
+int srgpt_llm_decode_step_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                               srgpt_stream_t stream);
+int srgpt_llm_decode_graph_create_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                                       srgpt_stream_t stream, srgpt_graph** out);
 int srgpt_graph_launch(srgpt_graph* g, int times, srgpt_stream_t stream);
 int srgpt_graph_destroy(srgpt_graph* g);
 

@@ -65,6 +65,14 @@ class Sampling(C.Structure):
                 ("counter", C.c_uint64), ("kept_out", vp)]
 
 
+class LogitsProc(C.Structure):
+    """srgpt_logits_proc (include/srgpt.h): the parameter block of the device-side logits processors; lives in DEVICE memory
+    (80 bytes)."""
+    _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram", i32), ("min_new_tokens", i32), ("n_eos", i32), ("eos", i64 * 8)]
+
+
+LOGITS_PROC_EOS_MAX = 8            # srgpt_logits_proc::eos
+LOGITS_PROC_HISTORY_MAX = 12288    # logits_proc.hip LP_MAX_HIST: ids per row
 SAMPLING_TOP_K_MAX = 64        # sample.hip SMP_K
 SAMPLING_KEPT_MAX = 256        # sample.hip SMP_LIST
 SAMPLING_VOCAB_MAX = 128 * 2048
@@ -122,6 +130,7 @@ _SIGNATURES = {
     "srgpt_sample_status": (i32, [vp, i32, vp]),
     "srgpt_sample_full_ws_bytes": (i64, [i32, i32]),
     "srgpt_sample_full": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "srgpt_logits_process": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, vp]),
     "srgpt_image_resize_normalize": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, i32, i32, vp]),
     "srgpt_mask_resize_nearest": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
     "srgpt_mask_pad_resize": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i32, vp]),
@@ -138,6 +147,9 @@ _SIGNATURES = {
     "srgpt_llm_sample_first_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp]),
     "srgpt_llm_decode_step_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp]),
     "srgpt_llm_decode_graph_create_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, C.POINTER(vp)]),
+    "srgpt_llm_sample_first_proc": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, vp]),
+    "srgpt_llm_decode_step_proc": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, vp]),
+    "srgpt_llm_decode_graph_create_proc": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, vp, C.POINTER(vp)]),
     "srgpt_graph_launch": (i32, [vp, i32, vp]),
     "srgpt_graph_destroy": (i32, [vp]),
 }

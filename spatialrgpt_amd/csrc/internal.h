@@ -53,6 +53,11 @@ int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void
                              int V, hipStream_t s);
 int srgpt_sample_slices();  // slices per row of both samplers (the argmax merge of model.hip reads as many)
 
+// ---- logits_proc.hip, for greedy_pick of model.hip: the logits processors' launch (n_dev != NULL: the history length on the device) ----
+int srgpt_logits_proc_launch(float* scores, const srgpt_logits_proc* lp, const int64_t* ids, int ld, int n, const int* n_dev, int B, int V,
+                             hipStream_t s);
+int srgpt_logits_proc_max_history();  // ids per row the kernel can hold
+
 // ---- flash.hip: the MFMA flash attention kernel's arguments and launcher, for srgpt_attention (attn.hip) ----
 struct AttnArgs {
   const bf16_t *q, *k, *v;

@@ -261,10 +261,13 @@ static inline bool advance_embeds(const srgpt_llm_weights* w, const srgpt_llm_st
 }
 
 // the next token of every sequence from st->logits: argmax (st->sampling == NULL) or a draw by the sampler `sampler` (sample.hip),
-// then the bookkeeping
-static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, int sampler, hipStream_t s) {
+// then the bookkeeping.  lp != NULL: the logits processors (logits_proc.hip) rewrite st->logits first, over the ids generated so far
+// (st->out_ids, *st->step of them)
+static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, int sampler,
+                       const srgpt_logits_proc* lp, hipStream_t s) {
   const int B = st->batch;
   const bool emb = advance_embeds(w, st);
+  if (lp) SRGPT_TRY(srgpt_logits_proc_launch(st->logits, lp, st->out_ids, st->max_new, 0, st->step, B, w->vocab, s));
   if (st->sampling) {
     SRGPT_CHECK(srgpt_sample_slices() == ARGMAX_BLOCKS, SRGPT_ERR_STATE, "sampling: slice count differs from the argmax merge's");
     if (sampler == SRGPT_SAMPLER_FULL)
@@ -627,12 +630,31 @@ static int check_sampler(const srgpt_llm_weights* w, const srgpt_llm_state* st, 
   return SRGPT_OK;
 }
 
+// the _proc entry points with a processor block: the history (st->out_ids, max_new ids per row) must fit the kernel
+static int check_proc(const srgpt_llm_state* st, const srgpt_logits_proc* lp, const char* fn) {
+  SRGPT_CHECK(!lp || (st->max_new > 0 && st->max_new <= srgpt_logits_proc_max_history()), SRGPT_ERR_UNSUPPORTED,
+              "%s: logits processors over max_new = %d ids (served: 1 .. %d)", fn, st->max_new, srgpt_logits_proc_max_history());
+  return SRGPT_OK;
+}
+
+static int sample_first_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                             srgpt_stream_t stream) {
+  hipStream_t s = as_stream(stream);
+  hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, s, st->step, 1, 0);  // the processors of the first token see 0 ids
+  const LlmWs d = carve_llm(w, st->batch, st->ws_tokens, st->ws);
+  return greedy_pick(w, st, d, 0, sampler, lp, s);
+}
+
 extern "C" int srgpt_llm_sample_first_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
   SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_sample_first_ex"));
-  hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, s, st->step, 1, 0);
-  const LlmWs d = carve_llm(w, st->batch, st->ws_tokens, st->ws);
-  return greedy_pick(w, st, d, 0, sampler, s);
+  return sample_first_impl(w, st, sampler, nullptr, stream);
+}
+
+extern "C" int srgpt_llm_sample_first_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                                           srgpt_stream_t stream) {
+  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_sample_first_proc"));
+  SRGPT_TRY(check_proc(st, lp, "srgpt_llm_sample_first_proc"));
+  return sample_first_impl(w, st, sampler, lp, stream);
 }
 
 extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
@@ -665,7 +687,8 @@ struct DecodeStep {
 
 // embed_first = false: the residual-stream buffer already holds the embeddings of st->tok (written by the advance_kernel of the
 // step before: the graph-captured greedy loop); the public entry always embeds (st->tok may have been set by the caller)
-static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, int sampler) {
+static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, int sampler,
+                            const srgpt_logits_proc* lp = nullptr) {
   SRGPT_TRY(check_llm(w, st));
   LlmFormat fmt;
   SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
@@ -706,12 +729,19 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
   }
   SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
-  return greedy_pick(w, st, d, 1, sampler, s);
+  return greedy_pick(w, st, d, 1, sampler, lp, s);
 }
 
 extern "C" int srgpt_llm_decode_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
   SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_step_ex"));
   return decode_step_impl(w, st, stream, true, sampler);
+}
+
+extern "C" int srgpt_llm_decode_step_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                                          srgpt_stream_t stream) {
+  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_step_proc"));
+  SRGPT_TRY(check_proc(st, lp, "srgpt_llm_decode_step_proc"));
+  return decode_step_impl(w, st, stream, true, sampler, lp);
 }
 
 extern "C" int srgpt_llm_decode_step(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
@@ -748,10 +778,11 @@ extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srg
 // ================================================================================================
 // hipGraph of one decode step
 // ================================================================================================
-extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
-                                                srgpt_graph** out) {
+static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
+                             srgpt_stream_t stream, srgpt_graph** out, const char* fn) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_decode_graph_create: null out");
-  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_graph_create_ex"));
+  SRGPT_TRY(check_sampler(w, st, sampler, fn));
+  SRGPT_TRY(check_proc(st, lp, fn));
   LlmFormat fmt;  // incomplete fp8 weights never begin a capture (the step below resolves the format again)
   SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
   hipStream_t s = as_stream(stream);
@@ -762,7 +793,7 @@ extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgp
     return SRGPT_ERR_STATE;
   }
   // replays continue from the token the previous step (or srgpt_llm_sample_first) picked: its embedding is already in place
-  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), sampler);
+  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), sampler, lp);
   const hipError_t ee = hipStreamEndCapture(s, &graph);
   if (rc != SRGPT_OK) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -781,6 +812,16 @@ extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgp
   }
   *out = new srgpt_graph{graph, exec};
   return SRGPT_OK;
+}
+
+extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
+                                                srgpt_graph** out) {
+  return graph_create_impl(w, st, sampler, nullptr, stream, out, "srgpt_llm_decode_graph_create_ex");
+}
+
+extern "C" int srgpt_llm_decode_graph_create_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler,
+                                                  const srgpt_logits_proc* lp, srgpt_stream_t stream, srgpt_graph** out) {
+  return graph_create_impl(w, st, sampler, lp, stream, out, "srgpt_llm_decode_graph_create_proc");
 }
 
 extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream,

@@ -51,9 +51,11 @@ class DecodeState:
         st.sampling = None
         self.c = st
         self.host_len = [0] * batch  # cached positions per row as known on the host (prefill lengths + steps taken)
-        self.graphs = {}             # "greedy" / "sample" / "sample_full" -> captured decode step (the pick kernels differ)
+        self.graphs = {}             # "greedy" / "sample" / "sample_full" (+ "+proc") -> captured decode step (the pick kernels differ)
         self.sampler = L.SAMPLER_TOPK64  # which device sampler draws while c.sampling is set (SRGPT_SAMPLER_*)
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
+        self.logits_proc: Optional[ops.LogitsProcParams] = None  # device block of the logits processors; ONE address likewise
+        self.proc = None             # its device pointer while the processors are on for the running request, else None
         self._eng = eng
 
     def seq_len(self) -> int:
@@ -74,12 +76,32 @@ class DecodeState:
         self.sampling.set(sampling["temperature"], sampling.get("top_k"), sampling.get("top_p"), sampling.get("seed", 0))
         self.c.sampling = self.sampling.ptr()
 
+    def set_logits_proc(self, proc: Optional[dict]):
+        """None: the step picks from the raw logits (the entry points and graphs without processors).  dict(repetition_penalty,
+        no_repeat_ngram_size, min_new_tokens, eos_token_ids): the step runs HF's logits processors on st.logits in front of the pick
+        (logits_proc.hip); the parameters go to the state's device block, so the "+proc" graph of a pick kind serves every setting."""
+        if proc is None:
+            self.proc = None
+            return
+        if self.max_new > L.LOGITS_PROC_HISTORY_MAX:
+            raise NotImplementedError(f"logits processors over {self.max_new} new tokens (served: {L.LOGITS_PROC_HISTORY_MAX})")
+        if self.logits_proc is None:
+            self.logits_proc = ops.LogitsProcParams(self._eng.device)
+        self.logits_proc.set(**proc)
+        self.proc = self.logits_proc.ptr()
+
     def ensure_graph(self):
         key = "greedy" if not self.c.sampling else ("sample_full" if self.sampler == L.SAMPLER_FULL else "sample")
+        if self.proc:
+            key += "+proc"
         if key not in self.graphs:
             g = L.vp()
-            L.check(L.load().srgpt_llm_decode_graph_create_ex(C.byref(self._eng.w.llm), C.byref(self.c), self.sampler, ops._stream(),
-                                                              C.byref(g)))
+            lib, w = L.load(), self._eng.w.llm
+            if self.proc:
+                L.check(lib.srgpt_llm_decode_graph_create_proc(C.byref(w), C.byref(self.c), self.sampler, self.proc, ops._stream(),
+                                                               C.byref(g)))
+            else:
+                L.check(lib.srgpt_llm_decode_graph_create_ex(C.byref(w), C.byref(self.c), self.sampler, ops._stream(), C.byref(g)))
             self.graphs[key] = g
         return self.graphs[key]
 
@@ -467,20 +489,24 @@ class SrgptEngine:
         return st.logits.clone()
 
     def greedy_decode(self, st: DecodeState, max_new_tokens: int, eos_token_id=None, pad_token_id=None,
-                      stopping_criteria=None, sampling: Optional[dict] = None) -> torch.Tensor:
+                      stopping_criteria=None, sampling: Optional[dict] = None, logits_proc: Optional[dict] = None) -> torch.Tensor:
         """HF generation-loop semantics (new ids only, finished rows padded), device-side steps via hipGraph.
         sampling = None: greedy.  sampling = dict(temperature, top_k, top_p, seed[, sampler]): every step DRAWS its token on the
         device (temperature -> top-k -> top-p -> categorical, sample.hip; `sampler` = L.SAMPLER_FULL for the settings the top-k-64
-        sampler does not serve) -- same loop, same graph mechanism, no per-token host work."""
+        sampler does not serve) -- same loop, same graph mechanism, no per-token host work.
+        logits_proc = dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_ids): HF's logits processors run on
+        the device in front of every pick (DecodeState.set_logits_proc); None: the steps without them."""
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             st.set_sampling(sampling)
+            st.set_logits_proc(logits_proc)
             try:
                 n_keep, eos = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
             finally:
                 st.c.sampling = None
                 st.sampler = L.SAMPLER_TOPK64
+                st.proc = None
         cur.wait_stream(self.stream)
         # the decode attention hands partials between workgroups inside a launch (arrival tickets): a ticket left non-zero means a
         # launch merged nothing and later steps used stale attention output -- fail loudly, never return such ids
@@ -497,7 +523,10 @@ class SrgptEngine:
     def _decode_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria):
         lib = L.load()
         stream = ops._stream()
-        L.check(lib.srgpt_llm_sample_first_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
+        if st.proc:
+            L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
+        else:
+            L.check(lib.srgpt_llm_sample_first_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
         eos = None  # ordered list of EOS ids (HF accepts an int or a list; Llama-3 checkpoints list two)
         if eos_token_id is not None:
             eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
@@ -512,7 +541,10 @@ class SrgptEngine:
                 L.check(lib.srgpt_graph_launch(graph, n, stream))
             else:
                 for _ in range(n):
-                    L.check(lib.srgpt_llm_decode_step_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
+                    if st.proc:
+                        L.check(lib.srgpt_llm_decode_step_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
+                    else:
+                        L.check(lib.srgpt_llm_decode_step_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
 
         def judge(ids, lo, hi):
             """host-side EOS / stopping-criteria scan of steps [lo, hi) of `ids` (CPU int64 [B, >= hi]); -> stop step or None."""

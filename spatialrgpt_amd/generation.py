@@ -12,6 +12,9 @@ The reference decodes through `self.llm.generate(inputs_embeds=..., **generation
   * sampling warpers in the order temperature -> top-k -> top-p (`_get_logits_warper`), each only when it would change anything
     (temperature != 1, top_k != 0, top_p < 1); `top_k` defaults to 50 in 4.37.2.
 
+  * the logits processors `_get_logits_processor` builds from `repetition_penalty`, `no_repeat_ngram_size`, `min_length` and
+    `min_new_tokens` (the device kernel of csrc/logits_proc.hip; `ResolvedGeneration.logits_processors`).
+
 `resolve_generation` reproduces that resolution; `warp_logits` is the three warpers on plain torch tensors (pinned against HF's own
 `TemperatureLogitsWarper` / `TopKLogitsWarper` / `TopPLogitsWarper` on CPU by tests/test_host_generation.py).
 """
@@ -25,7 +28,8 @@ import torch
 # GenerationConfig defaults of the pinned transformers==4.37.2 (generation/configuration_utils.py); newer releases moved to
 # `None` placeholders, the reference's behaviour is the pinned one
 HF_DEFAULTS = dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, max_length=20, max_new_tokens=None, min_new_tokens=None,
-                   num_beams=1, eos_token_id=None, pad_token_id=None, bos_token_id=None)
+                   num_beams=1, eos_token_id=None, pad_token_id=None, bos_token_id=None, repetition_penalty=1.0,
+                   no_repeat_ngram_size=0, min_length=0)
 
 _GEN_KEYS = tuple(HF_DEFAULTS)
 
@@ -50,6 +54,27 @@ class ResolvedGeneration:
     num_beams: int
     eos_token_ids: Optional[List[int]]  # None = never stop on a token; order preserved (pad falls back to the FIRST)
     pad_token_id: Optional[int]
+    # the logits processors `_get_logits_processor` builds from the config (served on the device: csrc/logits_proc.hip)
+    repetition_penalty: float = 1.0   # RepetitionPenaltyLogitsProcessor; 1.0: off
+    no_repeat_ngram_size: int = 0     # NoRepeatNGramLogitsProcessor; 0: off
+    min_length: int = 0               # MinLengthLogitsProcessor; 0: off
+
+    @property
+    def min_tokens(self) -> int:
+        """generated tokens before an EOS id may appear: generate(inputs_embeds=...) starts from EMPTY input_ids, so
+        MinLengthLogitsProcessor (min_length) and MinNewTokensLengthLogitsProcessor (min_new_tokens) count the same tokens"""
+        return max(int(self.min_length or 0), int(self.min_new_tokens or 0), 0)
+
+    def logits_processors(self) -> Optional[dict]:
+        """the processor settings that change a score, as `ops.LogitsProcParams.set` takes them; None: no processor is on (a
+        minimum length without an EOS id bans nothing)"""
+        mn = self.min_tokens if self.eos_token_ids else 0
+        if self.repetition_penalty == 1.0 and self.no_repeat_ngram_size == 0 and mn == 0:
+            return None
+        if mn > 0 and len(self.eos_token_ids) > 8:
+            raise NotImplementedError(f"a minimum length with {len(self.eos_token_ids)} EOS ids (the device block holds 8)")
+        return dict(repetition_penalty=self.repetition_penalty, no_repeat_ngram_size=self.no_repeat_ngram_size, min_new_tokens=mn,
+                    eos_token_ids=list(self.eos_token_ids) if mn > 0 else None)
 
 
 def _eos_list(eos) -> Optional[List[int]]:
@@ -81,7 +106,20 @@ def resolve_generation(stored: Optional[dict], **kwargs) -> ResolvedGeneration:
     if pad is None and eos is not None:
         pad = eos[0]  # "Setting `pad_token_id` to `eos_token_id`" (first element of a list)
     mn = cfg["min_new_tokens"]
-    return ResolvedGeneration(do_sample=bool(cfg["do_sample"]), temperature=cfg["temperature"], top_k=cfg["top_k"], top_p=cfg["top_p"],
+    # HF's own errors (RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor.__init__); None or the off value: no processor
+    rp = cfg["repetition_penalty"]
+    if rp is None or rp == 1.0:
+        rp = 1.0
+    elif not isinstance(rp, float) or not (rp > 0):
+        raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+    ng = cfg["no_repeat_ngram_size"]
+    if ng is None:
+        ng = 0
+    elif isinstance(ng, bool) or not isinstance(ng, int) or ng < 0:
+        raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {ng}")
+    ml = cfg["min_length"]
+    return ResolvedGeneration(repetition_penalty=float(rp), no_repeat_ngram_size=ng, min_length=0 if ml is None else max(int(ml), 0),
+                              do_sample=bool(cfg["do_sample"]), temperature=cfg["temperature"], top_k=cfg["top_k"], top_p=cfg["top_p"],
                               max_new_tokens=max_new, min_new_tokens=None if mn is None else int(mn),
                               num_beams=int(cfg["num_beams"] or 1), eos_token_ids=eos, pad_token_id=None if pad is None else int(pad))
 
@@ -346,7 +384,8 @@ def beam_sample_candidates(scores: torch.Tensor, n: int, generator: Optional[tor
 def beam_generate(first_logits: torch.Tensor, step, batch: int, num_beams: int, max_new_tokens: int,
                   eos_token_ids: Optional[List[int]], pad_token_id: Optional[int], do_sample: bool = False, temperature=None,
                   top_k=None, top_p=None, generator: Optional[torch.Generator] = None, length_penalty: float = 1.0,
-                  early_stopping=False, stopping_criteria=None, warp_before_beam_scores: bool = True) -> torch.Tensor:
+                  early_stopping=False, stopping_criteria=None, warp_before_beam_scores: bool = True,
+                  logits_processor=None) -> torch.Tensor:
     """`generate(num_beams > 1)` of the reference's callers -- `--num_beams` of eval_spatial.py:231-235, eval_region_cls.py:318-322,
     model_vqa.py:72-76, which pass `do_sample = temperature > 0` with `--temperature` defaulting to 0.2: the default flags plus
     `--num_beams 3` are BEAM-SAMPLE -- as transformers 4.37.2 runs them (GenerationMixin.beam_search / .beam_sample +
@@ -361,7 +400,10 @@ def beam_generate(first_logits: torch.Tensor, step, batch: int, num_beams: int, 
     the first num_beams that do not end in an EOS id and files the EOS ones that rank among the first num_beams as hypotheses.
 
     first_logits fp32 [batch * num_beams, V]; step(tokens int64 [batch * num_beams], beam_idx int64 [batch * num_beams]) -> logits of
-    the next position for rows continued from (old) rows beam_idx.  Returns int64 [batch, <= max_new_tokens]: new tokens only."""
+    the next position for rows continued from (old) rows beam_idx.  logits_processor(seqs, scores) -> scores (optional): HF's
+    `logits_processor(input_ids, next_token_scores)` -- seqs = the batch * num_beams running id lists (generated ids only), scores =
+    the log-softmax rows, processed BEFORE the warpers and the beam scores as 4.37.2's beam_search / beam_sample do.
+    Returns int64 [batch, <= max_new_tokens]: new tokens only."""
     dev = first_logits.device
     B, nb, G = batch, num_beams, max_new_tokens
     V = first_logits.shape[-1]
@@ -377,6 +419,8 @@ def beam_generate(first_logits: torch.Tensor, step, batch: int, num_beams: int, 
     keep_min = (len(eos) + 1) if (eos and len(eos) > 1) else 2
     while True:
         lp = torch.log_softmax(logits.float(), dim=-1)
+        if logits_processor is not None:
+            lp = logits_processor(seqs, lp)
         if do_sample and warp_before_beam_scores:
             lp = warp_logits(lp, temperature, top_k, top_p, min_tokens_to_keep=keep_min)
         sc = lp + beam_scores.reshape(B * nb, 1)

@@ -439,15 +439,22 @@ class LlavaLlamaModel:
     def _generate_from_embeds(self, inputs_embeds, attention_mask=None, do_sample=NOT_GIVEN, temperature=NOT_GIVEN,
                               top_p=NOT_GIVEN, top_k=NOT_GIVEN, num_beams=NOT_GIVEN, max_new_tokens=NOT_GIVEN,
                               max_length=NOT_GIVEN, min_new_tokens=NOT_GIVEN, use_cache=True, stopping_criteria=None,
-                              pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, **unused):
+                              pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, repetition_penalty=NOT_GIVEN,
+                              no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, **unused):
         """HF `GenerationMixin.generate(inputs_embeds=...)` as the reference reaches it (llava_llama.py:212): the stored
-        generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py)."""
+        generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py).
+        `repetition_penalty`, `no_repeat_ngram_size` and `min_length` / `min_new_tokens` run as HF's logits processors on the device
+        (csrc/logits_proc.hip) in every decoding mode; every other keyword is accepted and ignored."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
-                               min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id)
+                               min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
+                               repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                               min_length=min_length)
         max_new_tokens = g.max_new_tokens
         eos_ids = g.eos_token_ids
-        if g.min_new_tokens is not None and g.min_new_tokens >= max_new_tokens:
+        proc = g.logits_processors()  # None: no processor is on -- the request takes the entry points and graphs without them
+        if g.min_tokens >= max_new_tokens:
+            # every step bans the EOS ids (the general rule, in `proc`): no token can end the request, so nothing is judged per step
             eos_ids = None
         B, T, _ = inputs_embeds.shape
         lens = None
@@ -474,7 +481,8 @@ class LlavaLlamaModel:
             # beam-SAMPLE, with `--temperature 0` beam search proper
             sample = bool(g.do_sample and g.temperature is not None and g.temperature > 0)
             return self._beam_search(inputs_embeds, lens, g.num_beams, max_new_tokens, eos_ids, g.pad_token_id, stopping_criteria,
-                                     sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p) if sample else None)
+                                     sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p) if sample else None,
+                                     logits_proc=proc)
         st, _, _ = self.engine.prefill(inputs_embeds, max_new=max_new_tokens, lens=lens)
         if g.do_sample and g.temperature is not None and g.temperature > 0:
             from . import ops
@@ -489,14 +497,15 @@ class LlavaLlamaModel:
                 return self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
                                                  stopping_criteria=stopping_criteria,
                                                  sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed,
-                                                               sampler=kind))
+                                                               sampler=kind), logits_proc=proc)
             # a vocabulary above 262144 (no config of the reference's): warpers + draw as torch ops per token
             return self._sample_loop(st, max_new_tokens, g.temperature, g.top_p, g.top_k, eos_ids, g.pad_token_id,
-                                     stopping_criteria)
+                                     stopping_criteria, logits_proc=proc)
         return self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
-                                         stopping_criteria=stopping_criteria)
+                                         stopping_criteria=stopping_criteria, logits_proc=proc)
 
-    def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None):
+    def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
+                     logits_proc=None):
         """`generate(num_beams > 1)` -- the `--num_beams` flag of eval_spatial.py:234, eval_region_cls.py:321, model_vqa.py:75 (default
         1: the benchmarked path is the greedy loop); `sampling` (temperature / top_k / top_p) makes it beam-SAMPLE, which is what those
         CLIs ask for under their default `--temperature 0.2`.  HF 4.37.2 semantics in spatialrgpt_amd/generation.beam_generate; here
@@ -531,11 +540,23 @@ class LlavaLlamaModel:
 
         gen = None
         kw = {}
+        if logits_proc is not None:
+            # HF 4.37.2 beam_search / beam_sample: the processors see the log-softmax scores and each beam's generated ids
+            params = ops.LogitsProcParams(self.device).set(**logits_proc)
+            hist = torch.zeros((B * num_beams, max_new_tokens), dtype=torch.int64, device=self.device)
+
+            def process(seqs, scores):
+                n = len(seqs[0])
+                if n > 0:
+                    hist[:, :n] = torch.tensor(seqs, dtype=torch.int64).to(self.device)
+                return ops.logits_process(scores.contiguous(), params, hist, n)
+
+            kw["logits_processor"] = process
         if sampling is not None:
             # seeded from torch's default CPU generator, like the sampling path: torch.manual_seed makes a request reproducible
             gen = torch.Generator(device=self.device)
             gen.manual_seed(int(torch.randint(0, 2 ** 62, (1,)).item()))
-            kw = dict(do_sample=True, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], generator=gen)
+            kw.update(do_sample=True, temperature=sampling["temperature"], top_k=sampling["top_k"], top_p=sampling["top_p"], generator=gen)
         out = beam_generate(st.logits.clone(), step, B, num_beams, max_new_tokens, eos_ids, pad_token_id,
                             stopping_criteria=stopping_criteria, **kw)
         # the decode attention's hand-off health (arrival tickets re-armed), as on the greedy path
@@ -543,7 +564,7 @@ class LlavaLlamaModel:
         return out
 
     def _sample_loop(self, st, max_new_tokens, temperature, top_p, top_k, eos_token_id, pad_token_id, stopping_criteria,
-                     check_every: int = 8):
+                     check_every: int = 8, logits_proc=None):
         """temperature / top-k / top-p sampling over a vocabulary above the device samplers' 262144 entries (csrc/sample.hip); every
         setting of every config of the reference's runs on the device instead.  The transformer steps are the HIP decode step; the
         warpers (generation.warp_logits, pinned to HF's) and the categorical draw over the final logits use torch.  Host round trips:
@@ -561,10 +582,13 @@ class LlavaLlamaModel:
         eos_t = None if not eos else torch.tensor(eos, device=self.device, dtype=torch.int64)
         padv = None if not eos else (pad_token_id if pad_token_id is not None else eos[0])
         out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device)
+        params = None if logits_proc is None else ops.LogitsProcParams(self.device).set(**logits_proc)
         n = 0
         for step in range(max_new_tokens):
             if step > 0:
                 L.check(lib.srgpt_llm_decode_step(C.byref(eng.w.llm), C.byref(st.c), ops._stream()))
+            if params is not None:  # the processors run before the warpers (HF: logits_warper(logits_processor(scores)))
+                ops.logits_process(st.logits, params, out, step)
             probs = warp_logits(st.logits, temperature, top_k, top_p).softmax(-1)
             tok = torch.multinomial(probs, 1).squeeze(1)
             if eos:

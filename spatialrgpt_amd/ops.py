@@ -605,3 +605,59 @@ def sample_full(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = 
     bits = torch.arange(32, device=logits.device, dtype=torch.int32)
     kept = ((mask[:, :, None] >> bits) & 1).bool().reshape(B, nw * 32)[:, :V]
     return out, kept
+
+
+class LogitsProcParams:
+    """The device-resident parameter block of the logits processors (srgpt_logits_proc, include/srgpt.h): HF's
+    RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinLength / MinNewTokensLength processors.  One address for
+    the owner's lifetime (a captured decode step holds it); `set()` rewrites the contents."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.buf = torch.zeros((C.sizeof(L.LogitsProc),), dtype=torch.uint8, device=self.device)
+        self.host = L.LogitsProc()
+        self.set()
+
+    @staticmethod
+    def active(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_token_ids=None) -> bool:
+        """does this setting change any score?  (a minimum length without an EOS id bans nothing)"""
+        return bool((repetition_penalty is not None and float(repetition_penalty) != 1.0) or int(no_repeat_ngram_size or 0) > 0
+                    or (int(min_new_tokens or 0) > 0 and eos_token_ids))
+
+    def set(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, eos_token_ids=None):
+        """one small H2D copy on the current stream"""
+        eos = [int(e) for e in (eos_token_ids or [])] if int(min_new_tokens or 0) > 0 else []
+        if len(eos) > L.LOGITS_PROC_EOS_MAX:
+            raise NotImplementedError(f"a minimum length with {len(eos)} EOS ids (the device block holds {L.LOGITS_PROC_EOS_MAX})")
+        h = self.host
+        h.repetition_penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        h.no_repeat_ngram = min(int(no_repeat_ngram_size or 0), 2 ** 31 - 1)
+        h.min_new_tokens = min(int(min_new_tokens or 0), 2 ** 31 - 1)
+        h.n_eos = len(eos)
+        for j in range(L.LOGITS_PROC_EOS_MAX):
+            h.eos[j] = eos[j] if j < len(eos) else 0
+        self.buf.copy_(torch.frombuffer(bytearray(bytes(h)), dtype=torch.uint8), non_blocking=False)
+        return self
+
+    def ptr(self):
+        return self.buf.data_ptr()
+
+
+def logits_process(scores: torch.Tensor, params: LogitsProcParams, ids: torch.Tensor, n) -> torch.Tensor:
+    """the logits processors of `params` over fp32 scores [B, V], IN PLACE; ids int64 [B, ld], the first n of a row are its history.
+    n: an int, or a device int32 tensor of one element (read by the kernel, clamped to ld).  Returns `scores`."""
+    _dev(scores, ids)
+    if scores.dtype != torch.float32 or scores.ndim != 2 or not scores.is_contiguous():
+        raise ValueError("logits_process: scores must be contiguous fp32 [B, V]")
+    if ids.dtype != torch.int64 or ids.ndim != 2 or ids.shape[0] != scores.shape[0]:
+        raise ValueError("logits_process: ids must be int64 [B, ld]")
+    B, V = scores.shape
+    ids = _c(ids)
+    n_dev = None
+    if isinstance(n, torch.Tensor):
+        _dev(n)
+        if n.dtype != torch.int32 or n.numel() != 1:
+            raise ValueError("logits_process: a device count must be one int32")
+        n_dev, n = n, 0
+    L.check(L.load().srgpt_logits_process(_p(scores), params.ptr(), _p(ids), ids.shape[1], int(n), _p(n_dev), B, V, _stream()))
+    return scores

@@ -4,6 +4,7 @@ by routing the setting away from the device), and the top-k-64 sampler's (0.7, 5
 
   python scripts/sampling_full_timing.py             # tok/s table (best of --reps whole requests)
   python scripts/sampling_full_timing.py --trace     # decode only, full sampler at B = 1 and B = 8 (run under rocprofv3 --kernel-trace)
+SRGPT_LIB=<path of a libsrgpt_hip*.so build> selects the library, as for ubench_decode_step.py.
 """
 import argparse
 import os
@@ -15,6 +16,9 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from spatialrgpt_amd import _lib as L  # noqa: E402
+
+if os.environ.get("SRGPT_LIB"):
+    L.LIB_PATH = os.path.abspath(os.environ["SRGPT_LIB"])
 from spatialrgpt_amd import ops  # noqa: E402
 from spatialrgpt_amd.model import LlavaLlamaModel  # noqa: E402
 from spatialrgpt_amd.weights import synth_state_dict  # noqa: E402
@@ -65,7 +69,7 @@ def main():
             ops.SamplingParams.sampler = staticmethod(orig)
 
     base = None
-    print(f"configs[1] geometry (vila15_8b, bf16, bs 1, 8 regions, prompt 64, {G} new tokens), whole request, best of {args.reps}")
+    print(f"{os.path.basename(L.LIB_PATH)}: configs[1] geometry (vila15_8b, bf16, bs 1, 8 regions, prompt 64, {G} new tokens), whole request, best of {args.reps}")
     for T, k, p in SETTINGS:
         for crit in (None, never):
             legs = [("device", False)] + ([("torch loop (before)", True)] if (k == 0 or k > 64) else [])

@@ -46,12 +46,11 @@ int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const
                               const void* next_w, int next_n, int next_k, int next_fp8, srgpt_stream_t stream);
 void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* bytes);
 
-// ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping ----
+// ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping (slices, partials, workspaces: pick.h) ----
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s);
 int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
                              int V, hipStream_t s);
-int srgpt_sample_slices();  // slices per row of both samplers (the argmax merge of model.hip reads as many)
 
 // ---- logits_proc.hip, for greedy_pick of model.hip: the logits processors' launch (n_dev != NULL: the history length on the device) ----
 int srgpt_logits_proc_launch(float* scores, const srgpt_logits_proc* lp, const int64_t* ids, int ld, int n, const int* n_dev, int B, int V,

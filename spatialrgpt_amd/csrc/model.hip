@@ -6,6 +6,7 @@
 #include "common.h"
 #include "gemv_route.h"
 #include "internal.h"
+#include "pick.h"
 
 namespace {
 
@@ -50,18 +51,17 @@ struct LlmWs {
   float* dws;
   void* gws;  // split-K workspace of the prefill GEMMs
   size_t gws_bytes;
-  float* amax_v;  // [batch, ARGMAX_BLOCKS] partial maxima
-  int* amax_i;    // [batch, ARGMAX_BLOCKS] their indices
+  float* amax_v;  // [batch, PICK_SLICES] the pick's per-slice values (pick.h)
+  int* amax_i;    // [batch, PICK_SLICES] their indices
   int64_t* tok_emb;  // [batch] the token whose embedding row currently sits in xd (-1: none)
-  void* smp;         // sampling: the slices' top-k candidates (srgpt_sample_ws_bytes)
-  void* smpf;        // full sampler: the row's keys and threshold pair (the head of srgpt_sample_full_ws_bytes)
+  void* smp;         // sampling: the slices' top-k candidates (SampleWs, pick.h)
+  void* smpf;        // full sampler: the row's keys and threshold pair (the head of SampleFullWs)
   int* err;          // sticky error word of the decode step (bit 0: a caller-written st->tok outside the table), read by srgpt_llm_decode_sync_state
   float* rowss;   // decode, 2+ rows: two row-statistics tables [batch][SRGPT_ROWSS_STRIDE] (o_proj's and down_proj's output rows)
   void* a8;       // fp8_act: the e4m3 bytes of the current GEMM input [rows, max K]
   float* a8s;     // fp8_act: their per-row scales [rows]
   size_t total;
 };
-constexpr int ARGMAX_BLOCKS = 128;
 LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws) {
   const size_t es = dtype_size(w->dtype);
   const size_t rows = (size_t)batch * max_tokens;
@@ -82,12 +82,12 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
   l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_ws_floats(batch, w->heads, w->head_dim) * 4));
   l.gws_bytes = (size_t)srgpt_gemm_ws_bytes((int)rows, (int)(qkvw > (size_t)w->hidden ? qkvw : (size_t)w->hidden));
   l.gws = c.take(l.gws_bytes);
-  l.amax_v = reinterpret_cast<float*>(c.take((size_t)batch * ARGMAX_BLOCKS * 4));
-  l.amax_i = reinterpret_cast<int*>(c.take((size_t)batch * ARGMAX_BLOCKS * 4));
+  l.amax_v = reinterpret_cast<float*>(c.take((size_t)batch * PICK_SLICES * 4));
+  l.amax_i = reinterpret_cast<int*>(c.take((size_t)batch * PICK_SLICES * 4));
   l.tok_emb = reinterpret_cast<int64_t*>(c.take((size_t)batch * 8));
   l.err = reinterpret_cast<int*>(c.take(sizeof(int)));
-  l.smp = c.take((size_t)srgpt_sample_ws_bytes(batch));
-  l.smpf = c.take((size_t)batch * ((size_t)4 * w->vocab + 16));
+  l.smp = c.take((size_t)carve_sample_ws(nullptr, batch).bytes);
+  l.smpf = c.take(carve_sample_full_ws(nullptr, batch, w->vocab).head_bytes);
   l.rowss = reinterpret_cast<float*>(c.take((size_t)2 * batch * SRGPT_ROWSS_STRIDE * sizeof(float)));
   l.a8 = nullptr;
   l.a8s = nullptr;
@@ -110,44 +110,18 @@ __global__ void set_int_kernel(int* p, int n, int v) {
 // greedy pick, stage 1: each block scans a contiguous slice of one row (first max wins, like torch.argmax)
 __global__ __launch_bounds__(256) void argmax_partial_kernel(const float* __restrict__ logits, float* __restrict__ pv,
                                                              int* __restrict__ pi, int V) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
-  const int b = blockIdx.y, nb = gridDim.x;
-  const int per = (V + nb - 1) / nb;
-  const int lo = blockIdx.x * per, hi = min(lo + per, V);
-  const float* row = logits + (size_t)b * V;
+  const PickSlice sl = pick_slice(V);
+  const float* row = logits + (size_t)blockIdx.y * V;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) {
+  int bi = PICK_NONE;
+  for (int i = sl.lo + threadIdx.x; i < sl.hi; i += 256) {
     const float v = row[i];
     if (v > best) {  // ascending scan per thread: the first maximum is kept
       best = v;
       bi = i;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  if ((threadIdx.x & 63) == 0) {
-    sv[threadIdx.x >> 6] = best;
-    si[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int i = 1; i < 4; ++i)
-      if (sv[i] > best || (sv[i] == best && si[i] < bi)) {
-        best = sv[i];
-        bi = si[i];
-      }
-    pv[(size_t)b * nb + blockIdx.x] = best;
-    pi[(size_t)b * nb + blockIdx.x] = bi;
-  }
+  pick_store_slice(best, bi, pv, pi);
 }
 
 // stage 2 + bookkeeping: one wave per batch row merges the partials -> tok / out_ids[:, step] / pos / step, and (embed != NULL)
@@ -164,27 +138,8 @@ __global__ __launch_bounds__(1024) void advance_kernel(const float* __restrict__
   // sampler (select_drew = 0): the slices' maxima are merged here
   const bool drawn = sp != nullptr && select_drew && sp->top_k > 0;
   for (int b = threadIdx.x >> 6; b < B; b += blockDim.x >> 6) {
-    float best = -INFINITY;
-    int bi = drawn ? (int)tok[b] : 0x7fffffff;
-    for (int i = lane; i < (drawn ? 0 : nb); i += 64) {
-      const float v = pv[(size_t)b * nb + i];
-      const int ix = pi[(size_t)b * nb + i];
-      if (v > best || (v == best && ix < bi)) {
-        best = v;
-        bi = ix;
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
+    const int64_t t = drawn ? tok[b] : pick_merge_row(pv + (size_t)b * nb, pi + (size_t)b * nb, nb, lane);
     if (lane == 0) {
-      const int64_t t = bi == 0x7fffffff ? 0 : bi;
       tok[b] = t;
       if (embed && b < ADVANCE_MAXB) {
         picked[b] = (int)t;
@@ -260,27 +215,32 @@ static inline bool advance_embeds(const srgpt_llm_weights* w, const srgpt_llm_st
   return st->batch <= ADVANCE_MAXB && ((size_t)w->hidden * dtype_size(w->dtype)) % 16 == 0;
 }
 
-// the next token of every sequence from st->logits: argmax (st->sampling == NULL) or a draw by the sampler `sampler` (sample.hip),
-// then the bookkeeping.  lp != NULL: the logits processors (logits_proc.hip) rewrite st->logits first, over the ids generated so far
-// (st->out_ids, *st->step of them)
-static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, int sampler,
-                       const srgpt_logits_proc* lp, hipStream_t s) {
+// how a step picks: the sampler kind that draws while st->sampling is set (SRGPT_SAMPLER_*), and the logits processors' block
+// (NULL: none) -- what the plain, _ex and _proc forms of an entry point differ in
+struct Pick {
+  int sampler;
+  const srgpt_logits_proc* lp;
+};
+
+// the next token of every sequence from st->logits: argmax (st->sampling == NULL) or a draw by the sampler p.sampler (sample.hip),
+// then the bookkeeping.  p.lp != NULL: the logits processors (logits_proc.hip) rewrite st->logits first, over the ids generated so
+// far (st->out_ids, *st->step of them).  Every producer leaves PICK_SLICES pairs per row (pick.h) for advance_kernel's merge
+static int greedy_pick(const srgpt_llm_weights* w, srgpt_llm_state* st, const LlmWs& d, int bump_pos, Pick p, hipStream_t s) {
   const int B = st->batch;
   const bool emb = advance_embeds(w, st);
-  if (lp) SRGPT_TRY(srgpt_logits_proc_launch(st->logits, lp, st->out_ids, st->max_new, 0, st->step, B, w->vocab, s));
+  if (p.lp) SRGPT_TRY(srgpt_logits_proc_launch(st->logits, p.lp, st->out_ids, st->max_new, 0, st->step, B, w->vocab, s));
   if (st->sampling) {
-    SRGPT_CHECK(srgpt_sample_slices() == ARGMAX_BLOCKS, SRGPT_ERR_STATE, "sampling: slice count differs from the argmax merge's");
-    if (sampler == SRGPT_SAMPLER_FULL)
+    if (p.sampler == SRGPT_SAMPLER_FULL)
       SRGPT_TRY(srgpt_sample_full_launch(st->logits, st->sampling, d.smpf, d.amax_v, d.amax_i, nullptr, B, w->vocab, s));
     else
       SRGPT_TRY(srgpt_sample_launch(st->logits, st->sampling, st->tok, d.smp, d.amax_v, d.amax_i, d.err, B, w->vocab, s));
   } else {
-    hipLaunchKernelGGL(argmax_partial_kernel, dim3(ARGMAX_BLOCKS, B), dim3(256), 0, s, st->logits, d.amax_v, d.amax_i, w->vocab);
+    hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, st->logits, d.amax_v, d.amax_i, w->vocab);
   }
-  hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(B > 4 ? 1024 : 256), 0, s, d.amax_v, d.amax_i, ARGMAX_BLOCKS, st->tok, st->out_ids,
+  hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(B > 4 ? 1024 : 256), 0, s, d.amax_v, d.amax_i, PICK_SLICES, st->tok, st->out_ids,
                      st->pos, st->step, B, st->max_new, bump_pos, emb ? reinterpret_cast<const unsigned char*>(w->embed) : nullptr,
                      reinterpret_cast<unsigned char*>(d.xd), (int)((size_t)w->hidden * dtype_size(w->dtype)), d.tok_emb, st->sampling,
-                     sampler == SRGPT_SAMPLER_TOPK64 ? 1 : 0);
+                     p.sampler == SRGPT_SAMPLER_TOPK64 ? 1 : 0);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -620,45 +580,39 @@ extern "C" int srgpt_llm_prefill_ragged(const srgpt_llm_weights* w, srgpt_llm_st
   return prefill_impl(w, st, inputs_embeds, T, lens, all_logits, hidden_out, stream);
 }
 
-// the _ex entry points: a known sampler kind, a valid state, and (full sampler, sampling on) a vocabulary it can hold -- all on the
-// host, before any launch
-static int check_sampler(const srgpt_llm_weights* w, const srgpt_llm_state* st, int sampler, const char* fn) {
-  SRGPT_CHECK(sampler == SRGPT_SAMPLER_TOPK64 || sampler == SRGPT_SAMPLER_FULL, SRGPT_ERR_ARG, "%s: unknown sampler kind %d", fn, sampler);
+// every pick entry point, on the host before any launch: a known sampler kind, a valid state, (full sampler, sampling on) a
+// vocabulary it can hold, and (processors on) a history (st->out_ids, max_new ids per row) that fits their kernel
+static int check_pick(const srgpt_llm_weights* w, const srgpt_llm_state* st, Pick p, const char* fn) {
+  SRGPT_CHECK(p.sampler == SRGPT_SAMPLER_TOPK64 || p.sampler == SRGPT_SAMPLER_FULL, SRGPT_ERR_ARG, "%s: unknown sampler kind %d", fn,
+              p.sampler);
   SRGPT_TRY(check_llm(w, st));
-  SRGPT_CHECK(!(st->sampling && sampler == SRGPT_SAMPLER_FULL) || w->vocab <= ARGMAX_BLOCKS * 2048, SRGPT_ERR_UNSUPPORTED,
-              "%s: vocabulary %d exceeds the full sampler's %d", fn, w->vocab, ARGMAX_BLOCKS * 2048);
-  return SRGPT_OK;
-}
-
-// the _proc entry points with a processor block: the history (st->out_ids, max_new ids per row) must fit the kernel
-static int check_proc(const srgpt_llm_state* st, const srgpt_logits_proc* lp, const char* fn) {
-  SRGPT_CHECK(!lp || (st->max_new > 0 && st->max_new <= srgpt_logits_proc_max_history()), SRGPT_ERR_UNSUPPORTED,
+  if (st->sampling && p.sampler == SRGPT_SAMPLER_FULL) SRGPT_TRY(pick_check_vocab(w->vocab, fn));
+  SRGPT_CHECK(!p.lp || (st->max_new > 0 && st->max_new <= srgpt_logits_proc_max_history()), SRGPT_ERR_UNSUPPORTED,
               "%s: logits processors over max_new = %d ids (served: 1 .. %d)", fn, st->max_new, srgpt_logits_proc_max_history());
   return SRGPT_OK;
 }
 
-static int sample_first_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
-                             srgpt_stream_t stream) {
+static int sample_first_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pick p, srgpt_stream_t stream) {
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(64), 0, s, st->step, 1, 0);  // the processors of the first token see 0 ids
   const LlmWs d = carve_llm(w, st->batch, st->ws_tokens, st->ws);
-  return greedy_pick(w, st, d, 0, sampler, lp, s);
+  return greedy_pick(w, st, d, 0, p, s);
 }
 
 extern "C" int srgpt_llm_sample_first_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
-  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_sample_first_ex"));
-  return sample_first_impl(w, st, sampler, nullptr, stream);
+  SRGPT_TRY(check_pick(w, st, Pick{sampler, nullptr}, "srgpt_llm_sample_first_ex"));
+  return sample_first_impl(w, st, Pick{sampler, nullptr}, stream);
 }
 
 extern "C" int srgpt_llm_sample_first_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
                                            srgpt_stream_t stream) {
-  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_sample_first_proc"));
-  SRGPT_TRY(check_proc(st, lp, "srgpt_llm_sample_first_proc"));
-  return sample_first_impl(w, st, sampler, lp, stream);
+  SRGPT_TRY(check_pick(w, st, Pick{sampler, lp}, "srgpt_llm_sample_first_proc"));
+  return sample_first_impl(w, st, Pick{sampler, lp}, stream);
 }
 
 extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
-  return srgpt_llm_sample_first_ex(w, st, SRGPT_SAMPLER_TOPK64, stream);
+  SRGPT_TRY(check_pick(w, st, Pick{SRGPT_SAMPLER_TOPK64, nullptr}, "srgpt_llm_sample_first"));
+  return sample_first_impl(w, st, Pick{SRGPT_SAMPLER_TOPK64, nullptr}, stream);
 }
 
 namespace {
@@ -687,9 +641,7 @@ struct DecodeStep {
 
 // embed_first = false: the residual-stream buffer already holds the embeddings of st->tok (written by the advance_kernel of the
 // step before: the graph-captured greedy loop); the public entry always embeds (st->tok may have been set by the caller)
-static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, int sampler,
-                            const srgpt_logits_proc* lp = nullptr) {
-  SRGPT_TRY(check_llm(w, st));
+static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, Pick p) {
   LlmFormat fmt;
   SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
@@ -729,23 +681,23 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
   }
   SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
-  return greedy_pick(w, st, d, 1, sampler, lp, s);
+  return greedy_pick(w, st, d, 1, p, s);
 }
 
 extern "C" int srgpt_llm_decode_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream) {
-  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_step_ex"));
-  return decode_step_impl(w, st, stream, true, sampler);
+  SRGPT_TRY(check_pick(w, st, Pick{sampler, nullptr}, "srgpt_llm_decode_step_ex"));
+  return decode_step_impl(w, st, stream, true, Pick{sampler, nullptr});
 }
 
 extern "C" int srgpt_llm_decode_step_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
                                           srgpt_stream_t stream) {
-  SRGPT_TRY(check_sampler(w, st, sampler, "srgpt_llm_decode_step_proc"));
-  SRGPT_TRY(check_proc(st, lp, "srgpt_llm_decode_step_proc"));
-  return decode_step_impl(w, st, stream, true, sampler, lp);
+  SRGPT_TRY(check_pick(w, st, Pick{sampler, lp}, "srgpt_llm_decode_step_proc"));
+  return decode_step_impl(w, st, stream, true, Pick{sampler, lp});
 }
 
 extern "C" int srgpt_llm_decode_step(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream) {
-  return decode_step_impl(w, st, stream, true, SRGPT_SAMPLER_TOPK64);
+  SRGPT_TRY(check_pick(w, st, Pick{SRGPT_SAMPLER_TOPK64, nullptr}, "srgpt_llm_decode_step"));
+  return decode_step_impl(w, st, stream, true, Pick{SRGPT_SAMPLER_TOPK64, nullptr});
 }
 
 // Health of the decode steps since the last prefill (synchronises `stream` ONCE: both read-backs are queued, then one wait):
@@ -778,11 +730,13 @@ extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srg
 // ================================================================================================
 // hipGraph of one decode step
 // ================================================================================================
-static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, const srgpt_logits_proc* lp,
-                             srgpt_stream_t stream, srgpt_graph** out, const char* fn) {
+// the graph entry points' check: somewhere to put the graph, then check_pick
+static int check_graph(const srgpt_llm_weights* w, const srgpt_llm_state* st, Pick p, srgpt_graph** out, const char* fn) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_decode_graph_create: null out");
-  SRGPT_TRY(check_sampler(w, st, sampler, fn));
-  SRGPT_TRY(check_proc(st, lp, fn));
+  return check_pick(w, st, p, fn);
+}
+
+static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pick p, srgpt_stream_t stream, srgpt_graph** out) {
   LlmFormat fmt;  // incomplete fp8 weights never begin a capture (the step below resolves the format again)
   SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
   hipStream_t s = as_stream(stream);
@@ -793,7 +747,7 @@ static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, in
     return SRGPT_ERR_STATE;
   }
   // replays continue from the token the previous step (or srgpt_llm_sample_first) picked: its embedding is already in place
-  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), sampler, lp);
+  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), p);
   const hipError_t ee = hipStreamEndCapture(s, &graph);
   if (rc != SRGPT_OK) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -816,17 +770,20 @@ static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, in
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,
                                                 srgpt_graph** out) {
-  return graph_create_impl(w, st, sampler, nullptr, stream, out, "srgpt_llm_decode_graph_create_ex");
+  SRGPT_TRY(check_graph(w, st, Pick{sampler, nullptr}, out, "srgpt_llm_decode_graph_create_ex"));
+  return graph_create_impl(w, st, Pick{sampler, nullptr}, stream, out);
 }
 
 extern "C" int srgpt_llm_decode_graph_create_proc(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler,
                                                   const srgpt_logits_proc* lp, srgpt_stream_t stream, srgpt_graph** out) {
-  return graph_create_impl(w, st, sampler, lp, stream, out, "srgpt_llm_decode_graph_create_proc");
+  SRGPT_TRY(check_graph(w, st, Pick{sampler, lp}, out, "srgpt_llm_decode_graph_create_proc"));
+  return graph_create_impl(w, st, Pick{sampler, lp}, stream, out);
 }
 
 extern "C" int srgpt_llm_decode_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream,
                                              srgpt_graph** out) {
-  return srgpt_llm_decode_graph_create_ex(w, st, SRGPT_SAMPLER_TOPK64, stream, out);
+  SRGPT_TRY(check_graph(w, st, Pick{SRGPT_SAMPLER_TOPK64, nullptr}, out, "srgpt_llm_decode_graph_create"));
+  return graph_create_impl(w, st, Pick{SRGPT_SAMPLER_TOPK64, nullptr}, stream, out);
 }
 
 extern "C" int srgpt_graph_launch(srgpt_graph* g, int times, srgpt_stream_t stream) {

@@ -15,6 +15,8 @@
 //             <= 256 entries: top-p exactly as TopPLogitsWarper (ascending cumulative softmax, remove <= 1 - top_p, never the
 //             largest), and the draw by inverse CDF on one Philox4x32-10 uniform.
 //   launch 3  advance_kernel (model.hip) books the token like the greedy path and advances the Philox counter.
+// What the launches share with the argmax -- slice count and bounds, the vocabulary limit, the (value, index) tie rule and its
+// reductions, the Gumbel key, both workspace layouts -- is pick.h; sample_merge_kernel is launch 3 of the stand-alone ops.
 // That sampler serves top_k 1 .. 64 (any top_p) and pure temperature sampling.  The FULL sampler below (srgpt_sample_full, the
 // decode step's SRGPT_SAMPLER_FULL) serves every setting over the whole vocabulary:
 //   launch 1  sample_full_threshold_kernel  one 1024-thread block per sequence: keys of logits / T to the workspace; the kept set as
@@ -22,19 +24,17 @@
 //             over 64-bit fixed-point softmax mass (integer sums: bit-stable replays), a tie group cut by top-p losing its lowest
 //             indices first (CPU torch.sort's ascending order).
 //   launch 2  sample_full_draw_kernel       grid (128 slices, batch): masked Gumbel-max, per-slice (value, index) for the greedy
-//             merge (advance_kernel), Philox addressed like the top_k = 0 path.
+//             merge (advance_kernel / sample_merge_kernel), Philox addressed like the top_k = 0 path.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (step counter, sequence, vocabulary index | ~0): reproducible for
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
 // on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
 #include "common.h"
 #include "internal.h"
+#include "pick.h"
 
 namespace {
 
-constexpr int SMP_NB = 128;          // vocabulary slices per sequence
-constexpr int SMP_K = 64;            // candidates per slice = the largest top_k served on the device
-constexpr int SMP_SLICE_MAX = 2048;  // vocabulary entries of a slice (LDS): V <= 128 * 2048
-constexpr int SMP_LIST = 256;        // kept-set capacity: top_k plus ties at the k-th score
+constexpr int SMP_LIST = 256;  // kept-set capacity: top_k plus ties at the k-th score
 
 __device__ __forceinline__ unsigned key_of(float s) {
   const unsigned u = __float_as_uint(s);
@@ -42,21 +42,6 @@ __device__ __forceinline__ unsigned key_of(float s) {
 }
 __device__ __forceinline__ float score_of(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-struct U4 {
-  unsigned x, y, z, w;
-};
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
 }
 
 // k-th largest (k = 1 .. n) of keys[0 .. n) held in LDS; every thread of the block calls it (barriers inside).
@@ -113,54 +98,28 @@ __device__ unsigned block_select_kth(const unsigned* __restrict__ keys, int n, i
 __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __restrict__ logits, const srgpt_sampling* __restrict__ sp,
                                                              unsigned* __restrict__ cand_key, int* __restrict__ cand_idx,
                                                              float* __restrict__ pv, int* __restrict__ pi, int V) {
-  __shared__ unsigned keys[SMP_SLICE_MAX];
+  __shared__ unsigned keys[PICK_SLICE_MAX];
   __shared__ SelectLds L;
   __shared__ unsigned cnt;
-  __shared__ float sv[4];
-  __shared__ int si[4];
   const int b = blockIdx.y, nb = gridDim.x, blk = blockIdx.x, tid = threadIdx.x;
-  const int per = (V + nb - 1) / nb;
-  const int lo = blk * per, hi = min(lo + per, V), n = max(hi - lo, 0);
+  const PickSlice sl = pick_slice(V);
+  const int lo = sl.lo, hi = sl.hi, n = max(hi - lo, 0);
   const float* row = logits + (size_t)b * V;
   const float T = sp->temperature;
   const int topk = min(sp->top_k, SMP_K);
   if (topk <= 0) {
-    // ---- Gumbel-max: argmax_i (logit_i / T + g_i), g_i = -log(-log(u_i)), is a draw from softmax(logits / T) ----
+    // ---- Gumbel-max over logits / T: the slice's best key for the greedy merge ----
     const unsigned long long ctr = sp->counter, seed = sp->seed;
     float best = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = PICK_NONE;
     for (int i = lo + tid; i < hi; i += 256) {
-      const U4 r = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)b, (unsigned)i}, (unsigned)seed, (unsigned)(seed >> 32));
-      const float u = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-      const float v = row[i] / T - logf(-logf(u));
+      const float v = pick_gumbel_key(row[i] / T, ctr, seed, b, i);
       if (v > best) {
         best = v;
         bi = i;
       }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > best || (ov == best && oi < bi)) {
-        best = ov;
-        bi = oi;
-      }
-    }
-    if ((tid & 63) == 0) {
-      sv[tid >> 6] = best;
-      si[tid >> 6] = bi;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      for (int i = 1; i < 4; ++i)
-        if (sv[i] > best || (sv[i] == best && si[i] < bi)) {
-          best = sv[i];
-          bi = si[i];
-        }
-      pv[(size_t)b * nb + blk] = best;
-      pi[(size_t)b * nb + blk] = bi;
-    }
+    pick_store_slice(best, bi, pv, pi);
     return;
   }
   // ---- top-k of the slice ----
@@ -204,7 +163,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
 __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ cand_key,
                                                              const int* __restrict__ cand_idx, int64_t* __restrict__ tok, int nb,
                                                              int* __restrict__ err) {
-  constexpr int NC = SMP_NB * SMP_K;
+  constexpr int NC = PICK_SLICES * SMP_K;
   __shared__ unsigned keys[NC];
   __shared__ int idxs[NC];
   __shared__ SelectLds L;
@@ -306,22 +265,14 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_samplin
   }
 }
 
-__global__ void sample_bump_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int nb,
-                                   int64_t* __restrict__ tok, int B) {
-  // stand-alone op only (the decode step's advance_kernel does both): Gumbel mode merges the slice maxima; every mode advances the counter
-  if (sp->top_k <= 0)
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int i = 0; i < nb; ++i) {
-        const float v = pv[(size_t)b * nb + i];
-        const int ix = pi[(size_t)b * nb + i];
-        if (v > best || (v == best && ix < bi)) {
-          best = v;
-          bi = ix;
-        }
-      }
-      tok[b] = bi == 0x7fffffff ? 0 : bi;
+// the stand-alone ops only (the decode step's advance_kernel does both): merge the slices' maxima, one wave per row -- always (the full
+// sampler), or only in Gumbel mode (srgpt_sample: sample_select_kernel drew the token otherwise); every call advances the counter
+__global__ void sample_merge_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int64_t* __restrict__ tok,
+                                    int B, int always) {
+  if (always || sp->top_k <= 0)
+    for (int b = threadIdx.x >> 6; b < B; b += blockDim.x >> 6) {
+      const int t = pick_merge_row(pv + (size_t)b * PICK_SLICES, pi + (size_t)b * PICK_SLICES, PICK_SLICES, threadIdx.x & 63);
+      if ((threadIdx.x & 63) == 0) tok[b] = t;
     }
   __syncthreads();
   if (threadIdx.x == 0) sp->counter += 1;
@@ -536,56 +487,29 @@ __global__ __launch_bounds__(SFU_THREADS) void sample_full_threshold_kernel(cons
   }
 }
 
-// launch 2: masked Gumbel-max per vocabulary slice, grid (ARGMAX_BLOCKS slices, batch) -> the per-slice (value, index) pairs the
-// greedy merge (advance_kernel, or sample_full_merge_kernel for the stand-alone op) consumes.  Same Philox addressing as the top_k = 0
-// path of sample_partial_kernel.  kept_mask (optional): bit i % 32 of word i / 32 of the row = entry i kept.
+// launch 2: masked Gumbel-max per vocabulary slice, grid (PICK_SLICES, batch) -> the per-slice (value, index) pairs the greedy merge
+// (advance_kernel, or sample_merge_kernel for the stand-alone op) consumes.  Same Philox addressing as the top_k = 0 path of
+// sample_partial_kernel.  kept_mask (optional): bit i % 32 of word i / 32 of the row = entry i kept.
 __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ keys_ws,
                                                               const unsigned* __restrict__ thr, float* __restrict__ pv,
                                                               int* __restrict__ pi, unsigned* __restrict__ kept_mask, int V) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
   const int b = blockIdx.y, nb = gridDim.x, blk = blockIdx.x, tid = threadIdx.x;
-  const int per = (V + nb - 1) / nb;
-  const int lo = blk * per, hi = min(lo + per, V);
+  const PickSlice sl = pick_slice(V);
   const unsigned* keys = keys_ws + (size_t)b * V;
   const unsigned tkey = thr[(size_t)b * 4], tidx = thr[(size_t)b * 4 + 1];
   const unsigned long long ctr = sp->counter, seed = sp->seed;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int i = lo + tid; i < hi; i += 256) {
+  int bi = PICK_NONE;
+  for (int i = sl.lo + tid; i < sl.hi; i += 256) {
     const unsigned key = keys[i];
     if (key < tkey || (key == tkey && (unsigned)i < tidx)) continue;
-    const U4 r = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)b, (unsigned)i}, (unsigned)seed, (unsigned)(seed >> 32));
-    const float u = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0, 1)
-    const float v = score_of(key) - logf(-logf(u));
+    const float v = pick_gumbel_key(score_of(key), ctr, seed, b, i);
     if (v > best) {
       best = v;
       bi = i;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) {
-      best = ov;
-      bi = oi;
-    }
-  }
-  if ((tid & 63) == 0) {
-    sv[tid >> 6] = best;
-    si[tid >> 6] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < 4; ++i)
-      if (sv[i] > best || (sv[i] == best && si[i] < bi)) {
-        best = sv[i];
-        bi = si[i];
-      }
-    pv[(size_t)b * nb + blk] = best;
-    pi[(size_t)b * nb + blk] = bi;
-  }
+  pick_store_slice(best, bi, pv, pi);
   if (kept_mask) {
     const int nw = (V + 31) / 32;
     for (int w = blk * 256 + tid; w < nw; w += nb * 256) {
@@ -601,59 +525,32 @@ __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampl
   }
 }
 
-// stand-alone op only (the decode step's advance_kernel does both): merge the slices' maxima, advance the counter
-__global__ void sample_full_merge_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int nb,
-                                         int64_t* __restrict__ tok, int B) {
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = 0; i < nb; ++i) {
-      const float v = pv[(size_t)b * nb + i];
-      const int ix = pi[(size_t)b * nb + i];
-      if (v > best || (v == best && ix < bi)) {
-        best = v;
-        bi = ix;
-      }
-    }
-    tok[b] = bi == 0x7fffffff ? 0 : bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) sp->counter += 1;
-}
-
 }  // namespace
 
-// workspace: candidates (key + index) of every slice, then the Gumbel-mode slice maxima
-extern "C" int64_t srgpt_sample_ws_bytes(int B) {
-  if (B <= 0) return -1;
-  return (int64_t)B * SMP_NB * SMP_K * 8 + (int64_t)B * SMP_NB * 8 + 256;
-}
+// the top-k-64 sampler's workspace (SampleWs, pick.h)
+extern "C" int64_t srgpt_sample_ws_bytes(int B) { return B <= 0 ? -1 : carve_sample_ws(nullptr, B).bytes; }
 
 // internal (model.hip): launches 1 and 2; the caller books the token (advance_kernel) and advances the counter
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s) {
   SRGPT_CHECK(logits && sp && tok && ws && pv && pi && err, SRGPT_ERR_ARG, "srgpt_sample: null pointer");
-  SRGPT_CHECK(B > 0 && V > 0 && V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample: vocabulary %d exceeds %d", V,
-              SMP_NB * SMP_SLICE_MAX);
-  unsigned* ck = reinterpret_cast<unsigned*>(ws);
-  int* ci = reinterpret_cast<int*>(ck + (size_t)B * SMP_NB * SMP_K);
-  hipLaunchKernelGGL(sample_partial_kernel, dim3(SMP_NB, B), dim3(256), 0, s, logits, sp, ck, ci, pv, pi, V);
-  hipLaunchKernelGGL(sample_select_kernel, dim3(B), dim3(1024), 0, s, sp, ck, ci, tok, SMP_NB, err);
+  SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_UNSUPPORTED, "srgpt_sample: empty shape");
+  SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
+  const SampleWs c = carve_sample_ws(ws, B);
+  hipLaunchKernelGGL(sample_partial_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, logits, sp, c.cand_key, c.cand_idx, pv, pi, V);
+  hipLaunchKernelGGL(sample_select_kernel, dim3(B), dim3(1024), 0, s, sp, c.cand_key, c.cand_idx, tok, PICK_SLICES, err);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
   SRGPT_CHECK(logits && sp && tok_out && ws && B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample: null pointer or empty shape");
-  SRGPT_CHECK(V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample: vocabulary %d exceeds %d", V, SMP_NB * SMP_SLICE_MAX);
-  char* tail = reinterpret_cast<char*>(ws) + (size_t)B * SMP_NB * SMP_K * 8;
-  float* pv = reinterpret_cast<float*>(tail);
-  int* pi = reinterpret_cast<int*>(tail + (size_t)B * SMP_NB * 4);
-  int* err = reinterpret_cast<int*>(tail + (size_t)B * SMP_NB * 8);
+  SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
+  const SampleWs c = carve_sample_ws(ws, B);
   hipStream_t s = as_stream(stream);
-  SRGPT_HIP_TRY(hipMemsetAsync(err, 0, sizeof(int), s), "srgpt_sample: clearing the error word");
-  SRGPT_TRY(srgpt_sample_launch(logits, sp, tok_out, ws, pv, pi, err, B, V, s));
-  hipLaunchKernelGGL(sample_bump_kernel, dim3(1), dim3(256), 0, s, sp, pv, pi, SMP_NB, tok_out, B);
+  SRGPT_HIP_TRY(hipMemsetAsync(c.err, 0, sizeof(int), s), "srgpt_sample: clearing the error word");
+  SRGPT_TRY(srgpt_sample_launch(logits, sp, tok_out, ws, c.pv, c.pi, c.err, B, V, s));
+  hipLaunchKernelGGL(sample_merge_kernel, dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 0);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -661,9 +558,8 @@ extern "C" int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* to
 // health of the last srgpt_sample call(s) on this workspace (synchronises `stream`): the sticky error word at the tail of ws
 extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream) {
   SRGPT_CHECK(ws && B > 0, SRGPT_ERR_ARG, "srgpt_sample_status: bad args");
-  const char* tail = reinterpret_cast<const char*>(ws) + (size_t)B * SMP_NB * SMP_K * 8;
   int host = 0;
-  SRGPT_HIP_TRY(hipMemcpyAsync(&host, tail + (size_t)B * SMP_NB * 8, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_sample_status: copy");
+  SRGPT_HIP_TRY(hipMemcpyAsync(&host, carve_sample_ws(ws, B).err, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_sample_status: copy");
   SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_sample_status: synchronize");
   SRGPT_CHECK((host & 4) == 0, SRGPT_ERR_UNSUPPORTED,
               "sampling: top_k > %d, or a top-p filter without top-k, is not served by the device sampler (the draw used another distribution)", SMP_K);
@@ -671,41 +567,31 @@ extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream)
   return SRGPT_OK;
 }
 
-int srgpt_sample_slices() { return SMP_NB; }
-
-// ---- the full sampler ----
-// workspace: keys u32 [B][V] | thresholds u32 [B][4] | slice maxima f32 [B][128] | their indices i32 [B][128]
-extern "C" int64_t srgpt_sample_full_ws_bytes(int B, int V) {
-  if (B <= 0 || V <= 0) return -1;
-  return (int64_t)B * ((int64_t)4 * V + 16 + (int64_t)SMP_NB * 8);
-}
+// ---- the full sampler: its workspace is SampleFullWs (pick.h) ----
+extern "C" int64_t srgpt_sample_full_ws_bytes(int B, int V) { return B <= 0 || V <= 0 ? -1 : carve_sample_full_ws(nullptr, B, V).bytes; }
 
 // internal (model.hip): launches 1 and 2 into the caller's slice maxima pv / pi ([B][128]); the caller merges, books the token and
-// advances the counter.  keys_thr = the first B * (4 V + 16) bytes of a srgpt_sample_full_ws_bytes workspace.
+// advances the counter.  keys_thr = the head (keys and thresholds) of a SampleFullWs.
 int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
                              int V, hipStream_t s) {
   SRGPT_CHECK(logits && sp && keys_thr && pv && pi, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
-  SRGPT_CHECK(V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample_full: vocabulary %d exceeds %d", V, SMP_NB * SMP_SLICE_MAX);
-  unsigned* keys = reinterpret_cast<unsigned*>(keys_thr);
-  unsigned* thr = keys + (size_t)B * V;
-  hipLaunchKernelGGL(sample_full_threshold_kernel, dim3(B), dim3(SFU_THREADS), 0, s, logits, sp, keys, thr, V);
-  hipLaunchKernelGGL(sample_full_draw_kernel, dim3(SMP_NB, B), dim3(256), 0, s, sp, keys, thr, pv, pi, kept_mask, V);
+  SRGPT_TRY(pick_check_vocab(V, "srgpt_sample_full"));
+  const SampleFullWs c = carve_sample_full_ws(keys_thr, B, V);
+  hipLaunchKernelGGL(sample_full_threshold_kernel, dim3(B), dim3(SFU_THREADS), 0, s, logits, sp, c.keys, c.thr, V);
+  hipLaunchKernelGGL(sample_full_draw_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, sp, c.keys, c.thr, pv, pi, kept_mask, V);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
                                  srgpt_stream_t stream) {
-  SRGPT_CHECK(logits && sp && tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
+  SRGPT_CHECK(tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
-  SRGPT_CHECK(V <= SMP_NB * SMP_SLICE_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_sample_full: vocabulary %d exceeds %d", V, SMP_NB * SMP_SLICE_MAX);
-  char* tail = reinterpret_cast<char*>(ws) + (size_t)B * ((size_t)4 * V + 16);
-  float* pv = reinterpret_cast<float*>(tail);
-  int* pi = reinterpret_cast<int*>(tail + (size_t)B * SMP_NB * 4);
+  const SampleFullWs c = carve_sample_full_ws(ws, B, V);
   hipStream_t s = as_stream(stream);
-  SRGPT_TRY(srgpt_sample_full_launch(logits, sp, ws, pv, pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
-  hipLaunchKernelGGL(sample_full_merge_kernel, dim3(1), dim3(256), 0, s, sp, pv, pi, SMP_NB, tok_out, B);
+  SRGPT_TRY(srgpt_sample_full_launch(logits, sp, ws, c.pv, c.pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
+  hipLaunchKernelGGL(sample_merge_kernel, dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 1);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }

@@ -97,11 +97,8 @@ class DecodeState:
         if key not in self.graphs:
             g = L.vp()
             lib, w = L.load(), self._eng.w.llm
-            if self.proc:
-                L.check(lib.srgpt_llm_decode_graph_create_proc(C.byref(w), C.byref(self.c), self.sampler, self.proc, ops._stream(),
-                                                               C.byref(g)))
-            else:
-                L.check(lib.srgpt_llm_decode_graph_create_ex(C.byref(w), C.byref(self.c), self.sampler, ops._stream(), C.byref(g)))
+            # proc = None goes as NULL: exactly the graph of the _ex form (same launches)
+            L.check(lib.srgpt_llm_decode_graph_create_proc(C.byref(w), C.byref(self.c), self.sampler, self.proc, ops._stream(), C.byref(g)))
             self.graphs[key] = g
         return self.graphs[key]
 
@@ -523,10 +520,7 @@ class SrgptEngine:
     def _decode_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria):
         lib = L.load()
         stream = ops._stream()
-        if st.proc:
-            L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
-        else:
-            L.check(lib.srgpt_llm_sample_first_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
+        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))  # proc None: NULL
         eos = None  # ordered list of EOS ids (HF accepts an int or a list; Llama-3 checkpoints list two)
         if eos_token_id is not None:
             eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
@@ -541,10 +535,7 @@ class SrgptEngine:
                 L.check(lib.srgpt_graph_launch(graph, n, stream))
             else:
                 for _ in range(n):
-                    if st.proc:
-                        L.check(lib.srgpt_llm_decode_step_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
-                    else:
-                        L.check(lib.srgpt_llm_decode_step_ex(C.byref(self.w.llm), C.byref(st.c), st.sampler, stream))
+                    L.check(lib.srgpt_llm_decode_step_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
 
         def judge(ids, lo, hi):
             """host-side EOS / stopping-criteria scan of steps [lo, hi) of `ids` (CPU int64 [B, >= hi]); -> stop step or None."""

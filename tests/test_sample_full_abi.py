@@ -87,3 +87,41 @@ def test_every_sampling_setting_has_a_device_sampler():
     assert pick(0.7, 1000, None, 128 * 2048 + 1) is None and pick(0.0, 50, None, V) is None and pick(None, 50, None, V) is None
     # the top-k-64 sampler's own predicate keeps its meaning
     assert not SamplingParams.supported(0.7, 0, 0.9, V) and not SamplingParams.supported(0.7, 65, None, V)
+
+
+def test_sample_workspace_formula():
+    from spatialrgpt_amd import _lib
+
+    lib = _lib.load()
+    # candidates (key + index: 8 bytes) of 64 slots x 128 slices per row + 128 slice maxima (value + index) per row + the error word
+    for B in (1, 3, 16):
+        assert lib.srgpt_sample_ws_bytes(B) == B * 128 * 64 * 8 + B * 128 * 8 + 256
+    assert lib.srgpt_sample_ws_bytes(0) == -1
+
+
+# srgpt_llm_ws_bytes(weights, batch, max_tokens) as the build before the samplers' layouts moved to csrc/pick.h returned it:
+# (config, weight format, batch, max_tokens) -> bytes.  native: the config's dtype; fp8: bf16 activations; fp8_w8a8: fp8_act set.
+LLM_WS_BYTES = {
+    ("tiny", "native", 1, 32): 327424, ("tiny", "native", 8, 32): 2609408,
+    ("tiny", "fp8", 1, 32): 275712, ("tiny", "fp8", 8, 32): 2192128,
+    ("tiny", "fp8_w8a8", 1, 32): 281088, ("tiny", "fp8_w8a8", 8, 32): 2234112,
+    ("vila15_8b", "native", 1, 259): 84463872, ("vila15_8b", "native", 8, 259): 675702784,
+    ("vila15_8b", "fp8", 1, 259): 84463872, ("vila15_8b", "fp8", 8, 259): 675702784,
+    ("vila15_8b", "fp8_w8a8", 1, 259): 88178176, ("vila15_8b", "fp8_w8a8", 8, 259): 705415424,
+}
+
+
+def test_llm_workspace_bytes_are_unchanged():
+    from spatialrgpt_amd import _lib
+    from spatialrgpt_amd.config import SrgptConfig
+    from tests.util import load_tiny
+
+    lib = _lib.load()
+    cfgs = {"tiny": (SrgptConfig(**load_tiny("tiny_fp32.npz")[0]), _lib.F32), "vila15_8b": (SrgptConfig.vila15_8b(), _lib.BF16)}
+    for (name, fmt, B, T), want in LLM_WS_BYTES.items():
+        cfg, native = cfgs[name]
+        w = _lib.LlmWeights()
+        w.dtype, w.hidden, w.inter, w.layers = native if fmt == "native" else _lib.BF16, cfg.hidden, cfg.inter, cfg.layers
+        w.heads, w.kv_heads, w.head_dim, w.vocab = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.vocab
+        w.fp8_act = 1 if fmt == "fp8_w8a8" else 0
+        assert lib.srgpt_llm_ws_bytes(ctypes.byref(w), B, T) == want, (name, fmt, B, T)

@@ -203,6 +203,7 @@ int srgpt_rmsnorm(const void* x, const void* w, void* y, int rows, int cols, flo
  *   Q[b, t, h, :]  at q  + b*q_bs  + t*q_ts  + h*q_hs ; K/V[b, s, hk, :] likewise; O dense [b, t, h, d].
  *   causal: key s visible to query t iff s <= t + (Tk - Tq).
  *   kv_len (device int[B], may be NULL): per-row number of valid keys (right-padded batches).
+ *   A query with no visible key (kv_len[b] = 0, or causal with t + (Tk - Tq) < 0) yields zeros.
  * --------------------------------------------------------------------------------------------- */
 int srgpt_attention(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq,
                     int Hkv, int D, int64_t q_bs, int64_t q_ts, int64_t q_hs, int64_t k_bs, int64_t k_ts,

@@ -370,12 +370,25 @@ def rope_kv_append(qkv, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D, pos0
                                           Hkv, D, max_pos, dt_code(qkv), _stream()))
 
 
-def decode_attention(qkv, kcache, vcache, pos, cos_tab, sin_tab, Hq, Hkv, D):
+def decode_attention_ws(B, Hq, D, device):
+    """Workspace of srgpt_decode_attention for B sequences, zeroed -> (ws, tickets): `tickets` is the int32 view of the arrival
+    tickets behind the B * Hq * 64 * (D + 2) partial floats (include/srgpt.h), sharing ws's memory."""
+    n = int(L.load().srgpt_decode_attn_ws_floats(B, Hq, D))
+    ws = torch.zeros((n,), device=device, dtype=torch.float32)
+    return ws, ws[B * Hq * 64 * (D + 2):].view(torch.int32)
+
+
+def decode_attention(qkv, kcache, vcache, pos, cos_tab, sin_tab, Hq, Hkv, D, ws=None):
+    """ws: a caller-owned workspace (decode_attention_ws) whose tickets are zero, reused from launch to launch; None = a fresh one."""
     _dev(qkv, kcache, vcache, pos)
     B = qkv.shape[0]
     max_pos = kcache.shape[-2]
     out = torch.empty((B, Hq * D), device=qkv.device, dtype=qkv.dtype)
-    ws = torch.zeros((L.load().srgpt_decode_attn_ws_floats(B, Hq, D),), device=qkv.device, dtype=torch.float32)  # tickets start at 0
+    if ws is None:
+        ws = decode_attention_ws(B, Hq, D, qkv.device)[0]  # tickets start at 0
+    else:
+        _dev(ws)
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= L.load().srgpt_decode_attn_ws_floats(B, Hq, D)
     L.check(L.load().srgpt_decode_attention(_p(qkv), _p(kcache), _p(vcache), _p(pos), _p(cos_tab), _p(sin_tab), _p(out),
                                             _p(ws), B, Hq, Hkv, D, max_pos, dt_code(qkv), _stream()))
     return out

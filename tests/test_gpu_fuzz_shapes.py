@@ -82,6 +82,44 @@ def test_decode_attention_random_shapes(seed):
 
 
 @pytest.mark.parametrize("seed", range(N_CASES))
+def test_decode_attention_ragged_random_shapes(seed):
+    """one launch whose rows sit at DIFFERENT positions (tests/test_gpu_attention_ragged.py's checker): geometry as above, every
+    row's pos drawn on its own"""
+    from tests import test_gpu_attention_ragged as tr
+    ri, pick = _draw(8300 + seed)
+    dtype = pick([torch.bfloat16, torch.bfloat16, torch.float32])
+    Hkv = ri(1, 8)
+    Hq = Hkv * pick([1, 2, 4, 8])
+    D = pick([16, 32, 64, 128, 128, 128])
+    max_pos = pick([512, 1024, 2048, 4096])
+    B = ri(2, 8)
+    while B * Hkv * max_pos * D > 1 << 24 and B > 2:  # the caches are filled and the keys rotated on the host: at most 16 M
+        B -= 1                                        # elements per cache (first fewer rows, then a smaller cache)
+    while B * Hkv * max_pos * D > 1 << 24:
+        max_pos //= 2
+    pos = [pick([ri(0, 70), ri(0, max_pos - 1), ri(max_pos - max_pos // 4, max_pos - 1)]) for _ in range(B)]
+    tr._decode_ragged_case(dtype, Hq, Hkv, D, max_pos, pos, 2 if max(pos) + 2 <= max_pos else 1, seed=8300 + seed)
+
+
+@pytest.mark.parametrize("seed", range(N_CASES))
+def test_attention_kvlen_random_shapes(seed):
+    """srgpt_attention with a kv_len per row, NaN behind it (tests/test_gpu_attention_ragged.py's checker): shapes as
+    test_attention_random_shapes up to 800 keys, lengths near the 64-key tile edges half the time"""
+    from tests import test_gpu_attention_ragged as tr
+    ri, pick = _draw(8400 + seed)
+    dtype = pick([torch.bfloat16, torch.bfloat16, torch.float32])
+    Hkv = ri(1, 4)
+    Hq = Hkv * pick([1, 1, 2, 3, 4, 8])
+    D = pick([16, 32, 64, 72, 80, 96, 128])
+    causal = bool(ri(0, 1))
+    Tk = pick([ri(1, 70), ri(60, 800), ri(60, 800)])
+    Tq = Tk if (not causal or ri(0, 2)) else ri(1, Tk)
+    B = ri(2, 4)
+    lens = [min(Tk, max(1, pick([64 * ri(0, Tk // 64 + 1) + ri(-1, 1), ri(1, Tk)]))) for _ in range(B)]
+    tr._attn_kvlen_case(dtype, B, Tq, Tk, Hq, Hkv, D, causal, lens, seed=8400 + seed)
+
+
+@pytest.mark.parametrize("seed", range(N_CASES))
 def test_norms_random_shapes(seed):
     ri, pick = _draw(7500 + seed)
     dtype = pick([torch.bfloat16, torch.float32])

@@ -61,9 +61,14 @@ def _splitk_ws(device, M, N):
     return t
 
 
-def _ws_arg(device, M, N, enabled=True):
+def _ws_arg(device, M, N, enabled=True, ws=None):
     """(pointer, byte count) of the split-K workspace for an [M, N] product as the C ABI takes them; (None, 0) -- no split-K --
-    when the caller's condition is off or the slabs would be too large."""
+    when the caller's condition is off or the slabs would be too large.  `ws`: a caller-owned workspace (any contiguous tensor on
+    the device; all of its bytes are offered) in place of the shared one."""
+    if ws is not None:
+        _dev(ws)
+        assert ws.is_contiguous() and ws.data_ptr() % 16 == 0
+        return ws.data_ptr(), ws.numel() * ws.element_size()
     if not (enabled and M * N <= (1 << 24)):
         return None, 0
     ws = _splitk_ws(device, M, N)
@@ -71,8 +76,9 @@ def _ws_arg(device, M, N, enabled=True):
 
 
 def gemm(a, w, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False, bias_mod=0, res_mod=0,
-         out_mode=L.OUT_PLAIN, gw=0, out_shape=None):
-    """act(a @ w.T + bias) + residual.  a [M,K] (row stride may exceed K), w [N,K]."""
+         out_mode=L.OUT_PLAIN, gw=0, out_shape=None, ws=None):
+    """act(a @ w.T + bias) + residual.  a [M,K] (row stride may exceed K), w [N,K].  ws: a caller-owned split-K workspace
+    (None = the shared one, sized by this module)."""
     _dev(a, w, bias, residual)
     _same_dtype("gemm", a, weight=w, bias=bias, residual=residual)
     M, K = a.shape
@@ -82,17 +88,17 @@ def gemm(a, w, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False
         shape = out_shape if out_shape is not None else (M, N)
         out = torch.empty(shape, device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
     ldc = N if out_mode != L.OUT_PLAIN else out.stride(0) if out.dim() == 2 else N
-    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16)
+    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16, ws)
     L.check(L.load().srgpt_gemm(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, a.stride(0), ldc, act,
                                 bias_mod, res_mod, int(out_f32), out_mode, gw, ws, ws_bytes,
                                 dt_code(a), _stream()))
     return out
 
 
-def gemm_norm(a, w, residual, norm_w, eps, bias=None, norm_b=None, out=None, y=None):
+def gemm_norm(a, w, residual, norm_w, eps, bias=None, norm_b=None, out=None, y=None, ws=None):
     """(a @ w.T + bias + residual, norm(that)): the tail of an attention / MLP block and the next block's input norm in one call --
     RMSNorm (norm_b None: Llama) or LayerNorm (ViT).  `out` may be `residual` (in place), `y` may be `a`.  Bit-identical to gemm(...)
-    followed by rmsnorm(...) / layernorm(...)."""
+    followed by rmsnorm(...) / layernorm(...).  ws: as for gemm."""
     _dev(a, w, residual, norm_w, bias, norm_b)
     _same_dtype("gemm_norm", a, weight=w, residual=residual, norm_weight=norm_w, bias=bias, norm_bias=norm_b)
     M, K = a.shape
@@ -102,7 +108,7 @@ def gemm_norm(a, w, residual, norm_w, eps, bias=None, norm_b=None, out=None, y=N
         out = torch.empty((M, N), device=a.device, dtype=a.dtype)
     if y is None:
         y = torch.empty((M, N), device=a.device, dtype=a.dtype)
-    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16)
+    ws, ws_bytes = _ws_arg(a.device, M, N, a.dtype == torch.bfloat16, ws)
     kind = L.NORM_RMS if norm_b is None else L.NORM_LAYER
     L.check(L.load().srgpt_gemm_norm(_p(a), _p(w), _p(bias), _p(residual), _p(out), M, N, K, ws, ws_bytes,
                                      kind, _p(norm_w), _p(norm_b), _p(y), float(eps), dt_code(a), _stream()))
@@ -215,9 +221,9 @@ def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=N
     return (out, table) if publish else out
 
 
-def gemm_w8(a, w8, wscale, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False):
+def gemm_w8(a, w8, wscale, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False, ws=None):
     """act((a @ fp8(w8).T) * wscale + bias) + residual: a [M,K] bf16 (row stride may exceed K), w8 uint8 [N,K] (OCP e4m3fn),
-    wscale fp32 [N]."""
+    wscale fp32 [N].  ws: as for gemm."""
     _dev(a, w8, wscale, bias, residual)
     _same_dtype("gemm_w8", a, bias=bias, residual=residual)
     if a.dtype != torch.bfloat16 or w8.dtype != torch.uint8 or wscale.dtype != torch.float32:
@@ -227,7 +233,7 @@ def gemm_w8(a, w8, wscale, bias=None, residual=None, act=L.ACT_NONE, out=None, o
     assert w8.shape[1] == K and a.stride(1) == 1 and w8.is_contiguous() and wscale.numel() == N
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
-    ws, ws_bytes = _ws_arg(a.device, M, N)
+    ws, ws_bytes = _ws_arg(a.device, M, N, ws=ws)
     L.check(L.load().srgpt_gemm_w8(_p(a), _p(w8), _p(wscale), _p(bias), _p(residual), _p(out), M, N, K, a.stride(0), out.stride(0),
                                    act, int(out_f32), ws, ws_bytes, _stream()))
     return out
@@ -270,9 +276,10 @@ def quant_rows_e4m3_swiglu(gate_up):
     return q, sc
 
 
-def gemm_w8a8(a8, ascale, w8, wscale, bias=None, residual=None, out=None, out_f32=False):
+def gemm_w8a8(a8, ascale, w8, wscale, bias=None, residual=None, out=None, out_f32=False, ws=None):
     """((fp8(a8) @ fp8(w8).T) * ascale[:,None] * wscale[None,:] + bias) + residual on the fp8 matrix pipe: a8 uint8 [M,K],
-    w8 uint8 [N,K] (OCP e4m3fn), ascale fp32 [M], wscale fp32 [N]; bias / residual / out bf16 (out fp32 if out_f32)."""
+    w8 uint8 [N,K] (OCP e4m3fn), ascale fp32 [M], wscale fp32 [N]; bias / residual / out bf16 (out fp32 if out_f32).  ws: as
+    for gemm."""
     _dev(a8, ascale, w8, wscale, bias, residual)
     if a8.dtype != torch.uint8 or w8.dtype != torch.uint8 or ascale.dtype != torch.float32 or wscale.dtype != torch.float32:
         raise ValueError("gemm_w8a8: a8 / w8 must be uint8, ascale / wscale fp32")
@@ -284,7 +291,7 @@ def gemm_w8a8(a8, ascale, w8, wscale, bias=None, residual=None, out=None, out_f3
     assert w8.shape[1] == K and a8.stride(1) == 1 and w8.is_contiguous() and ascale.numel() == M and wscale.numel() == N
     if out is None:
         out = torch.empty((M, N), device=a8.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
-    ws, ws_bytes = _ws_arg(a8.device, M, N)
+    ws, ws_bytes = _ws_arg(a8.device, M, N, ws=ws)
     L.check(L.load().srgpt_gemm_w8a8(_p(a8), _p(ascale), _p(w8), _p(wscale), _p(bias), _p(residual), _p(out), M, N, K,
                                      a8.stride(0), out.stride(0), int(out_f32), ws, ws_bytes,
                                      _stream()))

@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import assert_close, load_kat
+from tests.util import assert_close, build_gemm_route_cli, load_kat
 
 pytestmark = pytest.mark.gpu
 
@@ -180,18 +180,33 @@ def test_gemm_deconv2x(dtype, n_img, g, C):
     assert_close(out.reshape(n_img, 4 * g * g, C), ref, _tol(ref, dtype), 0, "deconv2x")
 
 
+@pytest.fixture(scope="module")
+def route_cli(tmp_path_factory):
+    return build_gemm_route_cli(tmp_path_factory.mktemp("gemm_route"))
+
+
+# at 256 CUs and K < 2048 the 256 x 256 kernel runs only when the last round of its tiles is at least 88 % full (gemm_route.h)
+ON_96_ROW_TILES = {(3000, 4304, 1152), (2048, 4096, 1024), (2305, 3456, 256)}
+
+
 @pytest.mark.parametrize("M,N,K,what", [
-    (3000, 4304, 1152, "ragged M and N, 204 tiles, no split (ViT fc1 shape at ~2 images x 2)"),
-    (2048, 4096, 1024, "128 tiles -> split-K 2 (deterministic slabs)"),
+    (3000, 4304, 1152, "ragged M and N, 204 tiles = 80 % of a round -> 96-row tiles, no split (ViT fc1 shape at ~2 images x 2)"),
+    (2048, 4096, 1024, "128 tiles = half a round -> 96-row tiles, single buffer, no split"),
     (4096, 4096, 512, "exact tiles, 8 K tiles"),
     (2072, 28672, 4096, "batched prefill gate/up (8 requests x 259 rows)"),
     (11664, 1152, 4352, "batched ViT fc2 with K padded to a multiple of 64"),
-    (2305, 3456, 256, "minimum K (4 tiles): prologue/tail paths only")])
-def test_gemm_256_tile_kernel(M, N, K, what):
-    """gemm256.hip (256 x 256 x 64 tiles, 8 waves, counted LDS-DMA waits): every shape here takes that kernel.  Checked
-    against fp32 torch on the device with an ASYMMETRIC epilogue (bias + tanh-GELU + residual) and a plain one, twice (the
-    second run must be bit-identical: a DMA / barrier race would show as run-to-run differences)."""
+    (2305, 3456, 256, "minimum K (4 tiles), 140 tiles = 55 % of a round -> 96-row tiles, single buffer"),
+    (3841, 3841, 256, "minimum K (4 tiles): prologue/tail paths only, 256 tiles = one full round")])
+def test_gemm_256_tile_kernel(M, N, K, what, route_cli):
+    """gemm256.hip (256 x 256 x 64 tiles, 8 waves, counted LDS-DMA waits) and the shapes just outside its rule: on 256 CUs the
+    shapes of ON_96_ROW_TILES take gemm_bf16_glds<96, 128, 1>, every other one the 256 x 256 kernel unsplit -- asserted through
+    the route header.  Checked against fp32 torch on the device with an ASYMMETRIC epilogue (bias + tanh-GELU + residual) and a
+    plain one, twice (the second run must be bit-identical: a DMA / barrier race would show as run-to-run differences)."""
     ops, L = _ops()
+    if L.load().srgpt_device_cus() == 256:
+        r = route_cli([("gemm", M, N, K, int(M * N <= 1 << 24), 32 * M * N)], 256)[0]  # ops.py's workspace
+        want = ("glds", 96, 1, 1) if (M, N, K) in ON_96_ROW_TILES else ("tile_256", 256, 2, 1)
+        assert (r["family"], r["bm"], r["nbuf"], r["splits"]) == want, r
     g = torch.Generator(device=DEV).manual_seed(M + N + K)
     a = torch.randn((M, K), generator=g, device=DEV).to(torch.bfloat16)
     w = (torch.randn((N, K), generator=g, device=DEV) * 0.05).to(torch.bfloat16)

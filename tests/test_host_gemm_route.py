@@ -7,10 +7,10 @@ into tests/gemm_route_cli.cpp, no HIP -- has to reproduce every row."""
 import itertools
 import json
 import os
-import shutil
-import subprocess
 
 import pytest
+
+from tests.util import build_gemm_route_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CUS = 256
@@ -23,25 +23,8 @@ def cdiv(a, b):
 
 @pytest.fixture(scope="module")
 def cli(tmp_path_factory):
-    cxx = next((c for c in ("g++", "c++", "clang++") if shutil.which(c)), None)
-    assert cxx, "the route test needs a host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("gemm_route") / "gemm_route_cli")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "spatialrgpt_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "gemm_route_cli.cpp"), "-o", exe], check=True)
-
-    def run(queries):
-        """queries: (entry, M, N, K, have_ws, ws_bytes) -> dicts of the route (swiglu: the string)"""
-        text = "".join("%s %d %d %d %d %d\n" % q for q in queries)
-        out = subprocess.run([exe, str(CUS)], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
-        assert len(out) == len(queries)
-        res = []
-        for ln in out:
-            f = ln.split()
-            res.append(ln if len(f) == 1 else dict(family=f[0], bm=int(f[1]), nbuf=int(f[2]), splits=int(f[3]), tps=int(f[4]),
-                                                   nk=int(f[5])))
-        return res
-
-    return run
+    run = build_gemm_route_cli(tmp_path_factory.mktemp("gemm_route"))
+    return lambda queries: run(queries, CUS)
 
 
 def launch_of(entry, M, N, r):

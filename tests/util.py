@@ -2,12 +2,42 @@
 import json
 import math
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
+
+
+def build_gemm_route_cli(out_dir):
+    """Compile tests/gemm_route_cli.cpp -- spatialrgpt_amd/csrc/gemm_route.h alone, no HIP -- into `out_dir` with the first host
+    C++ compiler on the path (hipcc where there is no other) and return run(queries, cus=256): queries are
+    (entry, M, N, K, have_ws, ws_bytes) with entry = gemm / gemm_w8 / gemm_w8a8 / swiglu; the answers are dicts of the route
+    (family, bm, nbuf, splits, tps = K tiles per split, nk = K tiles), for swiglu the string "fused" / "unfused"."""
+    cxx = next((c for c in ("g++", "c++", "clang++", "hipcc") if shutil.which(c)), None)
+    rocm_hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")  # where csrc/Makefile finds it
+    if cxx is None and os.path.exists(rocm_hipcc):
+        cxx = rocm_hipcc
+    assert cxx, "the route query needs a host C++ compiler"
+    exe = os.path.join(str(out_dir), "gemm_route_cli")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "spatialrgpt_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "gemm_route_cli.cpp"), "-o", exe], check=True)
+
+    def run(queries, cus=256):
+        text = "".join("%s %d %d %d %d %d\n" % tuple(q) for q in queries)
+        out = subprocess.run([exe, str(int(cus))], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+        assert len(out) == len(queries)
+        res = []
+        for ln in out:
+            f = ln.split()
+            res.append(ln if len(f) == 1 else dict(family=f[0], bm=int(f[1]), nbuf=int(f[2]), splits=int(f[3]), tps=int(f[4]),
+                                                   nk=int(f[5])))
+        return res
+
+    return run
 
 
 def _t(a, dtype):

@@ -143,6 +143,10 @@ int srgpt_gemm_w8a8(const void* A8, const float* ascale, const void* W8, const f
  *   norm_w != NULL : x <- RMSNorm(x) * norm_w first (modeling_llama.py:61-75) (rounded to dtype like torch)
  *   swiglu != 0    : W = [gate rows(N); up rows(N)], out[n] = silu(gate.x) * (up.x) (modeling_llama.py:221)
  *   residual       : out = residual + (W x)   (decoder layer residual adds, modeling_llama.py:650-684)
+ * Rounding points (rnd = round to nearest even to dtype; fp32: none), the same in all three kernel files and on every route:
+ *   out = rnd(rnd(acc * wscale) + residual) with acc the fp32 sum (wscale: srgpt_gemv_w8 only), swiglu:
+ *   out = rnd(rnd(silu(rnd(gate))) * rnd(up)).  out_f32 != 0 stores THAT dtype-rounded value widened to fp32 -- not the unrounded
+ *   fp32 sum -- so bf16 logits read back as fp32 equal the bf16 output bit for bit (tests/test_gpu_gemv_exact.py).
  */
 int srgpt_gemv(const void* x, const void* W, const void* norm_w, float norm_eps, const void* residual,
                void* out, int batch, int N, int K, int swiglu, int out_f32, int dtype, srgpt_stream_t stream);

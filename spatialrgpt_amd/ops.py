@@ -191,11 +191,12 @@ def pack_decode_weights(w, rows: int):
 
 
 def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False,
-               rowss_in=None, publish=False, packed_rows=0, n_rows=None):
+               rowss_in=None, publish=False, packed_rows=0, n_rows=None, table=None):
     """srgpt_gemv_rowss: the decode product of 2+ bf16 rows as the batched decode step runs it.  `rowss_in`: the statistics
     table of x's rows ([B, 512] fp32, from the call that produced x) replaces the RMSNorm's own reduction; `publish`: also
     return the table of the output rows.  `packed_rows` > 0: w / w8 is the flat packed array of pack_decode_weights (n_rows = the
-    matrix' row count, 2 N for SwiGLU).  Returns out, or (out, table)."""
+    matrix' row count, 2 N for SwiGLU).  `table`: with `publish`, the caller's contiguous fp32 [B, 512] tensor to publish into (None: a
+    new one).  Returns out, or (out, table)."""
     wt = w8 if w8 is not None else w
     _dev(x, wt, wscale, norm_w, residual, rowss_in)
     _same_dtype("gemv_rowss", x, norm_weight=norm_w, residual=residual)
@@ -211,7 +212,12 @@ def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=N
     N = rows_total // 2 if swiglu else rows_total
     if out is None:
         out = torch.empty((B, N), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
-    table = torch.empty((B, L.ROWSS_STRIDE), device=x.device, dtype=torch.float32) if publish else None
+    if table is not None:
+        _dev(table)
+        if not publish or table.dtype != torch.float32 or tuple(table.shape) != (B, L.ROWSS_STRIDE) or not table.is_contiguous():
+            raise ValueError("gemv_rowss: table must be a contiguous fp32 [batch, 512] tensor, with publish=True")
+    elif publish:
+        table = torch.empty((B, L.ROWSS_STRIDE), device=x.device, dtype=torch.float32)
     if rowss_in is not None and (rowss_in.dtype != torch.float32 or tuple(rowss_in.shape) != (B, L.ROWSS_STRIDE)
                                  or not rowss_in.is_contiguous()):
         raise ValueError("gemv_rowss: rowss_in must be a contiguous fp32 [batch, 512] table")

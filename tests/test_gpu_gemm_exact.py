@@ -22,14 +22,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import build_gemm_route_cli
+from tests.util import FP8_NAN, SENTINEL, build_gemm_route_cli
+from tests.util import away as _away, check_guarded as _check_guarded, exact_f32 as _exact_f32, guarded as _guarded, ints as _ints
+from tests.util import poisoned as _poisoned, rne as _rne, trunc as _trunc
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 BF16, F32 = torch.bfloat16, torch.float32
-SENTINEL = {BF16: (torch.int16, 0x5A5A), F32: (torch.int32, 0x5A5A5A5A)}  # a finite, unlikely value in either type
-FP8_NAN = 0x7F  # e4m3fn
 LIVE_FLOOR = 0.01
 
 
@@ -56,29 +56,6 @@ def _assert_route(route_cli, entry, M, N, K, have_ws, ws_bytes, want):
 
 
 # ------------------------------------------------------------------------------------------------ the CPU side
-def _ints(shape, bound, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-bound, bound + 1, shape, generator=g).double()
-
-
-def _rne(x):
-    return x.to(BF16).float()
-
-
-def _trunc(x):
-    return (x.contiguous().view(torch.int32) & -65536).view(F32)
-
-
-def _away(x):  # round half away from zero
-    return ((x.contiguous().view(torch.int32) + 0x8000) & -65536).view(F32)
-
-
-def _exact_f32(x64):
-    x = x64.float()
-    assert torch.equal(x.double(), x64)
-    return x
-
-
 def _epilogue(acc, bias, res, rnd):
     v = rnd(acc if bias is None else acc + bias)
     return v if res is None else rnd(v + res)
@@ -105,41 +82,6 @@ def _assert_live(acc, bias, res, what):
 
 
 # ------------------------------------------------------------------------------------------------ the device side
-def _poisoned(t, rows_after=3, col0=0, cols_after=0, poison=float("nan")):
-    """`t` on the device as a slice of a larger allocation whose every other element is `poison`"""
-    if t.dim() == 1:
-        big = torch.full((t.numel() + 8,), poison, dtype=t.dtype)
-        big[:t.numel()] = t
-        return big.to(DEV)[:t.numel()]
-    R, Cc = t.shape
-    big = torch.full((R + rows_after, col0 + Cc + cols_after), poison, dtype=t.dtype)
-    big[:R, col0:col0 + Cc] = t
-    return big.to(DEV)[:R, col0:col0 + Cc]
-
-
-def _guarded(R, Cc, ldc, dtype):
-    """-> (allocation [R + 2, ldc] filled with the sentinel, its [R, Cc] slice the kernel writes)"""
-    idt, bits = SENTINEL[dtype]
-    buf = torch.empty((R + 2, ldc), dtype=dtype, device=DEV)
-    buf.view(idt).fill_(bits)
-    c0 = {0: 0, 2: 1, 8: 8}[ldc - Cc]  # 8 keeps the slice 16-byte aligned (the vectorised reductions), 1 does not
-    return buf, buf[:R, c0:c0 + Cc]
-
-
-def _check_guarded(buf, view, ref, what):
-    """view == ref and nothing else of buf was written; returns the bits of the view"""
-    got = view.clone()
-    if not torch.equal(got, ref):
-        bad = got != ref  # a NaN differs from everything
-        m, n = (int(i) for i in bad.nonzero()[0])
-        pytest.fail("%s: %d of %d elements differ, the first at (m, n) = (%d, %d): got %r, expected %r"
-                    % (what, int(bad.sum()), bad.numel(), m, n, float(got[m, n]), float(ref[m, n])))
-    idt, bits = SENTINEL[buf.dtype]
-    view.fill_(torch.tensor([bits], dtype=idt).view(buf.dtype).item())
-    assert bool((buf.view(idt) == bits).all()), what + ": written outside C"
-    return got
-
-
 def _owned_ws(nbytes):
     """-> (allocation, workspace): exactly `nbytes` of NaN with 4 KiB of sentinel behind them"""
     n = nbytes // 4

@@ -8,10 +8,10 @@ every row."""
 import itertools
 import json
 import os
-import shutil
-import subprocess
 
 import pytest
+
+from tests.util import build_gemv_route_cli
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_CAP = 150 * 1024
@@ -22,28 +22,7 @@ DTYPE_OF_ENTRY = {"gemv_bf16": "bf16", "gemv_f32": "f32", "gemv_w8": "fp8", "row
 
 @pytest.fixture(scope="module")
 def cli(tmp_path_factory):
-    cxx = next((c for c in ("g++", "c++", "clang++") if shutil.which(c)), None)
-    assert cxx, "the route test needs a host C++ compiler"
-    exe = str(tmp_path_factory.mktemp("gemv_route") / "gemv_route_cli")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "spatialrgpt_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "gemv_route_cli.cpp"), "-o", exe], check=True)
-
-    def run(queries, cus=256):
-        """queries: (dtype, rows, N, K, norm, swiglu, ss_in, packed) -> dicts of the route: family, chunk, rowss_supported, passes"""
-        text = "".join("%s %d %d %d %d %d %d %d\n" % q for q in queries)
-        out = subprocess.run([exe, str(cus)], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
-        assert len(out) == len(queries)
-        res = []
-        for ln in out:
-            head, *passes = ln.split(" | ")
-            family, chunk, supported = head.split()
-            names = ("rows", "NI", "NW", "PUB", "PK", "grid", "cw", "gr_shift", "lds") if family == "skinny" else \
-                    ("rows", "B", "NX", "UB", "NIT", "grid", "lds", "raise")
-            res.append(dict(family=family, chunk=int(chunk), rowss_supported=int(supported), passes=[dict(zip(names, map(int, p.split()))) for p in passes]))
-            assert all(len(p.split()) == len(names) for p in passes)
-        return res
-
-    return run
+    return build_gemv_route_cli(tmp_path_factory.mktemp("gemv_route"))
 
 
 def launch_of(dtype, swiglu, family, p):

@@ -6,25 +6,32 @@ import shutil
 import subprocess
 
 import numpy as np
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
-def build_gemm_route_cli(out_dir):
-    """Compile tests/gemm_route_cli.cpp -- spatialrgpt_amd/csrc/gemm_route.h alone, no HIP -- into `out_dir` with the first host
-    C++ compiler on the path (hipcc where there is no other) and return run(queries, cus=256): queries are
-    (entry, M, N, K, have_ws, ws_bytes) with entry = gemm / gemm_w8 / gemm_w8a8 / swiglu; the answers are dicts of the route
-    (family, bm, nbuf, splits, tps = K tiles per split, nk = K tiles), for swiglu the string "fused" / "unfused"."""
+def _build_route_cli(out_dir, name):
+    """Compile tests/<name>.cpp -- a route header of spatialrgpt_amd/csrc alone, no HIP -- into `out_dir` with the first host C++
+    compiler on the path (hipcc where there is no other); -> the program's path"""
     cxx = next((c for c in ("g++", "c++", "clang++", "hipcc") if shutil.which(c)), None)
     rocm_hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")  # where csrc/Makefile finds it
     if cxx is None and os.path.exists(rocm_hipcc):
         cxx = rocm_hipcc
     assert cxx, "the route query needs a host C++ compiler"
-    exe = os.path.join(str(out_dir), "gemm_route_cli")
+    exe = os.path.join(str(out_dir), name)
     subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "spatialrgpt_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "gemm_route_cli.cpp"), "-o", exe], check=True)
+                    os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], check=True)
+    return exe
+
+
+def build_gemm_route_cli(out_dir):
+    """tests/gemm_route_cli.cpp (spatialrgpt_amd/csrc/gemm_route.h) compiled into `out_dir`; returns run(queries, cus=256): queries
+    are (entry, M, N, K, have_ws, ws_bytes) with entry = gemm / gemm_w8 / gemm_w8a8 / swiglu; the answers are dicts of the route
+    (family, bm, nbuf, splits, tps = K tiles per split, nk = K tiles), for swiglu the string "fused" / "unfused"."""
+    exe = _build_route_cli(out_dir, "gemm_route_cli")
 
     def run(queries, cus=256):
         text = "".join("%s %d %d %d %d %d\n" % tuple(q) for q in queries)
@@ -38,6 +45,98 @@ def build_gemm_route_cli(out_dir):
         return res
 
     return run
+
+
+def build_gemv_route_cli(out_dir):
+    """tests/gemv_route_cli.cpp (spatialrgpt_amd/csrc/gemv_route.h) compiled into `out_dir`; returns run(queries, cus=256): queries
+    are (dtype, rows, N, K, norm, swiglu, ss_in, packed) with dtype = bf16 / f32 / fp8; the answers are dicts of the route: family
+    (gemv / gemv_reg / gemv_w8 / skinny), chunk, rowss_supported and, per weight pass of the call, its rows and launch (skinny: NI,
+    NW, PUB, PK, grid, cw, gr_shift, lds; the VALU families: B, NX, UB, NIT, grid, lds, raise)."""
+    exe = _build_route_cli(out_dir, "gemv_route_cli")
+
+    def run(queries, cus=256):
+        text = "".join("%s %d %d %d %d %d %d %d\n" % tuple(q) for q in queries)
+        out = subprocess.run([exe, str(int(cus))], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+        assert len(out) == len(queries)
+        res = []
+        for ln in out:
+            head, *passes = ln.split(" | ")
+            family, chunk, supported = head.split()
+            names = ("rows", "NI", "NW", "PUB", "PK", "grid", "cw", "gr_shift", "lds") if family == "skinny" else \
+                    ("rows", "B", "NX", "UB", "NIT", "grid", "lds", "raise")
+            res.append(dict(family=family, chunk=int(chunk), rowss_supported=int(supported), passes=[dict(zip(names, map(int, p.split()))) for p in passes]))
+            assert all(len(p.split()) == len(names) for p in passes)
+        return res
+
+    return run
+
+
+# ---- exact-data tests (tests/test_gpu_gemm_exact.py, tests/test_gpu_gemv_exact.py): integer operands, poisoned surroundings ----
+DEV = "cuda"
+BF16, F32 = torch.bfloat16, torch.float32
+SENTINEL = {BF16: (torch.int16, 0x5A5A), F32: (torch.int32, 0x5A5A5A5A)}  # a finite, unlikely value in either type
+FP8_NAN = 0x7F  # e4m3fn
+
+
+def ints(shape, bound, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-bound, bound + 1, shape, generator=g).double()
+
+
+def rne(x):
+    return x.to(BF16).float()
+
+
+def trunc(x):
+    return (x.contiguous().view(torch.int32) & -65536).view(F32)
+
+
+def away(x):  # round half away from zero
+    return ((x.contiguous().view(torch.int32) + 0x8000) & -65536).view(F32)
+
+
+def exact_f32(x64):
+    x = x64.float()
+    assert torch.equal(x.double(), x64)
+    return x
+
+
+def poisoned(t, rows_after=3, col0=0, cols_after=0, poison=float("nan")):
+    """`t` on the device as a slice of a larger allocation whose every other element is `poison`"""
+    if t.dim() == 1:
+        big = torch.full((t.numel() + 8,), poison, dtype=t.dtype)
+        big[:t.numel()] = t
+        return big.to(DEV)[:t.numel()]
+    R, Cc = t.shape
+    big = torch.full((R + rows_after, col0 + Cc + cols_after), poison, dtype=t.dtype)
+    big[:R, col0:col0 + Cc] = t
+    return big.to(DEV)[:R, col0:col0 + Cc]
+
+
+def guarded(R, Cc, ldc, dtype, row0=0):
+    """-> (allocation [R + 2, ldc] filled with the sentinel, its [R, Cc] slice the kernel writes, from row `row0` on)"""
+    idt, bits = SENTINEL[dtype]
+    buf = torch.empty((R + 2, ldc), dtype=dtype, device=DEV)
+    buf.view(idt).fill_(bits)
+    c0 = {0: 0, 2: 1, 8: 8}[ldc - Cc]  # 8 keeps the slice 16-byte aligned (the vectorised reductions), 1 does not
+    return buf, buf[row0:row0 + R, c0:c0 + Cc]
+
+
+def check_guarded(buf, view, ref, what, alt=None):
+    """view == ref (where `alt` is given: == ref or == alt, element by element) and nothing else of buf was written; returns the
+    bits of the view"""
+    got = view.clone()
+    bad = got != ref  # a NaN differs from everything
+    if alt is not None:
+        bad &= got != alt
+    if bool(bad.any()):
+        m, n = (int(i) for i in bad.nonzero()[0])
+        pytest.fail("%s: %d of %d elements differ, the first at (m, n) = (%d, %d): got %r, expected %r"
+                    % (what, int(bad.sum()), bad.numel(), m, n, float(got[m, n]), float(ref[m, n])))
+    idt, bits = SENTINEL[buf.dtype]
+    view.fill_(torch.tensor([bits], dtype=idt).view(buf.dtype).item())
+    assert bool((buf.view(idt) == bits).all()), what + ": written outside C"
+    return got
 
 
 def _t(a, dtype):

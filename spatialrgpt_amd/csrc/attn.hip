@@ -8,6 +8,7 @@
 
 #include <type_traits>
 
+#include "attn_route.h"
 #include "common.h"
 #include "internal.h"
 
@@ -74,40 +75,23 @@ __global__ __launch_bounds__(64) void simple_attn_kernel(const T* __restrict__ q
 // ================================================================================================
 // 3. decode attention: split over keys + combine
 // ================================================================================================
-constexpr int DEC_CHUNK_MAX = 256;
-constexpr int DEC_SPLIT_MAX = 64;
+constexpr int DEC_CHUNK_MAX = ATTN_DEC_CHUNK_MAX;  // attn_route.h: the routes, their thresholds and the workspace layout
 
 typedef SrgptPrefetch DecodePrefetch;  // common.h: L2 prefetch blocks appended to the launch (here: o_proj's weights)
 
-// splits per (sequence, kv head): enough blocks for ~2 per CU, capped at 16 for a single sequence (it needs them to spread its
-// K/V rows over the chip) and at 8 from two sequences up (the batch already spreads; more splits only multiply the merge work --
-// decode step at 4 sequences 3.44 ms with 8 splits vs 3.47 with 16, at 8 sequences 3.60 / 3.66, profiles/r02_decode_splits.txt),
-// never fewer than the score buffer requires (DEC_CHUNK_MAX keys per split)
-static inline int decode_nsplit(int max_pos, int B, int Hkv) {
-  int want = cdiv(2 * srgpt_device_cus(), Hkv * B);
-  const int cap = B == 1 ? 16 : 8;
-  if (want > cap) want = cap;
-  if (want < 1) want = 1;
-  int n = cdiv(max_pos, DEC_CHUNK_MAX);
-  if (n < want) n = want;
-  if (n > DEC_SPLIT_MAX) n = DEC_SPLIT_MAX;
-  return n;
-}
+// Partials are published WRITE-THROUGH (agent-scope relaxed atomic stores = global_store ... sc1) and read back with agent-scope
+// relaxed loads by whichever block of this (sequence, kv head) arrives last: no second launch for the merge.  One float, or a pair
+// as one 8-byte store.  (A function object like the two lambdas it replaces: as a free function it renamed registers in
+// decode_mfma_kernel<1> and <2>, profiles/NOTEBOOK.md.)
+struct PublishPartial {
+  __device__ void operator()(float* p, float v) const { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+  __device__ void operator()(float* p, float a, float b) const {
+    const unsigned long long u = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b) << 32);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
 
 // ---- the tail both decode kernels share: arrival ticket of the (sequence, kv head) group, merge by the last arriver ----
-// the MFMA kernel (bf16, head_dim 128): a block owns a FIXED range of 64 keys (4 waves x 16), so ceil(capacity / 64) blocks per
-// (sequence, kv head) -- those past the sequence end leave at once and the merge skips them; beyond 64 splits the ranges grow in steps of 64 keys
-// and the waves loop
-static inline int decode_nsplit_mfma(int max_pos) {
-  int n = cdiv(max_pos, 64);
-  if (n < 1) n = 1;
-  if (n > DEC_SPLIT_MAX) n = DEC_SPLIT_MAX;
-  return n;
-}
-static inline bool decode_use_mfma(int dtype_is_bf16, int D, int G) {
-  return dtype_is_bf16 && D == 128 && (G == 1 || G == 2 || G == 4 || G == 8);
-}
-
 template <typename T, int D, int G, int SCLD>
 __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, int* __restrict__ ticket, int nsplit,
                                                     T* __restrict__ outp, float* __restrict__ sc, float* __restrict__ stat_m,
@@ -127,24 +111,25 @@ __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, i
   // The first 16 splits' partials of this thread's pair of output dims AND the per-split statistics are requested back to
   // back: the merge pays one memory latency.  (G * D / 2 <= 256 * MAXW items; one or two per thread for the shipped shapes.)
   constexpr int PRE = 16;
+  constexpr size_t HEAD = attn_ws_row(1, 0, D), ROW = attn_ws_row(0, 1, D);  // floats between two heads' rows, two splits' rows
   constexpr int MAXW = (G * (D / 2) + 255) / 256;
   unsigned long long v[MAXW][PRE];
 #pragma unroll
   for (int wi = 0; wi < MAXW; ++wi) {
     const int w = min(tid + 256 * wi, G * (D / 2) - 1);
     const int gq = w / (D / 2), d = 2 * (w - gq * (D / 2));
-    const float* wp = wbase + (size_t)gq * DEC_SPLIT_MAX * (D + 2) + d;
+    const float* wp = wbase + gq * HEAD + d;
 #pragma unroll
     for (int j = 0; j < PRE; ++j)
-      v[wi][j] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + (size_t)min(j, nsplit - 1) * (D + 2)),
+      v[wi][j] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + min(j, nsplit - 1) * ROW),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   // per-head merge weights: wave gq handles head gq (G <= 8 heads over 4 waves), one split per lane (nsplit <= 64)
   for (int gq = wave; gq < G; gq += 4) {
-    const float* wp = wbase + (size_t)gq * DEC_SPLIT_MAX * (D + 2);
+    const float* wp = wbase + gq * HEAD;
     const bool ok = lane < nsplit;
     const int sidx = ok ? lane : nsplit - 1;
-    const unsigned long long ml = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + (size_t)sidx * (D + 2) + D),
+    const unsigned long long ml = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + sidx * ROW + D),
                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const float ms_raw = __uint_as_float((unsigned)ml), ls_raw = __uint_as_float((unsigned)(ml >> 32));
     const float ms = ok ? ms_raw : -INFINITY;
@@ -161,7 +146,7 @@ __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, i
     const int w = tid + 256 * wi;
     if (w < G * (D / 2)) {
       const int gq = w / (D / 2), d = 2 * (w - gq * (D / 2));
-      const float* wp = wbase + (size_t)gq * DEC_SPLIT_MAX * (D + 2) + d;
+      const float* wp = wbase + gq * HEAD + d;
       float n0 = 0.f, n1 = 0.f;
 #pragma unroll
       for (int j = 0; j < PRE; ++j)
@@ -175,7 +160,7 @@ __device__ __forceinline__ void decode_ticket_merge(float* __restrict__ wbase, i
         unsigned long long u[PRE];
 #pragma unroll
         for (int j = 0; j < PRE; ++j)
-          u[j] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + (size_t)min(s0 + j, nsplit - 1) * (D + 2)),
+          u[j] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + min(s0 + j, nsplit - 1) * ROW),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
         for (int j = 0; j < PRE; ++j)
@@ -283,19 +268,13 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
     }
   }
 
-  float* wbase = ws + (((size_t)b * Hkv + hk) * G) * (size_t)DEC_SPLIT_MAX * (D + 2);
-  // Partials are published WRITE-THROUGH (agent-scope relaxed atomic stores = global_store ... sc1) and read back with
-  // agent-scope relaxed loads by whichever block of this (sequence, kv head) arrives last: no second launch for the merge.
-  auto publish = [&](float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-  auto publish2 = [&](float* p, float a, float b2) {
-    const unsigned long long u = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b2) << 32);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  float* wbase = ws + attn_ws_group(b, hk, Hkv, G, D);
+  const PublishPartial publish;
   const bool empty = kbeg >= kend;
   if (empty) {  // empty split: neutral partial (zeros, m = -inf, l = 0)
     for (int w = tid; w < G * (D + 2); w += 256) {
       const int gq = w / (D + 2), d = w - gq * (D + 2);
-      publish(wbase + ((size_t)gq * DEC_SPLIT_MAX + split) * (D + 2) + d, (d == D) ? -INFINITY : 0.f);
+      publish(wbase + attn_ws_row(gq, split, D) + d, (d == D) ? -INFINITY : 0.f);
     }
   }
   if (!empty) {
@@ -400,14 +379,14 @@ __global__ __launch_bounds__(256) void decode_split_kernel(const T* __restrict__
   // 8-byte write-through stores (pairs of floats; rows of D + 2 floats are 8-byte aligned because D is even)
   for (int w = tid; w < G * (D / 2); w += 256) {
     const int gq = w / (D / 2), d = 2 * (w - gq * (D / 2));
-    float* wp = wbase + ((size_t)gq * DEC_SPLIT_MAX + split) * (D + 2);
-    publish2(wp + d, red[0][gq][d] + red[1][gq][d] + red[2][gq][d] + red[3][gq][d],
+    float* wp = wbase + attn_ws_row(gq, split, D);
+    publish(wp + d, red[0][gq][d] + red[1][gq][d] + red[2][gq][d] + red[3][gq][d],
              red[0][gq][d + 1] + red[1][gq][d + 1] + red[2][gq][d + 1] + red[3][gq][d + 1]);
-    if (d == 0) publish2(wp + D, stat_m[gq], stat_l[gq]);
+    if (d == 0) publish(wp + D, stat_m[gq], stat_l[gq]);
   }
   }  // !empty
 
-  decode_ticket_merge<T, D, G, DEC_CHUNK_MAX>(wbase, tickets + (size_t)b * Hkv + hk, nsplit,
+  decode_ticket_merge<T, D, G, DEC_CHUNK_MAX>(wbase, attn_ws_ticket(tickets, b, hk, Hkv), nsplit,
                                               out + ((size_t)b * Hq + (size_t)hk * G) * D, &sc[0][0], stat_m, stat_l, tid, lane, wave);
 }
 
@@ -605,7 +584,7 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
-    if (kb + 64 < kend) fetch(kb + 64);  // contexts beyond 64 keys per split (max_pos > 64 * DEC_SPLIT_MAX never; > 512 here)
+    if (kb + 64 < kend) fetch(kb + 64);  // contexts beyond 64 keys per split (max_pos > 64 * ATTN_DEC_SPLIT_MAX never; > 512 here)
   }
   // ---- the four waves meet: per-wave (m, l) and P.V through LDS ----
   if (lq < G && g4 == 0) {
@@ -615,11 +594,8 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
 #pragma unroll
   for (int h = 0; h < G; ++h) *reinterpret_cast<f32x2*>(&accs[wave][h][2 * lane]) = f32x2{acc[h][0], acc[h][1]};
   __syncthreads();
-  float* wbase = ws + (((size_t)b * Hkv + hk) * G) * (size_t)DEC_SPLIT_MAX * (D + 2);
-  auto publish2 = [&](float* p, float a, float b2) {
-    const unsigned long long u = (unsigned long long)__float_as_uint(a) | ((unsigned long long)__float_as_uint(b2) << 32);
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  float* wbase = ws + attn_ws_group(b, hk, Hkv, G, D);
+  const PublishPartial publish;
   for (int w = tid; w < G * (D / 2); w += 256) {
     const int gq = w / (D / 2), d = 2 * (w - gq * (D / 2));
     const float M = fmaxf(fmaxf(wm[0][gq], wm[1][gq]), fmaxf(wm[2][gq], wm[3][gq]));
@@ -631,74 +607,46 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
       n1 = fmaf(e, accs[wv][gq][d + 1], n1);
       L = fmaf(e, wl[wv][gq], L);
     }
-    float* wp = wbase + ((size_t)gq * DEC_SPLIT_MAX + split) * (D + 2);
-    publish2(wp + d, n0, n1);
-    if (d == 0) publish2(wp + D, M, L);
+    float* wp = wbase + attn_ws_row(gq, split, D);
+    publish(wp + d, n0, n1);
+    if (d == 0) publish(wp + D, M, L);
   }
-  decode_ticket_merge<T, D, G, 64>(wbase, tickets + (size_t)b * Hkv + hk, nlive, out + ((size_t)b * Hq + (size_t)hk * G) * D,
+  decode_ticket_merge<T, D, G, 64>(wbase, attn_ws_ticket(tickets, b, hk, Hkv), nlive, out + ((size_t)b * Hq + (size_t)hk * G) * D,
                                    &sc[0][0], stat_m, stat_l, tid, lane, wave);
 }
 
-template <typename T, int D>
-int launch_decode_d(int G, const void* qkv, void* kc, void* vc, const int* pos, const void* ct, const void* st,
-                    float* ws, int* tickets, void* out, int B, int Hq, int Hkv, int max_pos, int nsplit, float scale,
-                    const DecodePrefetch& pf, hipStream_t s) {
-  const int n_attn = Hkv * nsplit * B;
-  dim3 grid(n_attn + (pf.base ? pf.nblocks : 0));
-  if constexpr (std::is_same<T, bf16_t>::value && D == 128) {
-    if (decode_use_mfma(1, D, G)) {
-      const int kpb = cdiv(cdiv(max_pos, nsplit), 64) * 64;  // 64 keys per block up to 64 x 64 cached positions
-#define LM(GG)                                                                                                              \
-  hipLaunchKernelGGL((decode_mfma_kernel<GG>), grid, dim3(256), 0, s, (const bf16_t*)qkv, (bf16_t*)kc, (bf16_t*)vc, pos, \
-                     (const bf16_t*)ct, (const bf16_t*)st, ws, tickets, (bf16_t*)out, Hq, Hkv, max_pos, nsplit, kpb, scale, n_attn, pf)
-      switch (G) {
-        case 1: LM(1); return SRGPT_OK;
-        case 2: LM(2); return SRGPT_OK;
-        case 4: LM(4); return SRGPT_OK;
-        case 8: LM(8); return SRGPT_OK;
-        default: break;
-      }
-#undef LM
-    }
-  }
-#define LD(GG)                                                                                                     \
-  hipLaunchKernelGGL((decode_split_kernel<T, D, GG>), grid, dim3(256), 0, s, (const T*)qkv, (T*)kc, (T*)vc, pos, \
-                     (const T*)ct, (const T*)st, ws, tickets, (T*)out, Hq, Hkv, max_pos, nsplit, scale, n_attn, pf)
-  switch (G) {
-    case 1: LD(1); break;
-    case 2: LD(2); break;
-    case 4: LD(4); break;
-    case 8: LD(8); break;
-    default:
-      srgpt_set_error("srgpt_decode_attention: heads/kv_heads = %d not supported (1,2,4,8)", G);
-      return SRGPT_ERR_UNSUPPORTED;
-  }
-#undef LD
-  return SRGPT_OK;
-}
-
+// validated arguments -> the route (attn_route.h) -> its refusal, or the one launch of its template instance
 template <typename T>
 int launch_decode(const void* qkv, void* kc, void* vc, const int* pos, const void* ct, const void* st, void* out,
                   float* ws, int B, int Hq, int Hkv, int D, int max_pos, const DecodePrefetch& pf, hipStream_t s) {
-  const int G = Hq / Hkv;
-  const bool mfma = decode_use_mfma(std::is_same<T, bf16_t>::value ? 1 : 0, D, G);
-  const int nsplit = mfma ? decode_nsplit_mfma(max_pos) : decode_nsplit(max_pos, B, Hkv);
-  // VALU kernel: a split's scores live in LDS (sc[G][DEC_CHUNK_MAX]): the longest chunk is ceil(max_pos / nsplit) keys
-  SRGPT_CHECK(mfma || cdiv(max_pos, nsplit) <= DEC_CHUNK_MAX, SRGPT_ERR_UNSUPPORTED,
-              "srgpt_decode_attention: max_pos %d exceeds %d cached positions", max_pos, DEC_SPLIT_MAX * DEC_CHUNK_MAX);
+  const AttnDecodeRoute r = attn_decode_route(std::is_same<T, bf16_t>::value, B, Hq, Hkv, D, max_pos, srgpt_device_cus());
+  SRGPT_CHECK(r.status != ATTN_MAX_POS_TOO_LONG, SRGPT_ERR_UNSUPPORTED, "srgpt_decode_attention: max_pos %d exceeds %d cached positions",
+              max_pos, ATTN_DEC_SPLIT_MAX * ATTN_DEC_CHUNK_MAX);
+  SRGPT_CHECK(r.status != ATTN_BAD_HEAD_DIM, SRGPT_ERR_UNSUPPORTED, "srgpt_decode_attention: head_dim %d not supported (16,32,64,128)", D);
+  SRGPT_CHECK(r.status != ATTN_BAD_GROUP, SRGPT_ERR_UNSUPPORTED, "srgpt_decode_attention: heads/kv_heads = %d not supported (1,2,4,8)",
+              r.G);
   const float scale = 1.0f / sqrtf((float)D);
-  int* tickets = reinterpret_cast<int*>(ws + (size_t)B * Hq * DEC_SPLIT_MAX * (D + 2));  // int[B * Hkv] behind the partials
-  int rc;
-  switch (D) {
-    case 16: rc = launch_decode_d<T, 16>(G, qkv, kc, vc, pos, ct, st, ws, tickets, out, B, Hq, Hkv, max_pos, nsplit, scale, pf, s); break;
-    case 32: rc = launch_decode_d<T, 32>(G, qkv, kc, vc, pos, ct, st, ws, tickets, out, B, Hq, Hkv, max_pos, nsplit, scale, pf, s); break;
-    case 64: rc = launch_decode_d<T, 64>(G, qkv, kc, vc, pos, ct, st, ws, tickets, out, B, Hq, Hkv, max_pos, nsplit, scale, pf, s); break;
-    case 128: rc = launch_decode_d<T, 128>(G, qkv, kc, vc, pos, ct, st, ws, tickets, out, B, Hq, Hkv, max_pos, nsplit, scale, pf, s); break;
-    default:
-      srgpt_set_error("srgpt_decode_attention: head_dim %d not supported (16,32,64,128)", D);
-      return SRGPT_ERR_UNSUPPORTED;
+  int* tickets = reinterpret_cast<int*>(ws + attn_ws_partial_floats(B, Hq, D));
+  const dim3 grid(r.n_attn + (pf.base ? pf.nblocks : 0)), block(256);
+  int rc = SRGPT_OK;
+  if constexpr (std::is_same<T, bf16_t>::value) {
+    if (r.family == ATTN_DECODE_MFMA)
+      rc = srgpt_switch<1, 2, 4, 8>(r.G, "heads/kv_heads", [&](auto g_c) {
+        hipLaunchKernelGGL((decode_mfma_kernel<decltype(g_c)::value>), grid, block, 0, s, (const T*)qkv, (T*)kc, (T*)vc, pos,
+                           (const T*)ct, (const T*)st, ws, tickets, (T*)out, Hq, Hkv, max_pos, r.nsplit, r.kpb, scale, r.n_attn, pf);
+        return (int)SRGPT_OK;
+      });
   }
-  if (rc) return rc;
+  if (r.family == ATTN_DECODE_VALU)
+    rc = srgpt_switch<16, 32, 64, 128>(D, "head_dim", [&](auto d_c) {
+      return srgpt_switch<1, 2, 4, 8>(r.G, "heads/kv_heads", [&](auto g_c) {
+        hipLaunchKernelGGL((decode_split_kernel<T, decltype(d_c)::value, decltype(g_c)::value>), grid, block, 0, s, (const T*)qkv,
+                           (T*)kc, (T*)vc, pos, (const T*)ct, (const T*)st, ws, tickets, (T*)out, Hq, Hkv, max_pos, r.nsplit, scale,
+                           r.n_attn, pf);
+        return (int)SRGPT_OK;
+      });
+    });
+  SRGPT_TRY(rc);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -706,7 +654,7 @@ int launch_decode(const void* qkv, void* kc, void* vc, const int* pos, const voi
 }  // namespace
 
 extern "C" int64_t srgpt_decode_attn_ws_floats(int B, int Hq, int D) {
-  return (int64_t)B * Hq * DEC_SPLIT_MAX * (D + 2) + (int64_t)B * Hq;  // partials + arrival tickets (<= B * Hkv ints)
+  return (int64_t)attn_ws_floats(B, Hq, D);  // partials + arrival tickets (attn_route.h)
 }
 
 // internal entry (model.hip): decode attention + L2 prefetch of the weight matrix the next GEMV streams.
@@ -717,10 +665,9 @@ int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const
   SRGPT_CHECK(qkv && kcache && vcache && pos && cos_tab && sin_tab && out && ws, SRGPT_ERR_ARG,
               "srgpt_decode_attention: null pointer");
   SRGPT_CHECK(B > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, SRGPT_ERR_ARG, "srgpt_decode_attention: bad heads");
-  // bf16 activations only; 2 rounds = all of o_proj (measured 3.189 / 3.169 / 3.138 ms per token at 0 / 1 / 2 rounds).  B > 1 gets no
-  // prefetch blocks (common.h); o_proj's packed tiles pulled by this launch were measured without gain
-  // (profiles/r06_decode_prefetch_tiles.txt)
-  const DecodePrefetch pf = srgpt_prefetch_for_gemv(dtype == SRGPT_BF16 ? next_w : nullptr, next_n, next_k, 0, next_fp8, B, 2, 0);
+  // bf16 activations only.  B > 1 gets no prefetch blocks (common.h); o_proj's packed tiles pulled by this launch were measured without
+  // gain (profiles/r06_decode_prefetch_tiles.txt)
+  const DecodePrefetch pf = srgpt_prefetch_for_gemv(dtype == SRGPT_BF16 ? next_w : nullptr, next_n, next_k, next_fp8, B);
   if (dtype == SRGPT_BF16)
     return launch_decode<bf16_t>(qkv, kcache, vcache, pos, cos_tab, sin_tab, out, ws, B, Hq, Hkv, D, max_pos, pf,
                                  as_stream(stream));
@@ -734,8 +681,8 @@ int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const
 // the arrival tickets behind the partials (internal; model.hip zeroes them in every prefill so that a state whose workspace was
 // never zeroed, or whose last launch was aborted, heals -- ADVICE r2 -- and srgpt_llm_decode_sync_state reads them back)
 void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* bytes) {
-  if (bytes) *bytes = (size_t)B * Hq * sizeof(int);
-  return ws + (size_t)B * Hq * DEC_SPLIT_MAX * (D + 2);
+  if (bytes) *bytes = attn_ws_tickets_reserved(B, Hq) * sizeof(int);
+  return ws + attn_ws_partial_floats(B, Hq, D);
 }
 
 extern "C" int srgpt_decode_attention(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
@@ -752,29 +699,22 @@ extern "C" int srgpt_attention(const void* q, const void* k, const void* v, void
   SRGPT_CHECK(q && k && v && o, SRGPT_ERR_ARG, "srgpt_attention: null pointer");
   SRGPT_CHECK(B > 0 && Tq > 0 && Tk > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D <= 256, SRGPT_ERR_ARG,
               "srgpt_attention: bad shape B=%d Tq=%d Tk=%d Hq=%d Hkv=%d D=%d", B, Tq, Tk, Hq, Hkv, D);
+  SRGPT_CHECK(dtype == SRGPT_BF16 || dtype == SRGPT_F32, SRGPT_ERR_ARG, "srgpt_attention: bad dtype %d", dtype);
   hipStream_t s = as_stream(stream);
-  const bool vec_ok = D % 8 == 0 && D <= 128 && q_ts % 8 == 0 && q_hs % 8 == 0 && q_bs % 8 == 0 && k_ts % 8 == 0 &&
-                      k_hs % 8 == 0 && k_bs % 8 == 0 && v_ts % 8 == 0 && v_hs % 8 == 0 && v_bs % 8 == 0 &&
-                      ((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) &&
-                      ((uintptr_t)o % 8 == 0);
-  // the MFMA kernel takes the row maximum before scaling (scale > 0) and addresses a (batch, head) slice with 32-bit byte offsets;
-  // anything else goes to the one-wave-per-row kernel
-  const int64_t span = ((int64_t)Tk + 4 * 64) * (k_ts > v_ts ? k_ts : v_ts) * 2;
-  if (dtype == SRGPT_BF16 && vec_ok && scale > 0.f && span < srgpt_flash_slice_span_limit()) {
+  const bool qkv16 = (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0;
+  const AttnPrefillRoute r = attn_prefill_route(dtype == SRGPT_BF16, D, Tq, Tk, Hq, B, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs,
+                                                qkv16, (uintptr_t)o % 8 == 0, scale > 0.f);
+  const dim3 grid(r.grid_x, r.grid_y, r.grid_z), block(r.block);
+  if (r.family == ATTN_FLASH) {
     AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, Tq, Tk, Hq, Hkv, D,
                q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, kv_len};
-    srgpt_flash_bf16_launch(a, B, causal != 0, s);
+    SRGPT_TRY(srgpt_flash_bf16_launch(a, r, causal != 0, s));
   } else if (dtype == SRGPT_BF16) {
-    hipLaunchKernelGGL(simple_attn_kernel<bf16_t>, dim3(Tq, Hq, B), dim3(64), 0, s, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, (bf16_t*)o, Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts,
-                       v_hs, scale, causal, kv_len);
-  } else if (dtype == SRGPT_F32) {
-    hipLaunchKernelGGL(simple_attn_kernel<float>, dim3(Tq, Hq, B), dim3(64), 0, s, (const float*)q, (const float*)k,
-                       (const float*)v, (float*)o, Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts,
-                       v_hs, scale, causal, kv_len);
+    hipLaunchKernelGGL(simple_attn_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o,
+                       Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len);
   } else {
-    srgpt_set_error("srgpt_attention: bad dtype %d", dtype);
-    return SRGPT_ERR_ARG;
+    hipLaunchKernelGGL(simple_attn_kernel<float>, grid, block, 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, Tq,
+                       Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len);
   }
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/srgpt.h"
+#include "gemv_route.h"
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -234,27 +235,24 @@ __device__ __forceinline__ float apply_act(float x, int act) {
 // ------------------------------------------------------------------------------------------------
 struct SrgptPrefetch {
   const char* base;      // weight matrix of the next GEMV (NULL: no prefetch blocks)
-  long long row_bytes;   // stride between weight rows
-  int prefix_bytes;      // leading bytes of each row to pull (multiple of 1024; the whole row if >= row_bytes)
+  long long row_bytes;   // stride between weight rows (a multiple of 1024: whole rows are pulled)
   int n_units;           // work units of the next GEMV (a wave owns units unit0 + k * gemv_grid * 4)
   int unit_rows;         // rows per unit
-  int umul, rstride;     // row of (unit u, r) = u * umul + r * rstride  (plain: 1, -; SwiGLU gate/up: 1, N; fp8 column pair: 2, 1)
+  int umul, rstride;     // row of (unit u, r) = u * umul + r * rstride  (plain: 1, -; fp8 column pair: 2, 1)
   int gemv_grid;         // compute blocks the next GEMV launches
-  int rounds;            // how many of a wave's units to pull
   int nblocks;           // prefetch blocks appended to this launch (= gemv_grid)
   int n_rows;            // rows of the matrix: the row index is clamped (fp8 column pairs of an odd N would touch row N)
-  int batch;             // 1-KiB loads a wave keeps in flight (1: one at a time -- the trickle that leaves the host launch's own
-                         // loads alone; 2 / 4 / 8: faster, at the price of queueing in front of them)
-  int tile_bytes;        // > 0: TILE mode (round 6) -- the next launch is the batched MFMA product on a PACKED matrix whose block p
-                         // streams the contiguous tile p (16 rows x K): prefetch block p pulls that tile, its waves interleaved
-                         // (measured without gain, profiles/r06_decode_prefetch_tiles.txt: no host path fills it)
 };
+// how many of a wave's units a prefetch block pulls: 2 = all of o_proj (measured 3.189 / 3.169 / 3.138 ms per token at 0 / 1 / 2)
+constexpr int SRGPT_PREFETCH_ROUNDS = 2;
 
+// NB 1-KiB loads of a wave in flight (1: one at a time -- the trickle that leaves the host launch's own loads alone; more: faster, at
+// the price of queueing in front of them)
 template <int NB>
 __device__ __forceinline__ void srgpt_prefetch_rows(const SrgptPrefetch& pf, int p, int wave, int lane) {
-  const int per_row = (int)((pf.prefix_bytes < pf.row_bytes ? (long long)pf.prefix_bytes : pf.row_bytes) >> 10);
+  const int per_row = (int)(pf.row_bytes >> 10);
   int done = 0;
-  for (int u = p * 4 + wave; u < pf.n_units && done < pf.rounds; u += pf.gemv_grid * 4, ++done)
+  for (int u = p * 4 + wave; u < pf.n_units && done < SRGPT_PREFETCH_ROUNDS; u += pf.gemv_grid * 4, ++done)
     for (int r = 0; r < pf.unit_rows; ++r) {
       const long long ri = min((long long)u * pf.umul + (long long)r * pf.rstride, (long long)pf.n_rows - 1);
       const char* row = pf.base + (size_t)ri * pf.row_bytes + lane * 16;
@@ -267,66 +265,32 @@ __device__ __forceinline__ void srgpt_prefetch_rows(const SrgptPrefetch& pf, int
       }
     }
 }
-// tile mode: block p pulls tile p (+ k * gemv_grid), wave w the 1-KiB chunks w, w + nw, ...
-template <int NB>
-__device__ __forceinline__ void srgpt_prefetch_tiles(const SrgptPrefetch& pf, int p, int wave, int lane) {
-  const int nw = (int)blockDim.x >> 6, chunks = pf.tile_bytes >> 10;
-  int done = 0;
-  for (int t = p; t < pf.n_units && done < pf.rounds; t += pf.gemv_grid, ++done) {
-    const char* tb = pf.base + (size_t)t * pf.tile_bytes + lane * 16;
-    for (int c0 = wave; c0 < chunks; c0 += nw * NB) {
-      u32x4 v[NB];
-#pragma unroll
-      for (int c = 0; c < NB; ++c) v[c] = *reinterpret_cast<const u32x4*>(tb + ((size_t)min(c0 + c * nw, chunks - 1) << 10));
-#pragma unroll
-      for (int c = 0; c < NB; ++c) asm volatile("" ::"v"(v[c]));  // keep the loads; the data is dropped
-    }
-  }
-}
+// measured 1 / 2 / 4 / 8 loads in flight: 3.016 / 2.948 / 2.986 / 3.000 ms per token (profiles/r03_decode_attention.txt)
 __device__ __forceinline__ void srgpt_prefetch_block(const SrgptPrefetch& pf, int p, int wave, int lane) {
-  if (pf.tile_bytes > 0) {
-    switch (pf.batch) {
-      case 8: srgpt_prefetch_tiles<8>(pf, p, wave, lane); break;
-      case 4: srgpt_prefetch_tiles<4>(pf, p, wave, lane); break;
-      case 2: srgpt_prefetch_tiles<2>(pf, p, wave, lane); break;
-      default: srgpt_prefetch_tiles<1>(pf, p, wave, lane); break;
-    }
-    return;
-  }
-  switch (pf.batch) {
-    case 8: srgpt_prefetch_rows<8>(pf, p, wave, lane); break;
-    case 4: srgpt_prefetch_rows<4>(pf, p, wave, lane); break;
-    case 2: srgpt_prefetch_rows<2>(pf, p, wave, lane); break;
-    default: srgpt_prefetch_rows<1>(pf, p, wave, lane); break;
-  }
+  srgpt_prefetch_rows<2>(pf, p, wave, lane);
 }
 
 extern "C" int srgpt_device_cus(void);
-// descriptor for "the next launch is the batch-`batch` decode GEMV over W [N (2N if swiglu), K]" (bf16 rows, or fp8 bytes).
-// Mirrors the grid / unit mapping of gemv.hip's and gemv_w8.hip's launchers for one row (the VALU kernels); anything else
-// gets no prefetch: fp8 SwiGLU units of four rows, and 2+ rows (the skinny kernel -- its mapping, 4-row groups of block p's
-// 16-row units, was measured: o_proj +1 % at 8 fp8 rows, -2 % at 4 bf16 rows per decode step, not kept; at 2 rows, which moved
-// to the skinny kernel in round 3, the VALU mapping's prefetch costs 1.6 % per step: profiles/r03_skinny_min_batch.txt).
-static inline SrgptPrefetch srgpt_prefetch_for_gemv(const void* W, int N, int K, int swiglu, int fp8, int batch, int rounds,
-                                                    int prefix_bytes) {
-  SrgptPrefetch pf{nullptr, 0, 0, 0, 1, 1, 0, 1, 0, 0, 1, 1, 0};
+// descriptor for "the next launch is the batch-`batch` decode GEMV over W [N, K]" (bf16 rows, or fp8 bytes): prefetch block p pulls
+// what block p of that launch reads first, so grid and units are the ones gemv_route.h gives the launch itself -- one row on a VALU
+// family; anything else gets no prefetch: 2+ rows (the skinny kernel -- its mapping, 4-row groups of block p's 16-row units, was
+// measured: o_proj +1 % at 8 fp8 rows, -2 % at 4 bf16 rows per decode step, not kept; at 2 rows, which moved to the skinny kernel in
+// round 3, the VALU mapping's prefetch costs 1.6 % per step: profiles/r03_skinny_min_batch.txt).
+static inline SrgptPrefetch srgpt_prefetch_for_gemv(const void* W, int N, int K, int fp8, int batch) {
+  SrgptPrefetch pf{nullptr, 0, 0, 1, 1, 0, 1, 0, 0};
   const long long row_bytes = fp8 ? (long long)K : 2LL * K;
-  if (!W || batch > 1 || rounds <= 0 || row_bytes % 1024 != 0 || (fp8 && swiglu)) return pf;
-  const int cus = srgpt_device_cus();
-  const int per_cu = (size_t)batch * K * 2 > 70 * 1024 ? 1 : 2;
+  if (!W || batch > 1 || row_bytes % 1024 != 0) return pf;
+  const GemvFamily family = gemv_route(1, K, true, fp8 != 0, false).family;
+  if (family == GEMV_SKINNY) return pf;
+  const int grid = gemv_valu_launch(family, 1, N, K, true, false, srgpt_device_cus()).grid;
   pf.base = reinterpret_cast<const char*>(W);
   pf.row_bytes = row_bytes;
-  pf.prefix_bytes = prefix_bytes > 0 ? prefix_bytes : (int)row_bytes;
-  pf.n_units = fp8 ? (N + 1) / 2 : N;
-  pf.unit_rows = (fp8 || swiglu) ? 2 : 1;
+  pf.n_units = fp8 ? (N + 1) / 2 : N;  // a unit of GEMV_W8 is two output columns
+  pf.unit_rows = fp8 ? 2 : 1;
   pf.umul = fp8 ? 2 : 1;
   pf.rstride = fp8 ? 1 : N;
-  int grid = (pf.n_units + 3) / 4;
-  if (grid > cus * per_cu) grid = cus * per_cu;
   pf.gemv_grid = grid;
-  pf.rounds = rounds;
   pf.nblocks = grid;
-  pf.n_rows = swiglu ? 2 * N : N;
-  pf.batch = 2;  // measured 1 / 2 / 4 / 8: 3.016 / 2.948 / 2.986 / 3.000 ms per token (profiles/r03_decode_attention.txt)
+  pf.n_rows = N;
   return pf;
 }

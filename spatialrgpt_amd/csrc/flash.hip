@@ -20,12 +20,13 @@
 // This file holds the kernel and its launcher only; the C entry point (srgpt_attention) is in attn.hip.
 #include <type_traits>
 
+#include "attn_route.h"
 #include "common.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int QBLK = 64, KVBLK = 64;
+constexpr int QBLK = ATTN_FLASH_QBLK, KVBLK = 64;
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -231,22 +232,14 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
 
 }  // namespace
 
-int64_t srgpt_flash_slice_span_limit() { return (int64_t)1 << 31; }
-
-// launches the MFMA kernel; the caller has checked dtype, alignment, D <= 128, scale > 0 and the 32-bit span of a (batch, head) slice
-void srgpt_flash_bf16_launch(const AttnArgs& a, int B, bool causal, hipStream_t s) {
-  dim3 grid(cdiv(a.Tq, QBLK), a.Hq, B);
-  const int hdp = (a.D + 31) / 32 * 32;
-#define LF(H)                                                                  \
-  if (causal)                                                                  \
-    hipLaunchKernelGGL((flash_bf16_kernel<H, true>), grid, dim3(256), 0, s, a); \
-  else                                                                         \
-    hipLaunchKernelGGL((flash_bf16_kernel<H, false>), grid, dim3(256), 0, s, a)
-  switch (hdp) {
-    case 32: LF(32); break;
-    case 64: LF(64); break;
-    case 96: LF(96); break;
-    default: LF(128); break;
-  }
-#undef LF
+// launches the MFMA kernel on the instance and grid of an ATTN_FLASH route (attn_route.h: dtype, alignment, D <= 128, scale > 0 and the
+// 32-bit span of a (batch, head) slice are its conditions)
+int srgpt_flash_bf16_launch(const AttnArgs& a, const AttnPrefillRoute& r, bool causal, hipStream_t s) {
+  const dim3 grid(r.grid_x, r.grid_y, r.grid_z), block(r.block);
+  return srgpt_switch<32, 64, 96, 128>(r.hdp, "the padded head width", [&](auto hdp_c) {
+    return srgpt_switch<false, true>(causal, "causal", [&](auto causal_c) {
+      hipLaunchKernelGGL((flash_bf16_kernel<decltype(hdp_c)::value, decltype(causal_c)::value>), grid, block, 0, s, a);
+      return (int)SRGPT_OK;
+    });
+  });
 }

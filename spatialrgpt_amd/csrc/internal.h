@@ -8,6 +8,7 @@
 
 struct SrgptGemmEpilogue;  // gemm_epilogue.h
 struct GemmRoute;          // gemm_route.h
+struct AttnPrefillRoute;   // attn_route.h
 
 // ---- gemm256.hip / gemm288.hip: the 256 x 256 and the whole-M (up to 272 rows) bf16 MFMA tiles, dispatched by gemm.hip ----
 int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
@@ -66,5 +67,4 @@ struct AttnArgs {
   float scale;
   const int* kv_len;
 };
-int64_t srgpt_flash_slice_span_limit();  // byte offsets inside a (batch, head) K / V slice are 32-bit in the kernel
-void srgpt_flash_bf16_launch(const AttnArgs& a, int B, bool causal, hipStream_t s);
+int srgpt_flash_bf16_launch(const AttnArgs& a, const AttnPrefillRoute& r, bool causal, hipStream_t s);

@@ -59,7 +59,9 @@ def _decode_ragged_case(dtype, Hq, Hkv, D, max_pos, pos_list, steps, seed=300):
     pos0 = torch.tensor(pos_list, dtype=torch.int64)
     T = int(pos0.max()) + steps
     assert int(pos0.min()) >= 0 and T <= max_pos, (pos_list, steps, max_pos)  # the last launch appends row max(pos) + steps - 1
-    mfma = dtype == BF16 and D == 128 and G in (1, 2, 4, 8)  # decode_use_mfma, csrc/attn.hip
+    # attn_decode_route (csrc/attn_route.h); the "ragged mfma" / "ragged valu" rows of tests/golden/attn_routes.json pin the family
+    # of every parametrisation below (tests/test_host_attn_route.py)
+    mfma = dtype == BF16 and D == 128 and G in (1, 2, 4, 8)
     cos_t, sin_t = _rope_tables(Hq, Hkv, D, max_pos, dtype)
     ar = torch.arange(B)
 
@@ -213,8 +215,9 @@ def test_attention_causal_kvlen(dtype, D, Hq, Hkv, Tq, Tk, lens):
 
 
 def test_attention_causal_kvlen_bf16_one_wave():
-    # routing assumption: srgpt_attention (csrc/attn.hip) sends bf16 to the MFMA flash kernel only when `vec_ok`, which needs
-    # D % 8 == 0; head_dim 20 therefore runs simple_attn_kernel<bf16_t>, the one-wave kernel
+    # attn_prefill_route (csrc/attn_route.h) sends bf16 to the MFMA flash kernel only when `vec_ok`, which needs D % 8 == 0;
+    # head_dim 20 therefore runs simple_attn_kernel<bf16_t>, the one-wave kernel: the "ragged bf16 one-wave (head_dim 20)" row of
+    # tests/golden/attn_routes.json pins that (and the "ragged ..." rows beside it the family of every other prefill case here)
     _attn_kvlen_case(BF16, 2, 70, 70, 2, 2, 20, True, [70, 3])
 
 

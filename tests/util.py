@@ -71,6 +71,34 @@ def build_gemv_route_cli(out_dir):
     return run
 
 
+def build_attn_route_cli(out_dir):
+    """tests/attn_route_cli.cpp (spatialrgpt_amd/csrc/attn_route.h) compiled into `out_dir`; returns run(queries, cus=256): queries
+    are ("prefill", dtype, D, Tq, Tk, Hq, B, the nine strides, qkv_aligned16, o_aligned8, scale_positive) or ("decode", dtype, B, Hq,
+    Hkv, D, max_pos) with dtype = bf16 / f32; the answers are dicts -- prefill: family (flash / one_wave), hdp, grid [x, y, z], block;
+    decode: status (ok / max_pos / head_dim / group), family (decode_mfma / decode_valu), G, nsplit, kpb, n_attn and the workspace:
+    partial_floats, tickets_reserved, tickets_used, ws_floats, last_group, last_row, last_ticket."""
+    exe = _build_route_cli(out_dir, "attn_route_cli")
+
+    def run(queries, cus=256):
+        text = "".join(" ".join(str(x) for x in q) + "\n" for q in queries)
+        out = subprocess.run([exe, str(int(cus))], input=text, capture_output=True, text=True, check=True).stdout.split("\n")[:-1]
+        assert len(out) == len(queries)
+        res = []
+        for q, ln in zip(queries, out):
+            f = ln.split()
+            if q[0] == "prefill":
+                assert len(f) == 6
+                res.append(dict(family=f[0], hdp=int(f[1]), grid=[int(f[2]), int(f[3]), int(f[4])], block=int(f[5])))
+            else:
+                names = ("G", "nsplit", "kpb", "n_attn", "partial_floats", "tickets_reserved", "tickets_used", "ws_floats", "last_group",
+                         "last_row", "last_ticket")
+                assert len(f) == 2 + len(names)
+                res.append(dict(status=f[0], family=f[1], **dict(zip(names, map(int, f[2:])))))
+        return res
+
+    return run
+
+
 # ---- exact-data tests (tests/test_gpu_gemm_exact.py, tests/test_gpu_gemv_exact.py): integer operands, poisoned surroundings ----
 DEV = "cuda"
 BF16, F32 = torch.bfloat16, torch.float32

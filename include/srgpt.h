@@ -214,6 +214,20 @@ int srgpt_attention(const void* q, const void* k, const void* v, void* o, int B,
                     int64_t k_hs, int64_t v_bs, int64_t v_ts, int64_t v_hs, float scale, int causal,
                     const int* kv_len, int dtype, srgpt_stream_t stream);
 
+/* srgpt_attention_append: causal attention of NEW query rows over a LIVE cache, every row at a position of its own -- HF's cached
+ *   forward (modeling_llama.py:398-456: key_states / value_states grown by past_key_value, the queries of the new positions only;
+ *   llava_arch.py:355-385 is the caller's side of it) for a multi-token segment.
+ *   Query t of row b sits at absolute position q_pos0[b] + t (q_pos0: device int[B]); key s is visible to it iff
+ *   s <= q_pos0[b] + t and s < min(kv_len[b], Tk) (kv_len NULL: Tk).  Tk is the HOST's upper bound on the keys any row may see: it
+ *   sizes the tile loop and the kernel selection, which is srgpt_attention's, unchanged.  Shapes, strides and both kernel families as
+ *   for srgpt_attention; q_pos0 = NULL is SRGPT_ERR_ARG (that case is srgpt_attention).  With q_pos0[b] = Tk - Tq for every row the
+ *   output equals srgpt_attention(causal = 1) bit for bit.  A query with no visible key yields zeros; the output rows of padded
+ *   queries (t beyond the row's segment) are unspecified but stay inside o[B, Tq, Hq, D]. */
+int srgpt_attention_append(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq, int Hkv, int D,
+                           int64_t q_bs, int64_t q_ts, int64_t q_hs, int64_t k_bs, int64_t k_ts, int64_t k_hs, int64_t v_bs,
+                           int64_t v_ts, int64_t v_hs, float scale, const int* q_pos0, const int* kv_len, int dtype,
+                           srgpt_stream_t stream);
+
 /* RoPE + KV-cache append (modeling_llama.py:81-191 rotary, :451-456 cache growth -- here a static cache).
  *   qkv: [B*T, (Hq+2Hkv)*D] packed projections; q is rotated in place; rotated k and v are written to
  *   kcache/vcache [B, Hkv, max_pos, D] at positions pos0[b] + t  (pos0: device int[B], NULL = 0).
@@ -533,12 +547,29 @@ int srgpt_llm_prefill(const srgpt_llm_weights* w, srgpt_llm_state* st, const voi
  * padding holds; logits come from row lens[b]-1 and decoding continues at position lens[b] per sequence. */
 int srgpt_llm_prefill_ragged(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T,
                              const int* lens, float* all_logits, void* hidden_out, srgpt_stream_t stream);
+/* Append prefill (additions under ABI 9): continue every sequence of a LIVE state with a multi-token segment -- HF's cached forward
+ * over input_ids [B, T > 1] (modeling_llama.py:398-456; the caller's side: llava_arch.py:355-385), the next turn of a conversation
+ * or the next question over a shared prefix without re-running the rows already in the cache.
+ *   inputs_embeds [batch, T, hidden] RIGHT-padded; lens (device int[batch], NULL = T each) = rows to append per sequence, 1 .. T.
+ *   Row b continues at st->pos[b].  h_pos_max is a HOST int: the caller's upper bound on every st->pos[b] on entry (the call is
+ *   checked and sized without a synchronisation): T outside 1 .. ws_tokens, h_pos_max < 0 or h_pos_max + T > max_pos is
+ *   SRGPT_ERR_ARG before any launch.  The first launch validates every row on the device (0 <= pos[b] <= h_pos_max,
+ *   1 <= lens[b] <= T); a violating row raises the state's sticky error word (srgpt_llm_decode_sync_state: SRGPT_ERR_STATE) and is
+ *   appended at a clamped position: whatever st->pos holds, no byte outside the cache is written.
+ *   The launches are srgpt_llm_prefill's (every weight format) with the per-row positions in the RoPE / append and attention calls;
+ *   on a state whose rows are all at position 0 (lens NULL, h_pos_max 0) every byte written equals srgpt_llm_prefill's.
+ *   Afterwards pos[b] += lens[b], st->logits holds row lens[b] - 1 of every sequence, all_logits [batch, T, vocab] and hidden_out
+ *   [layers + 1, batch, T, hidden] (optional) the NEW rows.  A captured decode step re-embeds st->tok after this call.  The error
+ *   word is NOT cleared and the decode tickets are not touched (only a prefill re-arms them).  Cache rows pos[b] + lens[b] .. pos[b] +
+ *   T - 1 of a padded sequence receive the padding's k / v: they lie beyond the live length and the next append overwrites them. */
+int srgpt_llm_prefill_append(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T, const int* lens,
+                             int h_pos_max, float* all_logits, void* hidden_out, srgpt_stream_t stream);
 /* One greedy decode step, entirely device-side: embeds st->tok, runs the layers against the cache,
  * argmax -> st->tok, st->out_ids[:, *step], ++pos, ++*step.  No host sync. */
 int srgpt_llm_decode_step(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream);
 /* Health check of the decode steps since the last prefill (synchronises `stream` once): 0 when every arrival ticket of the decode
- * attention in st->ws is re-armed (zero) and no captured step met a caller-written token id outside the embedding table;
- * SRGPT_ERR_STATE otherwise (srgpt_last_error says which). */
+ * attention in st->ws is re-armed (zero), no captured step met a caller-written token id outside the embedding table and no
+ * srgpt_llm_prefill_append met a row outside its host bounds; SRGPT_ERR_STATE otherwise (srgpt_last_error says which). */
 int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, srgpt_stream_t stream);
 /* first token after prefill: argmax(st->logits) -> tok / out_ids[:,0] / step=1 */
 int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream);

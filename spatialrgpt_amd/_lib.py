@@ -110,6 +110,8 @@ _SIGNATURES = {
     "srgpt_rmsnorm": (i32, [vp, vp, vp, i32, i32, f32, i32, vp]),
     "srgpt_attention": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64,
                               i64, f32, i32, vp, i32, vp]),
+    "srgpt_attention_append": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, i64, i64,
+                                     i64, f32, vp, vp, i32, vp]),
     "srgpt_rope_kv_append": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_decode_attn_ws_floats": (i64, [i32, i32, i32]),
     "srgpt_decode_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
@@ -140,6 +142,7 @@ _SIGNATURES = {
     "srgpt_llm_ws_bytes": (i64, [C.POINTER(LlmWeights), i32, i32]),
     "srgpt_llm_prefill": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp, i32, vp, vp, vp]),
     "srgpt_llm_prefill_ragged": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp, i32, vp, vp, vp, vp]),
+    "srgpt_llm_prefill_append": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp, i32, vp, i32, vp, vp, vp]),
     "srgpt_llm_decode_step": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp]),
     "srgpt_llm_sample_first": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp]),
     "srgpt_llm_decode_sync_state": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), vp]),

@@ -23,7 +23,8 @@ __global__ __launch_bounds__(64) void simple_attn_kernel(const T* __restrict__ q
                                                          int Hq, int Hkv, int D, int64_t q_bs, int64_t q_ts,
                                                          int64_t q_hs, int64_t k_bs, int64_t k_ts, int64_t k_hs,
                                                          int64_t v_bs, int64_t v_ts, int64_t v_hs, float scale,
-                                                         int causal, const int* __restrict__ kv_len) {
+                                                         int causal, const int* __restrict__ kv_len,
+                                                         const int* __restrict__ q_pos0) {
   __shared__ float qs[256];
   const int t = blockIdx.x, h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
   const int hk = h / (Hq / Hkv);
@@ -33,7 +34,8 @@ __global__ __launch_bounds__(64) void simple_attn_kernel(const T* __restrict__ q
   __syncthreads();
   const T* kb = k + b * k_bs + hk * k_hs;
   const T* vb = v + b * v_bs + hk * v_hs;
-  const int last = causal ? min(klen - 1, t + (Tk - Tq)) : klen - 1;
+  // causal: query t sits at t + (Tk - Tq), or (srgpt_attention_append) at the row's own q_pos0[b] + t
+  const int last = causal ? min(klen - 1, t + (q_pos0 ? q_pos0[b] : Tk - Tq)) : klen - 1;
   float m = -INFINITY, l = 0.f;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};  // d = lane + 64 * i, D <= 256
   for (int k0 = 0; k0 <= last; k0 += 64) {
@@ -692,6 +694,31 @@ extern "C" int srgpt_decode_attention(const void* qkv, void* kcache, void* vcach
                                    0, 0, stream);
 }
 
+// srgpt_attention and srgpt_attention_append for validated arguments: the route (attn_route.h) and the one launch of its kernel.
+// q_pos0 = NULL: the uniform causal offset Tk - Tq; else (causal) the per-row one
+static int attention_launch(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq, int Hkv, int D,
+                            int64_t q_bs, int64_t q_ts, int64_t q_hs, int64_t k_bs, int64_t k_ts, int64_t k_hs, int64_t v_bs,
+                            int64_t v_ts, int64_t v_hs, float scale, int causal, const int* kv_len, const int* q_pos0, int dtype,
+                            hipStream_t s) {
+  const bool qkv16 = (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0;
+  const AttnPrefillRoute r = attn_prefill_route(dtype == SRGPT_BF16, D, Tq, Tk, Hq, B, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs,
+                                                qkv16, (uintptr_t)o % 8 == 0, scale > 0.f);
+  const dim3 grid(r.grid_x, r.grid_y, r.grid_z), block(r.block);
+  if (r.family == ATTN_FLASH) {
+    AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, Tq, Tk, Hq, Hkv, D,
+               q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, kv_len, q_pos0};
+    SRGPT_TRY(srgpt_flash_bf16_launch(a, r, causal != 0, s));
+  } else if (dtype == SRGPT_BF16) {
+    hipLaunchKernelGGL(simple_attn_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o,
+                       Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len, q_pos0);
+  } else {
+    hipLaunchKernelGGL(simple_attn_kernel<float>, grid, block, 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, Tq,
+                       Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len, q_pos0);
+  }
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
 extern "C" int srgpt_attention(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq,
                                int Hkv, int D, int64_t q_bs, int64_t q_ts, int64_t q_hs, int64_t k_bs, int64_t k_ts,
                                int64_t k_hs, int64_t v_bs, int64_t v_ts, int64_t v_hs, float scale, int causal,
@@ -700,22 +727,19 @@ extern "C" int srgpt_attention(const void* q, const void* k, const void* v, void
   SRGPT_CHECK(B > 0 && Tq > 0 && Tk > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D <= 256, SRGPT_ERR_ARG,
               "srgpt_attention: bad shape B=%d Tq=%d Tk=%d Hq=%d Hkv=%d D=%d", B, Tq, Tk, Hq, Hkv, D);
   SRGPT_CHECK(dtype == SRGPT_BF16 || dtype == SRGPT_F32, SRGPT_ERR_ARG, "srgpt_attention: bad dtype %d", dtype);
-  hipStream_t s = as_stream(stream);
-  const bool qkv16 = (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0;
-  const AttnPrefillRoute r = attn_prefill_route(dtype == SRGPT_BF16, D, Tq, Tk, Hq, B, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs,
-                                                qkv16, (uintptr_t)o % 8 == 0, scale > 0.f);
-  const dim3 grid(r.grid_x, r.grid_y, r.grid_z), block(r.block);
-  if (r.family == ATTN_FLASH) {
-    AttnArgs a{(const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, Tq, Tk, Hq, Hkv, D,
-               q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, kv_len};
-    SRGPT_TRY(srgpt_flash_bf16_launch(a, r, causal != 0, s));
-  } else if (dtype == SRGPT_BF16) {
-    hipLaunchKernelGGL(simple_attn_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o,
-                       Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len);
-  } else {
-    hipLaunchKernelGGL(simple_attn_kernel<float>, grid, block, 0, s, (const float*)q, (const float*)k, (const float*)v, (float*)o, Tq,
-                       Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len);
-  }
-  SRGPT_LAUNCH_CHECK();
-  return SRGPT_OK;
+  return attention_launch(q, k, v, o, B, Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, causal, kv_len,
+                          nullptr, dtype, as_stream(stream));
+}
+
+extern "C" int srgpt_attention_append(const void* q, const void* k, const void* v, void* o, int B, int Tq, int Tk, int Hq, int Hkv,
+                                      int D, int64_t q_bs, int64_t q_ts, int64_t q_hs, int64_t k_bs, int64_t k_ts, int64_t k_hs,
+                                      int64_t v_bs, int64_t v_ts, int64_t v_hs, float scale, const int* q_pos0, const int* kv_len,
+                                      int dtype, srgpt_stream_t stream) {
+  SRGPT_CHECK(q && k && v && o, SRGPT_ERR_ARG, "srgpt_attention_append: null pointer");
+  SRGPT_CHECK(q_pos0, SRGPT_ERR_ARG, "srgpt_attention_append: q_pos0 is null (a uniform causal offset is srgpt_attention)");
+  SRGPT_CHECK(B > 0 && Tq > 0 && Tk > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D <= 256, SRGPT_ERR_ARG,
+              "srgpt_attention_append: bad shape B=%d Tq=%d Tk=%d Hq=%d Hkv=%d D=%d", B, Tq, Tk, Hq, Hkv, D);
+  SRGPT_CHECK(dtype == SRGPT_BF16 || dtype == SRGPT_F32, SRGPT_ERR_ARG, "srgpt_attention_append: bad dtype %d", dtype);
+  return attention_launch(q, k, v, o, B, Tq, Tk, Hq, Hkv, D, q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs, scale, 1, kv_len,
+                          q_pos0, dtype, as_stream(stream));
 }

@@ -102,6 +102,9 @@ constexpr int decode_nsplit_valu(int max_pos, int B, int Hkv, int cus) {
 // srgpt_attention (prefill / ViT) for validated arguments: strides in elements, q/k/v 16-byte and o 8-byte aligned?, scale > 0?
 // The MFMA kernel loads 16-byte slots (head_dim and every stride a multiple of 8, head_dim <= 128), takes the row maximum before
 // scaling (scale > 0) and addresses a (batch, head) slice with 32-bit byte offsets; anything else goes to the one-wave-per-row kernel.
+// srgpt_attention_append (a per-row query position instead of the uniform offset Tk - Tq) takes this route UNCHANGED, evaluated with
+// Tk = the caller's bound on the keys any row may see: no row reads past min(kv_len[b], Tk), so the span test covers it, and the grid
+// depends on Tq alone.
 inline AttnPrefillRoute attn_prefill_route(bool bf16, int D, int Tq, int Tk, int Hq, int B, int64_t q_bs, int64_t q_ts, int64_t q_hs,
                                            int64_t k_bs, int64_t k_ts, int64_t k_hs, int64_t v_bs, int64_t v_ts, int64_t v_hs,
                                            bool qkv_aligned16, bool o_aligned8, bool scale_positive) {

@@ -17,7 +17,7 @@
 //     softmax on the raw products, masks only on tiles that contain a masked position, and -- the largest single item -- this file
 //     is compiled with MFMA accumulators in arch VGPRs (Makefile): in the default AGPR form the per-tile rescale of the output
 //     accumulators cost 24 v_accvgpr_read + 24 v_accvgpr_write per wave and tile.
-// This file holds the kernel and its launcher only; the C entry point (srgpt_attention) is in attn.hip.
+// This file holds the kernel and its launcher only; the C entry points (srgpt_attention, srgpt_attention_append) are in attn.hip.
 #include <type_traits>
 
 #include "attn_route.h"
@@ -48,7 +48,9 @@ __global__ __launch_bounds__(256) void flash_bf16_kernel(AttnArgs a) {
   const int hk = h / (a.Hq / a.Hkv);
   const int klen = a.kv_len ? min(a.kv_len[b], a.Tk) : a.Tk;
   const int qrow = q0 + wave * 16 + lq;  // query row owned by this lane column
-  const int coff = a.Tk - a.Tq;          // causal offset: key s visible iff s <= t + coff
+  // causal offset: key s visible iff s <= t + coff.  srgpt_attention: the uniform Tk - Tq; srgpt_attention_append: the row's own
+  // query position q_pos0[b] -- block-uniform either way (b = blockIdx.z), so everything below keeps its form
+  const int coff = a.q_pos0 ? a.q_pos0[b] : a.Tk - a.Tq;
 
   int kend = klen;
   if (CAUSAL) kend = min(kend, q0 + QBLK + coff);  // keys beyond the last query of the block are masked

@@ -66,5 +66,6 @@ struct AttnArgs {
   int64_t q_bs, q_ts, q_hs, k_bs, k_ts, k_hs, v_bs, v_ts, v_hs;
   float scale;
   const int* kv_len;
+  const int* q_pos0;  // srgpt_attention_append: the causal offset of row b is q_pos0[b]; NULL (srgpt_attention): Tk - Tq
 };
 int srgpt_flash_bf16_launch(const AttnArgs& a, const AttnPrefillRoute& r, bool causal, hipStream_t s);

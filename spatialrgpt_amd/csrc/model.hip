@@ -60,6 +60,10 @@ struct LlmWs {
   float* rowss;   // decode, 2+ rows: two row-statistics tables [batch][SRGPT_ROWSS_STRIDE] (o_proj's and down_proj's output rows)
   void* a8;       // fp8_act: the e4m3 bytes of the current GEMM input [rows, max K]
   float* a8s;     // fp8_act: their per-row scales [rows]
+  // srgpt_llm_prefill_append: [batch] the validated position every row's segment starts at, and [batch] that + the rows it appends
+  // (the keys the row may see, its pos after the call).  They LIVE IN qkvd: the decode step's q/k/v scratch is dead between steps
+  // (every step writes it before reading it) and holds >= 12 bytes per row, so the workspace does not grow
+  int *app_pos0, *app_kvlen;
   size_t total;
 };
 LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws) {
@@ -98,6 +102,9 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
     l.a8 = c.take(rows * kmax);
     l.a8s = reinterpret_cast<float*>(c.take(rows * 4));
   }
+  static_assert(sizeof(int) == 4, "two ints per row must fit the 12 bytes a row of qkvd has at least");
+  l.app_pos0 = reinterpret_cast<int*>(l.qkvd);
+  l.app_kvlen = l.qkvd ? l.app_pos0 + batch : nullptr;
   l.total = c.off;
   return l;
 }
@@ -105,6 +112,33 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
 __global__ void set_int_kernel(int* p, int n, int v) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+
+// srgpt_llm_prefill_append, first launch: every row's live length and segment length are DEVICE values the host only bounds
+// (h_pos_max, T).  A row outside 0 <= pos <= h_pos_max or 1 <= len <= T raises bit 8 of the state's sticky error word and gets the
+// nearest position / length that keeps every later write of the call inside the cache: pos0 in [0, max_pos - T], so rows
+// pos0 .. pos0 + T - 1 exist whatever pos held.  (The host has checked h_pos_max + T <= max_pos: a valid row is never moved.)
+constexpr int ERR_APPEND_ROW = 8;
+__global__ void append_begin_kernel(const int* __restrict__ pos, const int* __restrict__ lens, int B, int T, int h_pos_max, int max_pos,
+                                    int* __restrict__ pos0, int* __restrict__ kvlen, int* __restrict__ err) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int p = pos[b], n = lens ? lens[b] : T;
+  if (p < 0 || p > h_pos_max || n < 1 || n > T) atomicOr(err, ERR_APPEND_ROW);
+  const int p0 = min(max(p, 0), max_pos - T), n0 = min(max(n, 1), T);
+  pos0[b] = p0;
+  kvlen[b] = p0 + n0;
+}
+
+// ... and its last but one: out[b, :] = x[b, len - 1, :] (16-byte chunks), len = kvlen[b] - pos0[b], and pos[b] = kvlen[b]
+__global__ void append_end_kernel(const unsigned char* __restrict__ x, const int* __restrict__ pos0, const int* __restrict__ kvlen,
+                                  unsigned char* __restrict__ out, int* __restrict__ pos, int T, int row_bytes) {
+  const int b = blockIdx.x;
+  const int len = kvlen[b] - pos0[b];
+  const u32x4* src = reinterpret_cast<const u32x4*>(x + ((size_t)b * T + (len - 1)) * row_bytes);
+  u32x4* dst = reinterpret_cast<u32x4*>(out + (size_t)b * row_bytes);
+  for (int c = threadIdx.x; c < (row_bytes >> 4); c += blockDim.x) dst[c] = src[c];
+  if (threadIdx.x == 0) pos[b] = kvlen[b];
 }
 
 // greedy pick, stage 1: each block scans a contiguous slice of one row (first max wins, like torch.argmax)
@@ -394,6 +428,11 @@ struct Prefill {
   LlmFormat fmt;
   int B, T, rows, Hd, I, HqD, QW, dt;
   srgpt_stream_t stream;
+  // srgpt_llm_prefill_append: the rows continue at pos0[b] (device, validated) and see the keys below kvlen[b], at most Tk of
+  // them (the host's bound); NULL / NULL / T: a prefill, every row starts at position 0
+  const int* pos0;
+  const int* kvlen;
+  int Tk;
 
   int64_t gws_bytes() const { return (int64_t)l.gws_bytes; }
   char* cache(void* base, int i) const {
@@ -402,11 +441,16 @@ struct Prefill {
   // l.h = RMSNorm(l.x)
   int norm(const void* norm_w) const { return srgpt_rmsnorm(l.x, norm_w, l.h, rows, Hd, w->rms_eps, dt, stream); }
   int rope_append(int i) const {
-    return srgpt_rope_kv_append(l.qkv, cache(st->kcache, i), cache(st->vcache, i), nullptr, w->rope_cos, w->rope_sin, B, T, w->heads,
+    return srgpt_rope_kv_append(l.qkv, cache(st->kcache, i), cache(st->vcache, i), pos0, w->rope_cos, w->rope_sin, B, T, w->heads,
                                 w->kv_heads, w->head_dim, st->max_pos, dt, stream);
   }
   int attention(int i) const {
     const int Hkv = w->kv_heads, D = w->head_dim;
+    if (pos0)
+      return srgpt_attention_append(l.qkv, cache(st->kcache, i), cache(st->vcache, i), l.attn, B, T, Tk, w->heads, Hkv, D,
+                                    (int64_t)T * QW, QW, D, (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D,
+                                    (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D, 1.0f / sqrtf((float)D), pos0, kvlen, dt,
+                                    stream);
     return srgpt_attention(l.qkv, cache(st->kcache, i), cache(st->vcache, i), l.attn, B, T, T, w->heads, Hkv, D, (int64_t)T * QW, QW, D,
                            (int64_t)Hkv * st->max_pos * D, D, (int64_t)st->max_pos * D, (int64_t)Hkv * st->max_pos * D, D,
                            (int64_t)st->max_pos * D, 1.0f / sqrtf((float)D), 1, nullptr, dt, stream);
@@ -427,7 +471,7 @@ struct Prefill {
     const LayerMats m = layer_mats(w, fmt, i);
     if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
     // projection + RoPE + cache append: the rotation rides in the split-K reduction
-    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, m.qkv.w, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), nullptr,
+    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, m.qkv.w, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
                                         w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim, st->max_pos, dt, stream));
     SRGPT_TRY(attention(i));
     SRGPT_TRY(srgpt_gemm_norm(l.attn, m.o.w, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
@@ -491,14 +535,25 @@ struct Prefill {
 
 }  // namespace
 
+// h_pos_max < 0: a prefill (every row starts at position 0).  h_pos_max >= 0: srgpt_llm_prefill_append -- the rows continue at
+// st->pos[b] <= h_pos_max, the same launches with the per-row positions in the RoPE / append and attention calls, one validation
+// launch in front and without the prefill's re-arming of the decode tickets and the error word
 static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T, const int* lens,
-                        float* all_logits, void* hidden_out, srgpt_stream_t stream) {
+                        int h_pos_max, float* all_logits, void* hidden_out, srgpt_stream_t stream) {
+  const bool append = h_pos_max >= 0;
   SRGPT_TRY(check_llm(w, st));
-  SRGPT_CHECK(inputs_embeds && T > 0 && T <= st->max_pos, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds max_pos=%d", T,
-              st->max_pos);
-  SRGPT_CHECK(T <= st->ws_tokens, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds ws_tokens=%d", T, st->ws_tokens);
+  if (append) {
+    SRGPT_CHECK(inputs_embeds, SRGPT_ERR_ARG, "srgpt_llm_prefill_append: inputs_embeds is null");
+    SRGPT_CHECK(T > 0 && T <= st->ws_tokens, SRGPT_ERR_ARG, "srgpt_llm_prefill_append: T=%d outside 1 .. ws_tokens=%d", T, st->ws_tokens);
+    SRGPT_CHECK((int64_t)h_pos_max + T <= st->max_pos, SRGPT_ERR_ARG,
+                "srgpt_llm_prefill_append: h_pos_max=%d + T=%d exceeds max_pos=%d", h_pos_max, T, st->max_pos);
+  } else {
+    SRGPT_CHECK(inputs_embeds && T > 0 && T <= st->max_pos, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds max_pos=%d", T,
+                st->max_pos);
+    SRGPT_CHECK(T <= st->ws_tokens, SRGPT_ERR_ARG, "srgpt_llm_prefill: T=%d exceeds ws_tokens=%d", T, st->ws_tokens);
+  }
   LlmFormat fmt;
-  SRGPT_TRY(llm_format(w, "srgpt_llm_prefill", &fmt));
+  SRGPT_TRY(llm_format(w, append ? "srgpt_llm_prefill_append" : "srgpt_llm_prefill", &fmt));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, D = w->head_dim;
   const int B = st->batch, rows = B * T;
   if (fmt == FMT_W8A8)
@@ -507,10 +562,19 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
   const bool wide = Hd > 16384 || I > 16384;  // the fused quantisation kernels hold rows of up to 16384 columns
   const size_t es = dtype_size(dt);
   hipStream_t s = as_stream(stream);
-  const Prefill p{w, st, carve_llm(w, B, st->ws_tokens, st->ws), fmt, B, T, rows, Hd, I, Hq * D, (Hq + 2 * w->kv_heads) * D, dt, stream};
-  const LlmWs& l = p.l;
+  const LlmWs l = carve_llm(w, B, st->ws_tokens, st->ws);
+  const Prefill p{w, st, l, fmt, B, T, rows, Hd, I, Hq * D, (Hq + 2 * w->kv_heads) * D, dt, stream,
+                  append ? l.app_pos0 : nullptr, append ? l.app_kvlen : nullptr, append ? h_pos_max + T : T};
   const size_t hid_bytes = (size_t)rows * Hd * es;
-  {  // the decode attention's arrival tickets / sync words must be zero before the first step: every prefill re-arms them, so a
+  if (append) {
+    SRGPT_CHECK(Hd % (16 / (int)es) == 0, SRGPT_ERR_ARG, "srgpt_llm_prefill_append: hidden %d not a multiple of 16 bytes", Hd);
+    hipLaunchKernelGGL(append_begin_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, st->pos, lens, B, T, h_pos_max, st->max_pos, l.app_pos0,
+                       l.app_kvlen, l.err);
+    SRGPT_LAUNCH_CHECK();
+    // the rows in the residual-stream buffer of the decode step are not st->tok's any more: a captured step re-embeds.  The error
+    // word stays (sticky), and so do the decode tickets: every launch leaves them zero, re-arming here could hide an earlier failure
+    SRGPT_HIP_TRY(hipMemsetAsync(l.tok_emb, 0xFF, (size_t)B * sizeof(int64_t), s), "srgpt_llm_prefill_append: resetting the embedded-token record");
+  } else {  // the decode attention's arrival tickets / sync words must be zero before the first step: every prefill re-arms them, so a
      // caller-allocated (never zeroed) workspace or an aborted launch cannot leave the decode steps merging nothing
     size_t sync_bytes = 0;
     void* sync = srgpt_decode_attn_sync_words(l.dws, B, Hq, D, &sync_bytes);
@@ -545,7 +609,11 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
                               SRGPT_ACT_NONE, 1, nullptr, 0, stream));
   }
   // last position of every sequence -> logits (final norm fused into the GEMV prologue)
-  if (lens) {  // right-padded ragged batch: row b ends at lens[b] - 1 and decoding continues from position lens[b]
+  if (append) {  // row lens[b] - 1 of the segment; pos[b] += lens[b] (both as validated by the first launch)
+    hipLaunchKernelGGL(append_end_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const unsigned char*>(l.x), l.app_pos0, l.app_kvlen,
+                       reinterpret_cast<unsigned char*>(l.last), st->pos, T, (int)((size_t)Hd * es));
+    SRGPT_LAUNCH_CHECK();
+  } else if (lens) {  // right-padded ragged batch: row b ends at lens[b] - 1 and decoding continues from position lens[b]
     SRGPT_CHECK(Hd % (16 / (int)es) == 0, SRGPT_ERR_ARG, "srgpt_llm_prefill_ragged: hidden %d not a multiple of 16 bytes", Hd);
     if (dt == SRGPT_BF16)
       hipLaunchKernelGGL(gather_last_rows_kernel<bf16_t>, dim3(B), dim3(256), 0, s, (const bf16_t*)l.x, lens, (bf16_t*)l.last,
@@ -571,13 +639,19 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
 
 extern "C" int srgpt_llm_prefill(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T,
                                  float* all_logits, void* hidden_out, srgpt_stream_t stream) {
-  return prefill_impl(w, st, inputs_embeds, T, nullptr, all_logits, hidden_out, stream);
+  return prefill_impl(w, st, inputs_embeds, T, nullptr, -1, all_logits, hidden_out, stream);
 }
 
 extern "C" int srgpt_llm_prefill_ragged(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T,
                                         const int* lens, float* all_logits, void* hidden_out, srgpt_stream_t stream) {
   SRGPT_CHECK(lens, SRGPT_ERR_ARG, "srgpt_llm_prefill_ragged: lens is null");
-  return prefill_impl(w, st, inputs_embeds, T, lens, all_logits, hidden_out, stream);
+  return prefill_impl(w, st, inputs_embeds, T, lens, -1, all_logits, hidden_out, stream);
+}
+
+extern "C" int srgpt_llm_prefill_append(const srgpt_llm_weights* w, srgpt_llm_state* st, const void* inputs_embeds, int T, const int* lens,
+                                        int h_pos_max, float* all_logits, void* hidden_out, srgpt_stream_t stream) {
+  SRGPT_CHECK(h_pos_max >= 0, SRGPT_ERR_ARG, "srgpt_llm_prefill_append: h_pos_max=%d is negative", h_pos_max);
+  return prefill_impl(w, st, inputs_embeds, T, lens, h_pos_max, all_logits, hidden_out, stream);
 }
 
 // every pick entry point, on the host before any launch: a known sampler kind, a valid state, (full sampler, sampling on) a
@@ -716,6 +790,9 @@ extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srg
   const size_t n = host.size() - 1;
   for (size_t i = 0; i < n; ++i)
     SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "decode step: arrival ticket %zu of %zu is %d between steps (expected 0)", i, n, host[i]);
+  SRGPT_CHECK((host.back() & ERR_APPEND_ROW) == 0, SRGPT_ERR_STATE,
+              "srgpt_llm_prefill_append: a row's st->pos lay outside 0 .. h_pos_max or its length outside 1 .. T; the row was appended "
+              "at a clamped position");
   SRGPT_CHECK((host.back() & 4) == 0, SRGPT_ERR_UNSUPPORTED,
               "decode step: sampling parameters the device sampler does not serve (top_k > 64, or top_p < 1 without top_k): the draws "
               "used another distribution");

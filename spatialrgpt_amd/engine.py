@@ -56,11 +56,37 @@ class DecodeState:
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
         self.logits_proc: Optional[ops.LogitsProcParams] = None  # device block of the logits processors; ONE address likewise
         self.proc = None             # its device pointer while the processors are on for the running request, else None
+        # the PENDING token of every row after a decode loop: picked (the last id the request kept) but not yet cached -- the next
+        # append has to feed it first.  (ids [B, n] as the loop left them, kept ids per row), or None: nothing is pending
+        self.pending = None
+        self._pos_stale = False      # the device `pos` ran ahead of host_len (a decode loop that stopped early): see truncate()
         self._eng = eng
 
     def seq_len(self) -> int:
         """cached positions (longest row) -- what `past_key_values[-1][-1].shape[-2]` is for the reference (llava_arch.py:364)."""
         return max(self.host_len)
+
+    def pending_ids(self) -> Optional[torch.Tensor]:
+        """the pending token of every row (int64 [B], device), or None when every picked token is in the cache"""
+        if self.pending is None:
+            return None
+        ids, n = self.pending
+        return ids[torch.arange(self.batch, device=ids.device), torch.tensor([k - 1 for k in n], device=ids.device)]
+
+    def truncate(self, lens) -> "DecodeState":
+        """Cut every row back to lens[b] <= its current length (an int: every row): the device `pos` and host_len are set, the rows
+        beyond stay in memory and are overwritten by the next append.  This is what makes a shared prefix reusable (truncate to the
+        prefix, append the next question) and what rolls back the step a stopped decode loop ran ahead.  A row that is cut drops
+        its pending token."""
+        lens = [int(lens)] * self.batch if isinstance(lens, int) else [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if len(lens) != self.batch or any(n < 0 or n > have for n, have in zip(lens, self.host_len)):
+            raise ValueError(f"truncate: lens {lens} must be one length per row, each within 0 .. the row's {self.host_len} cached positions")
+        if lens != self.host_len:
+            self.pending = None
+        self.pos.copy_(torch.tensor(lens, dtype=torch.int32), non_blocking=False)
+        self.host_len = lens
+        self._pos_stale = False
+        return self
 
     def set_sampling(self, sampling: Optional[dict]):
         """None: the step picks argmax.  dict(temperature, top_k, top_p, seed[, sampler]): the step DRAWS (sample.hip) with the
@@ -448,13 +474,29 @@ class SrgptEngine:
             self._state = s
         return s
 
+    def new_state(self, batch: int, capacity: int, max_new: int, ws_tokens: Optional[int] = None) -> DecodeState:
+        """An independent, empty DecodeState whose cache holds `capacity` positions per row -- the caller's choice, where _get_state
+        derives it from one request: the handle of a conversation (append() turn after turn) or of a shared prefix.  ws_tokens:
+        rows per sequence one prefill / append call may carry (default: capacity); longer segments are appended in chunks."""
+        self._need("llm")
+        if capacity <= 0 or capacity > self.w.rope_len:
+            raise ValueError(f"cache of {capacity} positions: must be within 1 .. the RoPE table ({self.w.rope_len})")
+        return DecodeState(self, batch, int(capacity), max(min(int(ws_tokens or capacity), int(capacity)), 1), max(int(max_new), 1))
+
     def prefill(self, inputs_embeds: torch.Tensor, max_new: int = 1, all_logits: bool = False, hidden_states: bool = False,
-                lens: Optional[torch.Tensor] = None, fresh_state: bool = False):
+                lens: Optional[torch.Tensor] = None, fresh_state: bool = False, state: Optional[DecodeState] = None):
         """inputs_embeds [B,T,H]; `lens` (int [B]) marks a RIGHT-padded ragged batch: row b has lens[b] valid positions,
-        its logits come from position lens[b]-1 and decoding continues there.  Returns (state, logits_all|None, hiddens|None)."""
+        its logits come from position lens[b]-1 and decoding continues there.  `state`: prefill THIS state (new_state) instead of
+        the pooled / a derived one.  Returns (state, logits_all|None, hiddens|None)."""
         B, T, H = inputs_embeds.shape
         x = inputs_embeds.to(device=self.device, dtype=self.dtype).contiguous()
-        st = self._get_state(B, T, max_new, fresh=fresh_state)
+        if state is not None:
+            if state.batch != B or T > state.ws_tokens or T + max_new > state.max_pos or max_new > state.max_new:
+                raise ValueError(f"prefill: the given state (batch {state.batch}, {state.max_pos} positions, {state.ws_tokens} rows per "
+                                 f"call, {state.max_new} new tokens) cannot hold {B} x {T} rows + {max_new} new tokens")
+            st = state
+        else:
+            st = self._get_state(B, T, max_new, fresh=fresh_state)
         al = torch.empty((B, T, self.w.vocab), device=self.device, dtype=torch.float32) if all_logits else None
         hs = torch.empty((self.cfg.layers + 1, B, T, H), device=self.device, dtype=self.dtype) if hidden_states else None
         if lens is None:
@@ -469,7 +511,49 @@ class SrgptEngine:
                                                       None if al is None else al.data_ptr(),
                                                       None if hs is None else hs.data_ptr(), ops._stream()))
         st.host_len = [T] * B if lens is None else [int(v) for v in lens.tolist()]
+        st.pending, st._pos_stale = None, False
         return st, al, hs
+
+    def append(self, st: DecodeState, inputs_embeds: torch.Tensor, lens: Optional[torch.Tensor] = None, all_logits: bool = False,
+               hidden_states: bool = False):
+        """Continue every row of a live state with a multi-token segment (HF `forward(input_ids[B, T > 1], past_key_values=...)`,
+        srgpt_llm_prefill_append): inputs_embeds [B,T,H] RIGHT-padded, `lens` (int [B]) the rows to append per sequence (None: T
+        each).  Row b continues at its live length; st.logits holds the logits of every row's last appended position afterwards.
+        With lens = None a segment longer than st.ws_tokens runs as consecutive appends of at most ws_tokens rows (chunked prefill
+        with a bounded workspace).  Returns (state, logits_all [B,T,V]|None, hiddens [layers+1,B,T,H]|None) for the NEW rows."""
+        B, T, H = inputs_embeds.shape
+        if B != st.batch or T < 1:
+            raise ValueError(f"append: inputs_embeds must be [{st.batch}, T >= 1, hidden]")
+        cap = min(st.max_pos, self.w.rope_len)
+        if max(st.host_len) + T > cap:
+            raise ValueError(f"KV cache full ({cap} positions, {max(st.host_len)} live + {T} appended): re-run forward() with a larger "
+                             "cache_reserve / a longer RoPE table")
+        ld, lens_h = None, None
+        if lens is not None:
+            if T > st.ws_tokens:
+                raise ValueError(f"append: a ragged segment of {T} rows exceeds the state's {st.ws_tokens} rows per call")
+            lens_h = [int(v) for v in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+            if len(lens_h) != B or min(lens_h) < 1 or max(lens_h) > T:
+                raise ValueError(f"append: lens must be {B} lengths within 1 .. {T}")
+            ld = torch.tensor(lens_h, dtype=torch.int32).to(self.device)
+        if st._pos_stale:
+            st.truncate(list(st.host_len))  # a decode loop stopped early: the device position ran ahead of the kept tokens
+        x = inputs_embeds.to(device=self.device, dtype=self.dtype).contiguous()
+        lib, als, hss = L.load(), [], []
+        for t0 in range(0, T, st.ws_tokens):
+            n = min(st.ws_tokens, T - t0)
+            xc = x if n == T else x[:, t0:t0 + n].contiguous()
+            al = torch.empty((B, n, self.w.vocab), device=self.device, dtype=torch.float32) if all_logits else None
+            hs = torch.empty((self.cfg.layers + 1, B, n, H), device=self.device, dtype=self.dtype) if hidden_states else None
+            L.check(lib.srgpt_llm_prefill_append(C.byref(self.w.llm), C.byref(st.c), xc.data_ptr(), n, None if ld is None else ld.data_ptr(),
+                                                 max(st.host_len), None if al is None else al.data_ptr(),
+                                                 None if hs is None else hs.data_ptr(), ops._stream()))
+            st.host_len = [a + (n if lens_h is None else lens_h[b]) for b, a in enumerate(st.host_len)]
+            als.append(al)
+            hss.append(hs)
+        st.pending = None
+        return (st, (als[0] if len(als) == 1 else torch.cat(als, 1)) if all_logits else None,
+                (hss[0] if len(hss) == 1 else torch.cat(hss, 2)) if hidden_states else None)
 
     def step(self, st: DecodeState, input_ids: torch.Tensor) -> torch.Tensor:
         """One incremental forward over a cached state (HF `forward(input_ids[B,1], past_key_values=...)`): appends the
@@ -483,6 +567,7 @@ class SrgptEngine:
         st.tok.copy_(input_ids[:, 0].to(device=self.device, dtype=torch.int64))
         L.check(L.load().srgpt_llm_decode_step(C.byref(self.w.llm), C.byref(st.c), ops._stream()))
         st.host_len = [n + 1 for n in st.host_len]
+        st.pending = None
         return st.logits.clone()
 
     def greedy_decode(self, st: DecodeState, max_new_tokens: int, eos_token_id=None, pad_token_id=None,
@@ -499,7 +584,7 @@ class SrgptEngine:
             st.set_sampling(sampling)
             st.set_logits_proc(logits_proc)
             try:
-                n_keep, eos = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
+                n_keep, eos, n_rows = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
             finally:
                 st.c.sampling = None
                 st.sampler = L.SAMPLER_TOPK64
@@ -509,6 +594,11 @@ class SrgptEngine:
         # launch merged nothing and later steps used stale attention output -- fail loudly, never return such ids
         L.check(L.load().srgpt_llm_decode_sync_state(C.byref(self.w.llm), C.byref(st.c), ops._stream()))
         out = st.out_ids[:, :n_keep].clone()
+        # n kept tokens of a row (up to and including its first EOS) are n - 1 cached positions behind the prompt: the last one is
+        # PENDING, picked but not cached.  The device position may be ahead (a finished row of a batch keeps stepping; a stopped
+        # loop ran one step ahead): truncate() rolls it back before the state is continued
+        st.host_len = [a + n - 1 for a, n in zip(st.host_len, n_rows)]
+        st.pending, st._pos_stale = (out, n_rows), True
         if eos:
             # rows that finished early are padded with pad_token_id (HF behaviour)
             pad = pad_token_id if pad_token_id is not None else eos[0]  # HF: pad defaults to the FIRST eos id
@@ -529,6 +619,7 @@ class SrgptEngine:
         graph = st.ensure_graph() if self.use_graph and max_new_tokens > 1 else None
         B = st.batch
         finished = [False] * B
+        n_rows = [None] * B  # ids a row keeps: up to and including its first EOS
 
         def launch(n):
             if graph is not None:
@@ -543,6 +634,7 @@ class SrgptEngine:
                 for b in range(B):
                     if eos and not finished[b] and int(ids[b, s_]) in eos:
                         finished[b] = True
+                        n_rows[b] = s_ + 1
                 if eos and all(finished):
                     return s_ + 1
                 if interactive:
@@ -559,11 +651,12 @@ class SrgptEngine:
             # every `check_every` = 8 steps: a request that ends in EOS -- the reference's real eval mode, eval_spatial.py:221-237,
             # answers of a few dozen tokens -- ran 3.5 steps (10 ms at 2.9 ms per token) past its end on average; the run-ahead
             # loop wastes at most ONE step and costs 1.6 % while it runs (profiles/r04_sampling.txt)
-            return self._decode_loop_run_ahead(st, max_new_tokens, launch, judge), eos
+            n_keep = self._decode_loop_run_ahead(st, max_new_tokens, launch, judge)
+            return n_keep, eos, [n_keep if n is None else n for n in n_rows]
         # nothing can stop the request early (the benchmark: EOS disabled): all steps are queued at once, no host work per token
         if max_new_tokens > 1:
             launch(max_new_tokens - 1)
-        return max_new_tokens, eos
+        return max_new_tokens, eos, [max_new_tokens] * B
 
     def _decode_loop_run_ahead(self, st: DecodeState, max_new_tokens: int, launch, judge) -> int:
         """A stopping criterion (the demo's KeywordsStoppingCriteria, gradio_web_server_multi.py:195-197; model_vqa.py's conv stop

@@ -61,6 +61,23 @@ class CausalLMOutputWithPast:
         return self[k] if k in self else default
 
 
+class GenerateOutput:
+    """What `generate(return_dict_in_generate=True)` returns (transformers >= 4.36: GenerateDecoderOnlyOutput): `.sequences` -- the
+    new ids, exactly what the plain call returns -- and `.past_key_values`, the engine's DecodeState the request ran on: hand it to
+    the next `generate(..., past_key_values=...)` / `append()` to continue the conversation without re-running what it holds."""
+
+    _fields = ("sequences", "past_key_values")
+
+    def __init__(self, sequences=None, past_key_values=None):
+        self.sequences, self.past_key_values = sequences, past_key_values
+
+    def keys(self):
+        return list(self._fields)
+
+    def __getitem__(self, k):
+        return getattr(self, k) if isinstance(k, str) and k in self._fields else (self.sequences, self.past_key_values)[k]
+
+
 class _Facade:
     """nn.Module-looking handle (callers only use .to/.eval/.config/.is_loaded on sub-modules)."""
 
@@ -417,6 +434,83 @@ class LlavaLlamaModel:
 
     __call__ = forward
 
+    # ---- HF's cached forward over a multi-token segment (modeling_llama.py:398-456; llava_arch.py:355-385) ----
+    @torch.no_grad()
+    def append(self, past_key_values, input_ids=None, images=None, masks=None, depths=None, attention_mask=None, inputs_embeds=None,
+               output_hidden_states=None):
+        """Continue the cached sequences of `past_key_values` (the state a forward(use_cache=True) / generate(return_dict_in_generate=
+        True) returned) with a segment of any length: the next turn of a conversation, or the next question over a shared prefix
+        (`past_key_values.truncate(prefix_len)` first).  forward() keeps taking [B, 1] steps only; this is the multi-token door.
+        The segment goes through the same splice as a prompt on its own (images / masks / depths of the segment included); a padded
+        segment (attention_mask) appends every row's valid positions only.  Returns a CausalLMOutputWithPast whose logits
+        [B, T_new, V] are those of the NEW positions (padded positions: zeros), in the caller's padded layout."""
+        st = past_key_values
+        if st is None:
+            raise ValueError("append() continues a cached state: past_key_values is required")
+        if inputs_embeds is None:
+            if input_ids is None:
+                raise ValueError("append() needs input_ids or inputs_embeds")
+            if images is None:
+                inputs_embeds = self.engine.embed_tokens(input_ids)
+            else:
+                inputs_embeds, am, lens = self.engine.prepare_inputs(input_ids, images, depths, masks, attention_mask)
+                T = inputs_embeds.shape[1]
+                ar = torch.arange(T, device=inputs_embeds.device)[None, :]
+                ln = torch.tensor(lens, device=inputs_embeds.device)[:, None]
+                attention_mask = (ar >= T - ln) if self.config.padding_side == "left" else (ar < ln)
+        inputs_embeds = inputs_embeds.to(device=self.device, dtype=self.dtype)
+        B, T, _ = inputs_embeds.shape
+        keep = None if attention_mask is None else attention_mask.to(self.device).bool()
+        if keep is None or bool(keep.all()):
+            _, logits, hs = self.engine.append(st, inputs_embeds, all_logits=True, hidden_states=bool(output_hidden_states))
+        else:
+            # valid positions packed to the front (the ragged append is right-padded), results scattered back: as in forward()
+            lens = keep.sum(dim=1)
+            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)
+            valid = (torch.arange(T, device=keep.device)[None, :] < lens[:, None])
+            packed = torch.gather(inputs_embeds, 1, order[:, :, None].expand(-1, -1, inputs_embeds.shape[2]))
+            packed.masked_fill_(~valid[:, :, None], 0)
+            _, plog, hs = self.engine.append(st, packed, lens=lens, all_logits=True, hidden_states=bool(output_hidden_states))
+            plog.masked_fill_(~valid[:, :, None], 0)
+            logits = torch.empty_like(plog).scatter_(1, order[:, :, None].expand(-1, -1, plog.shape[2]), plog)
+            del plog
+            if hs is not None:
+                hs.masked_fill_(~valid[None, :, :, None], 0)
+                hs = torch.empty_like(hs).scatter_(2, order[None, :, :, None].expand(hs.shape[0], -1, -1, hs.shape[3]), hs)
+        return CausalLMOutputWithPast(logits=logits, past_key_values=st,
+                                      hidden_states=None if hs is None else tuple(hs[i] for i in range(hs.shape[0])))
+
+    def _state_for_generate(self, past_key_values, inputs_embeds, lens, max_new_tokens):
+        """the state a generate(past_key_values=... / return_dict_in_generate=True) call decodes on, prompt or segment already in its
+        cache.  No handle given: a FRESH state (never the pooled one: the caller keeps it) with `cache_reserve` spare positions
+        behind the request.  A handle: truncated to its true live length (a stopped decode loop ran one step ahead), then the
+        pending token's embedding row -- picked by the last request, not yet cached -- and the segment are appended."""
+        eng = self.engine
+        B, T, _ = inputs_embeds.shape
+        if past_key_values is None:
+            need = T + max_new_tokens
+            if need > eng.w.rope_len:
+                raise ValueError(f"sequence of {need} positions exceeds the RoPE table ({eng.w.rope_len})")
+            st = eng.new_state(B, min(need + self.cache_reserve, eng.w.rope_len), max(max_new_tokens, self.cache_reserve), ws_tokens=T)
+            eng.prefill(inputs_embeds, max_new=max_new_tokens, lens=lens, state=st)
+            return st
+        st = past_key_values
+        if B != 1 or st.batch != 1:
+            raise NotImplementedError("generate(past_key_values=...) continues one sequence (batch 1); batches append through "
+                                      "engine.append(lens=...)")
+        if max_new_tokens > st.max_new:
+            raise ValueError(f"max_new_tokens = {max_new_tokens} exceeds the {st.max_new} ids the cached state was built for: build it "
+                             "with a larger cache_reserve")
+        pend = st.pending_ids()
+        st.truncate(list(st.host_len))
+        seg = inputs_embeds if pend is None else torch.cat([eng.embed_tokens(pend[:, None]).to(inputs_embeds.dtype), inputs_embeds], 1)
+        cap = min(st.max_pos, eng.w.rope_len)
+        if st.host_len[0] + seg.shape[1] + max_new_tokens > cap:
+            raise ValueError(f"KV cache too small ({cap} positions) for {st.host_len[0]} cached + {seg.shape[1]} appended + "
+                             f"{max_new_tokens} new tokens: build the state with a larger cache_reserve")
+        eng.append(st, seg)
+        return st
+
     # ---- llava_llama.py:194-213 ----
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, depths=None, masks=None, attention_mask=None, **generation_kwargs):
@@ -440,11 +534,16 @@ class LlavaLlamaModel:
                               top_p=NOT_GIVEN, top_k=NOT_GIVEN, num_beams=NOT_GIVEN, max_new_tokens=NOT_GIVEN,
                               max_length=NOT_GIVEN, min_new_tokens=NOT_GIVEN, use_cache=True, stopping_criteria=None,
                               pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, repetition_penalty=NOT_GIVEN,
-                              no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, **unused):
+                              no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, past_key_values=None,
+                              return_dict_in_generate=False, **unused):
         """HF `GenerationMixin.generate(inputs_embeds=...)` as the reference reaches it (llava_llama.py:212): the stored
         generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py).
         `repetition_penalty`, `no_repeat_ngram_size` and `min_length` / `min_new_tokens` run as HF's logits processors on the device
-        (csrc/logits_proc.hip) in every decoding mode; every other keyword is accepted and ignored."""
+        (csrc/logits_proc.hip) in every decoding mode; every other keyword is accepted and ignored.
+        `past_key_values` (a state an earlier call returned): the request CONTINUES it with `inputs_embeds` as the next segment
+        instead of prefilling a prompt; `return_dict_in_generate=True`: the result is a GenerateOutput (.sequences,
+        .past_key_values).  Either keyword runs the request on a state of the caller's (batch 1, no beams: _state_for_generate);
+        without them this is the pooled-state path, unchanged."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
                                min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
@@ -476,6 +575,14 @@ class LlavaLlamaModel:
             inputs_embeds = packed.contiguous()
             if min(lens_h) == Tmax:
                 lens = None
+        on_handle = past_key_values is not None or bool(return_dict_in_generate)
+        if on_handle:
+            if g.num_beams != 1:
+                raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True) with num_beams > 1")
+            st = self._state_for_generate(past_key_values, inputs_embeds, lens, max_new_tokens)
+            done = (lambda ids: GenerateOutput(sequences=ids, past_key_values=st)) if return_dict_in_generate else (lambda ids: ids)
+        else:
+            done = lambda ids: ids  # noqa: E731
         if g.num_beams != 1:
             # `--num_beams N` of the eval CLIs; with their default `--temperature 0.2` (do_sample = temperature > 0) this is HF's
             # beam-SAMPLE, with `--temperature 0` beam search proper
@@ -483,7 +590,8 @@ class LlavaLlamaModel:
             return self._beam_search(inputs_embeds, lens, g.num_beams, max_new_tokens, eos_ids, g.pad_token_id, stopping_criteria,
                                      sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p) if sample else None,
                                      logits_proc=proc)
-        st, _, _ = self.engine.prefill(inputs_embeds, max_new=max_new_tokens, lens=lens)
+        if not on_handle:
+            st, _, _ = self.engine.prefill(inputs_embeds, max_new=max_new_tokens, lens=lens)
         if g.do_sample and g.temperature is not None and g.temperature > 0:
             from . import ops
 
@@ -494,15 +602,17 @@ class LlavaLlamaModel:
                 # request reproducible, as with HF's torch.multinomial (whose stream itself cannot be matched).  The top-k-64 sampler
                 # serves the demo's settings; the full sampler every other one (top_k > 64, top-p without top-k)
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-                return self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
-                                                 stopping_criteria=stopping_criteria,
-                                                 sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed,
-                                                               sampler=kind), logits_proc=proc)
+                return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
+                                                      stopping_criteria=stopping_criteria,
+                                                      sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed,
+                                                                    sampler=kind), logits_proc=proc))
             # a vocabulary above 262144 (no config of the reference's): warpers + draw as torch ops per token
+            if on_handle:
+                raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True): sampling over a vocabulary above 262144")
             return self._sample_loop(st, max_new_tokens, g.temperature, g.top_p, g.top_k, eos_ids, g.pad_token_id,
                                      stopping_criteria, logits_proc=proc)
-        return self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
-                                         stopping_criteria=stopping_criteria, logits_proc=proc)
+        return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
+                                              stopping_criteria=stopping_criteria, logits_proc=proc))
 
     def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
                      logits_proc=None):

@@ -344,6 +344,26 @@ def attention(q, k, v, causal=False, scale=None, kv_len=None):
     return o
 
 
+def attention_append(q, k, v, q_pos0, kv_len=None, Tk=None, scale=None):
+    """srgpt_attention_append: q [B,Tq,Hq,D] new query rows, row b at positions q_pos0[b] + t (int32 [B], device); k/v [B,>=Tk,Hkv,D]
+    the live cache (arbitrary strides with unit last stride); Tk = the host's bound on the keys any row may see (default: all of k);
+    kv_len (int32 [B], optional) the keys row b may see -> [B,Tq,Hq,D]."""
+    _dev(q, k, v, q_pos0)
+    _same_dtype("attention_append", q, k=k, v=v)
+    B, Tq, Hq, D = q.shape
+    Hkv = k.shape[2]
+    Tk = k.shape[1] if Tk is None else int(Tk)
+    assert q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1 and Tk <= k.shape[1] and Tk <= v.shape[1]
+    assert q_pos0.dtype == torch.int32 and q_pos0.shape == (B,) and q_pos0.is_contiguous()
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    o = torch.empty((B, Tq, Hq, D), device=q.device, dtype=q.dtype)
+    L.check(L.load().srgpt_attention_append(_p(q), _p(k), _p(v), _p(o), B, Tq, Tk, Hq, Hkv, D, q.stride(0), q.stride(1),
+                                            q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1),
+                                            v.stride(2), float(scale), _p(q_pos0), _p(kv_len), dt_code(q), _stream()))
+    return o
+
+
 def gemm_swiglu(a, wgu, out=None):
     """silu(a @ wg.T) * (a @ wu.T) for the stacked weight wgu = [wg; wu] ([2 I, K]): gemm + silu_mul in one call."""
     _dev(a, wgu)

@@ -320,6 +320,20 @@ int srgpt_splice_gather(const int* desc, const int* stats, int B, int Tcap, int 
                         const void* embed, const void* image_features, const void* mask_embeds, const void* depth_embeds,
                         const int64_t* labels, int P, int64_t ignore_index, void* out, int64_t* labels_out,
                         unsigned char* attn_mask_out, srgpt_stream_t stream);
+/* Additions under ABI 9: prefix reuse across requests -- how much of the last request is the head of this one.  Both only enqueue
+ * work (nothing allocates, nothing synchronises) and write ONE int; argument errors (a NULL pointer, a negative count, row_bytes < 1)
+ * are SRGPT_ERR_ARG before any launch.  The results are minima over "first row that differs": they do not depend on scheduling,
+ * and out[] needs no initial value.
+ * srgpt_rows_match: a, b = [rows, row_bytes] bytes, any alignment; out[0] = the number of LEADING rows of a that equal the same rows
+ *   of b byte for byte, 0 .. rows (-0.0 differs from 0.0, equal NaN bytes are equal; no hashing, so no false hit).  rows = 0: 0.
+ * srgpt_splice_match (one prompt): desc_new [len_new][2], desc_old [n_old_rows][2] as srgpt_splice_plan leaves a prompt's rows; only
+ *   the first int of a row (kind | src << 2) is compared.  The OLD sequence is desc_old's rows followed by n_gen_old rows of kind 0
+ *   whose src are the ids gen_old[j] (int64: the ids the earlier request generated).  out[0] = the number of leading rows
+ *   r < min(len_new, n_old_rows + n_gen_old) whose keys are equal; a row of kind 2 or 3 (mask / depth embedding) with
+ *   src >= n_regions_common counts as different.  Every length may be 0; the pointers must not be NULL even then. */
+int srgpt_rows_match(const void* a, const void* b, int rows, int64_t row_bytes, int* out, srgpt_stream_t stream);
+int srgpt_splice_match(const int* desc_new, int len_new, const int* desc_old, int n_old_rows, const int64_t* gen_old, int n_gen_old,
+                       int n_regions_common, int* out, srgpt_stream_t stream);
 /* ABI 9: beam search's cache permutation on the device (HF `_reorder_cache`): kcache / vcache [layers, batch * num_beams, kv_heads,
  * max_pos, head_dim]; row r of the first `live` positions of every layer := row beam_idx[r] (int64, device; an index never leaves
  * its batch item's num_beams rows).  In place, one launch; 2 ... 8 beams (else SRGPT_ERR_UNSUPPORTED: permute on the caller's side). */

@@ -102,6 +102,8 @@ _SIGNATURES = {
     "srgpt_splice_scratch_ints": (i64, [i32, i32]),
     "srgpt_splice_plan": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
     "srgpt_splice_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp]),
+    "srgpt_rows_match": (i32, [vp, vp, i32, i64, vp, vp]),
+    "srgpt_splice_match": (i32, [vp, i32, vp, i32, vp, i32, i32, vp, vp]),
     "srgpt_gemv_rowss_supported": (i32, [i32, i32, i32]),
     "srgpt_gemv_rowss": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "srgpt_packed_bytes": (C.c_size_t, [i32, i32, i32, i32]),

@@ -309,7 +309,7 @@ class SrgptEngine:
         return [None if m is None else int(m.shape[0]) for m in masks]
 
     def splice_plan(self, input_ids: torch.Tensor, attention_mask, n_images: int, region_counts, have_depths: bool,
-                    nimg_feat: Optional[int] = None) -> "SplicePlan":
+                    nimg_feat: Optional[int] = None, stats_buf: Optional[torch.Tensor] = None) -> "SplicePlan":
         """Token-stream splice, step 1 (llava_arch.py:420-611): the row -> source table of the whole batch, built ON THE DEVICE from
         the ids (csrc/splice.hip) -- the ids never travel; what comes back is 8 ints per prompt (lengths, counts, id range) for the
         batch length T and the reference's error / warning conditions.  prepare_inputs() calls this BEFORE it launches the vision
@@ -332,14 +332,24 @@ class SrgptEngine:
         Tcap = max(P + n_images * max(nf - 1, 0), 1)
         lib = L.load()
         desc = torch.empty((B, Tcap, 2), device=dev, dtype=torch.int32)
-        stats = torch.empty((B, L.SPLICE_STATS), device=dev, dtype=torch.int32)
+        if stats_buf is None:
+            stats = torch.empty((B, L.SPLICE_STATS), device=dev, dtype=torch.int32)
+        else:
+            assert stats_buf.dtype == torch.int32 and stats_buf.is_contiguous() and stats_buf.numel() >= B * L.SPLICE_STATS
+            stats = stats_buf[:B * L.SPLICE_STATS].view(B, L.SPLICE_STATS)
         scratch = torch.empty((max(int(lib.srgpt_splice_scratch_ints(B, n_images)), 1),), device=dev, dtype=torch.int32)
         mx = cfg.tokenizer_model_max_length
         L.check(lib.srgpt_splice_plan(ids.data_ptr(), None if am8 is None else am8.data_ptr(), B, P, nf, n_images, info_dev.data_ptr(),
                                       int(use_masks), int(use_depths), int(cfg.mask_token_id), int(cfg.depth_token_id),
                                       int(mx) if mx is not None else 0, Tcap, desc.data_ptr(), stats.data_ptr(), scratch.data_ptr(),
                                       ops._stream()))
-        host = stats.cpu().tolist()  # the request's one device -> host copy (B x 8 ints)
+        tail = None
+        if stats_buf is None:
+            host = stats.cpu().tolist()  # the request's one device -> host copy (B x 8 ints)
+        else:
+            flat = stats_buf.cpu().tolist()  # the same one copy, the caller's ints behind the statistics included
+            host = [flat[b * L.SPLICE_STATS:(b + 1) * L.SPLICE_STATS] for b in range(B)]
+            tail = flat[B * L.SPLICE_STATS:]
         for b, (ln, ln_raw, n_img, n_mask, n_depth, first_img, mn, mxid) in enumerate(host):
             if n_img > 0:
                 if first_img + n_img > n_images:
@@ -363,7 +373,7 @@ class SrgptEngine:
         return SplicePlan(ids=ids, B=B, P=P, nimg_feat=nf, n_images=n_images, Tcap=Tcap, desc=desc, stats=stats, lens=lens,
                           T=max(max(lens), 1), have_attention_mask=attention_mask is not None,
                           am_dtype=None if attention_mask is None else attention_mask.dtype,
-                          region_counts=region_counts, have_depths=have_depths, attention_mask=attention_mask)
+                          region_counts=region_counts, have_depths=have_depths, attention_mask=attention_mask, stats_tail=tail)
 
     def splice_apply(self, plan: "SplicePlan", image_features, mask_embeds, depth_embeds, labels=None):
         """Token-stream splice, step 2: ONE gather launch writes every row of inputs_embeds [B, T, H] from its source (embedding

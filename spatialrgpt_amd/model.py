@@ -183,7 +183,8 @@ class LlavaLlamaModel:
 
     def __init__(self, config=None, state_dict: Dict[str, torch.Tensor] = None, device="cuda",
                  dtype=torch.bfloat16, tokenizer=None, image_processor=None, rope_positions: int = 0,
-                 consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, **hf_kwargs):
+                 consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, prefix_reuse: bool = False,
+                 **hf_kwargs):
         self.hf_config = None
         if isinstance(config, LlavaConfig):
             # the reference's construction path: config carries the checkpoint location
@@ -217,6 +218,28 @@ class LlavaLlamaModel:
         self.training = False
         self.cache_reserve = 128  # forward(use_cache=True): cache positions reserved beyond the prompt
         self._warned_dtype = False
+        # prefix reuse (spatialrgpt_amd/reuse.py), opt-in: a generate(input_ids, images=...) call of batch 1 continues the LAST such
+        # request's KV cache over the rows both prompts share and skips the towers when the media are byte-equal.  Off: every
+        # request takes exactly the launches it takes without the feature, and nothing is retained
+        self.prefix_reuse = bool(prefix_reuse)
+        self._reuse = None        # PrefixReuse, made by the first request that takes the reuse path
+        self.reuse_stages = None  # a dict here receives the reuse path's inputs_embeds and embeddings, as prepare_inputs(stages=)
+
+    @property
+    def last_reuse(self):
+        """what the last request on the reuse path did: dict(mode "append" | "fresh", rows_reused, rows_appended, towers_skipped,
+        regions_common); None before the first one"""
+        return None if self._reuse is None else self._reuse.last
+
+    @property
+    def reuse_record(self):
+        """the retained request (reuse.ReuseRecord: media, tower features, splice table, DecodeState), or None"""
+        return None if self._reuse is None else self._reuse.record
+
+    def drop_reuse(self):
+        """forget the retained request (its features and its KV cache are freed with it)"""
+        if self._reuse is not None:
+            self._reuse.drop()
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path, *model_args, config=None, **kwargs):
@@ -322,6 +345,7 @@ class LlavaLlamaModel:
         if embed_size != self.engine.w.vocab:
             self.engine.w.resize_vocab(embed_size)
             self.engine._state = None
+            self.drop_reuse()  # its state's logits rows and its cached rows belong to the old table
             self.config.vocab_size = embed_size
         return self.engine.embed_tokens
 
@@ -514,6 +538,12 @@ class LlavaLlamaModel:
     # ---- llava_llama.py:194-213 ----
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, depths=None, masks=None, attention_mask=None, **generation_kwargs):
+        if self.prefix_reuse and input_ids is not None and images is not None and input_ids.shape[0] == 1 \
+                and generation_kwargs.get("past_key_values") is None and not generation_kwargs.get("return_dict_in_generate") \
+                and generation_kwargs.get("inputs_embeds") is None:
+            g = resolve_generation(self.generation_defaults(), **generation_kwargs)
+            if g.num_beams == 1:
+                return self._generate_with_reuse(input_ids, images, depths, masks, attention_mask, g.max_new_tokens, generation_kwargs)
         if images is not None:
             (_, _, attention_mask, _, inputs_embeds, _) = self.prepare_inputs_labels_for_multimodal(
                 input_ids, None, attention_mask, None, None, images, masks, depths)
@@ -521,6 +551,22 @@ class LlavaLlamaModel:
             inputs_embeds = self.engine.embed_tokens(input_ids)
         inputs_embeds = inputs_embeds.to(self.dtype)
         return self.llm.generate(inputs_embeds=inputs_embeds, attention_mask=attention_mask, **generation_kwargs)
+
+    def _generate_with_reuse(self, input_ids, images, depths, masks, attention_mask, max_new_tokens, generation_kwargs):
+        """the reuse path (reuse.PrefixReuse): the prompt goes into a state of the request's own -- the retained one, cut back to the
+        shared rows and continued, or a fresh one --, the decode loop is the one every request runs, the request is retained"""
+        from .reuse import PrefixReuse
+
+        if self._reuse is None:
+            self._reuse = PrefixReuse(self)
+        try:
+            st = self._reuse.prefill(input_ids, images, depths, masks, attention_mask, max_new_tokens)
+            out = self._generate_from_embeds(None, None, _state=st, **generation_kwargs)
+            self._reuse.commit()
+        except BaseException:
+            self._reuse.drop()  # a half-written state is nothing to continue
+            raise
+        return out
 
     def generation_defaults(self) -> dict:
         """the stored generation config `llm.generate` starts from (HF: <ckpt>/llm/generation_config.json, else the generation
@@ -535,7 +581,7 @@ class LlavaLlamaModel:
                               max_length=NOT_GIVEN, min_new_tokens=NOT_GIVEN, use_cache=True, stopping_criteria=None,
                               pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, repetition_penalty=NOT_GIVEN,
                               no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, past_key_values=None,
-                              return_dict_in_generate=False, **unused):
+                              return_dict_in_generate=False, _state=None, **unused):
         """HF `GenerationMixin.generate(inputs_embeds=...)` as the reference reaches it (llava_llama.py:212): the stored
         generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py).
         `repetition_penalty`, `no_repeat_ngram_size` and `min_length` / `min_new_tokens` run as HF's logits processors on the device
@@ -543,7 +589,8 @@ class LlavaLlamaModel:
         `past_key_values` (a state an earlier call returned): the request CONTINUES it with `inputs_embeds` as the next segment
         instead of prefilling a prompt; `return_dict_in_generate=True`: the result is a GenerateOutput (.sequences,
         .past_key_values).  Either keyword runs the request on a state of the caller's (batch 1, no beams: _state_for_generate);
-        without them this is the pooled-state path, unchanged."""
+        without them this is the pooled-state path, unchanged.  `_state` (the reuse path): a batch-1 state that already holds the
+        prompt; only the decode loop runs."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
                                min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
@@ -555,9 +602,10 @@ class LlavaLlamaModel:
         if g.min_tokens >= max_new_tokens:
             # every step bans the EOS ids (the general rule, in `proc`): no token can end the request, so nothing is judged per step
             eos_ids = None
-        B, T, _ = inputs_embeds.shape
         lens = None
-        if attention_mask is not None and not bool(attention_mask.bool().all()):
+        if _state is None:
+            B, T, _ = inputs_embeds.shape
+        if _state is None and attention_mask is not None and not bool(attention_mask.bool().all()):
             # ragged batch (llava_arch.py:549-611 pads to the longest row, right or left): pack every row's valid positions
             # to the front (right padding) and hand the lengths to the ragged prefill; decode is batched with one position
             # per sequence, exactly like the reference's padded generate()
@@ -575,8 +623,10 @@ class LlavaLlamaModel:
             inputs_embeds = packed.contiguous()
             if min(lens_h) == Tmax:
                 lens = None
-        on_handle = past_key_values is not None or bool(return_dict_in_generate)
-        if on_handle:
+        on_handle = _state is not None or past_key_values is not None or bool(return_dict_in_generate)
+        if _state is not None:
+            st, done = _state, (lambda ids: ids)
+        elif on_handle:
             if g.num_beams != 1:
                 raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True) with num_beams > 1")
             st = self._state_for_generate(past_key_values, inputs_embeds, lens, max_new_tokens)
@@ -607,7 +657,7 @@ class LlavaLlamaModel:
                                                       sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed,
                                                                     sampler=kind), logits_proc=proc))
             # a vocabulary above 262144 (no config of the reference's): warpers + draw as torch ops per token
-            if on_handle:
+            if on_handle and _state is None:
                 raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True): sampling over a vocabulary above 262144")
             return self._sample_loop(st, max_new_tokens, g.temperature, g.top_p, g.top_k, eos_ids, g.pad_token_id,
                                      stopping_criteria, logits_proc=proc)

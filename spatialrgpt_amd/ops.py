@@ -522,6 +522,35 @@ def embed_rows(table, ids):
     return out
 
 
+def rows_match(a: torch.Tensor, b: torch.Tensor, rows: int, out: torch.Tensor) -> torch.Tensor:
+    """out[0] (int32, device) = the number of leading rows of `a` equal to the same rows of `b` BYTE FOR BYTE (srgpt_rows_match);
+    a, b: contiguous tensors of one dtype (torch slices at any alignment) whose first `rows` entries along dim 0 are compared.
+    Only enqueues: the caller reads `out` back with whatever else it reads."""
+    _dev(a, b, out)
+    _same_dtype("rows_match", a, b=b)
+    assert a.is_contiguous() and b.is_contiguous() and out.dtype == torch.int32 and out.numel() >= 1
+    row_bytes = (a[0].numel() if a.dim() > 0 and a.shape[0] > 0 else 1) * a.element_size()
+    if rows > 0 and (a.shape[0] < rows or b.shape[0] < rows or a.shape[1:] != b.shape[1:]):
+        raise ValueError(f"rows_match: {rows} rows of {tuple(a.shape)} against {tuple(b.shape)}")
+    L.check(L.load().srgpt_rows_match(_p(a), _p(b), int(rows), max(int(row_bytes), 1), _p(out), _stream()))
+    return out
+
+
+def splice_match(desc_new, len_new: int, desc_old, n_old_rows: int, gen_old, n_gen_old: int, n_regions_common: int,
+                 out: torch.Tensor) -> torch.Tensor:
+    """out[0] (int32, device) = the leading rows of ONE prompt's splice table `desc_new` [>= len_new, 2] that name the sources of the
+    old row sequence: `desc_old`'s first n_old_rows rows, then the ids gen_old[:n_gen_old] (int64) as text rows; region rows beyond
+    `n_regions_common` never match (srgpt_splice_match).  Only enqueues."""
+    _dev(desc_new, desc_old, gen_old, out)
+    assert desc_new.dtype == torch.int32 and desc_old.dtype == torch.int32 and gen_old.dtype == torch.int64 and out.dtype == torch.int32
+    assert desc_new.is_contiguous() and desc_old.is_contiguous() and gen_old.is_contiguous() and out.numel() >= 1
+    if len_new * 2 > desc_new.numel() or n_old_rows * 2 > desc_old.numel() or n_gen_old > gen_old.numel():
+        raise ValueError("splice_match: a length exceeds its table")
+    L.check(L.load().srgpt_splice_match(_p(desc_new), int(len_new), _p(desc_old), int(n_old_rows), _p(gen_old), int(n_gen_old),
+                                        int(n_regions_common), _p(out), _stream()))
+    return out
+
+
 def scatter_rows(src, idx, dst, src_idx=None):
     """dst[idx[i]] = src[src_idx[i] if src_idx is given else i]"""
     _dev(src, idx, dst, src_idx)

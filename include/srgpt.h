@@ -251,6 +251,26 @@ int64_t srgpt_decode_attn_ws_floats(int B, int Hq, int D);
 int srgpt_decode_attention(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
                            const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D,
                            int max_pos, int dtype, srgpt_stream_t stream);
+/* Additions under ABI 9: decode attention for T NEW TOKENS per sequence in one launch -- the next token and T - 1 drafted ones of
+ * prompt-lookup decoding (HF generate(prompt_lookup_num_tokens = T - 1); the model side is the cached forward over input_ids
+ * [1, T], modeling_llama.py:398-456).  Token t of sequence b sits at position pos[b] + t and sees the keys s <= pos[b] + t.
+ *   qkv [B, T, (Hq+2Hkv)*D] raw projections; out [B, T, Hq*D]; pos, caches and tables as for srgpt_decode_attention.  The T new k / v
+ *   rows are roped and appended at pos[b] .. pos[b] + T - 1; pos itself is NOT advanced (the caller decides how many rows it keeps).
+ *   bf16 with D = 128 runs on the matrix pipe, query head g of token t in column t * G + g of the 16 the single-token kernel leaves
+ *   mostly empty (G = Hq / Hkv): T * G <= 16, else SRGPT_ERR_UNSUPPORTED before any launch.  qkv is only read.  Output row t EQUALS,
+ *   bit for bit, what srgpt_decode_attention returns for token t's projections at position pos[b] + t over a cache that holds the
+ *   rows before it, and so do the appended cache rows; the bits do not depend on max_pos up to 4096.
+ *   Every other dtype / head_dim (the fp32 parity path) is a composition: one RoPE / append launch, which ROTATES THE q HEADS OF
+ *   qkv IN PLACE like srgpt_rope_kv_append, then srgpt_attention_append's one-wave kernel with q_pos0 = pos and Tk = max_pos (it
+ *   reads no key behind a row's own position, whatever the cache holds there).  Slow, correct.
+ *   A token with pos[b] + t >= max_pos (or pos[b] outside 0 .. max_pos - 1) is neither appended nor attended: its output row is
+ *   unspecified but inside out, and no byte outside the caches is written whatever pos holds.
+ *   ws: srgpt_decode_attn_multi_ws_floats(B, T, Hq, D) floats -- B * T * Hq * 64 partial rows of D + 2 floats, then B * Hq arrival
+ *   tickets, which must be ZERO before the first launch; every launch leaves them zero again. */
+int64_t srgpt_decode_attn_multi_ws_floats(int B, int T, int Hq, int D);
+int srgpt_decode_attention_multi(void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
+                                 const void* sin_tab, void* out, float* ws, int B, int T, int Hq, int Hkv, int D,
+                                 int max_pos, int dtype, srgpt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Region extractor (SpatialRGPT specific).
@@ -619,6 +639,59 @@ int srgpt_llm_decode_graph_create_proc(const srgpt_llm_weights* w, srgpt_llm_sta
                                        srgpt_stream_t stream, srgpt_graph** out);
 int srgpt_graph_launch(srgpt_graph* g, int times, srgpt_stream_t stream);
 int srgpt_graph_destroy(srgpt_graph* g);
+
+/* ---------------------------------------------------------------------------------------------
+ * Prompt-lookup decoding (additions under ABI 9): HF generate(prompt_lookup_num_tokens = K) -- transformers 4.37
+ * generation/candidate_generator.py PromptLookupCandidateGenerator + GenerationMixin.assisted_decoding, greedy.  A decode step is
+ * weight-bound: its cost barely depends on the rows riding through it.  The lookup step carries T = K + 1 rows of ONE sequence -- the
+ * next token and K ids drafted from the sequence itself -- and emits 1 .. T tokens, the same ids the plain greedy loop emits.
+ *
+ * srgpt_lookup_draft (one block): the history is prompt_ids[n_prompt] (int64, may be NULL when n_prompt = 0) followed by the first
+ *   *step ids of out_ids (step: device int, clamped to 0 .. max_new).  An id outside [0, vocab) is a sentinel (-200): it never matches
+ *   and is never drafted.  For n = min(max_ngram, len - 1) down to 1: take the last n ids; find the EARLIEST earlier occurrence that
+ *   has a (non-sentinel) id after it; the up to K non-sentinel ids that follow are draft[0 .. *n_draft) (the rest of draft[K] is -1;
+ *   *n_draft = 0: no match).  The position is a minimum over the matches: the result does not depend on scheduling.
+ *   K 1 .. 15, max_ngram 1 .. 8, else SRGPT_ERR_ARG.
+ * srgpt_lookup_accept (one block): picks int64 [T] = the model's greedy pick behind each of the T rows (srgpt_argmax).  n_acc = the
+ *   longest prefix with draft[i] == picks[i], i < *n_draft (and pos[0] + i + 1 < max_pos).  The step emits picks[0 .. n_acc]: they go
+ *   to out_ids[*step ..], cut at max_new; *step and pos[0] advance by the number emitted, tok[0] = the last one emitted, tok_emb[0]
+ *   (optional) = -1, stats[3] (optional, device ints) += {1, *n_draft, n_acc}.  *step >= max_new on entry: nothing changes (a
+ *   run-ahead loop may launch once too often).  T 2 .. 16.
+ * --------------------------------------------------------------------------------------------- */
+int srgpt_lookup_draft(const int64_t* prompt_ids, int n_prompt, const int64_t* out_ids, const int* step, int max_new, int K,
+                       int max_ngram, int64_t vocab, int64_t* draft, int* n_draft, srgpt_stream_t stream);
+int srgpt_lookup_accept(const int64_t* picks, const int64_t* draft, const int* n_draft, int T, int64_t* tok, int64_t* out_ids,
+                        int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats, srgpt_stream_t stream);
+
+/* The lookup step's parameter block (HOST struct of device pointers; a captured graph keeps the addresses). */
+typedef struct {
+  int T;                     /* rows per step = K + 1, 2 .. 16; on the bf16 matrix-pipe attention T * heads / kv_heads <= 16 */
+  int max_ngram;             /* HF max_matching_ngram_size (default 2), 1 .. 8 */
+  const int64_t* prompt_ids; /* the request's input_ids row as the caller gave it (sentinels included), or NULL */
+  int n_prompt;
+  void* ws;                  /* srgpt_llm_lookup_ws_bytes(w, T) bytes, ZEROED once when allocated (it holds arrival tickets) */
+  float* logits;             /* [T, vocab] fp32: the logits behind each of the T rows */
+  int* stats;                /* device int[3]: steps, drafted, accepted -- incremented by every step */
+} srgpt_lookup;
+
+/* workspace bytes of a T-row lookup step: T rows of the decode step's buffers, two row-statistics tables, the workspace of
+ * srgpt_decode_attention_multi, the rows' pick partials and the draft scratch.  (srgpt_llm_ws_bytes does not change.) */
+int64_t srgpt_llm_lookup_ws_bytes(const srgpt_llm_weights* w, int T);
+/* One lookup step of a batch-1 GREEDY state, entirely device-side: srgpt_lookup_draft over (lk->prompt_ids, st->out_ids) -> the T
+ * rows' embeddings (st->tok, the drafts, then the last id repeated -- rows that can never be accepted) -> the layers of
+ * srgpt_llm_decode_step with T rows through the same products (bf16, W8A16 and the packed fp8 copies) and
+ * srgpt_decode_attention_multi -> lm_head into lk->logits -> the rows' argmax -> srgpt_lookup_accept on the state.  It equals that
+ * composition of the per-op entries bit for bit, and row 0 -- hence every emitted id -- does not depend on the drafts.
+ * st->sampling set, T beyond the attention's columns or 16: SRGPT_ERR_UNSUPPORTED; batch != 1, T < 2, NULL pointers: SRGPT_ERR_ARG;
+ * all before any launch.  Cache rows behind the accepted ones hold rejected drafts: they lie beyond st->pos and the next step
+ * overwrites them.  A plain captured step may follow (tok_emb = -1 makes it re-embed st->tok).
+ * srgpt_llm_lookup_graph_create captures one step; replay with srgpt_graph_launch.
+ * srgpt_llm_lookup_sync_state: srgpt_llm_decode_sync_state for such a state -- the lookup workspace's own arrival tickets are checked
+ * first (SRGPT_ERR_STATE), then the plain check runs unchanged. */
+int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream);
+int srgpt_llm_lookup_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream,
+                                  srgpt_graph** out);
+int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,14 @@ class LogitsProc(C.Structure):
     _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram", i32), ("min_new_tokens", i32), ("n_eos", i32), ("eos", i64 * 8)]
 
 
+class Lookup(C.Structure):
+    """srgpt_lookup (include/srgpt.h): the lookup step's parameter block; a HOST struct of device pointers."""
+    _fields_ = [("T", i32), ("max_ngram", i32), ("prompt_ids", vp), ("n_prompt", i32), ("ws", vp), ("logits", vp), ("stats", vp)]
+
+
+LOOKUP_ROWS_MAX = 16               # lookup.hip LOOKUP_ROWS_MAX: T = K + 1 rows of a lookup step
+LOOKUP_NGRAM_MAX = 8               # lookup.hip LOOKUP_NGRAM_MAX
+ATTN_MULTI_COLS = 16               # attn_route.h ATTN_DEC_MULTI_COLS: T * heads / kv_heads on the bf16 matrix-pipe attention
 LOGITS_PROC_EOS_MAX = 8            # srgpt_logits_proc::eos
 LOGITS_PROC_HISTORY_MAX = 12288    # logits_proc.hip LP_MAX_HIST: ids per row
 SAMPLING_TOP_K_MAX = 64        # sample.hip SMP_K
@@ -117,6 +125,8 @@ _SIGNATURES = {
     "srgpt_rope_kv_append": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_decode_attn_ws_floats": (i64, [i32, i32, i32]),
     "srgpt_decode_attention": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "srgpt_decode_attn_multi_ws_floats": (i64, [i32, i32, i32, i32]),
+    "srgpt_decode_attention_multi": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_region_pool_ws_floats": (i64, [i32, i32, i32]),
     "srgpt_region_pool": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, i32, i32, vp]),
     "srgpt_region_pool_u8": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp]),
@@ -157,6 +167,12 @@ _SIGNATURES = {
     "srgpt_llm_decode_graph_create_proc": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), i32, vp, vp, C.POINTER(vp)]),
     "srgpt_graph_launch": (i32, [vp, i32, vp]),
     "srgpt_graph_destroy": (i32, [vp]),
+    "srgpt_lookup_draft": (i32, [vp, i32, vp, vp, i32, i32, i32, i64, vp, vp, vp]),
+    "srgpt_lookup_accept": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "srgpt_llm_lookup_ws_bytes": (i64, [C.POINTER(LlmWeights), i32]),
+    "srgpt_llm_lookup_step": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(Lookup), vp]),
+    "srgpt_llm_lookup_graph_create": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(Lookup), vp, C.POINTER(vp)]),
+    "srgpt_llm_lookup_sync_state": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(Lookup), vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

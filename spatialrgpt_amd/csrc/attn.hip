@@ -4,6 +4,8 @@
 //  2. simple_attn_kernel -- one wave per (query, head); any dtype / head_dim; fp32 parity path.
 //  3. decode_split/combine -- single new token against the static KV cache, flash-decoding split over
 //     keys, fused RoPE of the new q/k and cache append.  HBM/latency bound.
+//  4. decode_mfma_multi  -- the same for T new tokens per sequence (prompt-lookup decoding): the drafted tokens' query heads in the
+//     columns of the MFMA B operand the single-token kernel leaves empty.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -617,6 +619,303 @@ __global__ __launch_bounds__(256) void decode_mfma_kernel(const bf16_t* __restri
                                    &sc[0][0], stat_m, stat_l, tid, lane, wave);
 }
 
+// ------------------------------------------------------------------------------------------------
+// decode attention for T new tokens per sequence (srgpt_decode_attention_multi): the next token and T - 1 drafted ones ride through
+// ONE pass over the cache.  decode_mfma_kernel multiplies against a 16-column B operand of which G columns are live; here column
+// c = t * G + g holds query head g of token t (T * G <= 16), token t sits at position P + t and sees the keys s <= P + t.  The T new
+// k / v rows are roped into LDS, appended by the split-0 block and read from LDS by every block -- never back from the cache.
+// Every column runs decode_mfma_kernel's arithmetic for ITS position, operation for operation: the same fixed key ranges, the same
+// per-wave online softmax, the same wave and split merges -- so row t equals what srgpt_decode_attention answers at position P + t
+// over a cache that holds rows P .. P + t - 1 (tests/test_gpu_attention_multi.py, bit for bit).  What the single-token kernel never
+// meets: a column that sees NO key of a 16-key group, of a wave or of a whole split (the keys behind its own position).  Such a group
+// leaves the column's running (m, l, P.V) untouched -- rescale 1, probabilities 0, no exp(-inf - -inf) --, such a wave or split
+// publishes the neutral partial (m = -inf, l = 0, zeros), which both merges add as exact zeros, as they do for a short sequence.
+// Rows at or beyond max_pos are neither appended nor attended (their columns are dead); a sequence whose pos lies outside the cache
+// leaves at once.
+// ------------------------------------------------------------------------------------------------
+constexpr int DMM_C = ATTN_DEC_MULTI_COLS;
+
+// decode_ticket_merge for a runtime number of columns: column c of the group -> out row (token c / G, head hk * G + c % G).  The same
+// weights, the same fma chain in split order, the same rounding.
+__device__ __forceinline__ void decode_multi_ticket_merge(float* __restrict__ wbase, int* __restrict__ ticket, int nsplit, int ncol,
+                                                          int G, bf16_t* __restrict__ outp, size_t tok_stride, float* __restrict__ sc,
+                                                          float* __restrict__ stat_m, float* __restrict__ stat_l, int tid, int lane,
+                                                          int wave) {
+  constexpr int D = 128, PRE = 16;
+  constexpr size_t HEAD = attn_ws_row(1, 0, D), ROW = attn_ws_row(0, 1, D);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    stat_l[0] = (t == nsplit - 1) ? 1.f : 0.f;
+  }
+  __syncthreads();
+  if (stat_l[0] == 0.f) return;
+  __syncthreads();
+  for (int c = wave; c < ncol; c += 4) {  // per-column merge weights: one split per lane
+    const float* wp = wbase + c * HEAD;
+    const bool ok = lane < nsplit;
+    const int sidx = ok ? lane : nsplit - 1;
+    const unsigned long long ml = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + sidx * ROW + D),
+                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float ms_raw = __uint_as_float((unsigned)ml), ls_raw = __uint_as_float((unsigned)(ml >> 32));
+    const float ms = ok ? ms_raw : -INFINITY;
+    const float ls = ok ? ls_raw : 0.f;
+    const float M = lanes_max<64>(ms);
+    const float wv = (ms > -INFINITY) ? __expf(ms - M) : 0.f;
+    const float den = lanes_sum<64>(wv * ls);
+    sc[c * 64 + lane] = wv;
+    if (lane == 0) stat_m[c] = den > 0.f ? 1.f / den : 0.f;
+  }
+  __syncthreads();
+  for (int w = tid; w < ncol * (D / 2); w += 256) {
+    const int c = w / (D / 2), d = 2 * (w - c * (D / 2));
+    const float* wp = wbase + c * HEAD + d;
+    float n0 = 0.f, n1 = 0.f;
+    for (int s0 = 0; s0 < nsplit; s0 += PRE) {  // 16 loads in flight, consumed in split order
+      unsigned long long u[PRE];
+#pragma unroll
+      for (int j = 0; j < PRE; ++j)
+        u[j] = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(wp + min(s0 + j, nsplit - 1) * ROW), __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+      for (int j = 0; j < PRE; ++j)
+        if (s0 + j < nsplit) {
+          n0 = fmaf(sc[c * 64 + s0 + j], __uint_as_float((unsigned)u[j]), n0);
+          n1 = fmaf(sc[c * 64 + s0 + j], __uint_as_float((unsigned)(u[j] >> 32)), n1);
+        }
+    }
+    bf16_t* op = outp + (size_t)(c / G) * tok_stride + (size_t)(c % G) * D + d;
+    op[0] = from_f<bf16_t>(n0 * stat_m[c]);
+    op[1] = from_f<bf16_t>(n1 * stat_m[c]);
+  }
+  if (tid == 0) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// NC: the live columns rounded up to 2 / 4 / 8 / 16 -- what sizes the per-column registers and LDS.  The columns in [T * G, NC) are
+// dead: zero queries, no visible key, nothing published.  (The column count as a RUNTIME bound inside the unrolled P.V loops made
+// the compiler predicate 512 fma and spill 12 000 registers: 400 us per launch.  G only enters index arithmetic: a runtime value.)
+template <int NC>
+__global__ __launch_bounds__(256) void decode_mfma_multi_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kcache,
+                                                                bf16_t* __restrict__ vcache, const int* __restrict__ pos,
+                                                                const bf16_t* __restrict__ cos_tab, const bf16_t* __restrict__ sin_tab,
+                                                                float* __restrict__ ws, int* __restrict__ tickets,
+                                                                bf16_t* __restrict__ out, int T, int G, int Hq, int Hkv,
+                                                                int max_pos, int nsplit, int kpb, float scale) {
+  typedef bf16_t Tb;
+  constexpr int D = 128, HALF = 64;
+  __shared__ __attribute__((aligned(16))) bf16_t qs[DMM_C * DM_QLD];      // B operand source: rows = columns (dead ones zero)
+  __shared__ __attribute__((aligned(16))) bf16_t knew[DMM_C][D], vnew[DMM_C][D];  // the new rows, by token
+  __shared__ __attribute__((aligned(16))) float pw[4][16][NC];            // a wave's probabilities [key][column]
+  __shared__ __attribute__((aligned(16))) float accs[4][NC][D];           // per-wave P.V
+  __shared__ float wm[4][NC], wl[4][NC];
+  __shared__ float sc[NC * 64];                                           // merge weights
+  __shared__ float stat_m[NC < 4 ? 4 : NC], stat_l[NC < 4 ? 4 : NC];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int hk = (int)blockIdx.x % Hkv, split = ((int)blockIdx.x / Hkv) % nsplit, b = (int)blockIdx.x / (Hkv * nsplit);
+  const int P = pos[b];
+  if (P < 0 || P >= max_pos) return;  // nothing of this sequence lies inside the cache (uniform over its blocks: no ticket is drawn)
+  const int Tv = min(T, max_pos - P);  // tokens whose rows exist: the others are neither appended nor attended
+  const int ncol = Tv * G, total = P + Tv;
+  const int kbeg = split * kpb, kend = min(kbeg + kpb, total);  // the keys ANY column of this block sees
+  const int nlive = min(nsplit, (total + kpb - 1) / kpb);
+  if (split >= nlive) return;  // uniform per block
+  const size_t QW = (size_t)(Hq + 2 * Hkv) * D;
+  const Tb* rows = qkv + (size_t)b * T * QW;
+  Tb* kc = kcache + ((size_t)b * Hkv + hk) * (size_t)max_pos * D;
+  Tb* vc = vcache + ((size_t)b * Hkv + hk) * (size_t)max_pos * D;
+  const int lq = lane & 15, g4 = lane >> 4;
+  const int lastrow = max(P - 1, 0);  // rows >= P are not in the cache yet
+  // this lane's column: token lq / G at position P + lq / G sees the keys below kend_c (0: a dead column)
+  const int kend_c = lq < ncol ? min(kbeg + kpb, P + lq / G + 1) : 0;
+
+  u32x4 kreg[4];
+  unsigned int vreg[16];
+  auto fetch = [&](int kb) {
+    const Tb* kr = kc + (size_t)min(kb + lq, lastrow) * D + g4 * 8;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) kreg[j] = *reinterpret_cast<const u32x4*>(kr + 32 * j);
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      vreg[i] = *reinterpret_cast<const unsigned int*>(vc + (size_t)min(kb + i, lastrow) * D + 2 * lane);
+  };
+  int kb = kbeg + 16 * wave;
+  fetch(kb);
+
+  // ---- rotate the Tv * G query heads and the Tv new keys at their own positions; stage v ----
+  for (int i = tid; i < (DMM_C - ncol) * (D / 2); i += 256) {  // dead columns of the B operand are zero
+    const int r = ncol + i / (D / 2), c = 2 * (i % (D / 2));
+    *reinterpret_cast<unsigned int*>(qs + r * DM_QLD + c) = 0u;
+  }
+  for (int w = tid; w < Tv * (G + 1) * HALF; w += 256) {
+    const int t = w / ((G + 1) * HALF), r = w - t * (G + 1) * HALF;
+    const int hh = r / HALF, i = r - hh * HALF;
+    const Tb* row = rows + (size_t)t * QW;
+    const Tb* p = (hh < G) ? row + (size_t)(hk * G + hh) * D : row + (size_t)(Hq + hk) * D;
+    const float x1 = to_f(p[i]), x2 = to_f(p[i + HALF]);
+    const float cv = to_f(cos_tab[(size_t)(P + t) * HALF + i]), sv = to_f(sin_tab[(size_t)(P + t) * HALF + i]);
+    const Tb o1 = from_f<Tb>(rnd<Tb>(x1 * cv) + rnd<Tb>(-x2 * sv));
+    const Tb o2 = from_f<Tb>(rnd<Tb>(x2 * cv) + rnd<Tb>(x1 * sv));
+    if (hh < G) {
+      qs[(t * G + hh) * DM_QLD + i] = o1;
+      qs[(t * G + hh) * DM_QLD + i + HALF] = o2;
+    } else {
+      knew[t][i] = o1;
+      knew[t][i + HALF] = o2;
+    }
+  }
+  for (int w = tid; w < Tv * D; w += 256) {
+    const int t = w / D, i = w - t * D;
+    vnew[t][i] = rows[(size_t)t * QW + (size_t)(Hq + Hkv + hk) * D + i];
+  }
+  __syncthreads();
+  if (split == 0) {  // exactly one block per (b, hk) appends rows P .. P + Tv - 1 (all below max_pos)
+    for (int w = tid; w < Tv * (D / 2); w += 256) {
+      const int t = w / (D / 2), i = w - t * (D / 2);
+      *reinterpret_cast<unsigned int*>(kc + (size_t)(P + t) * D + 2 * i) = *reinterpret_cast<const unsigned int*>(&knew[t][2 * i]);
+      *reinterpret_cast<unsigned int*>(vc + (size_t)(P + t) * D + 2 * i) = *reinterpret_cast<const unsigned int*>(&vnew[t][2 * i]);
+    }
+  }
+  bf16x8 qf[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) qf[j] = *reinterpret_cast<const bf16x8*>(qs + lq * DM_QLD + 32 * j + g4 * 8);
+
+  float m_run = -INFINITY, l_run = 0.f;  // per column: identical in the four lanes of a column
+  float acc[NC][2];
+#pragma unroll
+  for (int h = 0; h < NC; ++h) acc[h][0] = acc[h][1] = 0.f;
+
+  for (; kb < kend; kb += 64) {
+    // ---- S^T = K Q^T: lane (column lq, quad g4) ends with the scores of keys kb + 4 g4 + r ----
+    f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+    const int nk = kb + lq - P;  // >= 0: this lane's key row is new row nk (it exists where nk < Tv)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      u32x4 kv = kreg[j];
+      if (nk >= 0) kv = *reinterpret_cast<const u32x4*>(&knew[min(nk, Tv - 1)][32 * j + g4 * 8]);
+      sacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kv), qf[j], sacc, 0, 0, 0);
+    }
+    const bool live = kb < kend_c;  // this column sees at least the group's first key
+    float sv4[4], mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int key = kb + 4 * g4 + r;
+      sv4[r] = key < kend_c ? sacc[r] * scale : -INFINITY;
+      mx = fmaxf(mx, sv4[r]);
+    }
+    mx = rows_pair(mx, [](float a, float b2) { return fmaxf(a, b2); });
+    mx = halves_pair(mx, [](float a, float b2) { return fmaxf(a, b2); });
+    const float m_new = fmaxf(m_run, mx);  // live: finite; else m_run, possibly still -inf
+    const float alpha = live ? __expf(m_run - m_new) : 1.f;  // a group without a visible key rescales nothing
+    float rs = 0.f;
+    f32x4 pv;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pv[r] = live ? __expf(sv4[r] - m_new) : 0.f;
+      rs += pv[r];
+    }
+    rs = rows_pair(rs, [](float a, float b2) { return a + b2; });
+    rs = halves_pair(rs, [](float a, float b2) { return a + b2; });
+    l_run = l_run * alpha + rs;
+    m_run = m_new;
+    if (lq < NC) {  // a dead column's probabilities are zeros, its rescale 1
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pw[wave][4 * g4 + r][lq] = pv[r];
+    }
+    if (lq < NC && g4 == 0) wm[wave][lq] = alpha;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+      const float a_h = wm[wave][h];
+      acc[h][0] *= a_h;
+      acc[h][1] *= a_h;
+    }
+    // ---- P V: lane = output dims (2 lane, 2 lane + 1) ----
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int key = kb + i;
+      unsigned int vv = vreg[i];
+      if (key >= P) vv = *reinterpret_cast<const unsigned int*>(&vnew[min(key - P, Tv - 1)][2 * lane]);
+      if (key >= kend) vv = 0u;  // clamped rows may hold anything (0 * NaN)
+      const float v0 = bf16lo(vv), v1 = bf16hi(vv);
+#pragma unroll
+      for (int h = 0; h < NC; ++h) {
+        const float ph = pw[wave][i][h];
+        acc[h][0] = fmaf(ph, v0, acc[h][0]);
+        acc[h][1] = fmaf(ph, v1, acc[h][1]);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (kb + 64 < kend) fetch(kb + 64);
+  }
+  // ---- the four waves meet: per-wave (m, l) and P.V through LDS ----
+  if (lq < NC && g4 == 0) {
+    wm[wave][lq] = m_run;
+    wl[wave][lq] = l_run;
+  }
+#pragma unroll
+  for (int h = 0; h < NC; ++h) *reinterpret_cast<f32x2*>(&accs[wave][h][2 * lane]) = f32x2{acc[h][0], acc[h][1]};
+  __syncthreads();
+  float* wbase = ws + attn_ws_group(b, hk, Hkv, T * G, D);
+  const PublishPartial publish;
+  for (int w = tid; w < ncol * (D / 2); w += 256) {
+    const int gq = w / (D / 2), d = 2 * (w - gq * (D / 2));
+    const float M = fmaxf(fmaxf(wm[0][gq], wm[1][gq]), fmaxf(wm[2][gq], wm[3][gq]));
+    float n0 = 0.f, n1 = 0.f, L = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < 4; ++wv) {  // fixed wave order
+      const float e = (wm[wv][gq] > -INFINITY) ? __expf(wm[wv][gq] - M) : 0.f;
+      n0 = fmaf(e, accs[wv][gq][d], n0);
+      n1 = fmaf(e, accs[wv][gq][d + 1], n1);
+      L = fmaf(e, wl[wv][gq], L);
+    }
+    float* wp = wbase + attn_ws_row(gq, split, D);
+    publish(wp + d, n0, n1);
+    if (d == 0) publish(wp + D, M, L);
+  }
+  decode_multi_ticket_merge(wbase, attn_ws_ticket(tickets, b, hk, Hkv), nlive, ncol, G, out + ((size_t)b * T * Hq + (size_t)hk * G) * D,
+                               (size_t)Hq * D, sc, stat_m, stat_l, tid, lane, wave);
+}
+
+// the RoPE / append launch of the composed route: rope_kv_append_kernel's arithmetic (misc.hip) with the row guard of
+// srgpt_decode_attention_multi -- a token whose position lies outside the cache is neither rotated nor appended
+template <typename T>
+__global__ void rope_kv_append_guarded_kernel(T* __restrict__ qkv, T* __restrict__ kcache, T* __restrict__ vcache,
+                                              const int* __restrict__ pos0, const T* __restrict__ cos_tab,
+                                              const T* __restrict__ sin_tab, int Tn, int Hq, int Hkv, int D, int max_pos) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int half = D >> 1;
+  const int p0 = pos0[b];
+  if (p0 < 0 || p0 >= max_pos || p0 + t >= max_pos) return;
+  const int pos = p0 + t;
+  T* row = qkv + ((size_t)b * Tn + t) * (size_t)(Hq + 2 * Hkv) * D;
+  const int nrot = (Hq + Hkv) * half;
+  for (int w = threadIdx.x; w < nrot; w += blockDim.x) {
+    const int h = w / half, i = w - h * half;
+    const float c = to_f(cos_tab[(size_t)pos * half + i]), s = to_f(sin_tab[(size_t)pos * half + i]);
+    T* p = row + (size_t)h * D;
+    const float x1 = to_f(p[i]), x2 = to_f(p[i + half]);
+    const float o1 = rnd<T>(rnd<T>(x1 * c) + rnd<T>(-x2 * s));
+    const float o2 = rnd<T>(rnd<T>(x2 * c) + rnd<T>(x1 * s));
+    if (h < Hq) {
+      p[i] = from_f<T>(o1);
+      p[i + half] = from_f<T>(o2);
+    } else {
+      T* kc = kcache + (((size_t)b * Hkv + (h - Hq)) * max_pos + pos) * D;
+      kc[i] = from_f<T>(o1);
+      kc[i + half] = from_f<T>(o2);
+    }
+  }
+  const T* vsrc = row + (size_t)(Hq + Hkv) * D;
+  for (int w = threadIdx.x; w < Hkv * D; w += blockDim.x) {
+    const int h = w / D, i = w - h * D;
+    vcache[(((size_t)b * Hkv + h) * max_pos + pos) * D + i] = vsrc[w];
+  }
+}
+
 // validated arguments -> the route (attn_route.h) -> its refusal, or the one launch of its template instance
 template <typename T>
 int launch_decode(const void* qkv, void* kc, void* vc, const int* pos, const void* ct, const void* st, void* out,
@@ -692,6 +991,67 @@ extern "C" int srgpt_decode_attention(const void* qkv, void* kcache, void* vcach
                                       int max_pos, int dtype, srgpt_stream_t stream) {
   return srgpt_decode_attention_pf(qkv, kcache, vcache, pos, cos_tab, sin_tab, out, ws, B, Hq, Hkv, D, max_pos, dtype, nullptr, 0,
                                    0, 0, stream);
+}
+
+extern "C" int64_t srgpt_decode_attn_multi_ws_floats(int B, int T, int Hq, int D) {
+  return (int64_t)attn_multi_ws_floats(B, T, Hq, D);  // T * Hq columns' partials + arrival tickets (attn_route.h)
+}
+
+// the tickets of srgpt_decode_attention_multi's workspace (internal: srgpt_llm_lookup_sync_state of model.hip reads them back)
+void* srgpt_decode_attn_multi_sync_words(float* ws, int B, int T, int Hq, int D, size_t* bytes) {
+  if (bytes) *bytes = attn_ws_tickets_reserved(B, Hq) * sizeof(int);
+  return ws + attn_multi_ws_partial_floats(B, T, Hq, D);
+}
+
+extern "C" int srgpt_decode_attention_multi(void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
+                                            const void* sin_tab, void* out, float* ws, int B, int T, int Hq, int Hkv, int D, int max_pos,
+                                            int dtype, srgpt_stream_t stream) {
+  SRGPT_CHECK(qkv && kcache && vcache && pos && cos_tab && sin_tab && out && ws, SRGPT_ERR_ARG,
+              "srgpt_decode_attention_multi: null pointer");
+  SRGPT_CHECK(B > 0 && T > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0 && D > 0 && D <= 256 && D % 2 == 0 && max_pos > 0, SRGPT_ERR_ARG,
+              "srgpt_decode_attention_multi: bad shape B=%d T=%d Hq=%d Hkv=%d D=%d max_pos=%d", B, T, Hq, Hkv, D, max_pos);
+  SRGPT_CHECK(dtype == SRGPT_BF16 || dtype == SRGPT_F32, SRGPT_ERR_ARG, "srgpt_decode_attention_multi: bad dtype %d", dtype);
+  const AttnDecodeMultiRoute r = attn_decode_multi_route(dtype == SRGPT_BF16, B, T, Hq, Hkv, D, max_pos);
+  SRGPT_CHECK(r.status != ATTN_TOO_MANY_COLUMNS, SRGPT_ERR_UNSUPPORTED,
+              "srgpt_decode_attention_multi: T=%d tokens x %d heads per kv head exceed the %d columns of the MFMA kernel (T <= %d)", T, r.G,
+              ATTN_DEC_MULTI_COLS, attn_decode_multi_cap(r.G));
+  hipStream_t s = as_stream(stream);
+  const float scale = 1.0f / sqrtf((float)D);
+  if (r.family == ATTN_DECODE_MULTI_MFMA) {
+    typedef bf16_t Tb;
+    int* tickets = reinterpret_cast<int*>(ws + attn_multi_ws_partial_floats(B, T, Hq, D));
+    SRGPT_TRY((srgpt_switch<2, 4, 8, 16>(r.nc, "columns", [&](auto nc_c) {
+      hipLaunchKernelGGL((decode_mfma_multi_kernel<decltype(nc_c)::value>), dim3(r.blocks), dim3(256), 0, s, (const Tb*)qkv, (Tb*)kcache,
+                         (Tb*)vcache, pos, (const Tb*)cos_tab, (const Tb*)sin_tab, ws, tickets, (Tb*)out, T, r.G, Hq, Hkv, max_pos,
+                         r.nsplit, r.kpb, scale);
+      return (int)SRGPT_OK;
+    })));
+    SRGPT_LAUNCH_CHECK();
+    return SRGPT_OK;
+  }
+  // the parity path: the guarded RoPE / append launch (q rotated in place), then causal attention over the cache with q_pos0 = pos and
+  // the capacity as the bound on the keys
+  if (dtype == SRGPT_BF16)
+    hipLaunchKernelGGL(rope_kv_append_guarded_kernel<bf16_t>, dim3(T, B), dim3(256), 0, s, (bf16_t*)qkv, (bf16_t*)kcache, (bf16_t*)vcache,
+                       pos, (const bf16_t*)cos_tab, (const bf16_t*)sin_tab, T, Hq, Hkv, D, max_pos);
+  else
+    hipLaunchKernelGGL(rope_kv_append_guarded_kernel<float>, dim3(T, B), dim3(256), 0, s, (float*)qkv, (float*)kcache, (float*)vcache, pos,
+                       (const float*)cos_tab, (const float*)sin_tab, T, Hq, Hkv, D, max_pos);
+  SRGPT_LAUNCH_CHECK();
+  // srgpt_attention_append's one-wave kernel, on every dtype: it reads no key behind a row's own position, and the cache rows behind
+  // the live length may hold anything (the flash kernel would multiply them by a zero probability)
+  const int64_t QW = (int64_t)(Hq + 2 * Hkv) * D, hs = (int64_t)max_pos * D;
+  const dim3 grid(T, Hq, B), block(64);
+  if (dtype == SRGPT_BF16)
+    hipLaunchKernelGGL(simple_attn_kernel<bf16_t>, grid, block, 0, s, (const bf16_t*)qkv, (const bf16_t*)kcache, (const bf16_t*)vcache,
+                       (bf16_t*)out, T, max_pos, Hq, Hkv, D, (int64_t)T * QW, QW, (int64_t)D, (int64_t)Hkv * hs, (int64_t)D, hs,
+                       (int64_t)Hkv * hs, (int64_t)D, hs, scale, 1, (const int*)nullptr, pos);
+  else
+    hipLaunchKernelGGL(simple_attn_kernel<float>, grid, block, 0, s, (const float*)qkv, (const float*)kcache, (const float*)vcache,
+                       (float*)out, T, max_pos, Hq, Hkv, D, (int64_t)T * QW, QW, (int64_t)D, (int64_t)Hkv * hs, (int64_t)D, hs,
+                       (int64_t)Hkv * hs, (int64_t)D, hs, scale, 1, (const int*)nullptr, pos);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
 }
 
 // srgpt_attention and srgpt_attention_append for validated arguments: the route (attn_route.h) and the one launch of its kernel.

@@ -13,6 +13,8 @@ enum AttnFamily {
   ATTN_ONE_WAVE,     // simple_attn_kernel<T> (attn.hip): one wave per (query row, head); any dtype / head_dim; fp32 parity path
   ATTN_DECODE_MFMA,  // decode_mfma_kernel<G> (attn.hip): bf16, head_dim 128, fixed key ranges of kpb keys per block
   ATTN_DECODE_VALU,  // decode_split_kernel<T, D, G> (attn.hip): the sequence's keys cut evenly into nsplit chunks
+  ATTN_DECODE_MULTI_MFMA,      // decode_mfma_multi_kernel<NC> (attn.hip): T new tokens per sequence in the B operand's 16 columns
+  ATTN_DECODE_MULTI_COMPOSED,  // srgpt_decode_attention_multi off the matrix pipe: a RoPE / append launch + simple_attn_kernel<T>
 };
 
 // the refusals of srgpt_decode_attention, in the order they win where a call hits several
@@ -21,6 +23,7 @@ enum AttnStatus {
   ATTN_MAX_POS_TOO_LONG,  // the VALU kernel's score buffer (ATTN_DEC_CHUNK_MAX keys per split, ATTN_DEC_SPLIT_MAX splits)
   ATTN_BAD_HEAD_DIM,      // not 16 / 32 / 64 / 128
   ATTN_BAD_GROUP,         // heads / kv_heads not 1 / 2 / 4 / 8
+  ATTN_TOO_MANY_COLUMNS,  // srgpt_decode_attention_multi on the matrix pipe: T * G query heads do not fit the 16 columns
 };
 
 struct AttnPrefillRoute {
@@ -133,5 +136,49 @@ inline AttnDecodeRoute attn_decode_route(bool bf16, int B, int Hq, int Hkv, int 
   if (r.family == ATTN_DECODE_VALU && ceil_div(max_pos, r.nsplit) > ATTN_DEC_CHUNK_MAX) r.status = ATTN_MAX_POS_TOO_LONG;
   else if (D != 16 && D != 32 && D != 64 && D != 128) r.status = ATTN_BAD_HEAD_DIM;
   else if (r.G != 1 && r.G != 2 && r.G != 4 && r.G != 8) r.status = ATTN_BAD_GROUP;
+  return r;
+}
+
+// ------------------------------------------------------------------------------------------------
+// srgpt_decode_attention_multi: T new tokens per sequence (the next token and T - 1 drafted ones) against the cache in ONE launch.
+// The MFMA kernel puts query head g of token t into column c = t * G + g of the B operand, so T * G <= ATTN_DEC_MULTI_COLS; key
+// ranges, splits and keys per block are attn_decode_route's (they depend on max_pos alone).  The workspace is the decode workspace
+// with T * Hq "heads": the T * G columns of a (sequence, kv head) group are adjacent (attn_ws_group with G = cols, attn_ws_row with
+// gq = the column), the tickets -- B * Hq reserved, B * Hkv used -- lie behind the B * T * Hq * ATTN_DEC_SPLIT_MAX partial rows.
+// Everything off the matrix pipe (fp32, other head widths: the parity path) is a composition of existing launches and uses no
+// workspace: nsplit = kpb = blocks = 0.
+// ------------------------------------------------------------------------------------------------
+constexpr int ATTN_DEC_MULTI_COLS = 16;  // columns of the MFMA B operand
+
+struct AttnDecodeMultiRoute {
+  AttnStatus status;  // ATTN_OK or ATTN_TOO_MANY_COLUMNS
+  AttnFamily family;  // ATTN_DECODE_MULTI_MFMA / ATTN_DECODE_MULTI_COMPOSED
+  int G, T;
+  int cols;    // T * G: live columns of the B operand (ATTN_DECODE_MULTI_MFMA)
+  int nc;      // ... rounded up to 2 / 4 / 8 / 16: the kernel's template argument (0: no MFMA instance)
+  int nsplit;  // blocks per (sequence, kv head)
+  int kpb;     // keys per block
+  int blocks;  // blocks of the launch, 256 threads each
+  size_t ws_floats;  // srgpt_decode_attn_multi_ws_floats(B, T, Hq, D)
+};
+
+constexpr size_t attn_multi_ws_partial_floats(int B, int T, int Hq, int D) { return attn_ws_partial_floats(B, T * Hq, D); }
+constexpr size_t attn_multi_ws_floats(int B, int T, int Hq, int D) {
+  return attn_multi_ws_partial_floats(B, T, Hq, D) + attn_ws_tickets_reserved(B, Hq);
+}
+// the most tokens per sequence the MFMA kernel takes at a group size (0: the group is not one of its instances)
+constexpr int attn_decode_multi_cap(int G) { return (G == 1 || G == 2 || G == 4 || G == 8) ? ATTN_DEC_MULTI_COLS / G : 0; }
+
+// srgpt_decode_attention_multi for validated arguments (T >= 1, Hq % Hkv == 0)
+inline AttnDecodeMultiRoute attn_decode_multi_route(bool bf16, int B, int T, int Hq, int Hkv, int D, int max_pos) {
+  using namespace attn_route_detail;
+  AttnDecodeMultiRoute r{ATTN_OK, ATTN_DECODE_MULTI_COMPOSED, Hq / Hkv, T, T * (Hq / Hkv), 0, 0, 0, 0, attn_multi_ws_floats(B, T, Hq, D)};
+  if (!decode_use_mfma(bf16, D, r.G)) return r;
+  r.family = ATTN_DECODE_MULTI_MFMA;
+  r.nsplit = decode_nsplit_mfma(max_pos);
+  r.kpb = ceil_div(ceil_div(max_pos, r.nsplit), ATTN_DEC_MFMA_KEYS) * ATTN_DEC_MFMA_KEYS;  // attn_decode_route's ranges
+  r.blocks = Hkv * r.nsplit * B;
+  if (r.cols > ATTN_DEC_MULTI_COLS) r.status = ATTN_TOO_MANY_COLUMNS;
+  else r.nc = r.cols <= 2 ? 2 : r.cols <= 4 ? 4 : r.cols <= 8 ? 8 : 16;
   return r;
 }

@@ -47,6 +47,21 @@ int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const
                               const void* next_w, int next_n, int next_k, int next_fp8, srgpt_stream_t stream);
 void* srgpt_decode_attn_sync_words(float* ws, int B, int Hq, int D, size_t* bytes);
 
+// the arrival tickets of srgpt_decode_attention_multi's workspace (srgpt_llm_lookup_sync_state reads them back)
+void* srgpt_decode_attn_multi_sync_words(float* ws, int B, int T, int Hq, int D, size_t* bytes);
+
+// ---- lookup.hip, for the lookup step of model.hip: the draft launch with the step's extras (tok / row_ids: the T ids the step
+//      embeds, err: the state's sticky error word; all three NULL for the stand-alone entry) and the accept launch (picks NULL: the
+//      rows' picks are merged from the PICK_SLICES partials pv / pi of argmax_partial_kernel) ----
+int srgpt_lookup_rows_max();   // T = K + 1 rows a step can carry
+int srgpt_lookup_ngram_max();  // ids of the trailing n-gram the matcher compares
+int srgpt_lookup_draft_launch(const int64_t* prompt_ids, int n_prompt, const int64_t* out_ids, const int* step, int max_new, int K,
+                              int max_ngram, int64_t vocab, int64_t* draft, int* n_draft, const int64_t* tok, int64_t* row_ids, int* err,
+                              hipStream_t s);
+int srgpt_lookup_accept_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int T,
+                               int64_t* tok, int64_t* out_ids, int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
+                               hipStream_t s);
+
 // ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping (slices, partials, workspaces: pick.h) ----
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s);

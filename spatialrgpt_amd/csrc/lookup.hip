@@ -1,0 +1,162 @@
+// Prompt-lookup decoding (HF generate(prompt_lookup_num_tokens = K), transformers 4.37 generation/candidate_generator.py
+// PromptLookupCandidateGenerator): the two bookkeeping kernels around the T = K + 1 row decode step of model.hip.
+//  1. lookup_draft_kernel  -- drafts up to K ids by matching the trailing n-gram of the sequence against the sequence itself;
+//  2. lookup_accept_kernel -- compares the drafts with the model's picks, emits the agreed prefix + 1 and advances the state.
+// One block each, nothing allocated, no host round trip: both sit inside the captured step.
+#include "common.h"
+#include "internal.h"
+#include "pick.h"
+
+namespace {
+
+constexpr int LOOKUP_NGRAM_MAX = 8;   // ids of the trailing window the matcher compares
+constexpr int LOOKUP_ROWS_MAX = 16;   // T = K + 1 rows of a step: one wave of the accept block each
+
+// The history is prompt_ids[n_prompt] followed by the first n_gen ids of out_ids.  An id outside [0, vocab) is a sentinel (-200, an
+// id the embedding table does not hold): it never matches and is never drafted.
+struct History {
+  const int64_t* __restrict__ prompt;
+  const int64_t* __restrict__ gen;
+  int n_prompt, len;
+  int64_t vocab;
+  __device__ int64_t at(int i) const { return i < n_prompt ? prompt[i] : gen[i - n_prompt]; }
+  __device__ bool real(int64_t id) const { return id >= 0 && id < vocab; }
+};
+
+// for n = min(max_ngram, len - 1) .. 1: the EARLIEST i with history[i .. i + n) == the last n ids (all real) and a real id behind it
+// (i + n < len: the trailing n-gram itself never counts); the real ids that follow, at most K, are the drafts.  The position is a
+// minimum over the matches: it does not depend on scheduling.  row_ids (optional) = the T = K + 1 ids the step embeds: *tok, the
+// drafts, and behind them the last of these repeated (rows that can never be accepted).
+__global__ __launch_bounds__(1024) void lookup_draft_kernel(const int64_t* __restrict__ prompt_ids, int n_prompt,
+                                                            const int64_t* __restrict__ out_ids, const int* __restrict__ step, int max_new,
+                                                            int K, int max_ngram, int64_t vocab, int64_t* __restrict__ draft,
+                                                            int* __restrict__ n_draft, const int64_t* __restrict__ tok,
+                                                            int64_t* __restrict__ row_ids, int* __restrict__ err) {
+  __shared__ int best;
+  __shared__ int64_t tail[LOOKUP_NGRAM_MAX];
+  const int n_gen = min(max(*step, 0), max_new);
+  const History h{prompt_ids, out_ids, n_prompt, n_prompt + n_gen, vocab};
+  int found = -1, found_n = 0;
+  for (int n = min(max_ngram, h.len - 1); n >= 1 && found < 0; --n) {  // uniform over the block
+    __syncthreads();
+    if (threadIdx.x == 0) best = INT_MAX;
+    if ((int)threadIdx.x < n) tail[threadIdx.x] = h.at(h.len - n + threadIdx.x);
+    __syncthreads();
+    bool tail_real = true;
+    for (int j = 0; j < n; ++j) tail_real = tail_real && h.real(tail[j]);
+    if (tail_real) {
+      int mine = INT_MAX;
+      for (int i = threadIdx.x; i + n < h.len && mine == INT_MAX; i += blockDim.x) {
+        bool eq = h.real(h.at(i + n));
+        for (int j = 0; j < n && eq; ++j) eq = h.at(i + j) == tail[j];
+        if (eq) mine = i;  // ascending scan per thread: its earliest match
+      }
+      if (mine != INT_MAX) atomicMin(&best, mine);
+    }
+    __syncthreads();
+    if (best != INT_MAX) {
+      found = best;
+      found_n = n;
+    }
+  }
+  if (threadIdx.x != 0) return;
+  int nd = 0;
+  if (found >= 0)
+    for (int i = found + found_n; nd < K && i < h.len && h.real(h.at(i)); ++i) draft[nd++] = h.at(i);
+  for (int i = nd; i < K; ++i) draft[i] = -1;
+  *n_draft = nd;
+  if (row_ids) {
+    int64_t t0 = *tok;
+    if (!h.real(t0)) {  // a caller-written id outside the table cannot be embedded (the captured plain step's rule)
+      if (err) atomicOr(err, 1);
+      t0 = 0;
+    }
+    row_ids[0] = t0;
+    for (int i = 0; i < K; ++i) row_ids[1 + i] = i < nd ? draft[i] : (nd > 0 ? draft[nd - 1] : t0);
+  }
+}
+
+// picks (optional): the T rows' picks as srgpt_argmax leaves them; NULL: merged here from the PICK_SLICES partials per row (pick.h).
+// n_acc = the longest prefix with draft[i] == pick[i], i < n_draft (and P + i + 1 < max_pos: a row beyond the cache was not computed);
+// the step emits pick[0 .. n_acc], cut at max_new.
+__global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_kernel(const int64_t* __restrict__ picks, const float* __restrict__ pv,
+                                                                             const int* __restrict__ pi, const int64_t* __restrict__ draft,
+                                                                             const int* __restrict__ n_draft, int T, int64_t* __restrict__ tok,
+                                                                             int64_t* __restrict__ out_ids, int* __restrict__ pos,
+                                                                             int* __restrict__ step, int max_new, int max_pos,
+                                                                             int64_t* __restrict__ tok_emb, int* __restrict__ stats) {
+  __shared__ int64_t picked[LOOKUP_ROWS_MAX];
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  if (row < T) {
+    const int64_t t = picks ? picks[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
+    if (lane == 0) picked[row] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int s = *step;
+  if (s >= max_new) return;  // the run-ahead loop may launch once more than the request needs: nothing is bumped
+  const int P = pos[0];
+  const int nd = min(min(max(*n_draft, 0), T - 1), max(max_pos - 1 - P, 0));
+  int n_acc = 0;
+  while (n_acc < nd && draft[n_acc] == picked[n_acc]) ++n_acc;
+  const int emitted = min(n_acc + 1, max_new - s);
+  for (int i = 0; i < emitted; ++i) out_ids[s + i] = picked[i];
+  *step = s + emitted;
+  pos[0] = P + emitted;
+  tok[0] = picked[emitted - 1];
+  if (tok_emb) tok_emb[0] = -1;  // the residual-stream buffer of the plain step holds no row of this token: a captured step re-embeds
+  if (stats) {
+    stats[0] += 1;
+    stats[1] += nd;
+    stats[2] += n_acc;
+  }
+}
+
+int check_draft_args(int n_prompt, int max_new, int K, int max_ngram, int64_t vocab, const char* fn) {
+  SRGPT_CHECK(n_prompt >= 0 && max_new > 0 && vocab > 0, SRGPT_ERR_ARG, "%s: bad sizes n_prompt=%d max_new=%d vocab=%lld", fn, n_prompt,
+              max_new, (long long)vocab);
+  SRGPT_CHECK(K >= 1 && K < LOOKUP_ROWS_MAX, SRGPT_ERR_ARG, "%s: K=%d drafts outside 1 .. %d", fn, K, LOOKUP_ROWS_MAX - 1);
+  SRGPT_CHECK(max_ngram >= 1 && max_ngram <= LOOKUP_NGRAM_MAX, SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn, max_ngram,
+              LOOKUP_NGRAM_MAX);
+  return SRGPT_OK;
+}
+
+}  // namespace
+
+int srgpt_lookup_rows_max() { return LOOKUP_ROWS_MAX; }
+int srgpt_lookup_ngram_max() { return LOOKUP_NGRAM_MAX; }
+
+int srgpt_lookup_draft_launch(const int64_t* prompt_ids, int n_prompt, const int64_t* out_ids, const int* step, int max_new, int K,
+                              int max_ngram, int64_t vocab, int64_t* draft, int* n_draft, const int64_t* tok, int64_t* row_ids, int* err,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(lookup_draft_kernel, dim3(1), dim3(1024), 0, s, prompt_ids, n_prompt, out_ids, step, max_new, K, max_ngram, vocab,
+                     draft, n_draft, tok, row_ids, err);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+int srgpt_lookup_accept_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int T,
+                               int64_t* tok, int64_t* out_ids, int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(lookup_accept_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, picks, pv, pi, draft, n_draft, T, tok, out_ids, pos,
+                     step, max_new, max_pos, tok_emb, stats);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+extern "C" int srgpt_lookup_draft(const int64_t* prompt_ids, int n_prompt, const int64_t* out_ids, const int* step, int max_new, int K,
+                                  int max_ngram, int64_t vocab, int64_t* draft, int* n_draft, srgpt_stream_t stream) {
+  SRGPT_CHECK((prompt_ids || n_prompt == 0) && out_ids && step && draft && n_draft, SRGPT_ERR_ARG, "srgpt_lookup_draft: null pointer");
+  SRGPT_TRY(check_draft_args(n_prompt, max_new, K, max_ngram, vocab, "srgpt_lookup_draft"));
+  return srgpt_lookup_draft_launch(prompt_ids, n_prompt, out_ids, step, max_new, K, max_ngram, vocab, draft, n_draft, nullptr, nullptr,
+                                   nullptr, as_stream(stream));
+}
+
+extern "C" int srgpt_lookup_accept(const int64_t* picks, const int64_t* draft, const int* n_draft, int T, int64_t* tok, int64_t* out_ids,
+                                   int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats, srgpt_stream_t stream) {
+  SRGPT_CHECK(picks && draft && n_draft && tok && out_ids && pos && step, SRGPT_ERR_ARG, "srgpt_lookup_accept: null pointer");
+  SRGPT_CHECK(T >= 2 && T <= LOOKUP_ROWS_MAX && max_new > 0 && max_pos > 0, SRGPT_ERR_ARG,
+              "srgpt_lookup_accept: bad sizes T=%d (2 .. %d) max_new=%d max_pos=%d", T, LOOKUP_ROWS_MAX, max_new, max_pos);
+  return srgpt_lookup_accept_launch(picks, nullptr, nullptr, draft, n_draft, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb, stats,
+                                    as_stream(stream));
+}

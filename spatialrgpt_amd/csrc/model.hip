@@ -3,6 +3,7 @@
 // FFI crossings instead of ~10^4 (SURVEY 3.1 hot loops); all state lives in caller-owned buffers.
 #include <vector>
 
+#include "attn_route.h"
 #include "common.h"
 #include "gemv_route.h"
 #include "internal.h"
@@ -805,6 +806,132 @@ extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srg
 }
 
 // ================================================================================================
+// the lookup step: the next token and T - 1 drafted ones through ONE pass over the weights (prompt-lookup decoding)
+// ================================================================================================
+namespace {
+
+// srgpt_lookup::ws: T rows of the decode step's buffers, the two row-statistics tables, the multi-token attention's workspace (its
+// tickets zero between launches), the T rows' pick partials and the draft scratch
+struct LookupWs {
+  void *xd, *qkvd, *attnd, *actd;
+  float* rowss;
+  float* dws;
+  float* amax_v;
+  int* amax_i;
+  int64_t *draft, *row_ids;
+  int* n_draft;
+  size_t total;
+};
+LookupWs carve_lookup(const srgpt_llm_weights* w, int T, void* ws) {
+  const size_t es = dtype_size(w->dtype);
+  const size_t qkvw = (size_t)(w->heads + 2 * w->kv_heads) * w->head_dim;
+  Carver c(ws);
+  LookupWs l;
+  l.xd = c.take((size_t)T * w->hidden * es);
+  l.qkvd = c.take((size_t)T * qkvw * es);
+  l.attnd = c.take((size_t)T * w->heads * w->head_dim * es);
+  l.actd = c.take((size_t)T * w->inter * es);
+  l.rowss = reinterpret_cast<float*>(c.take((size_t)2 * T * SRGPT_ROWSS_STRIDE * sizeof(float)));
+  l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_multi_ws_floats(1, T, w->heads, w->head_dim) * 4));
+  l.amax_v = reinterpret_cast<float*>(c.take((size_t)T * PICK_SLICES * 4));
+  l.amax_i = reinterpret_cast<int*>(c.take((size_t)T * PICK_SLICES * 4));
+  l.draft = reinterpret_cast<int64_t*>(c.take((size_t)T * 8));
+  l.row_ids = reinterpret_cast<int64_t*>(c.take((size_t)T * 8));
+  l.n_draft = reinterpret_cast<int*>(c.take(sizeof(int)));
+  l.total = c.off;
+  return l;
+}
+
+}  // namespace
+
+extern "C" int64_t srgpt_llm_lookup_ws_bytes(const srgpt_llm_weights* w, int T) {
+  if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
+  return (int64_t)carve_lookup(w, T, nullptr).total;
+}
+
+// every lookup entry point, on the host before any launch
+static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, const char* fn) {
+  SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
+  SRGPT_TRY(check_llm(w, st));
+  SRGPT_CHECK(st->batch == 1, SRGPT_ERR_ARG, "%s: batch %d (the lookup step takes one sequence)", fn, st->batch);
+  SRGPT_CHECK(lk->T >= 2, SRGPT_ERR_ARG, "%s: T=%d rows (the next token and at least one draft)", fn, lk->T);
+  SRGPT_CHECK(lk->ws && lk->logits && lk->stats && (lk->prompt_ids || lk->n_prompt == 0) && lk->n_prompt >= 0, SRGPT_ERR_ARG,
+              "%s: lookup block has null buffers", fn);
+  SRGPT_CHECK(lk->max_ngram >= 1 && lk->max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn,
+              lk->max_ngram, srgpt_lookup_ngram_max());
+  SRGPT_CHECK(!st->sampling, SRGPT_ERR_UNSUPPORTED, "%s: greedy only (st->sampling is set: speculative sampling is not built)", fn);
+  SRGPT_CHECK(lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows exceed %d", fn, lk->T, srgpt_lookup_rows_max());
+  const AttnDecodeMultiRoute r =
+      attn_decode_multi_route(w->dtype == SRGPT_BF16, 1, lk->T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
+  SRGPT_CHECK(r.status == ATTN_OK, SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows x %d heads per kv head exceed the %d columns of the attention kernel",
+              fn, lk->T, r.G, ATTN_DEC_MULTI_COLS);
+  SRGPT_TRY(pick_check_vocab(w->vocab, fn));
+  LlmFormat fmt;
+  return llm_format(w, fn, &fmt);
+}
+
+// draft -> embed the T rows -> the layers of decode_step_impl with T rows through the same products and the multi-token attention
+// (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> lm_head -> the rows' argmax partials -> accept
+static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
+  LlmFormat fmt;
+  SRGPT_TRY(llm_format(w, "srgpt_llm_lookup_step", &fmt));
+  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
+  const int T = lk->T, QW = (Hq + 2 * Hkv) * D;
+  const size_t es = dtype_size(dt);
+  hipStream_t s = as_stream(stream);
+  const LlmWs d = carve_llm(w, 1, st->ws_tokens, st->ws);  // the state's sticky error word and embedded-token record
+  const LookupWs l = carve_lookup(w, T, lk->ws);
+  const size_t layer_kv = (size_t)Hkv * st->max_pos * D * es;
+  SRGPT_TRY(srgpt_lookup_draft_launch(lk->prompt_ids, lk->n_prompt, st->out_ids, st->step, st->max_new, T - 1, lk->max_ngram,
+                                      (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
+  SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, T, Hd, dt, stream));
+  const bool fp8 = fmt != FMT_DTYPE;
+  const DecodeStep ds{w, T, fp8, gemv_rowss_supported(T, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
+  float* const ss_attn = l.rowss;
+  float* const ss_mlp = l.rowss + (size_t)T * SRGPT_ROWSS_STRIDE;
+  for (int i = 0; i < w->layers; ++i) {
+    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
+    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(ds.gemv(m.qkv, l.xd, w->attn_norm[i], nullptr, l.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
+    SRGPT_TRY(srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, 1, T, Hq, Hkv, D,
+                                           st->max_pos, dt, stream));
+    SRGPT_TRY(ds.gemv(m.o, l.attnd, nullptr, l.xd, l.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
+    SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
+    SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
+  }
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
+                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, T), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
+  SRGPT_LAUNCH_CHECK();
+  return srgpt_lookup_accept_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos, st->step,
+                                    st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
+}
+
+extern "C" int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_step"));
+  return lookup_step_impl(w, st, lk, stream);
+}
+
+// srgpt_llm_decode_sync_state for a state the lookup step ran on: the lookup workspace's own arrival tickets first, then everything
+// the plain check reads (the state's tickets, its sticky error word)
+extern "C" int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk,
+                                           srgpt_stream_t stream) {
+  SRGPT_CHECK(lk && lk->ws && lk->T >= 2 && lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state: bad lookup block");
+  SRGPT_TRY(check_llm(w, st));
+  const LookupWs l = carve_lookup(w, lk->T, lk->ws);
+  size_t bytes = 0;
+  void* sync = srgpt_decode_attn_multi_sync_words(l.dws, 1, lk->T, w->heads, w->head_dim, &bytes);
+  std::vector<int> host(bytes / sizeof(int));
+  SRGPT_HIP_TRY(hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_lookup_sync_state: copy");
+  SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_llm_lookup_sync_state: synchronize");
+  for (size_t i = 0; i < host.size(); ++i)
+    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "lookup step: arrival ticket %zu of %zu is %d between steps (expected 0)", i, host.size(),
+                host[i]);
+  return srgpt_llm_decode_sync_state(w, st, stream);
+}
+
+// ================================================================================================
 // hipGraph of one decode step
 // ================================================================================================
 // the graph entry points' check: somewhere to put the graph, then check_pick
@@ -813,9 +940,9 @@ static int check_graph(const srgpt_llm_weights* w, const srgpt_llm_state* st, Pi
   return check_pick(w, st, p, fn);
 }
 
-static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pick p, srgpt_stream_t stream, srgpt_graph** out) {
-  LlmFormat fmt;  // incomplete fp8 weights never begin a capture (the step below resolves the format again)
-  SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
+// the launches of `step()` on `stream`, captured and instantiated
+template <typename F>
+static int capture_graph(srgpt_stream_t stream, srgpt_graph** out, F&& step) {
   hipStream_t s = as_stream(stream);
   (void)srgpt_device_cus();  // make sure no device query happens inside the capture
   hipGraph_t graph = nullptr;
@@ -823,8 +950,7 @@ static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pi
     srgpt_set_error("hipStreamBeginCapture failed");
     return SRGPT_ERR_STATE;
   }
-  // replays continue from the token the previous step (or srgpt_llm_sample_first) picked: its embedding is already in place
-  const int rc = decode_step_impl(w, st, stream, !advance_embeds(w, st), p);
+  const int rc = step();
   const hipError_t ee = hipStreamEndCapture(s, &graph);
   if (rc != SRGPT_OK) {
     if (graph) (void)hipGraphDestroy(graph);
@@ -843,6 +969,20 @@ static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pi
   }
   *out = new srgpt_graph{graph, exec};
   return SRGPT_OK;
+}
+
+static int graph_create_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, Pick p, srgpt_stream_t stream, srgpt_graph** out) {
+  LlmFormat fmt;  // incomplete fp8 weights never begin a capture (the step below resolves the format again)
+  SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
+  // replays continue from the token the previous step (or srgpt_llm_sample_first) picked: its embedding is already in place
+  return capture_graph(stream, out, [&] { return decode_step_impl(w, st, stream, !advance_embeds(w, st), p); });
+}
+
+extern "C" int srgpt_llm_lookup_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk,
+                                             srgpt_stream_t stream, srgpt_graph** out) {
+  SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create: null out");
+  SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_graph_create"));
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream); });
 }
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,

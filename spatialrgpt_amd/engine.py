@@ -60,6 +60,7 @@ class DecodeState:
         # append has to feed it first.  (ids [B, n] as the loop left them, kept ids per row), or None: nothing is pending
         self.pending = None
         self._pos_stale = False      # the device `pos` ran ahead of host_len (a decode loop that stopped early): see truncate()
+        self.lookup = None           # prompt-lookup decoding: the lookup step's buffers and parameter block (ensure_lookup)
         self._eng = eng
 
     def seq_len(self) -> int:
@@ -127,6 +128,44 @@ class DecodeState:
             L.check(lib.srgpt_llm_decode_graph_create_proc(C.byref(w), C.byref(self.c), self.sampler, self.proc, ops._stream(), C.byref(g)))
             self.graphs[key] = g
         return self.graphs[key]
+
+    def ensure_lookup(self, K: int, max_ngram: int, prompt_ids: Optional[torch.Tensor]):
+        """The lookup step's buffers (first use: workspace -- zeroed, it holds arrival tickets --, the [T, vocab] logits, the stats
+        block, the prompt-id buffer) and parameter block for T = K + 1 rows; a change of T, of max_ngram or a prompt longer than the
+        buffer rebuilds them and drops the captured "lookup" graph.  The prompt ids sit RIGHT-aligned in a buffer of fixed length
+        behind -1 sentinels (which never match and are never drafted): one captured graph serves every prompt."""
+        eng, dev = self._eng, self._eng.device
+        T, n = int(K) + 1, 0 if prompt_ids is None else int(prompt_ids.numel())
+        lk = self.lookup
+        if lk is None or lk["T"] != T or lk["max_ngram"] != max_ngram or n > lk["cap"]:
+            g = self.graphs.pop("lookup", None)
+            if g is not None:
+                L.load().srgpt_graph_destroy(g)
+            nbytes = L.load().srgpt_llm_lookup_ws_bytes(C.byref(eng.w.llm), T)
+            if nbytes < 0:
+                raise RuntimeError("srgpt_llm_lookup_ws_bytes failed")
+            cap = max(self.max_pos, n)
+            lk = dict(T=T, max_ngram=max_ngram, cap=cap, ws=torch.zeros((nbytes,), device=dev, dtype=torch.uint8),
+                      logits=torch.empty((T, eng.w.vocab), device=dev, dtype=torch.float32),
+                      stats=torch.zeros((3,), device=dev, dtype=torch.int32),
+                      prompt=torch.full((cap,), -1, device=dev, dtype=torch.int64), c=L.Lookup())
+            c = lk["c"]
+            c.T, c.max_ngram, c.prompt_ids, c.n_prompt = T, max_ngram, lk["prompt"].data_ptr(), cap
+            c.ws, c.logits, c.stats = lk["ws"].data_ptr(), lk["logits"].data_ptr(), lk["stats"].data_ptr()
+            self.lookup = lk
+        lk["prompt"].fill_(-1)
+        if n:
+            lk["prompt"][lk["cap"] - n:].copy_(prompt_ids.reshape(-1).to(device=dev, dtype=torch.int64))
+        lk["stats"].zero_()
+        return lk
+
+    def ensure_lookup_graph(self):
+        if "lookup" not in self.graphs:
+            g = L.vp()
+            L.check(L.load().srgpt_llm_lookup_graph_create(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup["c"]),
+                                                           ops._stream(), C.byref(g)))
+            self.graphs["lookup"] = g
+        return self.graphs["lookup"]
 
     def __del__(self):
         try:
@@ -581,20 +620,29 @@ class SrgptEngine:
         return st.logits.clone()
 
     def greedy_decode(self, st: DecodeState, max_new_tokens: int, eos_token_id=None, pad_token_id=None,
-                      stopping_criteria=None, sampling: Optional[dict] = None, logits_proc: Optional[dict] = None) -> torch.Tensor:
+                      stopping_criteria=None, sampling: Optional[dict] = None, logits_proc: Optional[dict] = None,
+                      lookup: Optional[dict] = None) -> torch.Tensor:
         """HF generation-loop semantics (new ids only, finished rows padded), device-side steps via hipGraph.
         sampling = None: greedy.  sampling = dict(temperature, top_k, top_p, seed[, sampler]): every step DRAWS its token on the
         device (temperature -> top-k -> top-p -> categorical, sample.hip; `sampler` = L.SAMPLER_FULL for the settings the top-k-64
         sampler does not serve) -- same loop, same graph mechanism, no per-token host work.
         logits_proc = dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_ids): HF's logits processors run on
-        the device in front of every pick (DecodeState.set_logits_proc); None: the steps without them."""
+        the device in front of every pick (DecodeState.set_logits_proc); None: the steps without them.
+        lookup = dict(K, max_ngram, prompt_ids): prompt-lookup decoding (batch 1, greedy, no processors -- the caller checks): every
+        step carries the next token and K ids drafted from prompt_ids + the generated ids (srgpt_llm_lookup_step) and emits 1 .. K + 1
+        tokens; the same ids, stop step and state as the plain loop.  self.last_lookup_stats = what it did."""
+        if lookup is not None and (st.batch != 1 or sampling is not None or logits_proc is not None):
+            raise ValueError("greedy_decode(lookup=...) takes a batch-1 greedy request without logits processors")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             st.set_sampling(sampling)
             st.set_logits_proc(logits_proc)
             try:
-                n_keep, eos, n_rows = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
+                if lookup is not None:
+                    n_keep, eos, n_rows = self._lookup_loop(st, max_new_tokens, eos_token_id, stopping_criteria, lookup)
+                else:
+                    n_keep, eos, n_rows = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
             finally:
                 st.c.sampling = None
                 st.sampler = L.SAMPLER_TOPK64
@@ -602,7 +650,10 @@ class SrgptEngine:
         cur.wait_stream(self.stream)
         # the decode attention hands partials between workgroups inside a launch (arrival tickets): a ticket left non-zero means a
         # launch merged nothing and later steps used stale attention output -- fail loudly, never return such ids
-        L.check(L.load().srgpt_llm_decode_sync_state(C.byref(self.w.llm), C.byref(st.c), ops._stream()))
+        if lookup is not None:  # the lookup workspace's own tickets, then the same check
+            L.check(L.load().srgpt_llm_lookup_sync_state(C.byref(self.w.llm), C.byref(st.c), C.byref(st.lookup["c"]), ops._stream()))
+        else:
+            L.check(L.load().srgpt_llm_decode_sync_state(C.byref(self.w.llm), C.byref(st.c), ops._stream()))
         out = st.out_ids[:, :n_keep].clone()
         # n kept tokens of a row (up to and including its first EOS) are n - 1 cached positions behind the prompt: the last one is
         # PENDING, picked but not cached.  The device position may be ahead (a finished row of a batch keeps stepping; a stopped
@@ -667,6 +718,78 @@ class SrgptEngine:
         if max_new_tokens > 1:
             launch(max_new_tokens - 1)
         return max_new_tokens, eos, [max_new_tokens] * B
+
+    def _lookup_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria, lookup: dict):
+        """The run-ahead loop over lookup steps.  A step emits a number of tokens only the device knows, so every round reads the step
+        counter, the stats block and the ids row behind the previous step through the copy stream -- after the NEXT step went out --
+        and judges every new id in order (EOS ids, then the stopping criteria: the order HF sees them in).  The first stop, or
+        max_new_tokens ids, ends the request; what the device emitted behind that (the rest of an accepted run, the step that ran
+        ahead) lies beyond the kept ids and the live cache rows, exactly like the plain loop's one step ahead.  With nothing that can
+        stop the request the loop still reads the counter: how many steps max_new_tokens ids take is not known in advance."""
+        lib, stream = L.load(), ops._stream()
+        eos = None
+        if eos_token_id is not None:
+            eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
+            eos = eos or None
+        lk = st.ensure_lookup(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"))
+        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), L.SAMPLER_TOPK64, None, stream))
+        graph = st.ensure_lookup_graph() if self.use_graph and max_new_tokens > 1 else None
+
+        def launch():
+            if graph is not None:
+                L.check(lib.srgpt_graph_launch(graph, 1, stream))
+            else:
+                L.check(lib.srgpt_llm_lookup_step(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), stream))
+
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        host_ids = torch.empty((1, max_new_tokens), dtype=torch.int64).pin_memory()
+        host_cnt = torch.empty((4,), dtype=torch.int32).pin_memory()  # the step counter, then the stats block
+        dec = torch.cuda.current_stream(self.device)
+
+        def mark():
+            ev = torch.cuda.Event()
+            ev.record(dec)
+            return ev
+
+        def fetch(ev):
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(ev)
+                host_cnt[:1].copy_(st.step, non_blocking=True)
+                host_cnt[1:].copy_(lk["stats"], non_blocking=True)
+                host_ids[0].copy_(st.out_ids[0, :max_new_tokens], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+            return done
+
+        def finish(n_keep, stop):
+            dec.wait_stream(self._copy_stream)
+            steps, drafted, accepted = (int(v) for v in host_cnt[1:].tolist())
+            self.last_lookup_stats = dict(steps=steps, tokens=n_keep, drafted=drafted, accepted=accepted)
+            return n_keep, eos, [n_keep]
+
+        interactive = stopping_criteria is not None and len(stopping_criteria) > 0
+        ev, judged = mark(), 0  # the first token (srgpt_llm_sample_first) is on the stream
+        for _ in range(max_new_tokens + 1):  # every step emits at least one id
+            ready = fetch(ev)
+            if max_new_tokens > 1:
+                launch()  # run ahead: the next step goes out before the ids behind `ev` are judged
+                ev = mark()
+            ready.synchronize()
+            have = min(int(host_cnt[0]), max_new_tokens)
+            for t in range(judged, have):
+                if eos and int(host_ids[0, t]) in eos:
+                    return finish(t + 1, True)
+                if interactive:
+                    full = host_ids[:, :t + 1]  # HF passes only the generated ids when generate() was fed inputs_embeds
+                    for crit in stopping_criteria:
+                        r = crit(full, None)
+                        if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
+                            return finish(t + 1, True)
+            judged = have
+            if judged >= max_new_tokens:
+                return finish(max_new_tokens, False)
+        raise RuntimeError("lookup decode loop: the device step counter did not advance")
 
     def _decode_loop_run_ahead(self, st: DecodeState, max_new_tokens: int, launch, judge) -> int:
         """A stopping criterion (the demo's KeywordsStoppingCriteria, gradio_web_server_multi.py:195-197; model_vqa.py's conv stop

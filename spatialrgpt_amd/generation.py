@@ -29,7 +29,7 @@ import torch
 # `None` placeholders, the reference's behaviour is the pinned one
 HF_DEFAULTS = dict(do_sample=False, temperature=1.0, top_k=50, top_p=1.0, max_length=20, max_new_tokens=None, min_new_tokens=None,
                    num_beams=1, eos_token_id=None, pad_token_id=None, bos_token_id=None, repetition_penalty=1.0,
-                   no_repeat_ngram_size=0, min_length=0)
+                   no_repeat_ngram_size=0, min_length=0, prompt_lookup_num_tokens=None, max_matching_ngram_size=None)
 
 _GEN_KEYS = tuple(HF_DEFAULTS)
 
@@ -58,6 +58,9 @@ class ResolvedGeneration:
     repetition_penalty: float = 1.0   # RepetitionPenaltyLogitsProcessor; 1.0: off
     no_repeat_ngram_size: int = 0     # NoRepeatNGramLogitsProcessor; 0: off
     min_length: int = 0               # MinLengthLogitsProcessor; 0: off
+    # prompt-lookup decoding (PromptLookupCandidateGenerator): drafts per step (None / 0: off) and the longest n-gram it matches
+    prompt_lookup_num_tokens: Optional[int] = None
+    max_matching_ngram_size: int = 2
 
     @property
     def min_tokens(self) -> int:
@@ -118,7 +121,13 @@ def resolve_generation(stored: Optional[dict], **kwargs) -> ResolvedGeneration:
     elif isinstance(ng, bool) or not isinstance(ng, int) or ng < 0:
         raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {ng}")
     ml = cfg["min_length"]
-    return ResolvedGeneration(repetition_penalty=float(rp), no_repeat_ngram_size=ng, min_length=0 if ml is None else max(int(ml), 0),
+    pl, mg = cfg["prompt_lookup_num_tokens"], cfg["max_matching_ngram_size"]
+    if pl is not None and (isinstance(pl, bool) or not isinstance(pl, int) or pl < 0):
+        raise ValueError(f"`prompt_lookup_num_tokens` has to be a non-negative integer, but is {pl}")
+    if mg is not None and (isinstance(mg, bool) or not isinstance(mg, int) or mg <= 0):
+        raise ValueError(f"`max_matching_ngram_size` has to be a strictly positive integer, but is {mg}")  # HF's own error
+    return ResolvedGeneration(prompt_lookup_num_tokens=pl or None, max_matching_ngram_size=2 if mg is None else mg,
+                              repetition_penalty=float(rp), no_repeat_ngram_size=ng, min_length=0 if ml is None else max(int(ml), 0),
                               do_sample=bool(cfg["do_sample"]), temperature=cfg["temperature"], top_k=cfg["top_k"], top_p=cfg["top_p"],
                               max_new_tokens=max_new, min_new_tokens=None if mn is None else int(mn),
                               num_beams=int(cfg["num_beams"] or 1), eos_token_ids=eos, pad_token_id=None if pad is None else int(pad))

@@ -224,6 +224,9 @@ class LlavaLlamaModel:
         self.prefix_reuse = bool(prefix_reuse)
         self._reuse = None        # PrefixReuse, made by the first request that takes the reuse path
         self.reuse_stages = None  # a dict here receives the reuse path's inputs_embeds and embeddings, as prepare_inputs(stages=)
+        # prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)): what the last request did -- dict(mode "lookup" | "plain",
+        # reason, steps, tokens, drafted, accepted); None before the first request.  The keyword is a hint: the ids never depend on it
+        self.last_lookup = None
 
     @property
     def last_reuse(self):
@@ -538,6 +541,9 @@ class LlavaLlamaModel:
     # ---- llava_llama.py:194-213 ----
     @torch.no_grad()
     def generate(self, input_ids=None, images=None, depths=None, masks=None, attention_mask=None, **generation_kwargs):
+        if input_ids is not None and input_ids.shape[0] == 1:
+            # prompt-lookup decoding drafts from the caller's ids as given (-200 and other sentinels included: they never match)
+            generation_kwargs.setdefault("_prompt_ids", input_ids[0])
         if self.prefix_reuse and input_ids is not None and images is not None and input_ids.shape[0] == 1 \
                 and generation_kwargs.get("past_key_values") is None and not generation_kwargs.get("return_dict_in_generate") \
                 and generation_kwargs.get("inputs_embeds") is None:
@@ -581,7 +587,8 @@ class LlavaLlamaModel:
                               max_length=NOT_GIVEN, min_new_tokens=NOT_GIVEN, use_cache=True, stopping_criteria=None,
                               pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, repetition_penalty=NOT_GIVEN,
                               no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, past_key_values=None,
-                              return_dict_in_generate=False, _state=None, **unused):
+                              return_dict_in_generate=False, _state=None, prompt_lookup_num_tokens=NOT_GIVEN,
+                              max_matching_ngram_size=NOT_GIVEN, _prompt_ids=None, **unused):
         """HF `GenerationMixin.generate(inputs_embeds=...)` as the reference reaches it (llava_llama.py:212): the stored
         generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py).
         `repetition_penalty`, `no_repeat_ngram_size` and `min_length` / `min_new_tokens` run as HF's logits processors on the device
@@ -590,12 +597,18 @@ class LlavaLlamaModel:
         instead of prefilling a prompt; `return_dict_in_generate=True`: the result is a GenerateOutput (.sequences,
         .past_key_values).  Either keyword runs the request on a state of the caller's (batch 1, no beams: _state_for_generate);
         without them this is the pooled-state path, unchanged.  `_state` (the reuse path): a batch-1 state that already holds the
-        prompt; only the decode loop runs."""
+        prompt; only the decode loop runs.
+        `prompt_lookup_num_tokens=K` (+ `max_matching_ngram_size`): HF's prompt-lookup decoding -- a batch-1 greedy request without
+        beams and logits processors runs lookup steps (engine.greedy_decode(lookup=...)): K drafts per step (clamped to what the
+        attention kernel's columns hold), taken from `_prompt_ids` (the caller's input_ids row; none for llm.generate(inputs_embeds=))
+        and the generated ids.  Every other request runs the plain loop, unchanged.  The ids are the same either way;
+        `self.last_lookup` says which happened and why."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
                                min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
                                repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                               min_length=min_length)
+                               min_length=min_length, prompt_lookup_num_tokens=prompt_lookup_num_tokens,
+                               max_matching_ngram_size=max_matching_ngram_size)
         max_new_tokens = g.max_new_tokens
         eos_ids = g.eos_token_ids
         proc = g.logits_processors()  # None: no processor is on -- the request takes the entry points and graphs without them
@@ -633,6 +646,8 @@ class LlavaLlamaModel:
             done = (lambda ids: GenerateOutput(sequences=ids, past_key_values=st)) if return_dict_in_generate else (lambda ids: ids)
         else:
             done = lambda ids: ids  # noqa: E731
+        lookup_k, why = self._lookup_plan(g, _state.batch if _state is not None else inputs_embeds.shape[0], proc)
+        self.last_lookup = dict(mode="plain", reason=why, steps=0, tokens=0, drafted=0, accepted=0)
         if g.num_beams != 1:
             # `--num_beams N` of the eval CLIs; with their default `--temperature 0.2` (do_sample = temperature > 0) this is HF's
             # beam-SAMPLE, with `--temperature 0` beam search proper
@@ -661,8 +676,42 @@ class LlavaLlamaModel:
                 raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True): sampling over a vocabulary above 262144")
             return self._sample_loop(st, max_new_tokens, g.temperature, g.top_p, g.top_k, eos_ids, g.pad_token_id,
                                      stopping_criteria, logits_proc=proc)
+        if lookup_k:
+            from . import _lib as L
+
+            ids = self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
+                                            stopping_criteria=stopping_criteria,
+                                            lookup=dict(K=lookup_k, max_ngram=min(g.max_matching_ngram_size, L.LOOKUP_NGRAM_MAX),
+                                                        prompt_ids=_prompt_ids))
+            self.last_lookup = dict(mode="lookup", reason=why, **self.engine.last_lookup_stats)
+            return done(ids)
         return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
                                               stopping_criteria=stopping_criteria, logits_proc=proc))
+
+    def _lookup_plan(self, g, batch: int, proc):
+        """-> (drafts per step or None, why): prompt-lookup decoding serves a batch-1 greedy request without beams and logits
+        processors; K is clamped to the rows the step's attention route carries at this geometry (csrc/attn_route.h: T * heads /
+        kv_heads <= 16 on the bf16 / head_dim-128 kernel, 16 rows otherwise)"""
+        from . import _lib as L
+
+        K = g.prompt_lookup_num_tokens
+        if not K:
+            return None, "prompt_lookup_num_tokens not set"
+        if batch != 1:
+            return None, f"batch {batch}: the lookup step takes one sequence"
+        if g.num_beams != 1:
+            return None, "num_beams > 1"
+        if g.do_sample and g.temperature is not None and g.temperature > 0:
+            return None, "do_sample: speculative sampling is not built"
+        if proc is not None:
+            return None, "logits processors are on"
+        c = self.engine.cfg
+        G = c.heads // c.kv_heads
+        mfma = self.engine.dtype == torch.bfloat16 and c.head_dim == 128 and G in (1, 2, 4, 8)
+        cap = (L.ATTN_MULTI_COLS // G if mfma else L.LOOKUP_ROWS_MAX) - 1
+        if cap < 1:
+            return None, "no spare attention column at this geometry"
+        return min(int(K), cap), f"K = {min(int(K), cap)} drafts per step" + (f" (asked for {K})" if K > cap else "")
 
     def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
                      logits_proc=None):

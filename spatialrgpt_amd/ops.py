@@ -427,6 +427,51 @@ def decode_attention(qkv, kcache, vcache, pos, cos_tab, sin_tab, Hq, Hkv, D, ws=
     return out
 
 
+def decode_attention_multi_ws(B, T, Hq, D, device):
+    """Workspace of srgpt_decode_attention_multi, zeroed -> (ws, tickets): `tickets` is the int32 view of the arrival tickets behind the
+    B * T * Hq * 64 * (D + 2) partial floats (include/srgpt.h), sharing ws's memory."""
+    n = int(L.load().srgpt_decode_attn_multi_ws_floats(B, T, Hq, D))
+    ws = torch.zeros((n,), device=device, dtype=torch.float32)
+    return ws, ws[B * T * Hq * 64 * (D + 2):].view(torch.int32)
+
+
+def decode_attention_multi(qkv, kcache, vcache, pos, cos_tab, sin_tab, Hq, Hkv, D, ws=None, out=None):
+    """qkv [B, T, (Hq + 2 Hkv) D] raw projections of T new tokens per sequence -> out [B, T, Hq D]; the caches receive rows
+    pos[b] .. pos[b] + T - 1.  Off the bf16 / head_dim-128 route the q heads of `qkv` are rotated in place (include/srgpt.h)."""
+    _dev(qkv, kcache, vcache, pos)
+    B, T = qkv.shape[0], qkv.shape[1]
+    max_pos = kcache.shape[-2]
+    if out is None:
+        out = torch.empty((B, T, Hq * D), device=qkv.device, dtype=qkv.dtype)
+    if ws is None:
+        ws = decode_attention_multi_ws(B, T, Hq, D, qkv.device)[0]
+    else:
+        _dev(ws)
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= L.load().srgpt_decode_attn_multi_ws_floats(B, T, Hq, D)
+    L.check(L.load().srgpt_decode_attention_multi(_p(qkv), _p(kcache), _p(vcache), _p(pos), _p(cos_tab), _p(sin_tab), _p(out), _p(ws),
+                                                  B, T, Hq, Hkv, D, max_pos, dt_code(qkv), _stream()))
+    return out
+
+
+def lookup_draft(prompt_ids, out_ids, step, K: int, max_ngram: int, vocab: int):
+    """srgpt_lookup_draft: prompt_ids int64 [n] (or None), out_ids int64 [max_new], step int32 [1], all on the device ->
+    (draft int64 [K], n_draft int32 [1])"""
+    _dev(out_ids, step)
+    n_prompt = 0 if prompt_ids is None else int(prompt_ids.numel())
+    draft = torch.empty((K,), dtype=torch.int64, device=out_ids.device)
+    n_draft = torch.empty((1,), dtype=torch.int32, device=out_ids.device)
+    L.check(L.load().srgpt_lookup_draft(_p(prompt_ids) if n_prompt else None, n_prompt, _p(out_ids), _p(step), int(out_ids.numel()), K,
+                                        max_ngram, vocab, _p(draft), _p(n_draft), _stream()))
+    return draft, n_draft
+
+
+def lookup_accept(picks, draft, n_draft, tok, out_ids, pos, step, max_pos: int, tok_emb=None, stats=None):
+    """srgpt_lookup_accept on the state's buffers (batch 1), in place"""
+    _dev(picks, draft, n_draft, tok, out_ids, pos, step)
+    L.check(L.load().srgpt_lookup_accept(_p(picks), _p(draft), _p(n_draft), int(picks.numel()), _p(tok), _p(out_ids), _p(pos), _p(step),
+                                         int(out_ids.numel()), max_pos, _p(tok_emb), _p(stats), _stream()))
+
+
 def region_pool(feat, masks, fw: Optional[int] = None):
     """MaskPooling for one image: feat [L,C], masks [M,mh,mw] (float32 or bfloat16) -> [M,C]."""
     _dev(feat, masks)

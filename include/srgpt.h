@@ -388,7 +388,8 @@ typedef struct {
   float top_p_rm;      /* (float)(1.0 - (double)top_p): the removal threshold exactly as HF's comparison sees it */
   uint64_t seed;
   uint64_t counter;
-  int* kept_out;       /* parity hook (device, may be NULL): int[batch][257] = the kept-set size, then its token ids best first */
+  int* kept_out;       /* parity hook (device, may be NULL): int[batch][257] = the kept-set size, then its token ids best first
+                        * (srgpt_sample_rows and the sampled lookup step: int[rows][257]) */
 } srgpt_sampling;
 
 /* Stand-alone draw over fp32 logits [B, V] with the parameter block above (what the decode step runs after its lm_head):
@@ -415,6 +416,17 @@ int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream);
 int64_t srgpt_sample_full_ws_bytes(int B, int V);
 int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
                       srgpt_stream_t stream);
+
+/* Rows are steps (additions under ABI 9).  The two samplers over logits [T, V] whose rows are T SUCCESSIVE STEPS OF ONE SEQUENCE -- what
+ * the sampled lookup step (srgpt_llm_lookup_step_ex) draws behind its T rows.  Row t reads the Philox stream at (counter + t,
+ * sequence 0), the 64-bit sum carried into the high word; slices, selects, tie rules and the kept set are the samplers' above (the
+ * kernels are the same templates, the addressing a compile-time mode).  Contract: tok_out[t] (and the kept set of row t: kept_out
+ * int[T][257], kept_mask [T][ceil(V / 32)]) equals what T successive B = 1 calls of srgpt_sample / srgpt_sample_full on row t alone
+ * return.  Both advance sp->counter by T.  Workspaces: srgpt_sample_ws_bytes(T), srgpt_sample_full_ws_bytes(T, V).  The error word
+ * and srgpt_sample_status(ws, T, stream) behave as for srgpt_sample. */
+int srgpt_sample_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int T, int V, srgpt_stream_t stream);
+int srgpt_sample_full_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int T, int V,
+                           srgpt_stream_t stream);
 
 /* Logits processors (additions under ABI 9): the part of HF's `LogitsProcessorList` that `generate(repetition_penalty=...,
  * no_repeat_ngram_size=..., min_length=... / min_new_tokens=...)` builds, transformers 4.37.2 generation/logits_process.py, on the
@@ -642,7 +654,8 @@ int srgpt_graph_destroy(srgpt_graph* g);
 
 /* ---------------------------------------------------------------------------------------------
  * Prompt-lookup decoding (additions under ABI 9): HF generate(prompt_lookup_num_tokens = K) -- transformers 4.37
- * generation/candidate_generator.py PromptLookupCandidateGenerator + GenerationMixin.assisted_decoding, greedy.  A decode step is
+ * generation/candidate_generator.py PromptLookupCandidateGenerator + GenerationMixin.assisted_decoding, greedy and (the _ex forms at
+ * the end of this section) sampled.  A decode step is
  * weight-bound: its cost barely depends on the rows riding through it.  The lookup step carries T = K + 1 rows of ONE sequence -- the
  * next token and K ids drafted from the sequence itself -- and emits 1 .. T tokens, the same ids the plain greedy loop emits.
  *
@@ -682,7 +695,7 @@ int64_t srgpt_llm_lookup_ws_bytes(const srgpt_llm_weights* w, int T);
  * srgpt_llm_decode_step with T rows through the same products (bf16, W8A16 and the packed fp8 copies) and
  * srgpt_decode_attention_multi -> lm_head into lk->logits -> the rows' argmax -> srgpt_lookup_accept on the state.  It equals that
  * composition of the per-op entries bit for bit, and row 0 -- hence every emitted id -- does not depend on the drafts.
- * st->sampling set, T beyond the attention's columns or 16: SRGPT_ERR_UNSUPPORTED; batch != 1, T < 2, NULL pointers: SRGPT_ERR_ARG;
+ * st->sampling set (the sampled step is the _ex form below), T beyond the attention's columns or 16: SRGPT_ERR_UNSUPPORTED; batch != 1, T < 2, NULL pointers: SRGPT_ERR_ARG;
  * all before any launch.  Cache rows behind the accepted ones hold rejected drafts: they lie beyond st->pos and the next step
  * overwrites them.  A plain captured step may follow (tok_emb = -1 makes it re-embed st->tok).
  * srgpt_llm_lookup_graph_create captures one step; replay with srgpt_graph_launch.
@@ -692,6 +705,25 @@ int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const
 int srgpt_llm_lookup_graph_create(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream,
                                   srgpt_graph** out);
 int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream);
+/* The lookup step under SAMPLING (additions under ABI 9).  Prompt lookup has no draft distribution, so this is HF's assisted decoding
+ * without candidate logits: one token is drawn from the warped distribution behind each of the T rows, the drafts are kept up to the
+ * first draw that differs, and that draw is emitted.  It is exact: row t's draw is used only when rows 0 .. t - 1 agreed, so it is a
+ * draw from the model's distribution behind the emitted prefix.
+ *   With st->sampling == NULL the _ex forms ARE the greedy step above (same launches; sample_ws may be NULL).  With st->sampling set
+ *   the step is the same through lm_head into lk->logits; then the sampler `sampler` (SRGPT_SAMPLER_*) runs in its rows-are-steps mode
+ *   over the T rows -- row t draws at Philox counter sp->counter + t, as srgpt_sample_rows / srgpt_sample_full_rows; its error bits go
+ *   to the state's sticky error word (srgpt_llm_decode_sync_state) -- and the accept takes the draws for picks and does
+ *   sp->counter += the ids emitted (0 when *st->step >= max_new on entry).  Generated id i is therefore drawn at counter c0 + i, as in
+ *   the plain sampled loop; a discarded row's random numbers influenced nothing that was kept.
+ *   sample_ws: srgpt_llm_lookup_sample_ws_bytes(w, T, sampler) bytes = srgpt_sample_ws_bytes(T) / srgpt_sample_full_ws_bytes(T, vocab)
+ *   (-1: T outside 2 .. 16, unknown kind, NULL weights).  Unknown sampler kind, or st->sampling set with sample_ws NULL: SRGPT_ERR_ARG;
+ *   every refusal of srgpt_llm_lookup_step but the greedy-only one applies; all before any launch.  A graph captured with st->sampling
+ *   set replays the sampled step of that kind.  srgpt_llm_lookup_sync_state serves both steps. */
+int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, int T, int sampler);
+int srgpt_llm_lookup_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler, void* sample_ws,
+                             srgpt_stream_t stream);
+int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
+                                     void* sample_ws, srgpt_stream_t stream, srgpt_graph** out);
 
 #ifdef __cplusplus
 }

@@ -61,12 +61,23 @@ int srgpt_lookup_draft_launch(const int64_t* prompt_ids, int n_prompt, const int
 int srgpt_lookup_accept_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int T,
                                int64_t* tok, int64_t* out_ids, int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
                                hipStream_t s);
+// the accept of a SAMPLED step: the rows' picks were drawn by a rows-are-steps sampler launch below -- int64 ids in `drawn` (the
+// top-k-64 sampler, select_drew, while sp->top_k >= 1) or PICK_SLICES partials per row in pv / pi; sp->counter += the ids emitted
+int srgpt_lookup_accept_sampled_launch(srgpt_sampling* sp, int select_drew, const int64_t* drawn, const float* pv, const int* pi,
+                                       const int64_t* draft, const int* n_draft, int T, int64_t* tok, int64_t* out_ids, int* pos, int* step,
+                                       int max_new, int max_pos, int64_t* tok_emb, int* stats, hipStream_t s);
 
 // ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping (slices, partials, workspaces: pick.h) ----
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s);
 int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
                              int V, hipStream_t s);
+// ... and for the sampled lookup step: the same launches over T rows that are successive steps of ONE sequence (row t draws at
+// Philox counter sp->counter + t, sequence 0: pick_draw, pick.h)
+int srgpt_sample_rows_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int T,
+                             int V, hipStream_t s);
+int srgpt_sample_full_rows_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask,
+                                  int T, int V, hipStream_t s);
 
 // ---- logits_proc.hip, for greedy_pick of model.hip: the logits processors' launch (n_dev != NULL: the history length on the device) ----
 int srgpt_logits_proc_launch(float* scores, const srgpt_logits_proc* lp, const int64_t* ids, int ld, int n, const int* n_dev, int B, int V,

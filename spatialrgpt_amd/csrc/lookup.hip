@@ -1,7 +1,8 @@
 // Prompt-lookup decoding (HF generate(prompt_lookup_num_tokens = K), transformers 4.37 generation/candidate_generator.py
 // PromptLookupCandidateGenerator): the two bookkeeping kernels around the T = K + 1 row decode step of model.hip.
 //  1. lookup_draft_kernel  -- drafts up to K ids by matching the trailing n-gram of the sequence against the sequence itself;
-//  2. lookup_accept_kernel -- compares the drafts with the model's picks, emits the agreed prefix + 1 and advances the state.
+//  2. lookup_accept_kernel -- compares the drafts with the model's picks, emits the agreed prefix + 1 and advances the state;
+//     lookup_accept_sampled_kernel -- the same on picks that were DRAWN (a sampled request), and advances the Philox counter.
 // One block each, nothing allocated, no host round trip: both sit inside the captured step.
 #include "common.h"
 #include "internal.h"
@@ -112,6 +113,48 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_kernel(con
   }
 }
 
+// the SAMPLED step: the T rows' picks are DRAWS, row t at Philox counter sp->counter + t (the samplers' rows-are-steps mode).  Where
+// they lie is read from the parameter block, as advance_kernel (model.hip) does: the top-k-64 sampler (select_drew) with top_k >= 1
+// left int64 ids in `drawn` (sample_select_kernel); its Gumbel mode and the full sampler left PICK_SLICES partials per row in pv / pi.
+// Row t's draw is used only when rows 0 .. t - 1 agreed with their drafts: it is a draw from the model's distribution behind the
+// emitted prefix (HF assisted decoding without candidate logits).  The counter advances by the ids emitted, so generated id i was
+// drawn at c0 + i whatever the steps accepted, as in the plain sampled loop; the random numbers of a discarded row influenced nothing
+// that was kept, and the next step's row 0 reads them again.
+__global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_sampled_kernel(
+    srgpt_sampling* __restrict__ sp, int select_drew, const int64_t* __restrict__ drawn, const float* __restrict__ pv,
+    const int* __restrict__ pi, const int64_t* __restrict__ draft, const int* __restrict__ n_draft, int T, int64_t* __restrict__ tok,
+    int64_t* __restrict__ out_ids, int* __restrict__ pos, int* __restrict__ step, int max_new, int max_pos, int64_t* __restrict__ tok_emb,
+    int* __restrict__ stats) {
+  __shared__ int64_t picked[LOOKUP_ROWS_MAX];
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  const bool ids = select_drew && sp->top_k > 0;
+  if (row < T) {
+    const int64_t t = ids ? drawn[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
+    if (lane == 0) picked[row] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  // from here on lookup_accept_kernel's rule, statement for statement (that kernel is pinned as it is), plus the counter
+  const int s = *step;
+  if (s >= max_new) return;  // run-ahead: nothing is bumped, the counter included (emitted = 0)
+  const int P = pos[0];
+  const int nd = min(min(max(*n_draft, 0), T - 1), max(max_pos - 1 - P, 0));
+  int n_acc = 0;
+  while (n_acc < nd && draft[n_acc] == picked[n_acc]) ++n_acc;
+  const int emitted = min(n_acc + 1, max_new - s);
+  for (int i = 0; i < emitted; ++i) out_ids[s + i] = picked[i];
+  *step = s + emitted;
+  pos[0] = P + emitted;
+  tok[0] = picked[emitted - 1];
+  if (tok_emb) tok_emb[0] = -1;
+  if (stats) {
+    stats[0] += 1;
+    stats[1] += nd;
+    stats[2] += n_acc;
+  }
+  sp->counter += (unsigned long long)emitted;
+}
+
 int check_draft_args(int n_prompt, int max_new, int K, int max_ngram, int64_t vocab, const char* fn) {
   SRGPT_CHECK(n_prompt >= 0 && max_new > 0 && vocab > 0, SRGPT_ERR_ARG, "%s: bad sizes n_prompt=%d max_new=%d vocab=%lld", fn, n_prompt,
               max_new, (long long)vocab);
@@ -140,6 +183,15 @@ int srgpt_lookup_accept_launch(const int64_t* picks, const float* pv, const int*
                                hipStream_t s) {
   hipLaunchKernelGGL(lookup_accept_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, picks, pv, pi, draft, n_draft, T, tok, out_ids, pos,
                      step, max_new, max_pos, tok_emb, stats);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+int srgpt_lookup_accept_sampled_launch(srgpt_sampling* sp, int select_drew, const int64_t* drawn, const float* pv, const int* pi,
+                                       const int64_t* draft, const int* n_draft, int T, int64_t* tok, int64_t* out_ids, int* pos, int* step,
+                                       int max_new, int max_pos, int64_t* tok_emb, int* stats, hipStream_t s) {
+  hipLaunchKernelGGL(lookup_accept_sampled_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, sp, select_drew, drawn, pv, pi, draft,
+                     n_draft, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb, stats);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }

@@ -850,7 +850,8 @@ extern "C" int64_t srgpt_llm_lookup_ws_bytes(const srgpt_llm_weights* w, int T) 
 }
 
 // every lookup entry point, on the host before any launch
-static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, const char* fn) {
+static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, const char* fn,
+                        bool greedy_only = true) {
   SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
   SRGPT_TRY(check_llm(w, st));
   SRGPT_CHECK(st->batch == 1, SRGPT_ERR_ARG, "%s: batch %d (the lookup step takes one sequence)", fn, st->batch);
@@ -859,7 +860,8 @@ static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, c
               "%s: lookup block has null buffers", fn);
   SRGPT_CHECK(lk->max_ngram >= 1 && lk->max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn,
               lk->max_ngram, srgpt_lookup_ngram_max());
-  SRGPT_CHECK(!st->sampling, SRGPT_ERR_UNSUPPORTED, "%s: greedy only (st->sampling is set: speculative sampling is not built)", fn);
+  SRGPT_CHECK(!greedy_only || !st->sampling, SRGPT_ERR_UNSUPPORTED,
+              "%s: greedy only (st->sampling is set: the sampled step is srgpt_llm_lookup_step_ex)", fn);
   SRGPT_CHECK(lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows exceed %d", fn, lk->T, srgpt_lookup_rows_max());
   const AttnDecodeMultiRoute r =
       attn_decode_multi_route(w->dtype == SRGPT_BF16, 1, lk->T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
@@ -870,9 +872,30 @@ static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, c
   return llm_format(w, fn, &fmt);
 }
 
+// the _ex entry points' check: a known sampler kind first, then check_lookup without the greedy-only refusal, then (sampling on)
+// somewhere for the sampler to work
+static int check_lookup_ex(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
+                           const void* sample_ws, const char* fn) {
+  SRGPT_CHECK(sampler == SRGPT_SAMPLER_TOPK64 || sampler == SRGPT_SAMPLER_FULL, SRGPT_ERR_ARG, "%s: unknown sampler kind %d", fn, sampler);
+  SRGPT_TRY(check_lookup(w, st, lk, fn, false));
+  SRGPT_CHECK(!st->sampling || sample_ws, SRGPT_ERR_ARG, "%s: st->sampling is set and sample_ws is null", fn);
+  return SRGPT_OK;
+}
+
+extern "C" int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, int T, int sampler) {
+  if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
+  if (sampler == SRGPT_SAMPLER_TOPK64) return srgpt_sample_ws_bytes(T);
+  if (sampler == SRGPT_SAMPLER_FULL) return srgpt_sample_full_ws_bytes(T, w->vocab);
+  return -1;
+}
+
 // draft -> embed the T rows -> the layers of decode_step_impl with T rows through the same products and the multi-token attention
-// (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> lm_head -> the rows' argmax partials -> accept
-static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
+// (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> lm_head -> the rows' picks -> accept.  Greedy (st->sampling == NULL):
+// the rows' argmax partials.  Sampled: the sampler `sampler` in its rows-are-steps mode over the T rows (sample_ws: its own workspace,
+// srgpt_llm_lookup_sample_ws_bytes; error bits go to the state's sticky word), then the accept that advances the Philox counter.  The
+// top-k-64 sampler's drawn ids go to the lookup workspace's row_ids, dead since the rows were embedded.
+static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream,
+                            int sampler = SRGPT_SAMPLER_TOPK64, void* sample_ws = nullptr) {
   LlmFormat fmt;
   SRGPT_TRY(llm_format(w, "srgpt_llm_lookup_step", &fmt));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
@@ -902,6 +925,18 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
   }
   SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
+  if (st->sampling) {
+    if (sampler == SRGPT_SAMPLER_FULL) {
+      const SampleFullWs c = carve_sample_full_ws(sample_ws, T, w->vocab);
+      SRGPT_TRY(srgpt_sample_full_rows_launch(lk->logits, st->sampling, sample_ws, c.pv, c.pi, nullptr, T, w->vocab, s));
+      return srgpt_lookup_accept_sampled_launch(st->sampling, 0, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
+                                                st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
+    }
+    const SampleWs c = carve_sample_ws(sample_ws, T);
+    SRGPT_TRY(srgpt_sample_rows_launch(lk->logits, st->sampling, l.row_ids, sample_ws, c.pv, c.pi, d.err, T, w->vocab, s));
+    return srgpt_lookup_accept_sampled_launch(st->sampling, 1, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
+                                              st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
+  }
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, T), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
   SRGPT_LAUNCH_CHECK();
   return srgpt_lookup_accept_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos, st->step,
@@ -911,6 +946,12 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
 extern "C" int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
   SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_step"));
   return lookup_step_impl(w, st, lk, stream);
+}
+
+extern "C" int srgpt_llm_lookup_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
+                                        void* sample_ws, srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_step_ex"));
+  return lookup_step_impl(w, st, lk, stream, sampler, sample_ws);
 }
 
 // srgpt_llm_decode_sync_state for a state the lookup step ran on: the lookup workspace's own arrival tickets first, then everything
@@ -983,6 +1024,13 @@ extern "C" int srgpt_llm_lookup_graph_create(const srgpt_llm_weights* w, srgpt_l
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create: null out");
   SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_graph_create"));
   return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream); });
+}
+
+extern "C" int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
+                                                void* sample_ws, srgpt_stream_t stream, srgpt_graph** out) {
+  SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_ex: null out");
+  SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_graph_create_ex"));
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream, sampler, sample_ws); });
 }
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,

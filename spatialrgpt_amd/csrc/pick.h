@@ -127,6 +127,17 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
   }
   return c;
 }
+// Where row b of a sampler launch reads that stream.  The rows are the sequences of ONE step (STEPS = false): (counter, b).  Or they
+// are successive steps of ONE sequence (STEPS = true, the lookup step's T rows): (counter + b, 0), the 64-bit sum carried into the
+// high word -- exactly what B = 1 calls at counter, counter + 1, ... read, so a row's draw does not depend on which launch made it
+struct PickDraw {
+  unsigned long long ctr;
+  int seq;
+};
+template <bool STEPS>
+__device__ __forceinline__ PickDraw pick_draw(unsigned long long counter, int b) {
+  return STEPS ? PickDraw{counter + (unsigned long long)b, 0} : PickDraw{counter, b};
+}
 // Gumbel-max: argmax_i (score_i + g_i), g_i = -log(-log(u_i)), u_i in (0, 1), is a draw from softmax(score).  The key of entry i of
 // row b at step counter ctr (srgpt_sampling::counter / ::seed)
 __device__ __forceinline__ float pick_gumbel_key(float score, unsigned long long ctr, unsigned long long seed, int b, int i) {

@@ -25,6 +25,10 @@
 //             indices first (CPU torch.sort's ascending order).
 //   launch 2  sample_full_draw_kernel       grid (128 slices, batch): masked Gumbel-max, per-slice (value, index) for the greedy
 //             merge (advance_kernel / sample_merge_kernel), Philox addressed like the top_k = 0 path.
+// ROWS ARE STEPS (template argument STEPS of the kernels that draw; srgpt_sample_rows / srgpt_sample_full_rows and the sampled lookup
+// step of model.hip): the rows of a launch are T successive steps of ONE sequence, row t reads the stream below at (step counter + t,
+// sequence 0) -- what a one-row call at that counter reads -- and nothing else differs.  The <false> instantiations are the kernels
+// as they were, instruction for instruction.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (step counter, sequence, vocabulary index | ~0): reproducible for
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
 // on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
@@ -95,6 +99,9 @@ __device__ unsigned block_select_kth(const unsigned* __restrict__ keys, int n, i
   return prefix;
 }
 
+// STEPS (every sampler kernel below): how row b addresses the Philox stream (PickDraw, pick.h) -- false: the rows are sequences of one
+// step, true: the rows are successive steps of ONE sequence (the lookup step's T rows).  Nothing else differs between the two.
+template <bool STEPS>
 __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __restrict__ logits, const srgpt_sampling* __restrict__ sp,
                                                              unsigned* __restrict__ cand_key, int* __restrict__ cand_idx,
                                                              float* __restrict__ pv, int* __restrict__ pi, int V) {
@@ -109,11 +116,12 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
   const int topk = min(sp->top_k, SMP_K);
   if (topk <= 0) {
     // ---- Gumbel-max over logits / T: the slice's best key for the greedy merge ----
-    const unsigned long long ctr = sp->counter, seed = sp->seed;
+    const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+    const unsigned long long seed = sp->seed;
     float best = -INFINITY;
     int bi = PICK_NONE;
     for (int i = lo + tid; i < hi; i += 256) {
-      const float v = pick_gumbel_key(row[i] / T, ctr, seed, b, i);
+      const float v = pick_gumbel_key(row[i] / T, dr.ctr, seed, dr.seq, i);
       if (v > best) {
         best = v;
         bi = i;
@@ -160,6 +168,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
   }
 }
 
+template <bool STEPS>
 __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ cand_key,
                                                              const int* __restrict__ cand_idx, int64_t* __restrict__ tok, int nb,
                                                              int* __restrict__ err) {
@@ -242,8 +251,9 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_samplin
     }
     float Z2 = 0.f;
     for (int r = 0; r < n2; ++r) Z2 += __expf(ss[r] - m);
-    const unsigned long long ctr = sp->counter, seed = sp->seed;
-    const U4 rr = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)b, 0xFFFFFFFFu}, (unsigned)seed, (unsigned)(seed >> 32));
+    const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+    const unsigned long long ctr = dr.ctr, seed = sp->seed;
+    const U4 rr = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)dr.seq, 0xFFFFFFFFu}, (unsigned)seed, (unsigned)(seed >> 32));
     const float u = (float)(rr.x >> 8) * (1.0f / 16777216.0f);  // [0, 1)
     const float target = u * Z2;
     int pick = n2 - 1;
@@ -266,7 +276,9 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_samplin
 }
 
 // the stand-alone ops only (the decode step's advance_kernel does both): merge the slices' maxima, one wave per row -- always (the full
-// sampler), or only in Gumbel mode (srgpt_sample: sample_select_kernel drew the token otherwise); every call advances the counter
+// sampler), or only in Gumbel mode (srgpt_sample: sample_select_kernel drew the token otherwise); every call advances the counter --
+// by one step, or (STEPS: the B rows were B steps) by B
+template <bool STEPS>
 __global__ void sample_merge_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int64_t* __restrict__ tok,
                                     int B, int always) {
   if (always || sp->top_k <= 0)
@@ -275,7 +287,7 @@ __global__ void sample_merge_kernel(srgpt_sampling* sp, const float* __restrict_
       if ((threadIdx.x & 63) == 0) tok[b] = t;
     }
   __syncthreads();
-  if (threadIdx.x == 0) sp->counter += 1;
+  if (threadIdx.x == 0) sp->counter += STEPS ? (unsigned long long)B : 1ull;
 }
 
 // ================================================================================================
@@ -368,6 +380,8 @@ __device__ unsigned long long hist_total(FullLds& L, int nbins) {
 // keys of logits / T to the workspace (each thread later re-reads only the entries it wrote) and takes the maximum; top-k is a 3-digit
 // radix select by counts, top-p the same digit walk by fixed-point softmax mass over the top-k survivors, and where the top-p cut runs
 // through a group of equal scores a 2-digit select over their indices says how many of them (lowest indices first) go.
+// (No STEPS mode: the kernel reads no random number, so rows that are steps and rows that are sequences are the same launch.  As a
+// template its <false> instantiation came out with two registers renamed; it stays a plain kernel and keeps its machine code.)
 __global__ __launch_bounds__(SFU_THREADS) void sample_full_threshold_kernel(const float* __restrict__ logits,
                                                                           const srgpt_sampling* __restrict__ sp,
                                                                           unsigned* __restrict__ keys_ws, unsigned* __restrict__ thr,
@@ -490,6 +504,7 @@ __global__ __launch_bounds__(SFU_THREADS) void sample_full_threshold_kernel(cons
 // launch 2: masked Gumbel-max per vocabulary slice, grid (PICK_SLICES, batch) -> the per-slice (value, index) pairs the greedy merge
 // (advance_kernel, or sample_merge_kernel for the stand-alone op) consumes.  Same Philox addressing as the top_k = 0 path of
 // sample_partial_kernel.  kept_mask (optional): bit i % 32 of word i / 32 of the row = entry i kept.
+template <bool STEPS>
 __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ keys_ws,
                                                               const unsigned* __restrict__ thr, float* __restrict__ pv,
                                                               int* __restrict__ pi, unsigned* __restrict__ kept_mask, int V) {
@@ -497,13 +512,14 @@ __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampl
   const PickSlice sl = pick_slice(V);
   const unsigned* keys = keys_ws + (size_t)b * V;
   const unsigned tkey = thr[(size_t)b * 4], tidx = thr[(size_t)b * 4 + 1];
-  const unsigned long long ctr = sp->counter, seed = sp->seed;
+  const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+  const unsigned long long seed = sp->seed;
   float best = -INFINITY;
   int bi = PICK_NONE;
   for (int i = sl.lo + tid; i < sl.hi; i += 256) {
     const unsigned key = keys[i];
     if (key < tkey || (key == tkey && (unsigned)i < tidx)) continue;
-    const float v = pick_gumbel_key(score_of(key), ctr, seed, b, i);
+    const float v = pick_gumbel_key(score_of(key), dr.ctr, seed, dr.seq, i);
     if (v > best) {
       best = v;
       bi = i;
@@ -530,29 +546,53 @@ __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampl
 // the top-k-64 sampler's workspace (SampleWs, pick.h)
 extern "C" int64_t srgpt_sample_ws_bytes(int B) { return B <= 0 ? -1 : carve_sample_ws(nullptr, B).bytes; }
 
-// internal (model.hip): launches 1 and 2; the caller books the token (advance_kernel) and advances the counter
-int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
-                        hipStream_t s) {
+// launches 1 and 2 of the top-k-64 sampler over B rows: sequences, or (STEPS) successive steps of one sequence
+template <bool STEPS>
+static int sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
+                         hipStream_t s) {
   SRGPT_CHECK(logits && sp && tok && ws && pv && pi && err, SRGPT_ERR_ARG, "srgpt_sample: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_UNSUPPORTED, "srgpt_sample: empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
   const SampleWs c = carve_sample_ws(ws, B);
-  hipLaunchKernelGGL(sample_partial_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, logits, sp, c.cand_key, c.cand_idx, pv, pi, V);
-  hipLaunchKernelGGL(sample_select_kernel, dim3(B), dim3(1024), 0, s, sp, c.cand_key, c.cand_idx, tok, PICK_SLICES, err);
+  hipLaunchKernelGGL((sample_partial_kernel<STEPS>), dim3(PICK_SLICES, B), dim3(256), 0, s, logits, sp, c.cand_key, c.cand_idx, pv, pi, V);
+  hipLaunchKernelGGL((sample_select_kernel<STEPS>), dim3(B), dim3(1024), 0, s, sp, c.cand_key, c.cand_idx, tok, PICK_SLICES, err);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
-extern "C" int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
+// internal (model.hip): launches 1 and 2; the caller books the token (advance_kernel) and advances the counter
+int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
+                        hipStream_t s) {
+  return sample_launch<false>(logits, sp, tok, ws, pv, pi, err, B, V, s);
+}
+
+// internal (model.hip, the sampled lookup step): the same over T rows that are successive steps of one sequence -- row t draws at
+// counter + t; the caller accepts (lookup.hip) and advances the counter by what it emitted
+int srgpt_sample_rows_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int T,
+                             int V, hipStream_t s) {
+  return sample_launch<true>(logits, sp, tok, ws, pv, pi, err, T, V, s);
+}
+
+// the stand-alone draw: clear the workspace's error word, launches 1 and 2, the Gumbel-mode merge and the counter
+template <bool STEPS>
+static int sample_op(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
   SRGPT_CHECK(logits && sp && tok_out && ws && B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample: null pointer or empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
   const SampleWs c = carve_sample_ws(ws, B);
   hipStream_t s = as_stream(stream);
   SRGPT_HIP_TRY(hipMemsetAsync(c.err, 0, sizeof(int), s), "srgpt_sample: clearing the error word");
-  SRGPT_TRY(srgpt_sample_launch(logits, sp, tok_out, ws, c.pv, c.pi, c.err, B, V, s));
-  hipLaunchKernelGGL(sample_merge_kernel, dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 0);
+  SRGPT_TRY(sample_launch<STEPS>(logits, sp, tok_out, ws, c.pv, c.pi, c.err, B, V, s));
+  hipLaunchKernelGGL((sample_merge_kernel<STEPS>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 0);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
+}
+
+extern "C" int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
+  return sample_op<false>(logits, sp, tok_out, ws, B, V, stream);
+}
+
+extern "C" int srgpt_sample_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int T, int V, srgpt_stream_t stream) {
+  return sample_op<true>(logits, sp, tok_out, ws, T, V, stream);
 }
 
 // health of the last srgpt_sample call(s) on this workspace (synchronises `stream`): the sticky error word at the tail of ws
@@ -570,28 +610,51 @@ extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream)
 // ---- the full sampler: its workspace is SampleFullWs (pick.h) ----
 extern "C" int64_t srgpt_sample_full_ws_bytes(int B, int V) { return B <= 0 || V <= 0 ? -1 : carve_sample_full_ws(nullptr, B, V).bytes; }
 
-// internal (model.hip): launches 1 and 2 into the caller's slice maxima pv / pi ([B][128]); the caller merges, books the token and
-// advances the counter.  keys_thr = the head (keys and thresholds) of a SampleFullWs.
-int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
-                             int V, hipStream_t s) {
+template <bool STEPS>
+static int sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
+                              int V, hipStream_t s) {
   SRGPT_CHECK(logits && sp && keys_thr && pv && pi, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample_full"));
   const SampleFullWs c = carve_sample_full_ws(keys_thr, B, V);
   hipLaunchKernelGGL(sample_full_threshold_kernel, dim3(B), dim3(SFU_THREADS), 0, s, logits, sp, c.keys, c.thr, V);
-  hipLaunchKernelGGL(sample_full_draw_kernel, dim3(PICK_SLICES, B), dim3(256), 0, s, sp, c.keys, c.thr, pv, pi, kept_mask, V);
+  hipLaunchKernelGGL((sample_full_draw_kernel<STEPS>), dim3(PICK_SLICES, B), dim3(256), 0, s, sp, c.keys, c.thr, pv, pi, kept_mask, V);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+// internal (model.hip): launches 1 and 2 into the caller's slice maxima pv / pi ([B][128]); the caller merges, books the token and
+// advances the counter.  keys_thr = the head (keys and thresholds) of a SampleFullWs.
+int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
+                             int V, hipStream_t s) {
+  return sample_full_launch<false>(logits, sp, keys_thr, pv, pi, kept_mask, B, V, s);
+}
+
+// internal (model.hip, the sampled lookup step): the same over T rows that are successive steps of one sequence
+int srgpt_sample_full_rows_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask,
+                                  int T, int V, hipStream_t s) {
+  return sample_full_launch<true>(logits, sp, keys_thr, pv, pi, kept_mask, T, V, s);
+}
+
+template <bool STEPS>
+static int sample_full_op(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
+                          srgpt_stream_t stream) {
+  SRGPT_CHECK(tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
+  SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
+  const SampleFullWs c = carve_sample_full_ws(ws, B, V);
+  hipStream_t s = as_stream(stream);
+  SRGPT_TRY(sample_full_launch<STEPS>(logits, sp, ws, c.pv, c.pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
+  hipLaunchKernelGGL((sample_merge_kernel<STEPS>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 1);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
                                  srgpt_stream_t stream) {
-  SRGPT_CHECK(tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
-  SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
-  const SampleFullWs c = carve_sample_full_ws(ws, B, V);
-  hipStream_t s = as_stream(stream);
-  SRGPT_TRY(srgpt_sample_full_launch(logits, sp, ws, c.pv, c.pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
-  hipLaunchKernelGGL(sample_merge_kernel, dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 1);
-  SRGPT_LAUNCH_CHECK();
-  return SRGPT_OK;
+  return sample_full_op<false>(logits, sp, tok_out, kept_mask, ws, B, V, stream);
+}
+
+extern "C" int srgpt_sample_full_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int T, int V,
+                                      srgpt_stream_t stream) {
+  return sample_full_op<true>(logits, sp, tok_out, kept_mask, ws, T, V, stream);
 }

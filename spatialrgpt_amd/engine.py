@@ -51,7 +51,8 @@ class DecodeState:
         st.sampling = None
         self.c = st
         self.host_len = [0] * batch  # cached positions per row as known on the host (prefill lengths + steps taken)
-        self.graphs = {}             # "greedy" / "sample" / "sample_full" (+ "+proc") -> captured decode step (the pick kernels differ)
+        self.graphs = {}             # "greedy" / "sample" / "sample_full" (+ "+proc") -> captured decode step (the pick kernels differ);
+        #                              "lookup" (+ "+sample" / "+sample_full") -> captured lookup step
         self.sampler = L.SAMPLER_TOPK64  # which device sampler draws while c.sampling is set (SRGPT_SAMPLER_*)
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
         self.logits_proc: Optional[ops.LogitsProcParams] = None  # device block of the logits processors; ONE address likewise
@@ -132,15 +133,15 @@ class DecodeState:
     def ensure_lookup(self, K: int, max_ngram: int, prompt_ids: Optional[torch.Tensor]):
         """The lookup step's buffers (first use: workspace -- zeroed, it holds arrival tickets --, the [T, vocab] logits, the stats
         block, the prompt-id buffer) and parameter block for T = K + 1 rows; a change of T, of max_ngram or a prompt longer than the
-        buffer rebuilds them and drops the captured "lookup" graph.  The prompt ids sit RIGHT-aligned in a buffer of fixed length
-        behind -1 sentinels (which never match and are never drafted): one captured graph serves every prompt."""
+        buffer rebuilds them and drops the captured lookup graphs.  While the state samples (set_sampling) the block also gets the
+        workspace of that sampler kind for T rows, made on first use (lk["sample_ws"][kind]).  The prompt ids sit RIGHT-aligned in a
+        buffer of fixed length behind -1 sentinels (which never match and are never drafted): one captured graph serves every prompt."""
         eng, dev = self._eng, self._eng.device
         T, n = int(K) + 1, 0 if prompt_ids is None else int(prompt_ids.numel())
         lk = self.lookup
         if lk is None or lk["T"] != T or lk["max_ngram"] != max_ngram or n > lk["cap"]:
-            g = self.graphs.pop("lookup", None)
-            if g is not None:
-                L.load().srgpt_graph_destroy(g)
+            for key in [k for k in self.graphs if k.startswith("lookup")]:
+                L.load().srgpt_graph_destroy(self.graphs.pop(key))
             nbytes = L.load().srgpt_llm_lookup_ws_bytes(C.byref(eng.w.llm), T)
             if nbytes < 0:
                 raise RuntimeError("srgpt_llm_lookup_ws_bytes failed")
@@ -148,7 +149,7 @@ class DecodeState:
             lk = dict(T=T, max_ngram=max_ngram, cap=cap, ws=torch.zeros((nbytes,), device=dev, dtype=torch.uint8),
                       logits=torch.empty((T, eng.w.vocab), device=dev, dtype=torch.float32),
                       stats=torch.zeros((3,), device=dev, dtype=torch.int32),
-                      prompt=torch.full((cap,), -1, device=dev, dtype=torch.int64), c=L.Lookup())
+                      prompt=torch.full((cap,), -1, device=dev, dtype=torch.int64), c=L.Lookup(), sample_ws={})
             c = lk["c"]
             c.T, c.max_ngram, c.prompt_ids, c.n_prompt = T, max_ngram, lk["prompt"].data_ptr(), cap
             c.ws, c.logits, c.stats = lk["ws"].data_ptr(), lk["logits"].data_ptr(), lk["stats"].data_ptr()
@@ -157,15 +158,26 @@ class DecodeState:
         if n:
             lk["prompt"][lk["cap"] - n:].copy_(prompt_ids.reshape(-1).to(device=dev, dtype=torch.int64))
         lk["stats"].zero_()
+        if self.c.sampling and self.sampler not in lk["sample_ws"]:
+            nbytes = L.load().srgpt_llm_lookup_sample_ws_bytes(C.byref(eng.w.llm), T, self.sampler)
+            if nbytes < 0:
+                raise RuntimeError("srgpt_llm_lookup_sample_ws_bytes failed")
+            lk["sample_ws"][self.sampler] = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
         return lk
 
+    def lookup_sample_ws(self):
+        """device pointer of the running request's sampler workspace for the lookup step; None: a greedy request"""
+        return self.lookup["sample_ws"][self.sampler].data_ptr() if self.c.sampling else None
+
     def ensure_lookup_graph(self):
-        if "lookup" not in self.graphs:
+        """the captured lookup step of the running request's pick: greedy, or sampled by the state's sampler kind"""
+        key = "lookup" if not self.c.sampling else ("lookup+sample_full" if self.sampler == L.SAMPLER_FULL else "lookup+sample")
+        if key not in self.graphs:
             g = L.vp()
-            L.check(L.load().srgpt_llm_lookup_graph_create(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup["c"]),
-                                                           ops._stream(), C.byref(g)))
-            self.graphs["lookup"] = g
-        return self.graphs["lookup"]
+            L.check(L.load().srgpt_llm_lookup_graph_create_ex(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup["c"]),
+                                                              self.sampler, self.lookup_sample_ws(), ops._stream(), C.byref(g)))
+            self.graphs[key] = g
+        return self.graphs[key]
 
     def __del__(self):
         try:
@@ -628,11 +640,13 @@ class SrgptEngine:
         sampler does not serve) -- same loop, same graph mechanism, no per-token host work.
         logits_proc = dict(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_ids): HF's logits processors run on
         the device in front of every pick (DecodeState.set_logits_proc); None: the steps without them.
-        lookup = dict(K, max_ngram, prompt_ids): prompt-lookup decoding (batch 1, greedy, no processors -- the caller checks): every
-        step carries the next token and K ids drafted from prompt_ids + the generated ids (srgpt_llm_lookup_step) and emits 1 .. K + 1
-        tokens; the same ids, stop step and state as the plain loop.  self.last_lookup_stats = what it did."""
-        if lookup is not None and (st.batch != 1 or sampling is not None or logits_proc is not None):
-            raise ValueError("greedy_decode(lookup=...) takes a batch-1 greedy request without logits processors")
+        lookup = dict(K, max_ngram, prompt_ids): prompt-lookup decoding (batch 1, no processors -- the caller checks): every step
+        carries the next token and K ids drafted from prompt_ids + the generated ids (srgpt_llm_lookup_step_ex) and emits 1 .. K + 1
+        tokens.  Greedy: the same ids, stop step and state as the plain loop.  With `sampling`: every row's token is DRAWN (row t at
+        Philox counter + t), the drafts are kept up to the first draw that differs -- generated id i is a draw from the model's
+        distribution at counter c0 + i, as in the plain sampled loop.  self.last_lookup_stats = what it did."""
+        if lookup is not None and (st.batch != 1 or logits_proc is not None):
+            raise ValueError("greedy_decode(lookup=...) takes a batch-1 request without logits processors")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
@@ -732,14 +746,15 @@ class SrgptEngine:
             eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
             eos = eos or None
         lk = st.ensure_lookup(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"))
-        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), L.SAMPLER_TOPK64, None, stream))
+        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, None, stream))
         graph = st.ensure_lookup_graph() if self.use_graph and max_new_tokens > 1 else None
 
         def launch():
             if graph is not None:
                 L.check(lib.srgpt_graph_launch(graph, 1, stream))
             else:
-                L.check(lib.srgpt_llm_lookup_step(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), stream))
+                L.check(lib.srgpt_llm_lookup_step_ex(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), st.sampler,
+                                                     st.lookup_sample_ws(), stream))
 
         if getattr(self, "_copy_stream", None) is None:
             self._copy_stream = torch.cuda.Stream(device=self.device)

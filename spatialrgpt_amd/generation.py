@@ -133,6 +133,40 @@ def resolve_generation(stored: Optional[dict], **kwargs) -> ResolvedGeneration:
                               num_beams=int(cfg["num_beams"] or 1), eos_token_ids=eos, pad_token_id=None if pad is None else int(pad))
 
 
+def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sampling: bool, vocab: int, heads: int, kv_heads: int,
+                head_dim: int, bf16: bool):
+    """-> (drafts per step or None, why): does a request with `prompt_lookup_num_tokens=K` run lookup steps?  A pure function of
+    the resolved generation settings `g` and the model's facts (the decision of LlavaLlamaModel._lookup_plan, as reuse.plan_reuse
+    is PrefixReuse's).  Prompt-lookup decoding serves a batch-1 request without beams and logits processors: a greedy one always, a
+    SAMPLED one (do_sample with a temperature > 0) only with the model's `lookup_sampling` switch on and a device sampler for its
+    settings (ops.SamplingParams.sampler: a vocabulary above 262144 has none and stays on the plain loop).  K is clamped to the
+    rows the step's attention route carries at this geometry (csrc/attn_route.h: T * heads / kv_heads <= 16 on the bf16 /
+    head_dim-128 kernel, 16 rows otherwise)."""
+    from . import _lib as L
+    from .ops import SamplingParams
+
+    K = g.prompt_lookup_num_tokens
+    if not K:
+        return None, "prompt_lookup_num_tokens not set"
+    if batch != 1:
+        return None, f"batch {batch}: the lookup step takes one sequence"
+    if g.num_beams != 1:
+        return None, "num_beams > 1"
+    if g.do_sample and g.temperature is not None and g.temperature > 0:
+        if not lookup_sampling:
+            return None, "do_sample: the model's lookup_sampling switch is off"
+        if SamplingParams.sampler(g.temperature, g.top_k, g.top_p, vocab) is None:
+            return None, f"do_sample: no device sampler serves a vocabulary of {vocab}"
+    if processors:
+        return None, "logits processors are on"
+    G = heads // kv_heads
+    mfma = bf16 and head_dim == 128 and G in (1, 2, 4, 8)
+    cap = (L.ATTN_MULTI_COLS // G if mfma else L.LOOKUP_ROWS_MAX) - 1
+    if cap < 1:
+        return None, "no spare attention column at this geometry"
+    return min(int(K), cap), f"K = {min(int(K), cap)} drafts per step" + (f" (asked for {K})" if K > cap else "")
+
+
 def warp_logits(logits: torch.Tensor, temperature=None, top_k=None, top_p=None, min_tokens_to_keep: int = 1) -> torch.Tensor:
     """[B, V] float logits -> warped logits (filtered entries = -inf), HF's order and rules:
     temperature (when not None and != 1) -> top-k (when not None and != 0) -> top-p (when not None and < 1)."""

@@ -184,7 +184,7 @@ class LlavaLlamaModel:
     def __init__(self, config=None, state_dict: Dict[str, torch.Tensor] = None, device="cuda",
                  dtype=torch.bfloat16, tokenizer=None, image_processor=None, rope_positions: int = 0,
                  consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, prefix_reuse: bool = False,
-                 **hf_kwargs):
+                 lookup_sampling: bool = False, **hf_kwargs):
         self.hf_config = None
         if isinstance(config, LlavaConfig):
             # the reference's construction path: config carries the checkpoint location
@@ -227,6 +227,10 @@ class LlavaLlamaModel:
         # prompt-lookup decoding (generate(prompt_lookup_num_tokens=K)): what the last request did -- dict(mode "lookup" | "plain",
         # reason, steps, tokens, drafted, accepted); None before the first request.  The keyword is a hint: the ids never depend on it
         self.last_lookup = None
+        # ... under sampling, opt-in: with the switch on a SAMPLED batch-1 request with the keyword runs sampled lookup steps (every row's
+        # token drawn on the device, the drafts kept up to the first draw that differs: exact).  Off: such a request runs the plain
+        # sampled loop, launch for launch, as it does without the feature
+        self.lookup_sampling = bool(lookup_sampling)
 
     @property
     def last_reuse(self):
@@ -598,11 +602,12 @@ class LlavaLlamaModel:
         .past_key_values).  Either keyword runs the request on a state of the caller's (batch 1, no beams: _state_for_generate);
         without them this is the pooled-state path, unchanged.  `_state` (the reuse path): a batch-1 state that already holds the
         prompt; only the decode loop runs.
-        `prompt_lookup_num_tokens=K` (+ `max_matching_ngram_size`): HF's prompt-lookup decoding -- a batch-1 greedy request without
-        beams and logits processors runs lookup steps (engine.greedy_decode(lookup=...)): K drafts per step (clamped to what the
+        `prompt_lookup_num_tokens=K` (+ `max_matching_ngram_size`): HF's prompt-lookup decoding -- a batch-1 greedy request (with
+        `self.lookup_sampling` on: a sampled one too) without beams and logits processors runs lookup steps (engine.greedy_decode(lookup=...)): K drafts per step (clamped to what the
         attention kernel's columns hold), taken from `_prompt_ids` (the caller's input_ids row; none for llm.generate(inputs_embeds=))
-        and the generated ids.  Every other request runs the plain loop, unchanged.  The ids are the same either way;
-        `self.last_lookup` says which happened and why."""
+        and the generated ids.  Every other request runs the plain loop, unchanged.  A greedy request's ids are the same either
+        way; a sampled one draws every id from the same distribution at the same Philox counter (generation.plan_lookup decides;
+        `self.last_lookup` says which happened and why)."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
                                min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
@@ -667,10 +672,18 @@ class LlavaLlamaModel:
                 # request reproducible, as with HF's torch.multinomial (whose stream itself cannot be matched).  The top-k-64 sampler
                 # serves the demo's settings; the full sampler every other one (top_k > 64, top-p without top-k)
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                sampling = dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed, sampler=kind)
+                if lookup_k:  # the lookup_sampling switch is on (_lookup_plan): the same draws, T rows per step
+                    from . import _lib as L
+
+                    ids = self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
+                                                    stopping_criteria=stopping_criteria, sampling=sampling,
+                                                    lookup=dict(K=lookup_k, max_ngram=min(g.max_matching_ngram_size, L.LOOKUP_NGRAM_MAX),
+                                                                prompt_ids=_prompt_ids))
+                    self.last_lookup = dict(mode="lookup", reason=why, **self.engine.last_lookup_stats)
+                    return done(ids)
                 return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
-                                                      stopping_criteria=stopping_criteria,
-                                                      sampling=dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed,
-                                                                    sampler=kind), logits_proc=proc))
+                                                      stopping_criteria=stopping_criteria, sampling=sampling, logits_proc=proc))
             # a vocabulary above 262144 (no config of the reference's): warpers + draw as torch ops per token
             if on_handle and _state is None:
                 raise NotImplementedError("generate(past_key_values=... / return_dict_in_generate=True): sampling over a vocabulary above 262144")
@@ -689,29 +702,12 @@ class LlavaLlamaModel:
                                               stopping_criteria=stopping_criteria, logits_proc=proc))
 
     def _lookup_plan(self, g, batch: int, proc):
-        """-> (drafts per step or None, why): prompt-lookup decoding serves a batch-1 greedy request without beams and logits
-        processors; K is clamped to the rows the step's attention route carries at this geometry (csrc/attn_route.h: T * heads /
-        kv_heads <= 16 on the bf16 / head_dim-128 kernel, 16 rows otherwise)"""
-        from . import _lib as L
+        """-> (drafts per step or None, why): generation.plan_lookup on this model's switch and geometry"""
+        from .generation import plan_lookup
 
-        K = g.prompt_lookup_num_tokens
-        if not K:
-            return None, "prompt_lookup_num_tokens not set"
-        if batch != 1:
-            return None, f"batch {batch}: the lookup step takes one sequence"
-        if g.num_beams != 1:
-            return None, "num_beams > 1"
-        if g.do_sample and g.temperature is not None and g.temperature > 0:
-            return None, "do_sample: speculative sampling is not built"
-        if proc is not None:
-            return None, "logits processors are on"
         c = self.engine.cfg
-        G = c.heads // c.kv_heads
-        mfma = self.engine.dtype == torch.bfloat16 and c.head_dim == 128 and G in (1, 2, 4, 8)
-        cap = (L.ATTN_MULTI_COLS // G if mfma else L.LOOKUP_ROWS_MAX) - 1
-        if cap < 1:
-            return None, "no spare attention column at this geometry"
-        return min(int(K), cap), f"K = {min(int(K), cap)} drafts per step" + (f" (asked for {K})" if K > cap else "")
+        return plan_lookup(g, batch, proc is not None, self.lookup_sampling, self.engine.w.vocab, c.heads, c.kv_heads, c.head_dim,
+                           self.engine.dtype == torch.bfloat16)
 
     def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
                      logits_proc=None):

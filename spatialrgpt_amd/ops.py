@@ -689,24 +689,49 @@ class SamplingParams:
         return self.buf.data_ptr()
 
 
-def sample(logits: torch.Tensor, params: SamplingParams, check: bool = False) -> torch.Tensor:
-    """one draw per row of fp32 logits [B, V] with the device-side sampler; advances params' counter.  -> int64 [B]"""
+def _sample(entry: str, logits: torch.Tensor, params: SamplingParams, check: bool, out: Optional[torch.Tensor]) -> torch.Tensor:
     _dev(logits)
     if logits.dtype != torch.float32 or logits.ndim != 2:
         raise ValueError("sample: logits must be fp32 [B, V]")
     B, V = logits.shape
     lib = L.load()
     ws = torch.empty((lib.srgpt_sample_ws_bytes(B),), dtype=torch.uint8, device=logits.device)
-    out = torch.empty((B,), dtype=torch.int64, device=logits.device)
-    L.check(lib.srgpt_sample(_p(_c(logits)), params.ptr(), _p(out), _p(ws), B, V, _stream()))
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    else:
+        _dev(out)
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == B
+    L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(ws), B, V, _stream()))
     if check:  # settings the device sampler does not serve raise instead of drawing from a clamped distribution
         L.check(lib.srgpt_sample_status(_p(ws), B, _stream()))
     return out
 
 
+def sample(logits: torch.Tensor, params: SamplingParams, check: bool = False) -> torch.Tensor:
+    """one draw per row of fp32 logits [B, V] with the device-side sampler; advances params' counter.  -> int64 [B]"""
+    return _sample("srgpt_sample", logits, params, check, None)
+
+
+def sample_rows(logits: torch.Tensor, params: SamplingParams, check: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """srgpt_sample_rows: the rows of fp32 logits [T, V] are T successive steps of ONE sequence -- row t draws at params' counter + t,
+    what T calls of `sample` on the rows one by one return; advances the counter by T.  `out` (int64 [T], optional): where the ids go.
+    A kept-set hook (SamplingParams(keep_kept_sets=True)) must hold T rows.  -> int64 [T]"""
+    return _sample("srgpt_sample_rows", logits, params, check, out)
+
+
 def sample_full(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = False):
     """one draw per row of fp32 logits [B, V] with the full device sampler (every temperature / top_k / top_p); advances params'
     counter.  -> int64 [B], or (ids, kept bool [B, V]) with kept_mask=True (the kept set, the parity hook)."""
+    return _sample_full("srgpt_sample_full", logits, params, kept_mask, None)
+
+
+def sample_full_rows(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = False, out: Optional[torch.Tensor] = None):
+    """srgpt_sample_full_rows: `sample_full` over rows that are T successive steps of ONE sequence (row t draws at params' counter + t;
+    the counter advances by T).  `out` (int64 [T], optional): where the ids go.  -> int64 [T], or (ids, kept bool [T, V])"""
+    return _sample_full("srgpt_sample_full_rows", logits, params, kept_mask, out)
+
+
+def _sample_full(entry: str, logits: torch.Tensor, params: SamplingParams, kept_mask: bool, out: Optional[torch.Tensor]):
     _dev(logits)
     if logits.dtype != torch.float32 or logits.ndim != 2:
         raise ValueError("sample_full: logits must be fp32 [B, V]")
@@ -716,10 +741,14 @@ def sample_full(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = 
     if nbytes < 0:
         raise ValueError("sample_full: empty shape")
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=logits.device)
-    out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    if out is None:
+        out = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    else:
+        _dev(out)
+        assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == B
     nw = (V + 31) // 32
     mask = torch.empty((B, nw), dtype=torch.int32, device=logits.device) if kept_mask else None
-    L.check(lib.srgpt_sample_full(_p(_c(logits)), params.ptr(), _p(out), _p(mask), _p(ws), B, V, _stream()))
+    L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(mask), _p(ws), B, V, _stream()))
     if not kept_mask:
         return out
     bits = torch.arange(32, device=logits.device, dtype=torch.int32)

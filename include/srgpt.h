@@ -725,6 +725,64 @@ int srgpt_llm_lookup_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, co
 int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
                                      void* sample_ws, srgpt_stream_t stream, srgpt_graph** out);
 
+/* The lookup step for a BATCH (additions under ABI 9): B = st->batch sequences of T = K + 1 rows each ride through one pass over the
+ * weights.  Every sequence is drafted from its OWN history, verified in the shared step and advanced by its OWN number of accepted
+ * drafts; greedy only.  Row r = b * T + t of every step buffer is token t of sequence b, the [B, T, ...] layout of
+ * srgpt_decode_attention_multi.  B * T <= 16: the rows one pass of the decode products' MFMA kernel carries.  The entry points above
+ * are unchanged and keep refusing a state of more than one sequence.
+ *
+ * srgpt_lookup_draft_batch (B blocks): srgpt_lookup_draft per sequence.  The history of sequence b is prompt_ids[b, 0 .. n_prompt[b])
+ *   (int64 rows of stride ld_prompt, every row's ids packed to the front; n_prompt: DEVICE int [B], clamped to 0 .. ld_prompt;
+ *   prompt_ids may be NULL when ld_prompt = 0) followed by the first steps[b] ids of out_ids[b, :] (out_ids int64 [B, max_new], steps:
+ *   device int [B], each clamped to 0 .. max_new).  draft int64 [B, K], n_draft int [B].  B 1 .. 16, K and max_ngram as above.
+ * srgpt_lookup_accept_batch (one block): picks int64 [B * T].  Sequence b takes srgpt_lookup_accept's rule on its own steps[b],
+ *   pos[b], tok[b], tok_emb[b] (optional), out_ids[b, :], draft[b, :] (row stride T - 1), n_draft[b] and picks[b * T ..], the clamp
+ *   pos[b] + i + 1 < max_pos included.  A sequence with steps[b] >= max_new is FROZEN: nothing of it is written or counted (it
+ *   accepted more than the others and waits for them).  Then *step = min over b of steps[b], the number of columns of out_ids every
+ *   sequence has filled -- the meaning *st->step has everywhere else -- and stats[3] (optional) += {1, the drafts, the accepted
+ *   drafts} summed over the sequences that advanced ({0, 0, 0} when every one is frozen).  B * T <= 16, else SRGPT_ERR_UNSUPPORTED.
+ * --------------------------------------------------------------------------------------------- */
+int srgpt_lookup_draft_batch(const int64_t* prompt_ids, int ld_prompt, const int* n_prompt, const int64_t* out_ids, const int* steps,
+                             int B, int max_new, int K, int max_ngram, int64_t vocab, int64_t* draft, int* n_draft,
+                             srgpt_stream_t stream);
+int srgpt_lookup_accept_batch(const int64_t* picks, const int64_t* draft, const int* n_draft, int B, int T, int64_t* tok,
+                              int64_t* out_ids, int* pos, int* steps, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
+                              srgpt_stream_t stream);
+
+/* The batched lookup step's parameter block (HOST struct of device pointers; a captured graph keeps the addresses). */
+typedef struct {
+  int T;                     /* rows per sequence = K + 1 >= 2; st->batch * T <= 16, and T * heads / kv_heads <= 16 on the bf16 matrix-pipe attention */
+  int max_ngram;             /* longest trailing n-gram the matcher compares, 1 .. 8 */
+  const int64_t* prompt_ids; /* int64 [B, ld_prompt]: every sequence's ids (sentinels included) packed to the front of its row; NULL when ld_prompt = 0 */
+  int ld_prompt;             /* row stride of prompt_ids, >= 0 */
+  const int* n_prompt;       /* device int [B]: ids in every row */
+  int* steps;                /* device int [B]: ids sequence b has emitted; the caller sets every entry to 1 behind srgpt_llm_sample_first */
+  void* ws;                  /* srgpt_llm_lookup_batch_ws_bytes(w, B, T) bytes, ZEROED once when allocated (it holds arrival tickets) */
+  float* logits;             /* [B * T, vocab] fp32: the logits behind each row */
+  int* stats;                /* device int[3]: steps, drafted, accepted -- incremented by every step that advanced a sequence */
+} srgpt_lookup_batch;
+
+/* workspace bytes of a batched lookup step: B * T rows of what srgpt_llm_lookup_ws_bytes counts per row, the workspace of
+ * srgpt_decode_attention_multi for (B, T), and [B, T] draft scratch.  -1: NULL weights, B < 1, T < 2 or B * T > 16. */
+int64_t srgpt_llm_lookup_batch_ws_bytes(const srgpt_llm_weights* w, int B, int T);
+/* One batched lookup step of a GREEDY state, entirely device-side: srgpt_lookup_draft_batch over (lk->prompt_ids, st->out_ids,
+ * lk->steps) -> the B * T rows' embeddings (per sequence: st->tok[b], its drafts, then the last id repeated) -> the layers of
+ * srgpt_llm_decode_step with B * T rows through the same products and srgpt_decode_attention_multi with B sequences at st->pos[b] ->
+ * lm_head into lk->logits -> the rows' argmax -> srgpt_lookup_accept_batch on the state and lk->steps (*st->step = min steps[b]).
+ * It equals that composition of the per-op entries bit for bit; with one sequence it leaves the bits srgpt_llm_lookup_step leaves.
+ * st->sampling set, st->batch * T > 16 (the message names both), T beyond the attention's columns: SRGPT_ERR_UNSUPPORTED; T < 2, NULL
+ * pointers, ld_prompt < 0: SRGPT_ERR_ARG; all before any launch.  A sequence the caller has finished keeps stepping until its
+ * steps[b] reaches st->max_new, like a finished row of the plain batched loop; st->pos of sequences that ran ahead is the caller's
+ * to roll back.  A plain captured step may follow.
+ * srgpt_llm_lookup_graph_create_batch captures one step; replay with srgpt_graph_launch.
+ * srgpt_llm_lookup_sync_state_batch: srgpt_llm_lookup_sync_state for such a state -- the (B, T) lookup workspace's arrival tickets
+ * (SRGPT_ERR_STATE), then srgpt_llm_decode_sync_state (the state's tickets and its sticky error word). */
+int srgpt_llm_lookup_step_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, srgpt_stream_t stream);
+int srgpt_llm_lookup_graph_create_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                        srgpt_stream_t stream, srgpt_graph** out);
+int srgpt_llm_lookup_sync_state_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                      srgpt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

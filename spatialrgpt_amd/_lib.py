@@ -76,6 +76,12 @@ class Lookup(C.Structure):
     _fields_ = [("T", i32), ("max_ngram", i32), ("prompt_ids", vp), ("n_prompt", i32), ("ws", vp), ("logits", vp), ("stats", vp)]
 
 
+class LookupBatch(C.Structure):
+    """srgpt_lookup_batch (include/srgpt.h): the batched lookup step's parameter block; a HOST struct of device pointers."""
+    _fields_ = [("T", i32), ("max_ngram", i32), ("prompt_ids", vp), ("ld_prompt", i32), ("n_prompt", vp), ("steps", vp), ("ws", vp),
+                ("logits", vp), ("stats", vp)]
+
+
 LOOKUP_ROWS_MAX = 16               # lookup.hip LOOKUP_ROWS_MAX: T = K + 1 rows of a lookup step
 LOOKUP_NGRAM_MAX = 8               # lookup.hip LOOKUP_NGRAM_MAX
 ATTN_MULTI_COLS = 16               # attn_route.h ATTN_DEC_MULTI_COLS: T * heads / kv_heads on the bf16 matrix-pipe attention
@@ -178,6 +184,12 @@ _SIGNATURES = {
     "srgpt_llm_lookup_sample_ws_bytes": (i64, [C.POINTER(LlmWeights), i32, i32]),
     "srgpt_llm_lookup_step_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(Lookup), i32, vp, vp]),
     "srgpt_llm_lookup_graph_create_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(Lookup), i32, vp, vp, C.POINTER(vp)]),
+    "srgpt_lookup_draft_batch": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp]),
+    "srgpt_lookup_accept_batch": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "srgpt_llm_lookup_batch_ws_bytes": (i64, [C.POINTER(LlmWeights), i32, i32]),
+    "srgpt_llm_lookup_step_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp]),
+    "srgpt_llm_lookup_graph_create_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp, C.POINTER(vp)]),
+    "srgpt_llm_lookup_sync_state_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -251,7 +251,7 @@ def load_model(model_path, device="cuda", dtype=torch.bfloat16, llm_weight_forma
 
 def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", dtype=torch.bfloat16, prefix_reuse=False, lookup_sampling=False,
-                          **kwargs):
+                          lookup_batch=False, **kwargs):
     if load_4bit:
         raise NotImplementedError("bitsandbytes 4-bit loading is out of scope (builder.py:40-60)")
     # load_8bit (bitsandbytes int8 in the reference, builder.py:51-52) maps to the engine's 8-bit option: weight-only OCP
@@ -264,6 +264,7 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
                                                    interpolate_mode=kwargs.pop("interpolate_mode", "linear"))
     model.prefix_reuse = bool(prefix_reuse)  # opt-in: unchanged callers continue the last request's cache (spatialrgpt_amd/reuse.py)
     model.lookup_sampling = bool(lookup_sampling)  # opt-in: sampled requests with prompt_lookup_num_tokens run sampled lookup steps
+    model.lookup_batch = bool(lookup_batch)  # opt-in: greedy batches with prompt_lookup_num_tokens run batched lookup steps
     lc = _read_json(os.path.join(model_path, "llm", "config.json"))
     context_len = _read_json(os.path.join(model_path, "config.json")).get("max_sequence_length", 2048) \
         if "max_sequence_length" in lc else 2048  # builder.py:207-211

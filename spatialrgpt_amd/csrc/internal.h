@@ -66,6 +66,14 @@ int srgpt_lookup_accept_launch(const int64_t* picks, const float* pv, const int*
 int srgpt_lookup_accept_sampled_launch(srgpt_sampling* sp, int select_drew, const int64_t* drawn, const float* pv, const int* pi,
                                        const int64_t* draft, const int* n_draft, int T, int64_t* tok, int64_t* out_ids, int* pos, int* step,
                                        int max_new, int max_pos, int64_t* tok_emb, int* stats, hipStream_t s);
+// the batched step's pair: B sequences of T = K + 1 rows, every sequence over its own history (prompt_ids [B, ld_prompt], n_prompt [B],
+// steps [B] on the device); draft [B, K], n_draft [B], row_ids [B, T]; the accept also leaves *step = min over b of steps[b]
+int srgpt_lookup_draft_batch_launch(const int64_t* prompt_ids, int ld_prompt, const int* n_prompt, const int64_t* out_ids, const int* steps,
+                                    int B, int max_new, int K, int max_ngram, int64_t vocab, int64_t* draft, int* n_draft,
+                                    const int64_t* tok, int64_t* row_ids, int* err, hipStream_t s);
+int srgpt_lookup_accept_batch_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int B,
+                                     int T, int64_t* tok, int64_t* out_ids, int* pos, int* steps, int* step, int max_new, int max_pos,
+                                     int64_t* tok_emb, int* stats, hipStream_t s);
 
 // ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping (slices, partials, workspaces: pick.h) ----
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,

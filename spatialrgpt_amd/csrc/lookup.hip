@@ -155,6 +155,125 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_sampled_ke
   sp->counter += (unsigned long long)emitted;
 }
 
+// ---- the batched step: B sequences, T rows each (row r = b * T + t of every step buffer is token t of sequence b) ----
+// lookup_draft_kernel for sequence b = blockIdx.x, statement for statement, over that row's own history: prompt_ids[b, 0 .. n_prompt[b])
+// (row stride ld_prompt; a device count outside 0 .. ld_prompt is clamped, so no id outside the row is read) followed by the first
+// min(max(steps[b], 0), max_new) ids of out_ids[b, :].  draft [B, K], n_draft [B], row_ids [B, K + 1] (optional, with tok [B]).
+__global__ __launch_bounds__(1024) void lookup_draft_batch_kernel(const int64_t* __restrict__ prompt_ids, int ld_prompt,
+                                                                  const int* __restrict__ n_prompt, const int64_t* __restrict__ out_ids,
+                                                                  const int* __restrict__ steps, int max_new, int K, int max_ngram,
+                                                                  int64_t vocab, int64_t* __restrict__ draft, int* __restrict__ n_draft,
+                                                                  const int64_t* __restrict__ tok, int64_t* __restrict__ row_ids,
+                                                                  int* __restrict__ err) {
+  __shared__ int best;
+  __shared__ int64_t tail[LOOKUP_NGRAM_MAX];
+  const int b = blockIdx.x;
+  const int np = min(max(n_prompt[b], 0), ld_prompt);
+  const int n_gen = min(max(steps[b], 0), max_new);
+  const History h{prompt_ids + (size_t)b * ld_prompt, out_ids + (size_t)b * max_new, np, np + n_gen, vocab};
+  draft += (size_t)b * K;
+  int found = -1, found_n = 0;
+  for (int n = min(max_ngram, h.len - 1); n >= 1 && found < 0; --n) {  // uniform over the block
+    __syncthreads();
+    if (threadIdx.x == 0) best = INT_MAX;
+    if ((int)threadIdx.x < n) tail[threadIdx.x] = h.at(h.len - n + threadIdx.x);
+    __syncthreads();
+    bool tail_real = true;
+    for (int j = 0; j < n; ++j) tail_real = tail_real && h.real(tail[j]);
+    if (tail_real) {
+      int mine = INT_MAX;
+      for (int i = threadIdx.x; i + n < h.len && mine == INT_MAX; i += blockDim.x) {
+        bool eq = h.real(h.at(i + n));
+        for (int j = 0; j < n && eq; ++j) eq = h.at(i + j) == tail[j];
+        if (eq) mine = i;  // ascending scan per thread: its earliest match
+      }
+      if (mine != INT_MAX) atomicMin(&best, mine);
+    }
+    __syncthreads();
+    if (best != INT_MAX) {
+      found = best;
+      found_n = n;
+    }
+  }
+  if (threadIdx.x != 0) return;
+  int nd = 0;
+  if (found >= 0)
+    for (int i = found + found_n; nd < K && i < h.len && h.real(h.at(i)); ++i) draft[nd++] = h.at(i);
+  for (int i = nd; i < K; ++i) draft[i] = -1;
+  n_draft[b] = nd;
+  if (row_ids) {
+    row_ids += (size_t)b * (K + 1);
+    int64_t t0 = tok[b];
+    if (!h.real(t0)) {  // a caller-written id outside the table cannot be embedded (the captured plain step's rule)
+      if (err) atomicOr(err, 1);
+      t0 = 0;
+    }
+    row_ids[0] = t0;
+    for (int i = 0; i < K; ++i) row_ids[1 + i] = i < nd ? draft[i] : (nd > 0 ? draft[nd - 1] : t0);
+  }
+}
+
+// One wave per row merges the B * T rows' picks (B * T <= LOOKUP_ROWS_MAX: lookup_accept_kernel's block); then thread b applies that
+// kernel's rule to sequence b: its own steps[b], pos[b], tok[b], tok_emb[b], out_ids[b, :], its T - 1 drafts and picks b * T .. .  A
+// row with steps[b] >= max_new is FROZEN: nothing of it is written or counted (the run-ahead rule, per row -- a row that accepted
+// more than the others gets there first and waits).  Then thread 0: *step = min over b of steps[b], the columns of out_ids every row
+// has filled; stats += {1 when a row advanced, the drafts, the accepted ones of the rows that did}, summed in row order.
+__global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_batch_kernel(
+    const int64_t* __restrict__ picks, const float* __restrict__ pv, const int* __restrict__ pi, const int64_t* __restrict__ draft,
+    const int* __restrict__ n_draft, int B, int T, int64_t* __restrict__ tok, int64_t* __restrict__ out_ids, int* __restrict__ pos,
+    int* __restrict__ steps, int* __restrict__ step, int max_new, int max_pos, int64_t* __restrict__ tok_emb, int* __restrict__ stats) {
+  __shared__ int64_t picked[LOOKUP_ROWS_MAX];
+  __shared__ int s_steps[LOOKUP_ROWS_MAX], s_nd[LOOKUP_ROWS_MAX], s_acc[LOOKUP_ROWS_MAX];  // per sequence; s_nd < 0: frozen
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  if (row < B * T) {
+    const int64_t t = picks ? picks[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
+    if (lane == 0) picked[row] = t;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < B) {
+    const int b = threadIdx.x;
+    const int64_t* const dr = draft + (size_t)b * (T - 1);
+    const int64_t* const pk = picked + b * T;
+    int64_t* const out = out_ids + (size_t)b * max_new;
+    int s = steps[b];
+    s_nd[b] = -1;
+    s_acc[b] = 0;
+    if (s >= 0 && s < max_new) {  // (a negative count is no state of a request: such a row is left alone, nothing is written in front of its ids)
+      const int P = pos[b];
+      const int nd = min(min(max(n_draft[b], 0), T - 1), max(max_pos - 1 - P, 0));
+      int n_acc = 0;
+      while (n_acc < nd && dr[n_acc] == pk[n_acc]) ++n_acc;
+      const int emitted = min(n_acc + 1, max_new - s);
+      for (int i = 0; i < emitted; ++i) out[s + i] = pk[i];
+      s += emitted;
+      steps[b] = s;
+      pos[b] = P + emitted;
+      tok[b] = pk[emitted - 1];
+      if (tok_emb) tok_emb[b] = -1;  // as lookup_accept_kernel: a captured plain step re-embeds
+      s_nd[b] = nd;
+      s_acc[b] = n_acc;
+    }
+    s_steps[b] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int lo = INT_MAX, live = 0, nd = 0, n_acc = 0;
+  for (int b = 0; b < B; ++b) {
+    lo = min(lo, s_steps[b]);
+    if (s_nd[b] >= 0) {
+      live = 1;
+      nd += s_nd[b];
+      n_acc += s_acc[b];
+    }
+  }
+  *step = lo;
+  if (stats && live) {
+    stats[0] += 1;
+    stats[1] += nd;
+    stats[2] += n_acc;
+  }
+}
+
 int check_draft_args(int n_prompt, int max_new, int K, int max_ngram, int64_t vocab, const char* fn) {
   SRGPT_CHECK(n_prompt >= 0 && max_new > 0 && vocab > 0, SRGPT_ERR_ARG, "%s: bad sizes n_prompt=%d max_new=%d vocab=%lld", fn, n_prompt,
               max_new, (long long)vocab);
@@ -196,6 +315,24 @@ int srgpt_lookup_accept_sampled_launch(srgpt_sampling* sp, int select_drew, cons
   return SRGPT_OK;
 }
 
+int srgpt_lookup_draft_batch_launch(const int64_t* prompt_ids, int ld_prompt, const int* n_prompt, const int64_t* out_ids, const int* steps,
+                                    int B, int max_new, int K, int max_ngram, int64_t vocab, int64_t* draft, int* n_draft,
+                                    const int64_t* tok, int64_t* row_ids, int* err, hipStream_t s) {
+  hipLaunchKernelGGL(lookup_draft_batch_kernel, dim3(B), dim3(1024), 0, s, prompt_ids, ld_prompt, n_prompt, out_ids, steps, max_new, K,
+                     max_ngram, vocab, draft, n_draft, tok, row_ids, err);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+int srgpt_lookup_accept_batch_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int B,
+                                     int T, int64_t* tok, int64_t* out_ids, int* pos, int* steps, int* step, int max_new, int max_pos,
+                                     int64_t* tok_emb, int* stats, hipStream_t s) {
+  hipLaunchKernelGGL(lookup_accept_batch_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, picks, pv, pi, draft, n_draft, B, T, tok,
+                     out_ids, pos, steps, step, max_new, max_pos, tok_emb, stats);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
 extern "C" int srgpt_lookup_draft(const int64_t* prompt_ids, int n_prompt, const int64_t* out_ids, const int* step, int max_new, int K,
                                   int max_ngram, int64_t vocab, int64_t* draft, int* n_draft, srgpt_stream_t stream) {
   SRGPT_CHECK((prompt_ids || n_prompt == 0) && out_ids && step && draft && n_draft, SRGPT_ERR_ARG, "srgpt_lookup_draft: null pointer");
@@ -211,4 +348,28 @@ extern "C" int srgpt_lookup_accept(const int64_t* picks, const int64_t* draft, c
               "srgpt_lookup_accept: bad sizes T=%d (2 .. %d) max_new=%d max_pos=%d", T, LOOKUP_ROWS_MAX, max_new, max_pos);
   return srgpt_lookup_accept_launch(picks, nullptr, nullptr, draft, n_draft, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb, stats,
                                     as_stream(stream));
+}
+
+extern "C" int srgpt_lookup_draft_batch(const int64_t* prompt_ids, int ld_prompt, const int* n_prompt, const int64_t* out_ids,
+                                        const int* steps, int B, int max_new, int K, int max_ngram, int64_t vocab, int64_t* draft,
+                                        int* n_draft, srgpt_stream_t stream) {
+  SRGPT_CHECK((prompt_ids || ld_prompt == 0) && n_prompt && out_ids && steps && draft && n_draft, SRGPT_ERR_ARG,
+              "srgpt_lookup_draft_batch: null pointer");
+  SRGPT_CHECK(B >= 1 && B <= LOOKUP_ROWS_MAX && ld_prompt >= 0, SRGPT_ERR_ARG, "srgpt_lookup_draft_batch: bad sizes B=%d (1 .. %d) ld_prompt=%d",
+              B, LOOKUP_ROWS_MAX, ld_prompt);
+  SRGPT_TRY(check_draft_args(0, max_new, K, max_ngram, vocab, "srgpt_lookup_draft_batch"));
+  return srgpt_lookup_draft_batch_launch(prompt_ids, ld_prompt, n_prompt, out_ids, steps, B, max_new, K, max_ngram, vocab, draft, n_draft,
+                                         nullptr, nullptr, nullptr, as_stream(stream));
+}
+
+extern "C" int srgpt_lookup_accept_batch(const int64_t* picks, const int64_t* draft, const int* n_draft, int B, int T, int64_t* tok,
+                                         int64_t* out_ids, int* pos, int* steps, int* step, int max_new, int max_pos, int64_t* tok_emb,
+                                         int* stats, srgpt_stream_t stream) {
+  SRGPT_CHECK(picks && draft && n_draft && tok && out_ids && pos && steps && step, SRGPT_ERR_ARG, "srgpt_lookup_accept_batch: null pointer");
+  SRGPT_CHECK(B >= 1 && T >= 2 && max_new > 0 && max_pos > 0, SRGPT_ERR_ARG, "srgpt_lookup_accept_batch: bad sizes B=%d T=%d (2 ..) max_new=%d max_pos=%d",
+              B, T, max_new, max_pos);
+  SRGPT_CHECK((int64_t)B * T <= LOOKUP_ROWS_MAX, SRGPT_ERR_UNSUPPORTED, "srgpt_lookup_accept_batch: B=%d x T=%d rows exceed %d", B, T,
+              LOOKUP_ROWS_MAX);
+  return srgpt_lookup_accept_batch_launch(picks, nullptr, nullptr, draft, n_draft, B, T, tok, out_ids, pos, steps, step, max_new, max_pos,
+                                          tok_emb, stats, as_stream(stream));
 }

@@ -973,6 +973,140 @@ extern "C" int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srg
 }
 
 // ================================================================================================
+// the batched lookup step: B sequences of T rows each through ONE pass over the weights (B * T <= 16 rows, the skinny kernel's pass)
+// ================================================================================================
+namespace {
+
+// srgpt_lookup_batch::ws: carve_lookup for B sequences -- B * T rows of the decode step's buffers and of the two row-statistics
+// tables, the multi-token attention's workspace for (B, T) (its tickets zero between launches), B * T rows of pick partials and the
+// [B, T] draft, row-id and count scratch
+struct LookupBatchWs {
+  void *xd, *qkvd, *attnd, *actd;
+  float* rowss;
+  float* dws;
+  float* amax_v;
+  int* amax_i;
+  int64_t *draft, *row_ids;
+  int* n_draft;
+  size_t total;
+};
+LookupBatchWs carve_lookup_batch(const srgpt_llm_weights* w, int B, int T, void* ws) {
+  const size_t es = dtype_size(w->dtype);
+  const size_t qkvw = (size_t)(w->heads + 2 * w->kv_heads) * w->head_dim;
+  const size_t rows = (size_t)B * T;
+  Carver c(ws);
+  LookupBatchWs l;
+  l.xd = c.take(rows * w->hidden * es);
+  l.qkvd = c.take(rows * qkvw * es);
+  l.attnd = c.take(rows * w->heads * w->head_dim * es);
+  l.actd = c.take(rows * w->inter * es);
+  l.rowss = reinterpret_cast<float*>(c.take(2 * rows * SRGPT_ROWSS_STRIDE * sizeof(float)));
+  l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_multi_ws_floats(B, T, w->heads, w->head_dim) * 4));
+  l.amax_v = reinterpret_cast<float*>(c.take(rows * PICK_SLICES * 4));
+  l.amax_i = reinterpret_cast<int*>(c.take(rows * PICK_SLICES * 4));
+  l.draft = reinterpret_cast<int64_t*>(c.take(rows * 8));
+  l.row_ids = reinterpret_cast<int64_t*>(c.take(rows * 8));
+  l.n_draft = reinterpret_cast<int*>(c.take(rows * sizeof(int)));
+  l.total = c.off;
+  return l;
+}
+
+}  // namespace
+
+extern "C" int64_t srgpt_llm_lookup_batch_ws_bytes(const srgpt_llm_weights* w, int B, int T) {
+  if (!w || B < 1 || T < 2 || (int64_t)B * T > srgpt_lookup_rows_max()) return -1;
+  return (int64_t)carve_lookup_batch(w, B, T, nullptr).total;
+}
+
+// every batched lookup entry point, on the host before any launch
+static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk, const char* fn) {
+  SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
+  SRGPT_TRY(check_llm(w, st));
+  SRGPT_CHECK(lk->T >= 2, SRGPT_ERR_ARG, "%s: T=%d rows per sequence (the next token and at least one draft)", fn, lk->T);
+  SRGPT_CHECK(!st->sampling, SRGPT_ERR_UNSUPPORTED,
+              "%s: greedy only (st->sampling is set: a sampled batch has one Philox counter, rows that emit different numbers of ids "
+              "would need one each)", fn);
+  SRGPT_CHECK((int64_t)st->batch * lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED,
+              "%s: batch %d x T=%d = %lld rows exceed the %d rows of one weight pass", fn, st->batch, lk->T, (long long)st->batch * lk->T,
+              srgpt_lookup_rows_max());
+  const AttnDecodeMultiRoute r =
+      attn_decode_multi_route(w->dtype == SRGPT_BF16, st->batch, lk->T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
+  SRGPT_CHECK(r.status == ATTN_OK, SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows x %d heads per kv head exceed the %d columns of the attention kernel",
+              fn, lk->T, r.G, ATTN_DEC_MULTI_COLS);
+  SRGPT_TRY(pick_check_vocab(w->vocab, fn));
+  SRGPT_CHECK(lk->ws && lk->logits && lk->stats && lk->steps && lk->n_prompt && (lk->prompt_ids || lk->ld_prompt == 0), SRGPT_ERR_ARG,
+              "%s: lookup block has null buffers", fn);
+  SRGPT_CHECK(lk->ld_prompt >= 0, SRGPT_ERR_ARG, "%s: ld_prompt=%d is negative", fn, lk->ld_prompt);
+  SRGPT_CHECK(lk->max_ngram >= 1 && lk->max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn,
+              lk->max_ngram, srgpt_lookup_ngram_max());
+  LlmFormat fmt;
+  return llm_format(w, fn, &fmt);
+}
+
+// lookup_step_impl's launches with rows = B * T: the batched draft (one block per sequence) -> embed the B * T ids -> per layer the
+// four products over B * T rows and srgpt_decode_attention_multi with B sequences (its existing template instances: T * G columns
+// per sequence, one position per sequence) -> lm_head -> the rows' argmax partials -> the batched accept
+static int lookup_step_batch_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, srgpt_stream_t stream) {
+  LlmFormat fmt;
+  SRGPT_TRY(llm_format(w, "srgpt_llm_lookup_step_batch", &fmt));
+  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
+  const int B = st->batch, T = lk->T, R = B * T, QW = (Hq + 2 * Hkv) * D;
+  const size_t es = dtype_size(dt);
+  hipStream_t s = as_stream(stream);
+  const LlmWs d = carve_llm(w, B, st->ws_tokens, st->ws);  // the state's sticky error word and embedded-token record
+  const LookupBatchWs l = carve_lookup_batch(w, B, T, lk->ws);
+  const size_t layer_kv = (size_t)B * Hkv * st->max_pos * D * es;
+  SRGPT_TRY(srgpt_lookup_draft_batch_launch(lk->prompt_ids, lk->ld_prompt, lk->n_prompt, st->out_ids, lk->steps, B, st->max_new, T - 1,
+                                            lk->max_ngram, (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
+  SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, R, Hd, dt, stream));
+  const bool fp8 = fmt != FMT_DTYPE;
+  const DecodeStep ds{w, R, fp8, gemv_rowss_supported(R, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
+  float* const ss_attn = l.rowss;
+  float* const ss_mlp = l.rowss + (size_t)R * SRGPT_ROWSS_STRIDE;
+  for (int i = 0; i < w->layers; ++i) {
+    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
+    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
+    const LayerMats m = layer_mats(w, fmt, i);
+    SRGPT_TRY(ds.gemv(m.qkv, l.xd, w->attn_norm[i], nullptr, l.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
+    SRGPT_TRY(srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, B, T, Hq, Hkv, D,
+                                           st->max_pos, dt, stream));
+    SRGPT_TRY(ds.gemv(m.o, l.attnd, nullptr, l.xd, l.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
+    SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
+    SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
+  }
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
+                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, R), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
+  SRGPT_LAUNCH_CHECK();
+  return srgpt_lookup_accept_batch_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, B, T, st->tok, st->out_ids, st->pos, lk->steps,
+                                          st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
+}
+
+extern "C" int srgpt_llm_lookup_step_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                           srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_step_batch"));
+  return lookup_step_batch_impl(w, st, lk, stream);
+}
+
+// srgpt_llm_lookup_sync_state for the batched step: the (B, T) lookup workspace's tickets, then the state's own check
+extern "C" int srgpt_llm_lookup_sync_state_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                                 srgpt_stream_t stream) {
+  SRGPT_CHECK(lk && lk->ws && lk->T >= 2, SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state_batch: bad lookup block");
+  SRGPT_TRY(check_llm(w, st));
+  SRGPT_CHECK((int64_t)st->batch * lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state_batch: bad lookup block");
+  const LookupBatchWs l = carve_lookup_batch(w, st->batch, lk->T, lk->ws);
+  size_t bytes = 0;
+  void* sync = srgpt_decode_attn_multi_sync_words(l.dws, st->batch, lk->T, w->heads, w->head_dim, &bytes);
+  std::vector<int> host(bytes / sizeof(int));
+  SRGPT_HIP_TRY(hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_lookup_sync_state_batch: copy");
+  SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_llm_lookup_sync_state_batch: synchronize");
+  for (size_t i = 0; i < host.size(); ++i)
+    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "batched lookup step: arrival ticket %zu of %zu is %d between steps (expected 0)", i,
+                host.size(), host[i]);
+  return srgpt_llm_decode_sync_state(w, st, stream);
+}
+
+// ================================================================================================
 // hipGraph of one decode step
 // ================================================================================================
 // the graph entry points' check: somewhere to put the graph, then check_pick
@@ -1031,6 +1165,13 @@ extern "C" int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgp
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_ex: null out");
   SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_graph_create_ex"));
   return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream, sampler, sample_ws); });
+}
+
+extern "C" int srgpt_llm_lookup_graph_create_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                                   srgpt_stream_t stream, srgpt_graph** out) {
+  SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_batch: null out");
+  SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_graph_create_batch"));
+  return capture_graph(stream, out, [&] { return lookup_step_batch_impl(w, st, lk, stream); });
 }
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,

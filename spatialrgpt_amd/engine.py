@@ -52,7 +52,7 @@ class DecodeState:
         self.c = st
         self.host_len = [0] * batch  # cached positions per row as known on the host (prefill lengths + steps taken)
         self.graphs = {}             # "greedy" / "sample" / "sample_full" (+ "+proc") -> captured decode step (the pick kernels differ);
-        #                              "lookup" (+ "+sample" / "+sample_full") -> captured lookup step
+        #                              "lookup" (+ "+sample" / "+sample_full") -> captured lookup step; "lookup_batch" -> the batched one
         self.sampler = L.SAMPLER_TOPK64  # which device sampler draws while c.sampling is set (SRGPT_SAMPLER_*)
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
         self.logits_proc: Optional[ops.LogitsProcParams] = None  # device block of the logits processors; ONE address likewise
@@ -62,6 +62,7 @@ class DecodeState:
         self.pending = None
         self._pos_stale = False      # the device `pos` ran ahead of host_len (a decode loop that stopped early): see truncate()
         self.lookup = None           # prompt-lookup decoding: the lookup step's buffers and parameter block (ensure_lookup)
+        self.lookup_b = None         # ... for a batch: the batched lookup step's buffers and parameter block (ensure_lookup_batch)
         self._eng = eng
 
     def seq_len(self) -> int:
@@ -164,6 +165,57 @@ class DecodeState:
                 raise RuntimeError("srgpt_llm_lookup_sample_ws_bytes failed")
             lk["sample_ws"][self.sampler] = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
         return lk
+
+    def ensure_lookup_batch(self, K: int, max_ngram: int, prompt_ids: Optional[torch.Tensor], prompt_mask: Optional[torch.Tensor] = None):
+        """ensure_lookup for the BATCHED step (srgpt_llm_lookup_step_batch): buffers for self.batch sequences of T = K + 1 rows, keyed
+        by (batch, T) -- workspace (zeroed: arrival tickets), [B * T, vocab] logits, stats, the per-row emission counts `steps` [B],
+        the prompt rows [B, cap] and their lengths `n_prompt` [B] on the device.  prompt_ids int64 [B, P] (None: no prompt ids, the
+        rows draft from their generated ids alone), prompt_mask [B, P] (None: every id is valid): every row contributes its valid
+        ids in order, packed to the front, sentinels included (they never match).  The addresses are fixed, so one captured graph
+        serves every prompt."""
+        eng, dev, B = self._eng, self._eng.device, self.batch
+        T, n = int(K) + 1, 0 if prompt_ids is None else int(prompt_ids.shape[1])
+        if prompt_ids is not None and (prompt_ids.dim() != 2 or prompt_ids.shape[0] != B):
+            raise ValueError(f"ensure_lookup_batch: prompt_ids must be [{B}, P]")
+        lk = self.lookup_b
+        if lk is None or lk["T"] != T or lk["max_ngram"] != max_ngram or n > lk["cap"]:
+            if "lookup_batch" in self.graphs:
+                L.load().srgpt_graph_destroy(self.graphs.pop("lookup_batch"))
+            nbytes = L.load().srgpt_llm_lookup_batch_ws_bytes(C.byref(eng.w.llm), B, T)
+            if nbytes < 0:
+                raise RuntimeError("srgpt_llm_lookup_batch_ws_bytes failed")
+            cap = max(self.max_pos, n)
+            lk = dict(B=B, T=T, max_ngram=max_ngram, cap=cap, ws=torch.zeros((nbytes,), device=dev, dtype=torch.uint8),
+                      logits=torch.empty((B * T, eng.w.vocab), device=dev, dtype=torch.float32),
+                      stats=torch.zeros((3,), device=dev, dtype=torch.int32), steps=torch.zeros((B,), device=dev, dtype=torch.int32),
+                      prompt=torch.full((B, cap), -1, device=dev, dtype=torch.int64),
+                      n_prompt=torch.zeros((B,), device=dev, dtype=torch.int32), c=L.LookupBatch())
+            c = lk["c"]
+            c.T, c.max_ngram, c.prompt_ids, c.ld_prompt, c.n_prompt = T, max_ngram, lk["prompt"].data_ptr(), cap, lk["n_prompt"].data_ptr()
+            c.steps, c.ws, c.logits, c.stats = lk["steps"].data_ptr(), lk["ws"].data_ptr(), lk["logits"].data_ptr(), lk["stats"].data_ptr()
+            self.lookup_b = lk
+        lk["prompt"].fill_(-1)
+        lk["n_prompt"].zero_()
+        if n:
+            ids = prompt_ids.to(device=dev, dtype=torch.int64)
+            keep = torch.ones_like(ids, dtype=torch.bool) if prompt_mask is None else prompt_mask.to(dev).bool()
+            # a stable sort of the keep flags moves every row's valid ids to the front, order preserved (as generate() packs the embeddings)
+            order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)
+            lens = keep.sum(dim=1)
+            packed = torch.where(torch.arange(n, device=dev)[None, :] < lens[:, None], torch.gather(ids, 1, order), torch.full_like(ids, -1))
+            lk["prompt"][:, :n].copy_(packed)
+            lk["n_prompt"].copy_(lens.to(torch.int32))
+        lk["stats"].zero_()
+        return lk
+
+    def ensure_lookup_batch_graph(self):
+        """the captured batched lookup step (greedy)"""
+        if "lookup_batch" not in self.graphs:
+            g = L.vp()
+            L.check(L.load().srgpt_llm_lookup_graph_create_batch(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup_b["c"]),
+                                                                 ops._stream(), C.byref(g)))
+            self.graphs["lookup_batch"] = g
+        return self.graphs["lookup_batch"]
 
     def lookup_sample_ws(self):
         """device pointer of the running request's sampler workspace for the lookup step; None: a greedy request"""
@@ -644,16 +696,24 @@ class SrgptEngine:
         carries the next token and K ids drafted from prompt_ids + the generated ids (srgpt_llm_lookup_step_ex) and emits 1 .. K + 1
         tokens.  Greedy: the same ids, stop step and state as the plain loop.  With `sampling`: every row's token is DRAWN (row t at
         Philox counter + t), the drafts are kept up to the first draw that differs -- generated id i is a draw from the model's
-        distribution at counter c0 + i, as in the plain sampled loop.  self.last_lookup_stats = what it did."""
-        if lookup is not None and (st.batch != 1 or logits_proc is not None):
+        distribution at counter c0 + i, as in the plain sampled loop.  self.last_lookup_stats = what it did.
+        A state of 2+ rows (greedy, batch * (K + 1) <= 16; lookup also carries prompt_ids [B, P] and prompt_mask): batched lookup
+        steps (srgpt_llm_lookup_step_batch, _lookup_loop_batch) -- every row drafted from its own ids and advanced by its own
+        accepted drafts; ids, padding and length as the plain batched loop's."""
+        batched = lookup is not None and st.batch > 1  # the caller opted in (LlavaLlamaModel.lookup_batch; generation.plan_lookup)
+        if lookup is not None and logits_proc is not None:
             raise ValueError("greedy_decode(lookup=...) takes a batch-1 request without logits processors")
+        if batched and (sampling is not None or (st.batch * (lookup["K"] + 1)) > L.LOOKUP_ROWS_MAX):
+            raise ValueError(f"greedy_decode(lookup=...) on batch {st.batch}: a greedy request of batch * (K + 1) <= {L.LOOKUP_ROWS_MAX} rows")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
             st.set_sampling(sampling)
             st.set_logits_proc(logits_proc)
             try:
-                if lookup is not None:
+                if batched:
+                    n_keep, eos, n_rows = self._lookup_loop_batch(st, max_new_tokens, eos_token_id, stopping_criteria, lookup)
+                elif lookup is not None:
                     n_keep, eos, n_rows = self._lookup_loop(st, max_new_tokens, eos_token_id, stopping_criteria, lookup)
                 else:
                     n_keep, eos, n_rows = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
@@ -664,7 +724,9 @@ class SrgptEngine:
         cur.wait_stream(self.stream)
         # the decode attention hands partials between workgroups inside a launch (arrival tickets): a ticket left non-zero means a
         # launch merged nothing and later steps used stale attention output -- fail loudly, never return such ids
-        if lookup is not None:  # the lookup workspace's own tickets, then the same check
+        if batched:
+            L.check(L.load().srgpt_llm_lookup_sync_state_batch(C.byref(self.w.llm), C.byref(st.c), C.byref(st.lookup_b["c"]), ops._stream()))
+        elif lookup is not None:  # the lookup workspace's own tickets, then the same check
             L.check(L.load().srgpt_llm_lookup_sync_state(C.byref(self.w.llm), C.byref(st.c), C.byref(st.lookup["c"]), ops._stream()))
         else:
             L.check(L.load().srgpt_llm_decode_sync_state(C.byref(self.w.llm), C.byref(st.c), ops._stream()))
@@ -805,6 +867,100 @@ class SrgptEngine:
             if judged >= max_new_tokens:
                 return finish(max_new_tokens, False)
         raise RuntimeError("lookup decode loop: the device step counter did not advance")
+
+    def _lookup_loop_batch(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria, lookup: dict):
+        """_lookup_loop for B rows (srgpt_llm_lookup_step_batch): the same run-ahead shape, but every row emits its own number of ids
+        per step, so every round fetches the per-row counts `steps` [B], the stats block and out_ids[:, :max_new_tokens] behind the
+        previous step -- after the next step went out.  Judging reproduces the plain batched loop's: EOS per row over that row's new
+        ids in order (the first one sets the ids the row keeps); the stopping criteria per COLUMN, in column order, on the columns
+        every row has reached, with ids[:, :s + 1] -- the tensors the plain loop hands them, whose stop column they therefore name.
+        The request ends at the first criteria stop, at the column the last row finished in, or with max_new_tokens columns filled.
+        Rows that accepted more ran ahead of the kept columns; their device positions are rolled back by truncate() like the plain
+        loop's one step ahead, and a row at st.max_new ids is frozen on the device until the others arrive."""
+        lib, stream, B = L.load(), ops._stream(), st.batch
+        eos = None
+        if eos_token_id is not None:
+            eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
+            eos = eos or None
+        lk = st.ensure_lookup_batch(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"), lookup.get("prompt_mask"))
+        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, None, stream))
+        lk["steps"].fill_(1)  # every row has emitted its first id
+        graph = st.ensure_lookup_batch_graph() if self.use_graph and max_new_tokens > 1 else None
+
+        def launch():
+            if graph is not None:
+                L.check(lib.srgpt_graph_launch(graph, 1, stream))
+            else:
+                L.check(lib.srgpt_llm_lookup_step_batch(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), stream))
+
+        if getattr(self, "_copy_stream", None) is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        # out_ids[:, :max_new_tokens] is strided when the state holds more ids per row: gathered into a contiguous device scratch on the
+        # copy stream, it leaves as one contiguous copy into pinned memory (the reason _decode_loop_run_ahead gives)
+        host_ids = torch.empty((B, max_new_tokens), dtype=torch.int64).pin_memory()
+        scratch = torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device)
+        host_cnt = torch.empty((B + 3,), dtype=torch.int32).pin_memory()  # the rows' counts, then the stats block
+        dec = torch.cuda.current_stream(self.device)
+
+        def mark():
+            ev = torch.cuda.Event()
+            ev.record(dec)
+            return ev
+
+        def fetch(ev):
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(ev)
+                host_cnt[:B].copy_(lk["steps"], non_blocking=True)
+                host_cnt[B:].copy_(lk["stats"], non_blocking=True)
+                scratch.copy_(st.out_ids[:, :max_new_tokens])
+                host_ids.copy_(scratch, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self._copy_stream)
+            return done
+
+        n_rows = [None] * B  # ids a row keeps: up to and including its first EOS
+
+        def finish(n_keep):
+            dec.wait_stream(self._copy_stream)
+            steps, drafted, accepted = (int(v) for v in host_cnt[B:].tolist())
+            rows = [n_keep if n is None else min(n, n_keep) for n in n_rows]
+            self.last_lookup_stats = dict(steps=steps, tokens=sum(rows), drafted=drafted, accepted=accepted, batch=B)
+            return n_keep, eos, rows
+
+        interactive = stopping_criteria is not None and len(stopping_criteria) > 0
+        ev = mark()  # the first token of every row (srgpt_llm_sample_first) is on the stream
+        seen, col = [0] * B, 0  # ids of row b scanned for EOS; columns judged by the criteria
+        for _ in range(max_new_tokens + 1):  # every step emits at least one id per live row
+            ready = fetch(ev)
+            if max_new_tokens > 1:
+                launch()  # run ahead: the next step goes out before the ids behind `ev` are judged
+                ev = mark()
+            ready.synchronize()
+            have = [min(int(v), max_new_tokens) for v in host_cnt[:B].tolist()]
+            if eos:
+                for b in range(B):
+                    for t in range(seen[b], have[b]):
+                        if n_rows[b] is None and int(host_ids[b, t]) in eos:
+                            n_rows[b] = t + 1
+            seen = have
+            reached = min(have)
+            # the column the last row finished in ends the request there (the plain loop judges a column's EOS ids before its criteria)
+            last = max(n_rows) if eos and all(n is not None for n in n_rows) else None
+            if interactive:
+                while col < reached:
+                    if last is not None and last == col + 1:
+                        return finish(last)
+                    full = host_ids[:, :col + 1]  # HF passes only the generated ids when generate() was fed inputs_embeds
+                    for crit in stopping_criteria:
+                        r = crit(full, None)
+                        if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
+                            return finish(col + 1)
+                    col += 1
+            elif last is not None:  # nothing judges the columns in between: every row's kept ids are known
+                return finish(last)
+            if reached >= max_new_tokens:
+                return finish(max_new_tokens)
+        raise RuntimeError("batched lookup decode loop: a row's device step counter did not advance")
 
     def _decode_loop_run_ahead(self, st: DecodeState, max_new_tokens: int, launch, judge) -> int:
         """A stopping criterion (the demo's KeywordsStoppingCriteria, gradio_web_server_multi.py:195-197; model_vqa.py's conv stop

@@ -134,20 +134,25 @@ def resolve_generation(stored: Optional[dict], **kwargs) -> ResolvedGeneration:
 
 
 def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sampling: bool, vocab: int, heads: int, kv_heads: int,
-                head_dim: int, bf16: bool):
+                head_dim: int, bf16: bool, lookup_batch: bool = False):
     """-> (drafts per step or None, why): does a request with `prompt_lookup_num_tokens=K` run lookup steps?  A pure function of
     the resolved generation settings `g` and the model's facts (the decision of LlavaLlamaModel._lookup_plan, as reuse.plan_reuse
     is PrefixReuse's).  Prompt-lookup decoding serves a batch-1 request without beams and logits processors: a greedy one always, a
     SAMPLED one (do_sample with a temperature > 0) only with the model's `lookup_sampling` switch on and a device sampler for its
     settings (ops.SamplingParams.sampler: a vocabulary above 262144 has none and stays on the plain loop).  K is clamped to the
     rows the step's attention route carries at this geometry (csrc/attn_route.h: T * heads / kv_heads <= 16 on the bf16 /
-    head_dim-128 kernel, 16 rows otherwise)."""
+    head_dim-128 kernel, 16 rows otherwise).
+    `lookup_batch` (the model's switch of that name, off by default): a GREEDY request of 2 .. 8 rows without beams and processors
+    runs batched lookup steps -- every row drafted from its own history, batch * (K + 1) <= 16 rows in one weight pass, so K is
+    clamped to 16 // batch - 1 as well.  Beams, processors and sampled batches keep the plain loop; batch 1 takes the path above."""
     from . import _lib as L
     from .ops import SamplingParams
 
     K = g.prompt_lookup_num_tokens
     if not K:
         return None, "prompt_lookup_num_tokens not set"
+    if batch != 1 and lookup_batch:
+        return _plan_lookup_batch(g, batch, processors, heads, kv_heads, head_dim, bf16)
     if batch != 1:
         return None, f"batch {batch}: the lookup step takes one sequence"
     if g.num_beams != 1:
@@ -165,6 +170,30 @@ def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sa
     if cap < 1:
         return None, "no spare attention column at this geometry"
     return min(int(K), cap), f"K = {min(int(K), cap)} drafts per step" + (f" (asked for {K})" if K > cap else "")
+
+
+def _plan_lookup_batch(g: "ResolvedGeneration", batch: int, processors: bool, heads: int, kv_heads: int, head_dim: int, bf16: bool):
+    """plan_lookup for batch > 1 with the model's `lookup_batch` switch on"""
+    from . import _lib as L
+
+    K = g.prompt_lookup_num_tokens
+    if g.num_beams != 1:
+        return None, "num_beams > 1"
+    if g.do_sample and g.temperature is not None and g.temperature > 0:
+        return None, (f"do_sample: batch {batch} draws from one Philox counter, rows that emit different numbers of ids would need "
+                      "one each")
+    if processors:
+        return None, "logits processors are on"
+    G = heads // kv_heads
+    mfma = bf16 and head_dim == 128 and G in (1, 2, 4, 8)
+    cap = (L.ATTN_MULTI_COLS // G if mfma else L.LOOKUP_ROWS_MAX) - 1
+    if cap < 1:
+        return None, "no spare attention column at this geometry"
+    rows = L.LOOKUP_ROWS_MAX // batch - 1
+    if rows < 1:
+        return None, f"batch {batch}: two rows per sequence exceed the {L.LOOKUP_ROWS_MAX}-row weight pass of a step"
+    k = min(int(K), cap, rows)
+    return k, f"K = {k} drafts per step, batch {batch}" + (f" (asked for {K})" if K > k else "")
 
 
 def warp_logits(logits: torch.Tensor, temperature=None, top_k=None, top_p=None, min_tokens_to_keep: int = 1) -> torch.Tensor:

@@ -184,7 +184,7 @@ class LlavaLlamaModel:
     def __init__(self, config=None, state_dict: Dict[str, torch.Tensor] = None, device="cuda",
                  dtype=torch.bfloat16, tokenizer=None, image_processor=None, rope_positions: int = 0,
                  consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, prefix_reuse: bool = False,
-                 lookup_sampling: bool = False, **hf_kwargs):
+                 lookup_sampling: bool = False, lookup_batch: bool = False, **hf_kwargs):
         self.hf_config = None
         if isinstance(config, LlavaConfig):
             # the reference's construction path: config carries the checkpoint location
@@ -231,6 +231,9 @@ class LlavaLlamaModel:
         # token drawn on the device, the drafts kept up to the first draw that differs: exact).  Off: such a request runs the plain
         # sampled loop, launch for launch, as it does without the feature
         self.lookup_sampling = bool(lookup_sampling)
+        # ... for batches, opt-in: with the switch on a GREEDY request of 2 .. 8 rows with the keyword runs batched lookup steps (every
+        # row drafted from its own history and advanced by its own accepted drafts, batch * (K + 1) <= 16 rows per step)
+        self.lookup_batch = bool(lookup_batch)
 
     @property
     def last_reuse(self):
@@ -548,6 +551,10 @@ class LlavaLlamaModel:
         if input_ids is not None and input_ids.shape[0] == 1:
             # prompt-lookup decoding drafts from the caller's ids as given (-200 and other sentinels included: they never match)
             generation_kwargs.setdefault("_prompt_ids", input_ids[0])
+        elif input_ids is not None and self.lookup_batch:
+            # ... and for a batch every row from its own valid ids, in order (the caller's mask: the splice below returns another)
+            generation_kwargs.setdefault("_prompt_ids", input_ids)
+            generation_kwargs.setdefault("_prompt_mask", attention_mask)
         if self.prefix_reuse and input_ids is not None and images is not None and input_ids.shape[0] == 1 \
                 and generation_kwargs.get("past_key_values") is None and not generation_kwargs.get("return_dict_in_generate") \
                 and generation_kwargs.get("inputs_embeds") is None:
@@ -592,7 +599,7 @@ class LlavaLlamaModel:
                               pad_token_id=NOT_GIVEN, eos_token_id=NOT_GIVEN, repetition_penalty=NOT_GIVEN,
                               no_repeat_ngram_size=NOT_GIVEN, min_length=NOT_GIVEN, past_key_values=None,
                               return_dict_in_generate=False, _state=None, prompt_lookup_num_tokens=NOT_GIVEN,
-                              max_matching_ngram_size=NOT_GIVEN, _prompt_ids=None, **unused):
+                              max_matching_ngram_size=NOT_GIVEN, _prompt_ids=None, _prompt_mask=None, **unused):
         """HF `GenerationMixin.generate(inputs_embeds=...)` as the reference reaches it (llava_llama.py:212): the stored
         generation config overwritten by the call's keywords, explicit Nones included (spatialrgpt_amd/generation.py).
         `repetition_penalty`, `no_repeat_ngram_size` and `min_length` / `min_new_tokens` run as HF's logits processors on the device
@@ -607,7 +614,9 @@ class LlavaLlamaModel:
         attention kernel's columns hold), taken from `_prompt_ids` (the caller's input_ids row; none for llm.generate(inputs_embeds=))
         and the generated ids.  Every other request runs the plain loop, unchanged.  A greedy request's ids are the same either
         way; a sampled one draws every id from the same distribution at the same Philox counter (generation.plan_lookup decides;
-        `self.last_lookup` says which happened and why)."""
+        `self.last_lookup` says which happened and why).  With `self.lookup_batch` on a greedy request of 2 .. 8 rows runs BATCHED
+        lookup steps: every row drafted from its own valid ids (`_prompt_ids` [B, P] with `_prompt_mask`, the caller's input_ids and
+        attention_mask) and advanced by its own accepted drafts; ids, padding and length as without the keyword."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
                                num_beams=num_beams, max_new_tokens=max_new_tokens, max_length=max_length,
                                min_new_tokens=min_new_tokens, pad_token_id=pad_token_id, eos_token_id=eos_token_id,
@@ -695,7 +704,7 @@ class LlavaLlamaModel:
             ids = self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
                                             stopping_criteria=stopping_criteria,
                                             lookup=dict(K=lookup_k, max_ngram=min(g.max_matching_ngram_size, L.LOOKUP_NGRAM_MAX),
-                                                        prompt_ids=_prompt_ids))
+                                                        prompt_ids=_prompt_ids, prompt_mask=_prompt_mask))
             self.last_lookup = dict(mode="lookup", reason=why, **self.engine.last_lookup_stats)
             return done(ids)
         return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
@@ -707,7 +716,7 @@ class LlavaLlamaModel:
 
         c = self.engine.cfg
         return plan_lookup(g, batch, proc is not None, self.lookup_sampling, self.engine.w.vocab, c.heads, c.kv_heads, c.head_dim,
-                           self.engine.dtype == torch.bfloat16)
+                           self.engine.dtype == torch.bfloat16, lookup_batch=self.lookup_batch)
 
     def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
                      logits_proc=None):

@@ -472,6 +472,33 @@ def lookup_accept(picks, draft, n_draft, tok, out_ids, pos, step, max_pos: int, 
                                          int(out_ids.numel()), max_pos, _p(tok_emb), _p(stats), _stream()))
 
 
+def lookup_draft_batch(prompt_ids, n_prompt, out_ids, steps, K: int, max_ngram: int, vocab: int, draft=None, n_draft=None):
+    """srgpt_lookup_draft_batch: prompt_ids int64 [B, ld] (or None), n_prompt int32 [B], out_ids int64 [B, max_new], steps int32 [B],
+    all on the device -> (draft int64 [B, K], n_draft int32 [B]); `draft` / `n_draft`: the caller's buffers instead of fresh ones"""
+    _dev(n_prompt, out_ids, steps)
+    B, max_new = out_ids.shape
+    ld = 0 if prompt_ids is None else int(prompt_ids.shape[1])
+    assert out_ids.is_contiguous() and (prompt_ids is None or (prompt_ids.is_contiguous() and prompt_ids.shape[0] == B))
+    if draft is None:
+        draft = torch.empty((B, K), dtype=torch.int64, device=out_ids.device)
+    if n_draft is None:
+        n_draft = torch.empty((B,), dtype=torch.int32, device=out_ids.device)
+    assert draft.is_contiguous() and draft.shape == (B, K) and n_draft.shape == (B,)
+    L.check(L.load().srgpt_lookup_draft_batch(_p(prompt_ids) if ld else None, ld, _p(n_prompt), _p(out_ids), _p(steps), B, max_new, K,
+                                              max_ngram, vocab, _p(draft), _p(n_draft), _stream()))
+    return draft, n_draft
+
+
+def lookup_accept_batch(picks, draft, n_draft, tok, out_ids, pos, steps, step, max_pos: int, tok_emb=None, stats=None):
+    """srgpt_lookup_accept_batch on the state's buffers, in place: picks int64 [B * T], draft [B, T - 1], out_ids [B, max_new]"""
+    _dev(picks, draft, n_draft, tok, out_ids, pos, steps, step)
+    B, max_new = out_ids.shape
+    T = int(draft.shape[1]) + 1
+    assert picks.numel() == B * T and out_ids.is_contiguous() and draft.is_contiguous()
+    L.check(L.load().srgpt_lookup_accept_batch(_p(picks), _p(draft), _p(n_draft), B, T, _p(tok), _p(out_ids), _p(pos), _p(steps), _p(step),
+                                               max_new, max_pos, _p(tok_emb), _p(stats), _stream()))
+
+
 def region_pool(feat, masks, fw: Optional[int] = None):
     """MaskPooling for one image: feat [L,C], masks [M,mh,mw] (float32 or bfloat16) -> [M,C]."""
     _dev(feat, masks)

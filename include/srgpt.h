@@ -153,7 +153,8 @@ int srgpt_gemv(const void* x, const void* W, const void* norm_w, float norm_eps,
 /* Same product with weight-only fp8 quantisation (W8A16, BASELINE config 5): W8 = OCP e4m3fn bytes [N (2N if swiglu), K],
  * wscale = one fp32 scale per weight row, x / norm_w / residual / out bf16 (out fp32 if out_f32):
  *   out[b, n] = round_bf16( (sum_k x[b,k] * fp8(W8[n,k])) * wscale[n] ), fp32 accumulation; same fusions as srgpt_gemv.
- * The reference has no fp8 path (it offers bitsandbytes 8/4-bit loading, builder.py:51-60); this replaces that option. */
+ * The reference has no fp8 path (it offers bitsandbytes 8/4-bit loading, builder.py:51-60); this replaces the 8-bit option
+ * (the 4-bit one: srgpt_gemv_w4 below). */
 int srgpt_gemv_w8(const void* x, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
                   const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
                   srgpt_stream_t stream);
@@ -186,6 +187,25 @@ int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* 
  * W / W8 with packed_rows = rows (0: row-major) and returns bit for bit what it returns for the row-major matrix. */
 size_t srgpt_packed_bytes(int N, int K, int elem_bytes, int rows);
 int srgpt_pack_decode_weights(const void* W, void* out, int N, int K, int elem_bytes, int rows, srgpt_stream_t stream);
+/* Additions under ABI 9: MXFP4 weights (OCP Microscaling FP4), the 4-bit option -- a quarter of the bf16 bytes per streamed matrix.
+ * The format of a matrix [N (2 N if swiglu), K], K % 32 == 0:
+ *   W4      uint8 [N, K / 2]: element k of a row sits in byte k / 2, the LOW nibble holds even k, the high nibble odd k; a code is
+ *           OCP e2m1: bit 3 the sign, bits 2 .. 0 the magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6}
+ *   wscale8 uint8 [N, K / 32]: one E8M0 byte per 32 consecutive values of a row, value = 2^(byte - 127).  The kernels take bytes
+ *           1 .. 254 (the quantiser of the Python host never emits 0 or 255; 255 is NaN in the OCP format and 0 is below the fp32
+ *           normal range the conversion instruction reads its scale from): other bytes give unspecified VALUES, never a fault.
+ *   value[n, k] = e2m1(code) * 2^(byte - 127), exact in bf16.
+ * Opt-in like fp8 and it changes the numbers: every 32 values share one power-of-two scale and have 15 levels.  What that costs in
+ * accuracy on a trained checkpoint is UNMEASURED (no checkpoint was available to this project).
+ * srgpt_gemv_w4: the decode product over such a matrix, x / norm_w / residual / out bf16 (out fp32 if out_f32):
+ *   out[b, n] = round_bf16( sum_k x[b, k] * value[n, k] ), fp32 accumulation of exact products; the fusions and the rounding points
+ *   of srgpt_gemv_w8 (above, "Rounding points") without a per-row fp32 scale.  A VALU kernel (v_cvt_scalef32_pk_f32_fp4 applies the
+ *   block scale while widening) for 1 .. 4 rows per launch; a longer call is cut into launches of at most 4 rows, each a pass over the
+ *   codes, all on this kernel.  K % 32 != 0, a NULL x / W4 / wscale8 / out, or swiglu with residual / out_f32: SRGPT_ERR_ARG.
+ * srgpt_dequant_mxfp4: out_bf16 [N, K] row-major = value[n, k] (what the prefill multiplies, and the parity hook). */
+int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float norm_eps, const void* residual,
+                  void* out, int batch, int N, int K, int swiglu, int out_f32, srgpt_stream_t stream);
+int srgpt_dequant_mxfp4(const void* W4, const void* wscale8, void* out_bf16, int N, int K, srgpt_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Normalisations.
@@ -560,6 +580,21 @@ typedef struct {
   const void* const* wgu8p;
   const void* const* wdown8p;
   int pk_rows_qkv, pk_rows_o, pk_rows_gu, pk_rows_down;
+  /* ABI 9: optional MXFP4 copies (codes + E8M0 block scales, see srgpt_gemv_w4) of the four per-layer matrices; all NULL: the formats
+   * above.  When wqkv4 != NULL they are the weights of those four (the dtype and fp8 arrays above are not read for them and may hold
+   * NULLs): the decode step, the lookup steps included, streams them through srgpt_gemv_w4 (a batch of more than 4 rows in passes of
+   * 4); prefill and append prefill expand each matrix with srgpt_dequant_mxfp4 into a bf16 scratch in the workspace just before its
+   * product and run the bf16 launches on it -- bit-identical to a bf16 engine on the dequantised weights, at the price of one more
+   * pass over bf16-sized bytes per matrix.  lm_head stays fp8: lm_head8 + lm_head_scale are required, multiplied as under the fp8
+   * format.  Needs dtype SRGPT_BF16, hidden, inter and heads * head_dim multiples of 32, and wqkv8 == NULL. */
+  const void* const* wqkv4;
+  const void* const* wqkv4_scale;
+  const void* const* wo4;
+  const void* const* wo4_scale;
+  const void* const* wgu4;
+  const void* const* wgu4_scale;
+  const void* const* wdown4;
+  const void* const* wdown4_scale;
 } srgpt_llm_weights;
 
 typedef struct {
@@ -580,6 +615,7 @@ typedef struct {
                              * and the graphs captured from this state DRAW the next token (see srgpt_sampling) */
 } srgpt_llm_state;
 
+/* (MXFP4 weights: plus one bf16 scratch for the largest of the four layer matrices; every other format: unchanged) */
 int64_t srgpt_llm_ws_bytes(const srgpt_llm_weights* w, int batch, int max_tokens);
 /* Prefill: inputs_embeds [B, T, hidden] (already spliced), all rows valid (equal-length prompts).
  * Fills the cache, sets pos[b] = T, writes last-position logits to st->logits; if all_logits != NULL

@@ -1,0 +1,248 @@
+"""What llm_weight_format="mxfp4" costs and gains against fp8 and bf16.  -> profiles/mxfp4.txt
+
+    python scripts/time_mxfp4.py [--out profiles/mxfp4.txt] [--rows 259] [--only steps|products] [--tree DIR]
+
+VILA1.5-8B geometry (bench.make_cfg, synth_state_dict seed 0), one process, three engines (bf16, fp8, mxfp4) on one card.  Every
+timed call is: the state put back outside the window, device synchronise, an event, the work, an event, synchronise.  The lines of a
+section alternate block by block (one untimed call in front of every block); three repetitions, the median of each is printed with
+the min .. max of all calls -- the run-to-run spread a ratio has to clear.
+
+  steps     the captured batch-1 decode step over `rows` cached rows: bf16, fp8, mxfp4
+  lookup    the captured lookup step at K = 3 (T = 4 rows): fp8, mxfp4
+  batch 8   the captured batch-8 step: fp8 (the MFMA kernel, one pass of 8 rows) against mxfp4 (two passes of 4 rows)
+  products  q/k/v, o_proj, gate/up and down_proj alone at 1 .. 4 rows, srgpt_gemv_w8 against srgpt_gemv_w4: a captured graph of one
+            launch per layer (32 different matrices: nothing is served from a cache), us per launch
+  prefill   the 259-row prefill and a 32-row append over it, eager calls: fp8 against mxfp4 (which expands every matrix to bf16 first)
+  bytes     llm_weight_bytes() of the three engines
+
+--only steps: the bf16 and fp8 steps alone -- what a tree without the format has; --tree DIR imports the package from another
+checkout (the parent commit), so the same lines can be taken on both in turn.  --only products: the fp8 and mxfp4 steps and the
+products section alone (how a build with another W4_UNIT_COLS in csrc/gemv_route.h was compared)."""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    OUT.append(s)
+
+
+def med3(reps, unit=1.0):
+    return "  ".join("%8.3f" % (statistics.median(r) * unit) for r in reps) + "    %8.3f .. %8.3f" % (
+        min(min(r) for r in reps) * unit, max(max(r) for r in reps) * unit)
+
+
+def mid(reps):
+    return statistics.median([statistics.median(r) for r in reps])
+
+
+def timed(fn, reset, stream):
+    """ms of fn() on `stream`: the events sit on the stream the work runs on"""
+    with torch.cuda.stream(stream):
+        if reset:
+            reset()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+    return a.elapsed_time(b)
+
+
+def interleaved(lines, args, warm=5):
+    """lines: name -> (fn, reset, stream).  -> name -> [reps][calls] ms"""
+    for line in lines.values():
+        for _ in range(warm):
+            timed(*line)
+    reps = {k: [[] for _ in range(args.reps)] for k in lines}
+    for r in range(args.reps):
+        for _ in range(args.blocks):
+            for k, line in lines.items():
+                timed(*line)
+                reps[k][r] += [timed(*line) for _ in range(args.per_block)]
+    return reps
+
+
+def report(title, reps, base, unit=1.0, what="ms"):
+    say(title + ": events %s, median of each of %d repetitions    min .. max of all calls" % (what, len(next(iter(reps.values())))))
+    for k, r in reps.items():
+        say("  %-28s %s    ratio to %s %.3f" % (k, med3(r, unit), base, mid(r) / mid(reps[base])))
+    say()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mxfp4.txt"))
+    ap.add_argument("--rows", type=int, default=259)
+    ap.add_argument("--blocks", type=int, default=4)
+    ap.add_argument("--per-block", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", default="all", choices=["all", "steps", "products"])
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.tree))
+    sys.path.insert(1, ROOT)
+    assert torch.cuda.is_available(), "a timing needs the MI355X"
+    import bench
+    from spatialrgpt_amd import _lib as L, ops
+    from spatialrgpt_amd.engine import SrgptEngine
+    from spatialrgpt_amd.weights import synth_state_dict
+
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    cfg = bench.make_cfg("vila15_8b")
+    lib = L.load()
+    have4 = hasattr(lib, "srgpt_gemv_w4")
+    formats = ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only == "all" else [])
+    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4"}
+    eng = {}
+    for f in formats:
+        sd = synth_state_dict(cfg, seed=0, dtype=dt, device=dev)
+        eng[f] = SrgptEngine(cfg, sd, device=dev, dtype=dt, rope_positions=1024, consume_state_dict=True, llm_weight_format=f)
+        del sd
+    say("scripts/time_mxfp4.py --only %s, tree %s: VILA1.5-8B geometry (hidden %d, inter %d, %d layers, heads %d / %d, vocab %d), "
+        "synthetic weights, %s, %d CUs" % (args.only, os.path.relpath(os.path.abspath(args.tree), ROOT), cfg.hidden, cfg.inter, cfg.layers, cfg.heads, cfg.kv_heads,
+                                           cfg.vocab, torch.cuda.get_device_name(0), lib.srgpt_device_cus()))
+    say()
+    g = torch.Generator(device=dev).manual_seed(3)
+
+    def step_line(f, B, T=None):
+        """a fresh state of B sequences over `rows` cached rows and its captured plain (T None) or lookup (T rows) step"""
+        e = eng[f]
+        x = (torch.randn((B, args.rows, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
+        st, _, _ = e.prefill(x, max_new=64, fresh_state=True)
+        with torch.cuda.stream(e.stream):
+            e.stream.wait_stream(torch.cuda.default_stream())
+            L.check(lib.srgpt_llm_sample_first(C.byref(e.w.llm), C.byref(st.c), ops._stream()))
+            if T is None:
+                graph = st.ensure_graph()
+            else:
+                st.ensure_lookup(T - 1, 2, None)
+                graph = st.ensure_lookup_graph()
+        torch.cuda.synchronize()
+
+        def reset():
+            st.pos.fill_(args.rows)
+            st.step.fill_(1)
+
+        def fn():
+            L.check(lib.srgpt_graph_launch(graph, 1, ops._stream()))
+
+        def check():
+            rc = lib.srgpt_llm_decode_sync_state(C.byref(e.w.llm), C.byref(st.c), ops._stream())
+            assert rc == 0, L.last_error()
+
+        return (fn, reset, e.stream), check, st
+
+    checks, keep = [], []
+
+    def section(title, specs, base):
+        lines = {}
+        for label, (f, B, T) in specs.items():
+            line, check, st = step_line(f, B, T)
+            lines[label] = line
+            checks.append(check)
+            keep.append(st)
+        reps = interleaved(lines, args)
+        report(title, reps, base)
+        return reps
+
+    shared = torch.cuda.Stream()  # the product graphs' stream
+
+    section("captured batch-1 decode step, %d cached rows" % args.rows, {name[f]: (f, 1, None) for f in formats}, "fp8")
+    if args.only == "all" and have4:
+        section("captured lookup step, K = 3 (T = 4 rows), batch 1", {"fp8": ("fp8", 1, 4), "mxfp4": ("mxfp4", 1, 4)}, "fp8")
+        section("captured batch-8 decode step (fp8: one MFMA pass of 8 rows; mxfp4: two VALU passes of 4)",
+                {"fp8": ("fp8", 8, None), "mxfp4": ("mxfp4", 8, None)}, "fp8")
+    for c in checks:
+        c()
+    keep.clear()
+    if args.only in ("all", "products") and have4:
+        # ---- the four products alone
+        w8, w4 = eng["fp8"].w, eng["mxfp4"].w
+        Hd, I, HqD, QW = cfg.hidden, cfg.inter, cfg.heads * cfg.head_dim, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim
+        shapes = {"q/k/v   [%d, %d] norm" % (QW, Hd): ("wqkv", QW, Hd, True, False, False),
+                  "o_proj  [%d, %d] residual" % (Hd, HqD): ("wo", Hd, HqD, False, True, False),
+                  "gate/up [2 x %d, %d] norm, SwiGLU" % (I, Hd): ("wgu", I, Hd, True, False, True),
+                  "down    [%d, %d] residual" % (Hd, I): ("wdown", Hd, I, False, True, False)}
+        say("the four products alone, one launch per layer (%d matrices) in a captured graph: us per launch" % cfg.layers)
+        with torch.cuda.stream(shared):
+            for title, (k, N, K, norm, res, sw) in shapes.items():
+                for rows in (1, 2, 3, 4):
+                    x = (torch.randn((rows, K), device=dev, generator=g) * 0.5).to(dt)
+                    nw = torch.ones((K,), device=dev, dtype=dt) if norm else None
+                    r = (torch.randn((rows, N), device=dev, generator=g) * 0.5).to(dt) if res else None
+                    out = torch.empty((rows, N), device=dev, dtype=dt)
+
+                    def launches(fmt):
+                        for i in range(cfg.layers):
+                            if fmt == "fp8":
+                                ops.gemv_w8(x, w8.llm_q[k][0][i], w8.llm_q[k][1][i], nw, 1e-5, r, sw, out=out)
+                            else:
+                                ops.gemv_w4(x, w4.llm_q4[k][0][i], w4.llm_q4[k][1][i], nw, 1e-5, r, sw, out=out)
+
+                    lines = {}
+                    for fmt in ("fp8", "mxfp4"):
+                        launches(fmt)  # first use of an instance outside the capture
+                        torch.cuda.synchronize()
+                        gr = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(gr, stream=shared):
+                            launches(fmt)
+                        lines[fmt] = (gr.replay, None, shared)
+                    reps = interleaved(lines, args)
+                    say("  %-36s %d row%s   fp8 %7.2f (%7.2f .. %7.2f)   mxfp4 %7.2f (%7.2f .. %7.2f)   mxfp4 / fp8 %.3f" % (
+                        title, rows, " " if rows == 1 else "s",
+                        mid(reps["fp8"]) * 1e3 / cfg.layers, min(map(min, reps["fp8"])) * 1e3 / cfg.layers, max(map(max, reps["fp8"])) * 1e3 / cfg.layers,
+                        mid(reps["mxfp4"]) * 1e3 / cfg.layers, min(map(min, reps["mxfp4"])) * 1e3 / cfg.layers, max(map(max, reps["mxfp4"])) * 1e3 / cfg.layers,
+                        mid(reps["mxfp4"]) / mid(reps["fp8"])))
+        say()
+
+    if args.only == "all" and have4:
+        # ---- prefill and append
+        x = (torch.randn((1, args.rows + 32, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
+        head, tail = x[:, :args.rows].contiguous(), x[:, args.rows:].contiguous()
+        lines_p, lines_a = {}, {}
+        for f in ("fp8", "mxfp4"):
+            e = eng[f]
+            st = e.new_state(1, 512, 4)
+            keep.append(st)
+
+            def prefill(e=e, st=st):
+                e.prefill(head, max_new=4, state=st)
+
+            def append(e=e, st=st):
+                e.append(st, tail)
+
+            def back(st=st):
+                st.pos.fill_(args.rows)
+                st.host_len = [args.rows]
+
+            with torch.cuda.stream(e.stream):
+                prefill()
+            torch.cuda.synchronize()
+            lines_p[f] = (prefill, None, e.stream)
+            lines_a[f] = (append, back, e.stream)
+        report("%d-row prefill, eager" % args.rows, interleaved(lines_p, args), "fp8")
+        report("32-row append over %d cached rows, eager" % args.rows, interleaved(lines_a, args), "fp8")
+
+    say("llm_weight_bytes() (streamed per decoded token at batch 1):")
+    base = eng[formats[0]].w.llm_weight_bytes()
+    for f in formats:
+        n = eng[f].w.llm_weight_bytes()
+        say("  %-6s %12d bytes   %.3f of %s" % (name[f], n, n / base, name[formats[0]]))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(OUT) + "\n")
+
+
+if __name__ == "__main__":
+    main()

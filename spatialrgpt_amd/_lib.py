@@ -48,6 +48,8 @@ class LlmWeights(C.Structure):
         ("fp8_act", i32),
         ("wqkv8p", C.POINTER(vp)), ("wo8p", C.POINTER(vp)), ("wgu8p", C.POINTER(vp)), ("wdown8p", C.POINTER(vp)),
         ("pk_rows_qkv", i32), ("pk_rows_o", i32), ("pk_rows_gu", i32), ("pk_rows_down", i32),
+        ("wqkv4", C.POINTER(vp)), ("wqkv4_scale", C.POINTER(vp)), ("wo4", C.POINTER(vp)), ("wo4_scale", C.POINTER(vp)),
+        ("wgu4", C.POINTER(vp)), ("wgu4_scale", C.POINTER(vp)), ("wdown4", C.POINTER(vp)), ("wdown4_scale", C.POINTER(vp)),
     ]
 
 
@@ -113,6 +115,8 @@ _SIGNATURES = {
     "srgpt_gemm_w8a8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "srgpt_gemv": (i32, [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemv_w8": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "srgpt_gemv_w4": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "srgpt_dequant_mxfp4": (i32, [vp, vp, vp, i32, i32, vp]),
     "srgpt_splice_scratch_ints": (i64, [i32, i32]),
     "srgpt_splice_plan": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
     "srgpt_splice_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp]),

@@ -253,7 +253,8 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
                           device="cuda", dtype=torch.bfloat16, prefix_reuse=False, lookup_sampling=False,
                           lookup_batch=False, **kwargs):
     if load_4bit:
-        raise NotImplementedError("bitsandbytes 4-bit loading is out of scope (builder.py:40-60)")
+        raise NotImplementedError("bitsandbytes 4-bit loading is out of scope (builder.py:40-60); the engine's own 4-bit option is "
+                                  "llm_weight_format=\"mxfp4\" (INTEGRATION.md)")
     # load_8bit (bitsandbytes int8 in the reference, builder.py:51-52) maps to the engine's 8-bit option: weight-only OCP
     # fp8 (e4m3fn, one scale per output row) for the LLM matrices the decode step streams
     llm_weight_format = "fp8" if load_8bit else kwargs.pop("llm_weight_format", "native")

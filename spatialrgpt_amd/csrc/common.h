@@ -276,8 +276,16 @@ extern "C" int srgpt_device_cus(void);
 // family; anything else gets no prefetch: 2+ rows (the skinny kernel -- its mapping, 4-row groups of block p's 16-row units, was
 // measured: o_proj +1 % at 8 fp8 rows, -2 % at 4 bf16 rows per decode step, not kept; at 2 rows, which moved to the skinny kernel in
 // round 3, the VALU mapping's prefetch costs 1.6 % per step: profiles/r03_skinny_min_batch.txt).
+// fp8 == SRGPT_PREFETCH_W4: W holds MXFP4 codes (gemv_w4.hip: K / 2 bytes per row, a unit is W4_UNIT_COLS consecutive rows).
+constexpr int SRGPT_PREFETCH_W4 = 2;
 static inline SrgptPrefetch srgpt_prefetch_for_gemv(const void* W, int N, int K, int fp8, int batch) {
   SrgptPrefetch pf{nullptr, 0, 0, 1, 1, 0, 1, 0, 0};
+  if (fp8 == SRGPT_PREFETCH_W4) {
+    if (!W || batch > 1 || K % 2048 != 0) return pf;  // whole 1-KiB wave loads per row of codes
+    const int grid = gemv_w4_launch(1, N, K, false, srgpt_device_cus()).grid;
+    return SrgptPrefetch{reinterpret_cast<const char*>(W), K / 2, (N + W4_UNIT_COLS - 1) / W4_UNIT_COLS, W4_UNIT_COLS, W4_UNIT_COLS, 1,
+                         grid, grid, N};
+  }
   const long long row_bytes = fp8 ? (long long)K : 2LL * K;
   if (!W || batch > 1 || row_bytes % 1024 != 0) return pf;
   const GemvFamily family = gemv_route(1, K, true, fp8 != 0, false).family;

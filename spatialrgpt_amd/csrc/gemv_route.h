@@ -10,6 +10,7 @@ enum GemvFamily {
   GEMV_REG,     // gemv_reg_kernel<SWIGLU, false, NIT> (gemv.hip): VALU, one bf16 row held in registers
   GEMV_W8,      // gemv_w8_kernel<1, SWIGLU, NX> (gemv_w8.hip): VALU, one bf16 row, fp8 weights
   GEMV_SKINNY,  // skinny_kernel<SWIGLU, NI, NW, W8, PUB, PK> (skinny.hip): MFMA, up to 16 bf16 rows
+  GEMV_W4,      // gemv_w4_kernel<B, SWIGLU, NX> (gemv_w4.hip): VALU, 1 - 4 bf16 rows, MXFP4 weights (its own route functions below)
 };
 
 // How a call is cut: ceil(rows / chunk) launches of up to `chunk` rows, each streaming the weights once, ALL on `family` -- a
@@ -155,5 +156,28 @@ inline GemvSkinnyLaunch gemv_skinny_launch(int rows, int N, bool norm, bool ss_i
   l.PUB = ss_in;
   l.PK = packed != 0;
   l.lds = gemv_skinny_lds(l.NI, l.NW, l.PK);
+  return l;
+}
+
+// ---- srgpt_gemv_w4 (gemv_w4.hip): MXFP4 weights, bf16 activations.  One kernel family for every row count: there is no MFMA kernel
+// for the format, so a longer call is cut into launches of at most W4_MAX_ROWS rows (the kernel's template argument), each a pass
+// over the code bytes.  A unit (one wave's work item) is W4_UNIT_COLS output columns.  A K = 4096 row of codes is only two 1-KiB
+// wave loads, so four columns would put gemv_w8.hip's 8 (SwiGLU: 16) KiB per wave in flight -- measured, that is SLOWER than two
+// (profiles/mxfp4.txt: the batch-1 step 1.48 ms at 2 columns, 1.64 at 4, 1.98 at 8; per product 2 wins or ties at 1 - 2 rows): twice
+// the units give the short launches twice the waves, and 4 - 8 KiB per wave over 8 waves per CU already cover the HBM latency.
+constexpr int W4_MAX_ROWS = 4;
+constexpr int W4_UNIT_COLS = 2;
+
+inline GemvRoute gemv_w4_route(int rows) { return GemvRoute{GEMV_W4, rows < W4_MAX_ROWS ? (rows < 1 ? 1 : rows) : W4_MAX_ROWS}; }
+
+// one launch: B rows (one chunk of gemv_w4_route); K % 32 == 0
+inline GemvValuLaunch gemv_w4_launch(int B, int N, int K, bool swiglu, int cus) {
+  using namespace gemv_route_detail;
+  (void)swiglu;  // a SwiGLU unit is the same W4_UNIT_COLS output columns (twice the weight rows)
+  GemvValuLaunch l{B, 0, 0, 0, 0, (long long)B * K * 2, false};
+  l.raise_lds_limit = l.lds > 48 * 1024;
+  l.NX = valu_nx(B * (K / 8));
+  l.NIT = ceil_div(K / 32, 64);
+  l.grid = valu_grid(ceil_div(N, W4_UNIT_COLS), l.lds, cus);
   return l;
 }

@@ -65,6 +65,7 @@ struct LlmWs {
   // (the keys the row may see, its pos after the call).  They LIVE IN qkvd: the decode step's q/k/v scratch is dead between steps
   // (every step writes it before reading it) and holds >= 12 bytes per row, so the workspace does not grow
   int *app_pos0, *app_kvlen;
+  void* w4;  // MXFP4 weights: the bf16 expansion of the matrix the prefill multiplies next (sized for the largest of the four)
   size_t total;
 };
 LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws) {
@@ -106,6 +107,14 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
   static_assert(sizeof(int) == 4, "two ints per row must fit the 12 bytes a row of qkvd has at least");
   l.app_pos0 = reinterpret_cast<int*>(l.qkvd);
   l.app_kvlen = l.qkvd ? l.app_pos0 + batch : nullptr;
+  l.w4 = nullptr;
+  if (w->wqkv4) {  // last: the layout of every other format is untouched
+    const size_t hqd = (size_t)w->heads * w->head_dim;
+    size_t n = qkvw * w->hidden;
+    if (hqd * w->hidden > n) n = hqd * w->hidden;
+    if (2 * (size_t)w->inter * w->hidden > n) n = 2 * (size_t)w->inter * w->hidden;
+    l.w4 = c.take(n * 2);
+  }
   l.total = c.off;
   return l;
 }
@@ -384,12 +393,24 @@ namespace {
 // FMT_DTYPE: the dtype matrices (srgpt_gemm / srgpt_gemv).  fp8 copies present -> they are the weights and the dtype matrices are
 // not touched: FMT_W8A16 (srgpt_gemm_w8 / srgpt_gemv_w8; the decode step streams half the bytes per token), or with fp8_act
 // FMT_W8A8: the prefill's per-token e4m3 activations on the fp8 matrix pipe (include/srgpt.h).  The decode step and the
-// all-position lm_head (fp32 logits, parity hook) are W8A16 under both fp8 formats.
-enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8 };
+// all-position lm_head (fp32 logits, parity hook) are W8A16 under both fp8 formats.  MXFP4 copies present -> FMT_W4A16: the four
+// layer matrices are codes + block scales (srgpt_gemv_w4 in the decode steps, srgpt_dequant_mxfp4 + the bf16 launches in the
+// prefill), lm_head is fp8 and multiplied as under FMT_W8A16.
+enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8, FMT_W4A16 };
 
 // the format of `w` and the check that fp8 weights are complete, on the host before any launch; `fn`: the entry point the message names
 int llm_format(const srgpt_llm_weights* w, const char* fn, LlmFormat* fmt) {
   *fmt = FMT_DTYPE;
+  if (w->wqkv4) {
+    SRGPT_CHECK(w->dtype == SRGPT_BF16 && w->wo4 && w->wgu4 && w->wdown4 && w->wqkv4_scale && w->wo4_scale && w->wgu4_scale &&
+                    w->wdown4_scale && w->lm_head8 && w->lm_head_scale,
+                SRGPT_ERR_ARG, "%s: MXFP4 weights need bf16 activations, all four matrices + block scales and the fp8 lm_head + scales", fn);
+    SRGPT_CHECK(!w->wqkv8, SRGPT_ERR_ARG, "%s: both fp8 and MXFP4 copies of the layer matrices are set", fn);
+    SRGPT_CHECK(w->hidden % 32 == 0 && w->inter % 32 == 0 && (w->heads * w->head_dim) % 32 == 0, SRGPT_ERR_ARG,
+                "%s: MXFP4 weights need hidden, inter and heads * head_dim to be multiples of 32", fn);
+    *fmt = FMT_W4A16;
+    return SRGPT_OK;
+  }
   if (!w->wqkv8) return SRGPT_OK;
   SRGPT_CHECK(w->dtype == SRGPT_BF16 && w->wo8 && w->wgu8 && w->wdown8 && w->lm_head8 && w->wqkv_scale && w->wo_scale &&
                   w->wgu_scale && w->wdown_scale && w->lm_head_scale,
@@ -405,14 +426,21 @@ struct Mat {
   const float* scale;  // their row scales
   const void* pk;      // packed copy of the fp8 bytes for the MFMA decode kernel, or NULL: stream the row-major ones
   int pk_rows;         // its rows per granule
+  const void* w4;      // MXFP4 codes (FMT_W4A16 only; then w / w8 are not read)
+  const void* scale4;  // their E8M0 block scales
 };
 struct LayerMats {
   Mat qkv, o, gu, down;
 };
 LayerMats layer_mats(const srgpt_llm_weights* w, LlmFormat fmt, int i) {
+  if (fmt == FMT_W4A16) {
+    auto mat4 = [&](const void* const* W4, const void* const* sc4) { return Mat{nullptr, nullptr, nullptr, nullptr, 0, W4[i], sc4[i]}; };
+    return LayerMats{mat4(w->wqkv4, w->wqkv4_scale), mat4(w->wo4, w->wo4_scale), mat4(w->wgu4, w->wgu4_scale),
+                     mat4(w->wdown4, w->wdown4_scale)};
+  }
   const bool fp8 = fmt != FMT_DTYPE;
   auto mat = [&](const void* const* W, const void* const* W8, const float* const* sc, const void* const* pk, int pk_rows) {
-    return Mat{W[i], fp8 ? W8[i] : nullptr, fp8 ? sc[i] : nullptr, fp8 && pk != nullptr ? pk[i] : nullptr, pk_rows};
+    return Mat{W[i], fp8 ? W8[i] : nullptr, fp8 ? sc[i] : nullptr, fp8 && pk != nullptr ? pk[i] : nullptr, pk_rows, nullptr, nullptr};
   };
   return LayerMats{mat(w->wqkv, w->wqkv8, w->wqkv_scale, w->wqkv8p, w->pk_rows_qkv), mat(w->wo, w->wo8, w->wo_scale, w->wo8p, w->pk_rows_o),
                    mat(w->wgu, w->wgu8, w->wgu_scale, w->wgu8p, w->pk_rows_gu),
@@ -470,19 +498,46 @@ struct Prefill {
   // bit-identical to the two launches, one launch and one pass over the rows less per norm), so only layer 0 normalises l.x itself
   int layer_dtype(int i) const {
     const LayerMats m = layer_mats(w, fmt, i);
+    return layer_bf16_launches(i, [](const Mat& a, int, int, const void** W) {
+      *W = a.w;
+      return (int)SRGPT_OK;
+    }, m);
+  }
+
+  // MXFP4 matrices: each is expanded (srgpt_dequant_mxfp4, exact) into the workspace's one bf16 scratch just before its product, and
+  // the launches are layer_dtype's on the scratch: every byte the prefill writes equals a bf16 engine's on the dequantised weights.
+  // The stream orders product -> next expansion, so one scratch serves the four.  Price: one more pass over bf16-sized bytes per
+  // matrix (include/srgpt.h); a W4 operand inside the GEMM is what is left.
+  int layer_w4a16(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    return layer_bf16_launches(i, [this](const Mat& a, int N, int K, const void** W) {
+      *W = l.w4;
+      return srgpt_dequant_mxfp4(a.w4, a.scale4, l.w4, N, K, stream);
+    }, m);
+  }
+
+  // the launches of a layer over row-major matrices of the engine dtype; get(mat, N, K, &W) makes matrix `mat` [N, K] available at W
+  // just before the product that reads it
+  template <typename Get>
+  int layer_bf16_launches(int i, Get&& get, const LayerMats& m) const {
+    const void* W = nullptr;
     if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
     // projection + RoPE + cache append: the rotation rides in the split-K reduction
-    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, m.qkv.w, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
+    SRGPT_TRY(get(m.qkv, QW, Hd, &W));
+    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, W, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
                                         w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim, st->max_pos, dt, stream));
     SRGPT_TRY(attention(i));
-    SRGPT_TRY(srgpt_gemm_norm(l.attn, m.o.w, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
+    SRGPT_TRY(get(m.o, Hd, HqD, &W));
+    SRGPT_TRY(srgpt_gemm_norm(l.attn, W, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
                               l.h, w->rms_eps, dt, stream));
     // gate / up + SiLU * up: the activation is the product's epilogue on the whole-M kernel
-    SRGPT_TRY(srgpt_gemm_swiglu(l.h, m.gu.w, l.act, rows, I, Hd, l.gu, l.gws, gws_bytes(), dt, stream));
+    SRGPT_TRY(get(m.gu, 2 * I, Hd, &W));
+    SRGPT_TRY(srgpt_gemm_swiglu(l.h, W, l.act, rows, I, Hd, l.gu, l.gws, gws_bytes(), dt, stream));
+    SRGPT_TRY(get(m.down, Hd, I, &W));
     if (i + 1 < w->layers)
-      return srgpt_gemm_norm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->attn_norm[i + 1],
+      return srgpt_gemm_norm(l.act, W, nullptr, l.x, l.x, rows, Hd, I, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->attn_norm[i + 1],
                              nullptr, l.h, w->rms_eps, dt, stream);
-    return srgpt_gemm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, I, Hd, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, l.gws,
+    return srgpt_gemm(l.act, W, nullptr, l.x, l.x, rows, Hd, I, I, Hd, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, l.gws,
                       gws_bytes(), dt, stream);
   }
 
@@ -594,6 +649,7 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
       case FMT_DTYPE: SRGPT_TRY(p.layer_dtype(i)); break;
       case FMT_W8A16: SRGPT_TRY(p.layer_w8a16(i)); break;
       case FMT_W8A8: SRGPT_TRY(wide ? p.layer_w8a8_wide(i) : p.layer_w8a8(i)); break;
+      case FMT_W4A16: SRGPT_TRY(p.layer_w4a16(i)); break;
     }
     if (hidden_out)
       SRGPT_HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(hidden_out) + (size_t)(i + 1) * hid_bytes, l.x, hid_bytes,
@@ -702,8 +758,17 @@ struct DecodeStep {
   bool fp8, pub;
   srgpt_stream_t stream;
 
+  // fp8: the matrices that are not MXFP4 (under FMT_W4A16: lm_head) are fp8
+  static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, int rows, srgpt_stream_t stream) {
+    const bool fp8 = fmt != FMT_DTYPE;
+    const bool pub = fmt != FMT_W4A16 && gemv_rowss_supported(rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
+    return DecodeStep{w, rows, fp8, pub, stream};
+  }
+
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
            const float* ss_in, float* ss_out) const {
+    if (m.w4)  // MXFP4 layer matrix (pub is false under the format: its kernel neither reads nor publishes row statistics)
+      return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
     if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
       return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out,
                               m.pk ? m.pk_rows : 0, stream);
@@ -735,8 +800,8 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
                        (int64_t)w->vocab, d.err);
     SRGPT_LAUNCH_CHECK();
   }
-  const bool fp8 = fmt != FMT_DTYPE;
-  const DecodeStep ds{w, B, fp8, gemv_rowss_supported(B, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
+  const bool fp8 = fmt != FMT_DTYPE, w4 = fmt == FMT_W4A16;
+  const DecodeStep ds = DecodeStep::make(w, fmt, B, stream);
   // the row statistics (layer 0's q/k/v normalises the embedding rows itself)
   float* const ss_attn = d.rowss;                                       // rows after the attention block's residual add
   float* const ss_mlp = d.rowss + (size_t)B * SRGPT_ROWSS_STRIDE;       // rows after the MLP block's
@@ -749,12 +814,13 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
     // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
     // (profiles/r03_fused_attention_oproj.txt)
     SRGPT_TRY(srgpt_decode_attention_pf(d.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, d.attnd, d.dws, B, Hq, Hkv, D,
-                                        st->max_pos, dt, fp8 ? m.o.w8 : m.o.w, Hd, Hq * D, fp8 ? 1 : 0, stream));
+                                        st->max_pos, dt, w4 ? m.o.w4 : fp8 ? m.o.w8 : m.o.w, Hd, Hq * D,
+                                        w4 ? SRGPT_PREFETCH_W4 : fp8 ? 1 : 0, stream));
     SRGPT_TRY(ds.gemv(m.o, d.attnd, nullptr, d.xd, d.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
     SRGPT_TRY(ds.gemv(m.gu, d.xd, w->mlp_norm[i], nullptr, d.actd, I, Hd, 1, 0, ss_attn, nullptr));
     SRGPT_TRY(ds.gemv(m.down, d.actd, nullptr, d.xd, d.xd, Hd, I, 0, 0, nullptr, ss_mlp));
   }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
   return greedy_pick(w, st, d, 1, p, s);
 }
@@ -908,8 +974,7 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
   SRGPT_TRY(srgpt_lookup_draft_launch(lk->prompt_ids, lk->n_prompt, st->out_ids, st->step, st->max_new, T - 1, lk->max_ngram,
                                       (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
   SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, T, Hd, dt, stream));
-  const bool fp8 = fmt != FMT_DTYPE;
-  const DecodeStep ds{w, T, fp8, gemv_rowss_supported(T, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
+  const DecodeStep ds = DecodeStep::make(w, fmt, T, stream);
   float* const ss_attn = l.rowss;
   float* const ss_mlp = l.rowss + (size_t)T * SRGPT_ROWSS_STRIDE;
   for (int i = 0; i < w->layers; ++i) {
@@ -923,7 +988,7 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
     SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
     SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
   }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
   if (st->sampling) {
     if (sampler == SRGPT_SAMPLER_FULL) {
@@ -1059,8 +1124,7 @@ static int lookup_step_batch_impl(const srgpt_llm_weights* w, srgpt_llm_state* s
   SRGPT_TRY(srgpt_lookup_draft_batch_launch(lk->prompt_ids, lk->ld_prompt, lk->n_prompt, st->out_ids, lk->steps, B, st->max_new, T - 1,
                                             lk->max_ngram, (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
   SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, R, Hd, dt, stream));
-  const bool fp8 = fmt != FMT_DTYPE;
-  const DecodeStep ds{w, R, fp8, gemv_rowss_supported(R, dt == SRGPT_BF16, fp8, srgpt_device_cus()), stream};
+  const DecodeStep ds = DecodeStep::make(w, fmt, R, stream);
   float* const ss_attn = l.rowss;
   float* const ss_mlp = l.rowss + (size_t)R * SRGPT_ROWSS_STRIDE;
   for (int i = 0; i < w->layers; ++i) {
@@ -1074,7 +1138,7 @@ static int lookup_step_batch_impl(const srgpt_llm_weights* w, srgpt_llm_state* s
     SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
     SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
   }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
+  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
                     0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, R), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
   SRGPT_LAUNCH_CHECK();

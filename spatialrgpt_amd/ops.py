@@ -157,6 +157,77 @@ def gemv_w8(x, w8, wscale, norm_w=None, eps=0.0, residual=None, swiglu=False, ou
     return out
 
 
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitudes of the OCP e2m1 codes 0 .. 7 (bit 3 of a code: the sign)
+
+
+def quantize_mxfp4_rows(w: torch.Tensor):
+    """Weight-only MXFP4 quantisation (OCP Microscaling FP4; include/srgpt.h, srgpt_gemv_w4): w [N, K], K % 32 == 0.  Per block of
+    32 consecutive values of a row: scale = the smallest power of two with max|block| / scale <= 6 (quantize_fp8_rows' rule: frexp /
+    ldexp, exact on every device, nothing saturates), its exponent clamped to [-64, 64]; codes = round to nearest even of
+    block / scale onto the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6} with a sign bit.  An all-zero block gets scale 1 and zero codes.
+    Returns (codes uint8 [N, K / 2]: element k in byte k / 2, low nibble = even k; scales uint8 [N, K / 32]: E8M0 bytes, value
+    2^(byte - 127), never 0 or 255; the dequantised weights code * scale in w.dtype -- exact in bf16).
+    Like fp8 the format is opt-in and changes the numbers; its accuracy cost on a trained checkpoint is unmeasured."""
+    if w.dim() != 2 or w.shape[1] % 32:
+        raise ValueError(f"quantize_mxfp4_rows: a matrix [N, K] with K % 32 == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    wf = w.float().reshape(N, K // 32, 32)
+    amax = wf.abs().amax(dim=2)
+    m, e = torch.frexp(amax.clamp_min(2.0 ** -100))                 # amax = m * 2^e, m in [0.5, 1)
+    k = (e - 3 + (m > 0.75).to(e.dtype)).clamp(-64, 64)              # 6 = 0.75 * 2^3
+    k = torch.where(amax == 0, torch.zeros_like(k), k)
+    a = (wf * torch.ldexp(torch.ones_like(m), -k)[:, :, None]).abs().clamp_max(6.0)  # (only a clamped exponent can exceed 6)
+    # round to nearest even on the grid: steps of 0.5 below 2, of 1 below 4, of 2 above -- torch.round is half-to-even, and the even
+    # multiples of each step are the codes with a zero mantissa bit
+    r = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+    grid = torch.tensor(_E2M1_GRID, device=w.device, dtype=torch.float32)
+    mag = torch.bucketize(r, grid)                                    # r is on the grid: its index
+    neg = (wf < 0) & (mag > 0)                                        # (no negative zero: a zero has code 0)
+    code = (mag | neg.to(mag.dtype) << 3).to(torch.uint8).reshape(N, K)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    scales = (k + 127).to(torch.uint8).contiguous()
+    deq = (torch.where(neg, -r, r) * torch.ldexp(torch.ones_like(m), k)[:, :, None]).reshape(N, K).to(w.dtype)
+    return codes, scales, deq.contiguous()
+
+
+def _check_mxfp4(op: str, w4: torch.Tensor, wscale8: torch.Tensor):
+    if w4.dtype != torch.uint8 or wscale8.dtype != torch.uint8 or w4.dim() != 2 or wscale8.dim() != 2:
+        raise ValueError(f"{op}: codes and scales must be uint8 matrices")
+    if not (w4.is_contiguous() and wscale8.is_contiguous()) or w4.shape[0] != wscale8.shape[0] or w4.shape[1] != 16 * wscale8.shape[1]:
+        raise ValueError(f"{op}: codes [N, K / 2] and scales [N, K / 32] must be contiguous and agree, got {tuple(w4.shape)} and "
+                         f"{tuple(wscale8.shape)}")
+
+
+def gemv_w4(x, w4, wscale8, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False):
+    """decode product with MXFP4 weights: x [B,K] bf16, w4 uint8 [N(,2N if swiglu),K/2] codes, wscale8 uint8 [rows,K/32] -> [B,N]."""
+    _dev(x, w4, wscale8, norm_w, residual)
+    _same_dtype("gemv_w4", x, norm_weight=norm_w, residual=residual)
+    if x.dtype != torch.bfloat16:
+        raise ValueError("gemv_w4: x must be bf16")
+    _check_mxfp4("gemv_w4", w4, wscale8)
+    B, K = x.shape
+    if w4.shape[1] * 2 != K:
+        raise ValueError(f"gemv_w4: x has K = {K}, the codes {w4.shape[1] * 2}")
+    N = w4.shape[0] // 2 if swiglu else w4.shape[0]
+    if out is None:
+        out = torch.empty((B, N), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    L.check(L.load().srgpt_gemv_w4(_p(_c(x)), _p(w4), _p(wscale8), _p(norm_w), float(eps), _p(residual), _p(out), B, N, K,
+                                   int(swiglu), int(out_f32), _stream()))
+    return out
+
+
+def dequant_mxfp4(w4, wscale8, out=None):
+    """the exact bf16 matrix [N, K] of MXFP4 codes [N, K / 2] and E8M0 block scales [N, K / 32] (srgpt_dequant_mxfp4)."""
+    _dev(w4, wscale8)
+    _check_mxfp4("dequant_mxfp4", w4, wscale8)
+    N, K = w4.shape[0], w4.shape[1] * 2
+    if out is None:
+        out = torch.empty((N, K), device=w4.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (N, K)
+    L.check(L.load().srgpt_dequant_mxfp4(_p(w4), _p(wscale8), _p(out), N, K, _stream()))
+    return out
+
+
 def kv_beam_reorder(kcache, vcache, beam_idx, num_beams: int, live: int) -> bool:
     """srgpt_kv_beam_reorder: in-place permutation of the live cache rows by the beam indices (kcache / vcache [layers, batch *
     num_beams, kv_heads, max_pos, head_dim], beam_idx int64 [batch * num_beams] on the device).  False: this beam count is not

@@ -55,7 +55,11 @@ class PreparedWeights:
         """llm_weight_format: "native" (the engine dtype) or "fp8" -- weight-only OCP e4m3fn quantisation of the five
         streamed LLM matrices with one fp32 (power-of-two) scale per output row (BASELINE config 5; bf16 engines only).  The
         fp8 bytes are the ONLY copy of those matrices in HBM: decode streams them (srgpt_gemv_w8), prefill multiplies them
-        (srgpt_gemm_w8); `dequantised(name, layer)` rebuilds the bf16 values for checks."""
+        (srgpt_gemm_w8); `dequantised(name, layer)` rebuilds the bf16 values for checks.
+        "mxfp4": the 4-bit option (bf16 engines only) -- the four per-layer matrices as OCP e2m1 codes with one E8M0 scale per 32
+        values (ops.quantize_mxfp4_rows; include/srgpt.h, srgpt_gemv_w4), a quarter of the bf16 bytes and the only copy in HBM;
+        lm_head is held as under "fp8".  Decode streams the codes (srgpt_gemv_w4); prefill expands each matrix into a bf16 scratch
+        just before its product.  Opt-in, it changes the numbers; its accuracy cost on a trained checkpoint is unmeasured."""
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         # parts: which components to materialise -- all of them for the model, ONE for the module-level factories
         # (spatialrgpt_amd/factories.py: the reference's build_vision_tower / build_mm_projector / build_region_extractor /
@@ -67,7 +71,7 @@ class PreparedWeights:
         self.vit = self.llm = None
         self.vocab = 0
         self.rope_len = 0
-        if llm_weight_format not in ("native", "fp8", "fp8_w8a8"):
+        if llm_weight_format not in ("native", "fp8", "fp8_w8a8", "mxfp4"):
             raise ValueError(f"unknown llm_weight_format {llm_weight_format!r}")
         # "fp8_w8a8": the same fp8 weights; prefill additionally quantises every GEMM input per token to e4m3 and multiplies on
         # the fp8 matrix pipe (srgpt_gemm_w8a8) -- opt-in, it changes the numbers; decode stays W8A16
@@ -78,6 +82,11 @@ class PreparedWeights:
                 raise ValueError("fp8_w8a8 needs hidden, inter and heads * head_dim to be multiples of 128")
         if llm_weight_format == "fp8" and dtype != torch.bfloat16:
             raise ValueError("fp8 LLM weights need a bf16 engine")
+        if llm_weight_format == "mxfp4":
+            if dtype != torch.bfloat16:
+                raise ValueError("mxfp4 LLM weights need a bf16 engine")
+            if cfg.hidden % 32 or cfg.inter % 32 or (cfg.heads * cfg.head_dim) % 32:
+                raise ValueError("mxfp4 needs hidden, inter and heads * head_dim to be multiples of 32")
         self.llm_weight_format = llm_weight_format
         if decode_layout not in ("packed", "rowmajor"):
             raise ValueError(f"unknown decode_layout {decode_layout!r}")
@@ -189,7 +198,22 @@ class PreparedWeights:
             lt["wgu"].append(torch.cat([get(q + "mlp.gate_proj.weight"), get(q + "mlp.up_proj.weight")], 0).contiguous())
             lt["wdown"].append(get(q + "mlp.down_proj.weight"))
         self.llm_t = lt
-        self.llm_q = None
+        self.llm_q = None   # fp8: name -> (codes per layer, row scales per layer); {} under "mxfp4" (lm_head alone is fp8)
+        self.llm_q4 = None  # mxfp4: name -> (codes per layer, E8M0 block scales per layer)
+        if llm_weight_format == "mxfp4":
+            from . import ops  # local import: ops needs the loaded library
+
+            q4 = {k: ([], []) for k in ("wqkv", "wo", "wgu", "wdown")}
+            for k in q4:
+                for i in range(cfg.layers):
+                    codes, scales, _ = ops.quantize_mxfp4_rows(lt[k][i])
+                    lt[k][i] = None  # the bf16 matrix is dropped: nothing reads it
+                    q4[k][0].append(codes)
+                    q4[k][1].append(scales)
+            self.lm_head8, self.lm_head_scale, _ = ops.quantize_fp8_rows(self.lm_head)
+            self.lm_head = None
+            self.llm_q4, self.llm_q = q4, {}
+            self.llm_pk, self.pk_rows = {}, {}
         if llm_weight_format == "fp8":
             from . import ops  # local import: ops needs the loaded library
 
@@ -246,6 +270,12 @@ class PreparedWeights:
                     self._keep.append(ap)
                     setattr(lw, k + "8p", ap)
                     setattr(lw, field, self.pk_rows[k])
+        if self.llm_q4 is not None:
+            for k, (cs, scs) in self.llm_q4.items():
+                a4, asc = _ptr_array(cs), _ptr_array(scs)
+                self._keep += [a4, asc]
+                setattr(lw, k + "4", a4)
+                setattr(lw, k + "4_scale", asc)
         lw.fp8_act = 1 if self.fp8_act else 0
         self.llm = lw
         self.vocab = self.embed.shape[0]
@@ -288,9 +318,12 @@ class PreparedWeights:
         self.vocab = n
 
     def dequantised(self, name: str, layer: int = 0) -> torch.Tensor:
-        """bf16 values of an fp8-held matrix ("wqkv" | "wo" | "wgu" | "wdown" | "lm_head"): code * scale, exact in bf16."""
+        """bf16 values of an fp8- or mxfp4-held matrix ("wqkv" | "wo" | "wgu" | "wdown" | "lm_head"): code * scale, exact in bf16."""
         if self.llm_q is None:
-            raise ValueError("weights are not fp8")
+            raise ValueError("weights are not fp8 or mxfp4")
+        if self.llm_q4 is not None and name != "lm_head":
+            from . import ops
+            return ops.dequant_mxfp4(self.llm_q4[name][0][layer], self.llm_q4[name][1][layer])
         q8, sc = (self.lm_head8, self.lm_head_scale) if name == "lm_head" else (self.llm_q[name][0][layer], self.llm_q[name][1][layer])
         return (q8.view(torch.float8_e4m3fn).float() * sc[:, None]).to(self.dtype)
 
@@ -306,6 +339,8 @@ class PreparedWeights:
         n += self.lm_head8.numel() + 4 * self.lm_head_scale.numel()
         for qs, scs in self.llm_q.values():
             n += sum(t.numel() for t in qs) + 4 * sum(t.numel() for t in scs)
+        for cs, scs in (self.llm_q4 or {}).values():
+            n += sum(t.numel() for t in cs) + sum(t.numel() for t in scs)
         return n
 
 

@@ -3,7 +3,9 @@
 //  1. lookup_draft_kernel  -- drafts up to K ids by matching the trailing n-gram of the sequence against the sequence itself;
 //  2. lookup_accept_kernel -- compares the drafts with the model's picks, emits the agreed prefix + 1 and advances the state;
 //     lookup_accept_sampled_kernel -- the same on picks that were DRAWN (a sampled request), and advances the Philox counter.
-// One block each, nothing allocated, no host round trip: both sit inside the captured step.
+// One block each, nothing allocated, no host round trip: both sit inside the captured step.  The batched step's pair
+// (lookup_draft_batch_kernel: one block per sequence, lookup_accept_batch_kernel: one thread per sequence) does the same for B
+// sequences.  Each rule is written once: draft_sequence and accept_sequence; the kernels find their sequence's words and call them.
 #include "common.h"
 #include "internal.h"
 #include "pick.h"
@@ -24,19 +26,15 @@ struct History {
   __device__ bool real(int64_t id) const { return id >= 0 && id < vocab; }
 };
 
-// for n = min(max_ngram, len - 1) .. 1: the EARLIEST i with history[i .. i + n) == the last n ids (all real) and a real id behind it
-// (i + n < len: the trailing n-gram itself never counts); the real ids that follow, at most K, are the drafts.  The position is a
-// minimum over the matches: it does not depend on scheduling.  row_ids (optional) = the T = K + 1 ids the step embeds: *tok, the
-// drafts, and behind them the last of these repeated (rows that can never be accepted).
-__global__ __launch_bounds__(1024) void lookup_draft_kernel(const int64_t* __restrict__ prompt_ids, int n_prompt,
-                                                            const int64_t* __restrict__ out_ids, const int* __restrict__ step, int max_new,
-                                                            int K, int max_ngram, int64_t vocab, int64_t* __restrict__ draft,
-                                                            int* __restrict__ n_draft, const int64_t* __restrict__ tok,
-                                                            int64_t* __restrict__ row_ids, int* __restrict__ err) {
+// The draft of ONE sequence, by the whole block.  For n = min(max_ngram, len - 1) .. 1: the EARLIEST i with history[i .. i + n) == the
+// last n ids (all real) and a real id behind it (i + n < len: the trailing n-gram itself never counts); the real ids that follow, at
+// most K, are the drafts.  The position is a minimum over the matches: it does not depend on scheduling.  row_ids (optional, with
+// tok) = the T = K + 1 ids the step embeds: *tok, the drafts, and behind them the last of these repeated (rows that can never be
+// accepted).
+__device__ void draft_sequence(const History& h, int K, int max_ngram, int64_t* __restrict__ draft, int* __restrict__ n_draft,
+                               const int64_t* __restrict__ tok, int64_t* __restrict__ row_ids, int* __restrict__ err) {
   __shared__ int best;
   __shared__ int64_t tail[LOOKUP_NGRAM_MAX];
-  const int n_gen = min(max(*step, 0), max_new);
-  const History h{prompt_ids, out_ids, n_prompt, n_prompt + n_gen, vocab};
   int found = -1, found_n = 0;
   for (int n = min(max_ngram, h.len - 1); n >= 1 && found < 0; --n) {  // uniform over the block
     __syncthreads();
@@ -77,9 +75,79 @@ __global__ __launch_bounds__(1024) void lookup_draft_kernel(const int64_t* __res
   }
 }
 
-// picks (optional): the T rows' picks as srgpt_argmax leaves them; NULL: merged here from the PICK_SLICES partials per row (pick.h).
-// n_acc = the longest prefix with draft[i] == pick[i], i < n_draft (and P + i + 1 < max_pos: a row beyond the cache was not computed);
-// the step emits pick[0 .. n_acc], cut at max_new.
+// one sequence: the history is prompt_ids[0 .. n_prompt) (a host count) and the first min(max(*step, 0), max_new) ids of out_ids
+__global__ __launch_bounds__(1024) void lookup_draft_kernel(const int64_t* __restrict__ prompt_ids, int n_prompt,
+                                                            const int64_t* __restrict__ out_ids, const int* __restrict__ step, int max_new,
+                                                            int K, int max_ngram, int64_t vocab, int64_t* __restrict__ draft,
+                                                            int* __restrict__ n_draft, const int64_t* __restrict__ tok,
+                                                            int64_t* __restrict__ row_ids, int* __restrict__ err) {
+  const int n_gen = min(max(*step, 0), max_new);
+  draft_sequence(History{prompt_ids, out_ids, n_prompt, n_prompt + n_gen, vocab}, K, max_ngram, draft, n_draft, tok, row_ids, err);
+}
+
+// ---- the batched step: B sequences, T rows each (row r = b * T + t of every step buffer is token t of sequence b) ----
+// sequence b = blockIdx.x over its own history: prompt_ids[b, 0 .. n_prompt[b]) (row stride ld_prompt; a device count outside
+// 0 .. ld_prompt is clamped, so no id outside the row is read) followed by the first min(max(steps[b], 0), max_new) ids of
+// out_ids[b, :].  draft [B, K], n_draft [B], row_ids [B, K + 1] (optional, with tok [B]).
+__global__ __launch_bounds__(1024) void lookup_draft_batch_kernel(const int64_t* __restrict__ prompt_ids, int ld_prompt,
+                                                                  const int* __restrict__ n_prompt, const int64_t* __restrict__ out_ids,
+                                                                  const int* __restrict__ steps, int max_new, int K, int max_ngram,
+                                                                  int64_t vocab, int64_t* __restrict__ draft, int* __restrict__ n_draft,
+                                                                  const int64_t* __restrict__ tok, int64_t* __restrict__ row_ids,
+                                                                  int* __restrict__ err) {
+  const int b = blockIdx.x;
+  const int np = min(max(n_prompt[b], 0), ld_prompt);
+  const int n_gen = min(max(steps[b], 0), max_new);
+  draft_sequence(History{prompt_ids + (size_t)b * ld_prompt, out_ids + (size_t)b * max_new, np, np + n_gen, vocab}, K, max_ngram,
+                 draft + (size_t)b * K, n_draft + b, tok ? tok + b : nullptr, row_ids ? row_ids + (size_t)b * (K + 1) : nullptr, err);
+}
+
+// The accept blocks have one wave per row (rows <= LOOKUP_ROWS_MAX): picked[row] = ids[row] where the rows' picks are int64 ids
+// already, or (ids == NULL) the merge of the row's PICK_SLICES partials in pv / pi (pick.h).  Ends in a barrier.
+__device__ void gather_picks(const int64_t* __restrict__ ids, const float* __restrict__ pv, const int* __restrict__ pi, int rows,
+                             int64_t* picked) {
+  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  if (row < rows) {
+    const int64_t t = ids ? ids[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
+    if (lane == 0) picked[row] = t;
+  }
+  __syncthreads();
+}
+
+// The accept of ONE sequence, by one thread, over that sequence's own words (*step: the ids it has emitted, *pos, *tok, *tok_emb,
+// out_ids: its row, draft: its T - 1 drafts, picked: its T rows' picks).  nd = the drafts that count: n_draft clamped to 0 .. T - 1
+// and to the rows the cache had room for (P + i + 1 < max_pos: a row beyond the cache was not computed); n_acc = the longest prefix
+// with draft[i] == picked[i], i < nd; the sequence emits picked[0 .. n_acc], cut at max_new.  A sequence whose count is outside
+// 0 .. max_new - 1 is FROZEN (emitted = 0): nothing of it is written.  At max_new and beyond that is the run-ahead rule (the loop may
+// launch once more than the request needs); a negative count is no state of a request, and nothing is written in front of its ids.
+struct Accepted {
+  int emitted, nd, n_acc;  // emitted == 0: frozen
+};
+__device__ Accepted accept_sequence(const int64_t* draft, int n_draft, const int64_t* picked, int T, int64_t* tok, int64_t* out_ids,
+                                    int* pos, int* step, int max_new, int max_pos, int64_t* tok_emb) {
+  const int s = *step;
+  if (s < 0 || s >= max_new) return Accepted{0, 0, 0};
+  const int P = *pos;
+  const int nd = min(min(max(n_draft, 0), T - 1), max(max_pos - 1 - P, 0));
+  int n_acc = 0;
+  while (n_acc < nd && draft[n_acc] == picked[n_acc]) ++n_acc;
+  const int emitted = min(n_acc + 1, max_new - s);
+  for (int i = 0; i < emitted; ++i) out_ids[s + i] = picked[i];
+  *step = s + emitted;
+  *pos = P + emitted;
+  *tok = picked[emitted - 1];
+  if (tok_emb) *tok_emb = -1;  // the residual-stream buffer of the plain step holds no row of this token: a captured step re-embeds
+  return Accepted{emitted, nd, n_acc};
+}
+
+__device__ void count_step(int* __restrict__ stats, int nd, int n_acc) {
+  if (!stats) return;
+  stats[0] += 1;
+  stats[1] += nd;
+  stats[2] += n_acc;
+}
+
+// picks (optional): the T rows' picks as srgpt_argmax leaves them; NULL: merged from the partials
 __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_kernel(const int64_t* __restrict__ picks, const float* __restrict__ pv,
                                                                              const int* __restrict__ pi, const int64_t* __restrict__ draft,
                                                                              const int* __restrict__ n_draft, int T, int64_t* __restrict__ tok,
@@ -87,30 +155,10 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_kernel(con
                                                                              int* __restrict__ step, int max_new, int max_pos,
                                                                              int64_t* __restrict__ tok_emb, int* __restrict__ stats) {
   __shared__ int64_t picked[LOOKUP_ROWS_MAX];
-  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
-  if (row < T) {
-    const int64_t t = picks ? picks[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
-    if (lane == 0) picked[row] = t;
-  }
-  __syncthreads();
+  gather_picks(picks, pv, pi, T, picked);
   if (threadIdx.x != 0) return;
-  const int s = *step;
-  if (s >= max_new) return;  // the run-ahead loop may launch once more than the request needs: nothing is bumped
-  const int P = pos[0];
-  const int nd = min(min(max(*n_draft, 0), T - 1), max(max_pos - 1 - P, 0));
-  int n_acc = 0;
-  while (n_acc < nd && draft[n_acc] == picked[n_acc]) ++n_acc;
-  const int emitted = min(n_acc + 1, max_new - s);
-  for (int i = 0; i < emitted; ++i) out_ids[s + i] = picked[i];
-  *step = s + emitted;
-  pos[0] = P + emitted;
-  tok[0] = picked[emitted - 1];
-  if (tok_emb) tok_emb[0] = -1;  // the residual-stream buffer of the plain step holds no row of this token: a captured step re-embeds
-  if (stats) {
-    stats[0] += 1;
-    stats[1] += nd;
-    stats[2] += n_acc;
-  }
+  const Accepted a = accept_sequence(draft, *n_draft, picked, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb);
+  if (a.emitted) count_step(stats, a.nd, a.n_acc);
 }
 
 // the SAMPLED step: the T rows' picks are DRAWS, row t at Philox counter sp->counter + t (the samplers' rows-are-steps mode).  Where
@@ -126,152 +174,46 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_sampled_ke
     int64_t* __restrict__ out_ids, int* __restrict__ pos, int* __restrict__ step, int max_new, int max_pos, int64_t* __restrict__ tok_emb,
     int* __restrict__ stats) {
   __shared__ int64_t picked[LOOKUP_ROWS_MAX];
-  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
-  const bool ids = select_drew && sp->top_k > 0;
-  if (row < T) {
-    const int64_t t = ids ? drawn[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
-    if (lane == 0) picked[row] = t;
-  }
-  __syncthreads();
+  gather_picks(select_drew && sp->top_k > 0 ? drawn : nullptr, pv, pi, T, picked);
   if (threadIdx.x != 0) return;
-  // from here on lookup_accept_kernel's rule, statement for statement (that kernel is pinned as it is), plus the counter
-  const int s = *step;
-  if (s >= max_new) return;  // run-ahead: nothing is bumped, the counter included (emitted = 0)
-  const int P = pos[0];
-  const int nd = min(min(max(*n_draft, 0), T - 1), max(max_pos - 1 - P, 0));
-  int n_acc = 0;
-  while (n_acc < nd && draft[n_acc] == picked[n_acc]) ++n_acc;
-  const int emitted = min(n_acc + 1, max_new - s);
-  for (int i = 0; i < emitted; ++i) out_ids[s + i] = picked[i];
-  *step = s + emitted;
-  pos[0] = P + emitted;
-  tok[0] = picked[emitted - 1];
-  if (tok_emb) tok_emb[0] = -1;
-  if (stats) {
-    stats[0] += 1;
-    stats[1] += nd;
-    stats[2] += n_acc;
-  }
-  sp->counter += (unsigned long long)emitted;
+  const Accepted a = accept_sequence(draft, *n_draft, picked, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb);
+  if (!a.emitted) return;  // frozen: nothing is bumped, the counter included
+  count_step(stats, a.nd, a.n_acc);
+  sp->counter += (unsigned long long)a.emitted;
 }
 
-// ---- the batched step: B sequences, T rows each (row r = b * T + t of every step buffer is token t of sequence b) ----
-// lookup_draft_kernel for sequence b = blockIdx.x, statement for statement, over that row's own history: prompt_ids[b, 0 .. n_prompt[b])
-// (row stride ld_prompt; a device count outside 0 .. ld_prompt is clamped, so no id outside the row is read) followed by the first
-// min(max(steps[b], 0), max_new) ids of out_ids[b, :].  draft [B, K], n_draft [B], row_ids [B, K + 1] (optional, with tok [B]).
-__global__ __launch_bounds__(1024) void lookup_draft_batch_kernel(const int64_t* __restrict__ prompt_ids, int ld_prompt,
-                                                                  const int* __restrict__ n_prompt, const int64_t* __restrict__ out_ids,
-                                                                  const int* __restrict__ steps, int max_new, int K, int max_ngram,
-                                                                  int64_t vocab, int64_t* __restrict__ draft, int* __restrict__ n_draft,
-                                                                  const int64_t* __restrict__ tok, int64_t* __restrict__ row_ids,
-                                                                  int* __restrict__ err) {
-  __shared__ int best;
-  __shared__ int64_t tail[LOOKUP_NGRAM_MAX];
-  const int b = blockIdx.x;
-  const int np = min(max(n_prompt[b], 0), ld_prompt);
-  const int n_gen = min(max(steps[b], 0), max_new);
-  const History h{prompt_ids + (size_t)b * ld_prompt, out_ids + (size_t)b * max_new, np, np + n_gen, vocab};
-  draft += (size_t)b * K;
-  int found = -1, found_n = 0;
-  for (int n = min(max_ngram, h.len - 1); n >= 1 && found < 0; --n) {  // uniform over the block
-    __syncthreads();
-    if (threadIdx.x == 0) best = INT_MAX;
-    if ((int)threadIdx.x < n) tail[threadIdx.x] = h.at(h.len - n + threadIdx.x);
-    __syncthreads();
-    bool tail_real = true;
-    for (int j = 0; j < n; ++j) tail_real = tail_real && h.real(tail[j]);
-    if (tail_real) {
-      int mine = INT_MAX;
-      for (int i = threadIdx.x; i + n < h.len && mine == INT_MAX; i += blockDim.x) {
-        bool eq = h.real(h.at(i + n));
-        for (int j = 0; j < n && eq; ++j) eq = h.at(i + j) == tail[j];
-        if (eq) mine = i;  // ascending scan per thread: its earliest match
-      }
-      if (mine != INT_MAX) atomicMin(&best, mine);
-    }
-    __syncthreads();
-    if (best != INT_MAX) {
-      found = best;
-      found_n = n;
-    }
-  }
-  if (threadIdx.x != 0) return;
-  int nd = 0;
-  if (found >= 0)
-    for (int i = found + found_n; nd < K && i < h.len && h.real(h.at(i)); ++i) draft[nd++] = h.at(i);
-  for (int i = nd; i < K; ++i) draft[i] = -1;
-  n_draft[b] = nd;
-  if (row_ids) {
-    row_ids += (size_t)b * (K + 1);
-    int64_t t0 = tok[b];
-    if (!h.real(t0)) {  // a caller-written id outside the table cannot be embedded (the captured plain step's rule)
-      if (err) atomicOr(err, 1);
-      t0 = 0;
-    }
-    row_ids[0] = t0;
-    for (int i = 0; i < K; ++i) row_ids[1 + i] = i < nd ? draft[i] : (nd > 0 ? draft[nd - 1] : t0);
-  }
-}
-
-// One wave per row merges the B * T rows' picks (B * T <= LOOKUP_ROWS_MAX: lookup_accept_kernel's block); then thread b applies that
-// kernel's rule to sequence b: its own steps[b], pos[b], tok[b], tok_emb[b], out_ids[b, :], its T - 1 drafts and picks b * T .. .  A
-// row with steps[b] >= max_new is FROZEN: nothing of it is written or counted (the run-ahead rule, per row -- a row that accepted
-// more than the others gets there first and waits).  Then thread 0: *step = min over b of steps[b], the columns of out_ids every row
-// has filled; stats += {1 when a row advanced, the drafts, the accepted ones of the rows that did}, summed in row order.
+// One wave per row gathers the B * T rows' picks (B * T <= LOOKUP_ROWS_MAX); then thread b accepts sequence b: its own steps[b], pos[b],
+// tok[b], tok_emb[b], out_ids[b, :], its T - 1 drafts and picks b * T .. .  A frozen sequence is neither written nor counted (the
+// run-ahead rule, per row -- a row that accepted more than the others gets there first and waits).  Then thread 0: *step = min over
+// b of steps[b], the columns of out_ids every row has filled; stats += {1 when a row advanced, the drafts, the accepted ones of the
+// rows that did}, summed in row order.
 __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_batch_kernel(
     const int64_t* __restrict__ picks, const float* __restrict__ pv, const int* __restrict__ pi, const int64_t* __restrict__ draft,
     const int* __restrict__ n_draft, int B, int T, int64_t* __restrict__ tok, int64_t* __restrict__ out_ids, int* __restrict__ pos,
     int* __restrict__ steps, int* __restrict__ step, int max_new, int max_pos, int64_t* __restrict__ tok_emb, int* __restrict__ stats) {
   __shared__ int64_t picked[LOOKUP_ROWS_MAX];
-  __shared__ int s_steps[LOOKUP_ROWS_MAX], s_nd[LOOKUP_ROWS_MAX], s_acc[LOOKUP_ROWS_MAX];  // per sequence; s_nd < 0: frozen
-  const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
-  if (row < B * T) {
-    const int64_t t = picks ? picks[row] : (int64_t)pick_merge_row(pv + (size_t)row * PICK_SLICES, pi + (size_t)row * PICK_SLICES, PICK_SLICES, lane);
-    if (lane == 0) picked[row] = t;
-  }
-  __syncthreads();
+  __shared__ int s_steps[LOOKUP_ROWS_MAX];
+  __shared__ Accepted s_acc[LOOKUP_ROWS_MAX];  // per sequence
+  gather_picks(picks, pv, pi, B * T, picked);
   if ((int)threadIdx.x < B) {
     const int b = threadIdx.x;
-    const int64_t* const dr = draft + (size_t)b * (T - 1);
-    const int64_t* const pk = picked + b * T;
-    int64_t* const out = out_ids + (size_t)b * max_new;
-    int s = steps[b];
-    s_nd[b] = -1;
-    s_acc[b] = 0;
-    if (s >= 0 && s < max_new) {  // (a negative count is no state of a request: such a row is left alone, nothing is written in front of its ids)
-      const int P = pos[b];
-      const int nd = min(min(max(n_draft[b], 0), T - 1), max(max_pos - 1 - P, 0));
-      int n_acc = 0;
-      while (n_acc < nd && dr[n_acc] == pk[n_acc]) ++n_acc;
-      const int emitted = min(n_acc + 1, max_new - s);
-      for (int i = 0; i < emitted; ++i) out[s + i] = pk[i];
-      s += emitted;
-      steps[b] = s;
-      pos[b] = P + emitted;
-      tok[b] = pk[emitted - 1];
-      if (tok_emb) tok_emb[b] = -1;  // as lookup_accept_kernel: a captured plain step re-embeds
-      s_nd[b] = nd;
-      s_acc[b] = n_acc;
-    }
-    s_steps[b] = s;
+    s_acc[b] = accept_sequence(draft + (size_t)b * (T - 1), n_draft[b], picked + b * T, T, tok + b, out_ids + (size_t)b * max_new, pos + b,
+                               steps + b, max_new, max_pos, tok_emb ? tok_emb + b : nullptr);
+    s_steps[b] = steps[b];
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
   int lo = INT_MAX, live = 0, nd = 0, n_acc = 0;
   for (int b = 0; b < B; ++b) {
     lo = min(lo, s_steps[b]);
-    if (s_nd[b] >= 0) {
+    if (s_acc[b].emitted) {
       live = 1;
-      nd += s_nd[b];
-      n_acc += s_acc[b];
+      nd += s_acc[b].nd;
+      n_acc += s_acc[b].n_acc;
     }
   }
   *step = lo;
-  if (stats && live) {
-    stats[0] += 1;
-    stats[1] += nd;
-    stats[2] += n_acc;
-  }
+  if (live) count_step(stats, nd, n_acc);
 }
 
 int check_draft_args(int n_prompt, int max_new, int K, int max_ngram, int64_t vocab, const char* fn) {

@@ -446,6 +446,8 @@ LayerMats layer_mats(const srgpt_llm_weights* w, LlmFormat fmt, int i) {
                    mat(w->wgu, w->wgu8, w->wgu_scale, w->wgu8p, w->pk_rows_gu),
                    mat(w->wdown, w->wdown8, w->wdown_scale, w->wdown8p, w->pk_rows_down)};
 }
+// lm_head has no packed and no MXFP4 copy: engine dtype, or fp8 under every other format
+Mat lm_head_mat(const srgpt_llm_weights* w) { return Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}; }
 
 // ---- prefill ----
 // One prefill's shapes, workspace and stream; the launches its layers are made of; and, per weight format, the launch sequence of
@@ -749,31 +751,67 @@ extern "C" int srgpt_llm_sample_first(const srgpt_llm_weights* w, srgpt_llm_stat
 namespace {
 
 // ---- decode step ----
-// One product of the decode step, by the entry the step's route (gemv_route.h) and the weights allow.  pub: 2+ bf16 rows (the MFMA
-// kernel): o_proj / down_proj publish the sum of squares of the rows they write (ss_out), the RMSNorm of the next product reads 512
-// partial sums per row (ss_in) instead of re-reading every row in every block (skinny.hip): the per-op form is srgpt_gemv_rowss.
+// The row buffers a decode-shaped step runs in: `rows` rows of the residual stream, of q/k/v, of the attention's output and of the
+// MLP's activation, and the two row-statistics tables.  The plain step's are the state workspace's (LlmWs, rows = batch), a lookup
+// step's its own workspace's (LookupWs, rows = batch * T).
+struct StepRows {
+  void *xd, *qkvd, *attnd, *actd;
+  float* ss_attn;  // statistics of the rows after the attention block's residual add
+  float* ss_mlp;   // ... after the MLP block's
+  int rows;
+};
+StepRows step_rows(void* xd, void* qkvd, void* attnd, void* actd, float* rowss, int rows) {
+  return StepRows{xd, qkvd, attnd, actd, rowss, rowss + (size_t)rows * SRGPT_ROWSS_STRIDE, rows};
+}
+
+// One product of a step, by the entry the step's route (gemv_route.h) and the weights allow, and the one sequence of products every
+// decode-shaped step is made of.  pub: 2+ bf16 rows (the MFMA kernel): o_proj / down_proj publish the sum of squares of the rows
+// they write (ss_out), the RMSNorm of the next product reads 512 partial sums per row (ss_in) instead of re-reading every row in
+// every block (skinny.hip): the per-op form is srgpt_gemv_rowss.
 struct DecodeStep {
   const srgpt_llm_weights* w;
-  int B;
+  LlmFormat fmt;
+  StepRows r;
   bool fp8, pub;
   srgpt_stream_t stream;
 
   // fp8: the matrices that are not MXFP4 (under FMT_W4A16: lm_head) are fp8
-  static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, int rows, srgpt_stream_t stream) {
+  static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, const StepRows& r, srgpt_stream_t stream) {
     const bool fp8 = fmt != FMT_DTYPE;
-    const bool pub = fmt != FMT_W4A16 && gemv_rowss_supported(rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
-    return DecodeStep{w, rows, fp8, pub, stream};
+    const bool pub = fmt != FMT_W4A16 && gemv_rowss_supported(r.rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
+    return DecodeStep{w, fmt, r, fp8, pub, stream};
   }
 
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
            const float* ss_in, float* ss_out) const {
     if (m.w4)  // MXFP4 layer matrix (pub is false under the format: its kernel neither reads nor publishes row statistics)
-      return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
+      return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
     if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
-      return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, ss_in, ss_out,
+      return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out,
                               m.pk ? m.pk_rows : 0, stream);
-    if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, stream);
-    return srgpt_gemv(x, m.w, norm, w->rms_eps, res, out, B, N, K, swiglu, f32, w->dtype, stream);
+    if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
+    return srgpt_gemv(x, m.w, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, w->dtype, stream);
+  }
+
+  // r.xd holds the rows' embeddings: the w->layers layers over the KV cache of `st`, then lm_head -> logits [rows, vocab] fp32.
+  // attention(i, m, kc, vc) launches layer i's attention from r.qkvd over that layer's cache into r.attnd (m: the layer's matrices,
+  // for the launch that prefetches o_proj) -- the one launch the steps differ in.  Layer 0's q/k/v normalises the embedding rows
+  // itself; every later norm reads the statistics the product before it published.
+  template <typename Attn>
+  int layers_lm_head(const srgpt_llm_state* st, float* logits, Attn&& attention) const {
+    const int Hd = w->hidden, I = w->inter, HqD = w->heads * w->head_dim, QW = (w->heads + 2 * w->kv_heads) * w->head_dim;
+    const size_t layer_kv = (size_t)st->batch * w->kv_heads * st->max_pos * w->head_dim * dtype_size(w->dtype);
+    for (int i = 0; i < w->layers; ++i) {
+      char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
+      char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
+      const LayerMats m = layer_mats(w, fmt, i);
+      SRGPT_TRY(gemv(m.qkv, r.xd, w->attn_norm[i], nullptr, r.qkvd, QW, Hd, 0, 0, i > 0 ? r.ss_mlp : nullptr, nullptr));
+      SRGPT_TRY(attention(i, m, kc, vc));
+      SRGPT_TRY(gemv(m.o, r.attnd, nullptr, r.xd, r.xd, Hd, HqD, 0, 0, nullptr, r.ss_attn));
+      SRGPT_TRY(gemv(m.gu, r.xd, w->mlp_norm[i], nullptr, r.actd, I, Hd, 1, 0, r.ss_attn, nullptr));
+      SRGPT_TRY(gemv(m.down, r.actd, nullptr, r.xd, r.xd, Hd, I, 0, 0, nullptr, r.ss_mlp));
+    }
+    return gemv(lm_head_mat(w), r.xd, w->final_norm, nullptr, logits, w->vocab, Hd, 0, 1, w->layers > 0 ? r.ss_mlp : nullptr, nullptr);
   }
 };
 
@@ -784,44 +822,28 @@ struct DecodeStep {
 static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srgpt_stream_t stream, bool embed_first, Pick p) {
   LlmFormat fmt;
   SRGPT_TRY(llm_format(w, "srgpt_llm_decode_step", &fmt));
-  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
-  const int B = st->batch, QW = (Hq + 2 * Hkv) * D;
-  const size_t es = dtype_size(dt);
+  const int dt = w->dtype, Hd = w->hidden, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim, B = st->batch;
   hipStream_t s = as_stream(stream);
   const LlmWs d = carve_llm(w, B, st->ws_tokens, st->ws);  // same carve as prefill (sized by ws_tokens)
-  const size_t layer_kv = (size_t)B * Hkv * st->max_pos * D * es;
   if (embed_first) {
     SRGPT_TRY(srgpt_embed_rows(w->embed, st->tok, d.xd, B, Hd, dt, stream));
     hipLaunchKernelGGL(record_embedded_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, st->tok, d.tok_emb, B);
     SRGPT_LAUNCH_CHECK();
   } else {  // captured step: one tiny launch that copies nothing unless the caller changed st->tok behind the graph's back
     hipLaunchKernelGGL(embed_sync_kernel, dim3(B < 64 ? B : 64), dim3(256), 0, s, st->tok, d.tok_emb,
-                       reinterpret_cast<const unsigned char*>(w->embed), reinterpret_cast<unsigned char*>(d.xd), B, (int)((size_t)Hd * es),
-                       (int64_t)w->vocab, d.err);
+                       reinterpret_cast<const unsigned char*>(w->embed), reinterpret_cast<unsigned char*>(d.xd), B,
+                       (int)((size_t)Hd * dtype_size(dt)), (int64_t)w->vocab, d.err);
     SRGPT_LAUNCH_CHECK();
   }
   const bool fp8 = fmt != FMT_DTYPE, w4 = fmt == FMT_W4A16;
-  const DecodeStep ds = DecodeStep::make(w, fmt, B, stream);
-  // the row statistics (layer 0's q/k/v normalises the embedding rows itself)
-  float* const ss_attn = d.rowss;                                       // rows after the attention block's residual add
-  float* const ss_mlp = d.rowss + (size_t)B * SRGPT_ROWSS_STRIDE;       // rows after the MLP block's
-  for (int i = 0; i < w->layers; ++i) {
-    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
-    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
-    const LayerMats m = layer_mats(w, fmt, i);
-    SRGPT_TRY(ds.gemv(m.qkv, d.xd, w->attn_norm[i], nullptr, d.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
-    // the attention launch also pulls o_proj's weights into L2 (HBM is idle while it runs).  Round 3 built the next step -- o_proj
-    // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
-    // (profiles/r03_fused_attention_oproj.txt)
-    SRGPT_TRY(srgpt_decode_attention_pf(d.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, d.attnd, d.dws, B, Hq, Hkv, D,
-                                        st->max_pos, dt, w4 ? m.o.w4 : fp8 ? m.o.w8 : m.o.w, Hd, Hq * D,
-                                        w4 ? SRGPT_PREFETCH_W4 : fp8 ? 1 : 0, stream));
-    SRGPT_TRY(ds.gemv(m.o, d.attnd, nullptr, d.xd, d.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
-    SRGPT_TRY(ds.gemv(m.gu, d.xd, w->mlp_norm[i], nullptr, d.actd, I, Hd, 1, 0, ss_attn, nullptr));
-    SRGPT_TRY(ds.gemv(m.down, d.actd, nullptr, d.xd, d.xd, Hd, I, 0, 0, nullptr, ss_mlp));
-  }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, d.xd, w->final_norm, nullptr, st->logits, w->vocab, Hd,
-                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
+  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(d.xd, d.qkvd, d.attnd, d.actd, d.rowss, B), stream);
+  // the attention launch also pulls o_proj's weights into L2 (HBM is idle while it runs).  Round 3 built the next step -- o_proj
+  // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
+  // (profiles/r03_fused_attention_oproj.txt)
+  SRGPT_TRY(ds.layers_lm_head(st, st->logits, [&](int, const LayerMats& m, void* kc, void* vc) {
+    return srgpt_decode_attention_pf(d.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, d.attnd, d.dws, B, Hq, Hkv, D, st->max_pos, dt,
+                                     w4 ? m.o.w4 : fp8 ? m.o.w8 : m.o.w, Hd, Hq * D, w4 ? SRGPT_PREFETCH_W4 : fp8 ? 1 : 0, stream);
+  }));
   return greedy_pick(w, st, d, 1, p, s);
 }
 
@@ -841,43 +863,57 @@ extern "C" int srgpt_llm_decode_step(const srgpt_llm_weights* w, srgpt_llm_state
   return decode_step_impl(w, st, stream, true, Pick{SRGPT_SAMPLER_TOPK64, nullptr});
 }
 
-// Health of the decode steps since the last prefill (synchronises `stream` ONCE: both read-backs are queued, then one wait):
-// (1) between steps every arrival ticket of the decode attention (the split that draws the last ticket merges and re-arms it) must
-// be zero again -- a non-zero ticket means a launch was aborted or merged nothing, and every later step would silently use stale
-// attention output; (2) the sticky error word of the captured step (a caller-written token id outside the embedding table).
+// Reads back the `bytes` of arrival tickets at `sync` behind the work queued on `stream` and checks them: between steps every ticket
+// of a decode attention (the split that draws the last ticket merges and re-arms it) must be zero again -- a non-zero ticket means a
+// launch was aborted or merged nothing, and every later step would silently use stale attention output.  `what` names the step in
+// that message, `fn` the entry point in a failed HIP call's.  word (optional): one more device int read into *word_host by the same
+// wait (`stream` is synchronised ONCE: the read-backs are queued, then one wait).
+static int check_tickets(const void* sync, size_t bytes, srgpt_stream_t stream, const char* fn, const char* what,
+                         const int* word = nullptr, int* word_host = nullptr) {
+  std::vector<int> host(bytes / sizeof(int));
+  hipError_t e = hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream));
+  if (e == hipSuccess && word) e = hipMemcpyAsync(word_host, word, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream));
+  SRGPT_CHECK(e == hipSuccess, SRGPT_ERR_LAUNCH, "%s: copy failed: %s", fn, hipGetErrorString(e));
+  e = hipStreamSynchronize(as_stream(stream));
+  SRGPT_CHECK(e == hipSuccess, SRGPT_ERR_LAUNCH, "%s: synchronize failed: %s", fn, hipGetErrorString(e));
+  for (size_t i = 0; i < host.size(); ++i)
+    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "%s: arrival ticket %zu of %zu is %d between steps (expected 0)", what, i, host.size(),
+                host[i]);
+  return SRGPT_OK;
+}
+
+// Health of the decode steps since the last prefill: (1) the arrival tickets of the decode attention; (2) the sticky error word of
+// the captured step (a caller-written token id outside the embedding table), of the samplers and of srgpt_llm_prefill_append.
 extern "C" int srgpt_llm_decode_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, srgpt_stream_t stream) {
   SRGPT_TRY(check_llm(w, st));
   const LlmWs d = carve_llm(w, st->batch, st->ws_tokens, st->ws);
   size_t bytes = 0;
   void* sync = srgpt_decode_attn_sync_words(d.dws, st->batch, w->heads, w->head_dim, &bytes);
-  std::vector<int> host(bytes / sizeof(int) + 1);
-  SRGPT_HIP_TRY(hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_decode_sync_state: copy");
-  SRGPT_HIP_TRY(hipMemcpyAsync(&host.back(), d.err, sizeof(int), hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_decode_sync_state: copy");
-  SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_llm_decode_sync_state: synchronize");
-  const size_t n = host.size() - 1;
-  for (size_t i = 0; i < n; ++i)
-    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "decode step: arrival ticket %zu of %zu is %d between steps (expected 0)", i, n, host[i]);
-  SRGPT_CHECK((host.back() & ERR_APPEND_ROW) == 0, SRGPT_ERR_STATE,
+  int err = 0;
+  SRGPT_TRY(check_tickets(sync, bytes, stream, "srgpt_llm_decode_sync_state", "decode step", d.err, &err));
+  SRGPT_CHECK((err & ERR_APPEND_ROW) == 0, SRGPT_ERR_STATE,
               "srgpt_llm_prefill_append: a row's st->pos lay outside 0 .. h_pos_max or its length outside 1 .. T; the row was appended "
               "at a clamped position");
-  SRGPT_CHECK((host.back() & 4) == 0, SRGPT_ERR_UNSUPPORTED,
+  SRGPT_CHECK((err & 4) == 0, SRGPT_ERR_UNSUPPORTED,
               "decode step: sampling parameters the device sampler does not serve (top_k > 64, or top_p < 1 without top_k): the draws "
               "used another distribution");
-  SRGPT_CHECK((host.back() & 2) == 0, SRGPT_ERR_STATE,
+  SRGPT_CHECK((err & 2) == 0, SRGPT_ERR_STATE,
               "decode step: more than 256 vocabulary entries tie at the top-k threshold of a sampling step (kept set truncated)");
-  SRGPT_CHECK((host.back() & 1) == 0, SRGPT_ERR_STATE,
+  SRGPT_CHECK((err & 1) == 0, SRGPT_ERR_STATE,
               "decode step: a token id written into st->tok lies outside the embedding table [0, %d); the step ran on a stale row",
               w->vocab);
   return SRGPT_OK;
 }
 
 // ================================================================================================
-// the lookup step: the next token and T - 1 drafted ones through ONE pass over the weights (prompt-lookup decoding)
+// the lookup steps: the next token and T - 1 drafted ones of each of B sequences through ONE pass over the weights (prompt-lookup
+// decoding; B * T <= 16 rows, the skinny kernel's pass).  srgpt_lookup is the B = 1 form, srgpt_lookup_batch the per-row one.
 // ================================================================================================
 namespace {
 
-// srgpt_lookup::ws: T rows of the decode step's buffers, the two row-statistics tables, the multi-token attention's workspace (its
-// tickets zero between launches), the T rows' pick partials and the draft scratch
+// srgpt_lookup::ws (B = 1) / srgpt_lookup_batch::ws: B * T rows of the decode step's buffers and of the two row-statistics tables, the
+// multi-token attention's workspace for (B, T) (its tickets zero between launches), the rows' pick partials and the [B, T] draft,
+// row-id and count scratch
 struct LookupWs {
   void *xd, *qkvd, *attnd, *actd;
   float* rowss;
@@ -888,34 +924,79 @@ struct LookupWs {
   int* n_draft;
   size_t total;
 };
-LookupWs carve_lookup(const srgpt_llm_weights* w, int T, void* ws) {
+LookupWs carve_lookup(const srgpt_llm_weights* w, int B, int T, void* ws) {
   const size_t es = dtype_size(w->dtype);
   const size_t qkvw = (size_t)(w->heads + 2 * w->kv_heads) * w->head_dim;
+  const size_t rows = (size_t)B * T;
   Carver c(ws);
   LookupWs l;
-  l.xd = c.take((size_t)T * w->hidden * es);
-  l.qkvd = c.take((size_t)T * qkvw * es);
-  l.attnd = c.take((size_t)T * w->heads * w->head_dim * es);
-  l.actd = c.take((size_t)T * w->inter * es);
-  l.rowss = reinterpret_cast<float*>(c.take((size_t)2 * T * SRGPT_ROWSS_STRIDE * sizeof(float)));
-  l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_multi_ws_floats(1, T, w->heads, w->head_dim) * 4));
-  l.amax_v = reinterpret_cast<float*>(c.take((size_t)T * PICK_SLICES * 4));
-  l.amax_i = reinterpret_cast<int*>(c.take((size_t)T * PICK_SLICES * 4));
-  l.draft = reinterpret_cast<int64_t*>(c.take((size_t)T * 8));
-  l.row_ids = reinterpret_cast<int64_t*>(c.take((size_t)T * 8));
-  l.n_draft = reinterpret_cast<int*>(c.take(sizeof(int)));
+  l.xd = c.take(rows * w->hidden * es);
+  l.qkvd = c.take(rows * qkvw * es);
+  l.attnd = c.take(rows * w->heads * w->head_dim * es);
+  l.actd = c.take(rows * w->inter * es);
+  l.rowss = reinterpret_cast<float*>(c.take(2 * rows * SRGPT_ROWSS_STRIDE * sizeof(float)));
+  l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_multi_ws_floats(B, T, w->heads, w->head_dim) * 4));
+  l.amax_v = reinterpret_cast<float*>(c.take(rows * PICK_SLICES * 4));
+  l.amax_i = reinterpret_cast<int*>(c.take(rows * PICK_SLICES * 4));
+  l.draft = reinterpret_cast<int64_t*>(c.take(rows * 8));
+  l.row_ids = reinterpret_cast<int64_t*>(c.take(rows * 8));
+  l.n_draft = reinterpret_cast<int*>(c.take(rows * sizeof(int)));  // one count per sequence; up to 16 rows are one 256-byte unit
   l.total = c.off;
   return l;
+}
+
+// One lookup step as lookup_step_impl runs it, built from srgpt_lookup (B = 1) or srgpt_lookup_batch (steps != NULL)
+struct LookupReq {
+  int B, T, max_ngram;
+  void* ws;
+  float* logits;
+  int* stats;
+  const int64_t* prompt_ids;
+  // batched: the row stride of prompt_ids and, on the device, every row's id count and emission count
+  int ld_prompt;
+  const int* n_prompt_dev;
+  int* steps;
+  // single: the id count (a host int of the public struct), the sampler kind of a sampled step and its workspace
+  int n_prompt, sampler;
+  void* sample_ws;
+};
+LookupReq lookup_req(const srgpt_lookup* lk, int sampler = SRGPT_SAMPLER_TOPK64, void* sample_ws = nullptr) {
+  return LookupReq{1, lk->T, lk->max_ngram, lk->ws, lk->logits, lk->stats, lk->prompt_ids, 0, nullptr, nullptr, lk->n_prompt, sampler, sample_ws};
+}
+LookupReq lookup_req(const srgpt_lookup_batch* lk, int B) {
+  return LookupReq{B, lk->T, lk->max_ngram, lk->ws, lk->logits, lk->stats, lk->prompt_ids, lk->ld_prompt, lk->n_prompt, lk->steps, 0,
+                   SRGPT_SAMPLER_TOPK64, nullptr};
 }
 
 }  // namespace
 
 extern "C" int64_t srgpt_llm_lookup_ws_bytes(const srgpt_llm_weights* w, int T) {
   if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
-  return (int64_t)carve_lookup(w, T, nullptr).total;
+  return (int64_t)carve_lookup(w, 1, T, nullptr).total;
 }
 
-// every lookup entry point, on the host before any launch
+extern "C" int64_t srgpt_llm_lookup_batch_ws_bytes(const srgpt_llm_weights* w, int B, int T) {
+  if (!w || B < 1 || T < 2 || (int64_t)B * T > srgpt_lookup_rows_max()) return -1;
+  return (int64_t)carve_lookup(w, B, T, nullptr).total;
+}
+
+// The parts the two host checks below share.  The checks themselves stay apart: they refuse overlapping things in different orders,
+// and which refusal an argument set gets first is pinned.
+// -- the multi-token attention serves T rows per sequence, and the pick a vocabulary of this size
+static int check_lookup_rows(const srgpt_llm_weights* w, const srgpt_llm_state* st, int T, const char* fn) {
+  const AttnDecodeMultiRoute r =
+      attn_decode_multi_route(w->dtype == SRGPT_BF16, st->batch, T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
+  SRGPT_CHECK(r.status == ATTN_OK, SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows x %d heads per kv head exceed the %d columns of the attention kernel",
+              fn, T, r.G, ATTN_DEC_MULTI_COLS);
+  return pick_check_vocab(w->vocab, fn);
+}
+static int check_max_ngram(int max_ngram, const char* fn) {
+  SRGPT_CHECK(max_ngram >= 1 && max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn, max_ngram,
+              srgpt_lookup_ngram_max());
+  return SRGPT_OK;
+}
+
+// every single-sequence lookup entry point, on the host before any launch
 static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk, const char* fn,
                         bool greedy_only = true) {
   SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
@@ -924,16 +1005,11 @@ static int check_lookup(const srgpt_llm_weights* w, const srgpt_llm_state* st, c
   SRGPT_CHECK(lk->T >= 2, SRGPT_ERR_ARG, "%s: T=%d rows (the next token and at least one draft)", fn, lk->T);
   SRGPT_CHECK(lk->ws && lk->logits && lk->stats && (lk->prompt_ids || lk->n_prompt == 0) && lk->n_prompt >= 0, SRGPT_ERR_ARG,
               "%s: lookup block has null buffers", fn);
-  SRGPT_CHECK(lk->max_ngram >= 1 && lk->max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn,
-              lk->max_ngram, srgpt_lookup_ngram_max());
+  SRGPT_TRY(check_max_ngram(lk->max_ngram, fn));
   SRGPT_CHECK(!greedy_only || !st->sampling, SRGPT_ERR_UNSUPPORTED,
               "%s: greedy only (st->sampling is set: the sampled step is srgpt_llm_lookup_step_ex)", fn);
   SRGPT_CHECK(lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows exceed %d", fn, lk->T, srgpt_lookup_rows_max());
-  const AttnDecodeMultiRoute r =
-      attn_decode_multi_route(w->dtype == SRGPT_BF16, 1, lk->T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
-  SRGPT_CHECK(r.status == ATTN_OK, SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows x %d heads per kv head exceed the %d columns of the attention kernel",
-              fn, lk->T, r.G, ATTN_DEC_MULTI_COLS);
-  SRGPT_TRY(pick_check_vocab(w->vocab, fn));
+  SRGPT_TRY(check_lookup_rows(w, st, lk->T, fn));
   LlmFormat fmt;
   return llm_format(w, fn, &fmt);
 }
@@ -948,141 +1024,6 @@ static int check_lookup_ex(const srgpt_llm_weights* w, const srgpt_llm_state* st
   return SRGPT_OK;
 }
 
-extern "C" int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, int T, int sampler) {
-  if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
-  if (sampler == SRGPT_SAMPLER_TOPK64) return srgpt_sample_ws_bytes(T);
-  if (sampler == SRGPT_SAMPLER_FULL) return srgpt_sample_full_ws_bytes(T, w->vocab);
-  return -1;
-}
-
-// draft -> embed the T rows -> the layers of decode_step_impl with T rows through the same products and the multi-token attention
-// (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> lm_head -> the rows' picks -> accept.  Greedy (st->sampling == NULL):
-// the rows' argmax partials.  Sampled: the sampler `sampler` in its rows-are-steps mode over the T rows (sample_ws: its own workspace,
-// srgpt_llm_lookup_sample_ws_bytes; error bits go to the state's sticky word), then the accept that advances the Philox counter.  The
-// top-k-64 sampler's drawn ids go to the lookup workspace's row_ids, dead since the rows were embedded.
-static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream,
-                            int sampler = SRGPT_SAMPLER_TOPK64, void* sample_ws = nullptr) {
-  LlmFormat fmt;
-  SRGPT_TRY(llm_format(w, "srgpt_llm_lookup_step", &fmt));
-  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
-  const int T = lk->T, QW = (Hq + 2 * Hkv) * D;
-  const size_t es = dtype_size(dt);
-  hipStream_t s = as_stream(stream);
-  const LlmWs d = carve_llm(w, 1, st->ws_tokens, st->ws);  // the state's sticky error word and embedded-token record
-  const LookupWs l = carve_lookup(w, T, lk->ws);
-  const size_t layer_kv = (size_t)Hkv * st->max_pos * D * es;
-  SRGPT_TRY(srgpt_lookup_draft_launch(lk->prompt_ids, lk->n_prompt, st->out_ids, st->step, st->max_new, T - 1, lk->max_ngram,
-                                      (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
-  SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, T, Hd, dt, stream));
-  const DecodeStep ds = DecodeStep::make(w, fmt, T, stream);
-  float* const ss_attn = l.rowss;
-  float* const ss_mlp = l.rowss + (size_t)T * SRGPT_ROWSS_STRIDE;
-  for (int i = 0; i < w->layers; ++i) {
-    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
-    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
-    const LayerMats m = layer_mats(w, fmt, i);
-    SRGPT_TRY(ds.gemv(m.qkv, l.xd, w->attn_norm[i], nullptr, l.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
-    SRGPT_TRY(srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, 1, T, Hq, Hkv, D,
-                                           st->max_pos, dt, stream));
-    SRGPT_TRY(ds.gemv(m.o, l.attnd, nullptr, l.xd, l.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
-    SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
-    SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
-  }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
-                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
-  if (st->sampling) {
-    if (sampler == SRGPT_SAMPLER_FULL) {
-      const SampleFullWs c = carve_sample_full_ws(sample_ws, T, w->vocab);
-      SRGPT_TRY(srgpt_sample_full_rows_launch(lk->logits, st->sampling, sample_ws, c.pv, c.pi, nullptr, T, w->vocab, s));
-      return srgpt_lookup_accept_sampled_launch(st->sampling, 0, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
-                                                st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
-    }
-    const SampleWs c = carve_sample_ws(sample_ws, T);
-    SRGPT_TRY(srgpt_sample_rows_launch(lk->logits, st->sampling, l.row_ids, sample_ws, c.pv, c.pi, d.err, T, w->vocab, s));
-    return srgpt_lookup_accept_sampled_launch(st->sampling, 1, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
-                                              st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
-  }
-  hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, T), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
-  SRGPT_LAUNCH_CHECK();
-  return srgpt_lookup_accept_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos, st->step,
-                                    st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
-}
-
-extern "C" int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
-  SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_step"));
-  return lookup_step_impl(w, st, lk, stream);
-}
-
-extern "C" int srgpt_llm_lookup_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
-                                        void* sample_ws, srgpt_stream_t stream) {
-  SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_step_ex"));
-  return lookup_step_impl(w, st, lk, stream, sampler, sample_ws);
-}
-
-// srgpt_llm_decode_sync_state for a state the lookup step ran on: the lookup workspace's own arrival tickets first, then everything
-// the plain check reads (the state's tickets, its sticky error word)
-extern "C" int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk,
-                                           srgpt_stream_t stream) {
-  SRGPT_CHECK(lk && lk->ws && lk->T >= 2 && lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state: bad lookup block");
-  SRGPT_TRY(check_llm(w, st));
-  const LookupWs l = carve_lookup(w, lk->T, lk->ws);
-  size_t bytes = 0;
-  void* sync = srgpt_decode_attn_multi_sync_words(l.dws, 1, lk->T, w->heads, w->head_dim, &bytes);
-  std::vector<int> host(bytes / sizeof(int));
-  SRGPT_HIP_TRY(hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_lookup_sync_state: copy");
-  SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_llm_lookup_sync_state: synchronize");
-  for (size_t i = 0; i < host.size(); ++i)
-    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "lookup step: arrival ticket %zu of %zu is %d between steps (expected 0)", i, host.size(),
-                host[i]);
-  return srgpt_llm_decode_sync_state(w, st, stream);
-}
-
-// ================================================================================================
-// the batched lookup step: B sequences of T rows each through ONE pass over the weights (B * T <= 16 rows, the skinny kernel's pass)
-// ================================================================================================
-namespace {
-
-// srgpt_lookup_batch::ws: carve_lookup for B sequences -- B * T rows of the decode step's buffers and of the two row-statistics
-// tables, the multi-token attention's workspace for (B, T) (its tickets zero between launches), B * T rows of pick partials and the
-// [B, T] draft, row-id and count scratch
-struct LookupBatchWs {
-  void *xd, *qkvd, *attnd, *actd;
-  float* rowss;
-  float* dws;
-  float* amax_v;
-  int* amax_i;
-  int64_t *draft, *row_ids;
-  int* n_draft;
-  size_t total;
-};
-LookupBatchWs carve_lookup_batch(const srgpt_llm_weights* w, int B, int T, void* ws) {
-  const size_t es = dtype_size(w->dtype);
-  const size_t qkvw = (size_t)(w->heads + 2 * w->kv_heads) * w->head_dim;
-  const size_t rows = (size_t)B * T;
-  Carver c(ws);
-  LookupBatchWs l;
-  l.xd = c.take(rows * w->hidden * es);
-  l.qkvd = c.take(rows * qkvw * es);
-  l.attnd = c.take(rows * w->heads * w->head_dim * es);
-  l.actd = c.take(rows * w->inter * es);
-  l.rowss = reinterpret_cast<float*>(c.take(2 * rows * SRGPT_ROWSS_STRIDE * sizeof(float)));
-  l.dws = reinterpret_cast<float*>(c.take((size_t)srgpt_decode_attn_multi_ws_floats(B, T, w->heads, w->head_dim) * 4));
-  l.amax_v = reinterpret_cast<float*>(c.take(rows * PICK_SLICES * 4));
-  l.amax_i = reinterpret_cast<int*>(c.take(rows * PICK_SLICES * 4));
-  l.draft = reinterpret_cast<int64_t*>(c.take(rows * 8));
-  l.row_ids = reinterpret_cast<int64_t*>(c.take(rows * 8));
-  l.n_draft = reinterpret_cast<int*>(c.take(rows * sizeof(int)));
-  l.total = c.off;
-  return l;
-}
-
-}  // namespace
-
-extern "C" int64_t srgpt_llm_lookup_batch_ws_bytes(const srgpt_llm_weights* w, int B, int T) {
-  if (!w || B < 1 || T < 2 || (int64_t)B * T > srgpt_lookup_rows_max()) return -1;
-  return (int64_t)carve_lookup_batch(w, B, T, nullptr).total;
-}
-
 // every batched lookup entry point, on the host before any launch
 static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk, const char* fn) {
   SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
@@ -1094,80 +1035,112 @@ static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state*
   SRGPT_CHECK((int64_t)st->batch * lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED,
               "%s: batch %d x T=%d = %lld rows exceed the %d rows of one weight pass", fn, st->batch, lk->T, (long long)st->batch * lk->T,
               srgpt_lookup_rows_max());
-  const AttnDecodeMultiRoute r =
-      attn_decode_multi_route(w->dtype == SRGPT_BF16, st->batch, lk->T, w->heads, w->kv_heads, w->head_dim, st->max_pos);
-  SRGPT_CHECK(r.status == ATTN_OK, SRGPT_ERR_UNSUPPORTED, "%s: T=%d rows x %d heads per kv head exceed the %d columns of the attention kernel",
-              fn, lk->T, r.G, ATTN_DEC_MULTI_COLS);
-  SRGPT_TRY(pick_check_vocab(w->vocab, fn));
+  SRGPT_TRY(check_lookup_rows(w, st, lk->T, fn));
   SRGPT_CHECK(lk->ws && lk->logits && lk->stats && lk->steps && lk->n_prompt && (lk->prompt_ids || lk->ld_prompt == 0), SRGPT_ERR_ARG,
               "%s: lookup block has null buffers", fn);
   SRGPT_CHECK(lk->ld_prompt >= 0, SRGPT_ERR_ARG, "%s: ld_prompt=%d is negative", fn, lk->ld_prompt);
-  SRGPT_CHECK(lk->max_ngram >= 1 && lk->max_ngram <= srgpt_lookup_ngram_max(), SRGPT_ERR_ARG, "%s: max_ngram=%d outside 1 .. %d", fn,
-              lk->max_ngram, srgpt_lookup_ngram_max());
+  SRGPT_TRY(check_max_ngram(lk->max_ngram, fn));
   LlmFormat fmt;
   return llm_format(w, fn, &fmt);
 }
 
-// lookup_step_impl's launches with rows = B * T: the batched draft (one block per sequence) -> embed the B * T ids -> per layer the
-// four products over B * T rows and srgpt_decode_attention_multi with B sequences (its existing template instances: T * G columns
-// per sequence, one position per sequence) -> lm_head -> the rows' argmax partials -> the batched accept
-static int lookup_step_batch_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, srgpt_stream_t stream) {
+extern "C" int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, int T, int sampler) {
+  if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
+  if (sampler == SRGPT_SAMPLER_TOPK64) return srgpt_sample_ws_bytes(T);
+  if (sampler == SRGPT_SAMPLER_FULL) return srgpt_sample_full_ws_bytes(T, w->vocab);
+  return -1;
+}
+
+// draft -> embed the R = B * T ids -> the layers and lm_head of the plain step over R rows, with the multi-token attention for B
+// sequences of T rows (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> the rows' picks -> accept.  The forms differ in
+// the first and the last launch only.  Draft: the batched kernel reads every row's id count from the device, the single one takes
+// the public struct's host int.  Accept: greedy (st->sampling == NULL) the rows' argmax partials, then the single or the batched
+// accept; sampled (single only: check_lookup_batch refuses it) the sampler q.sampler in its rows-are-steps mode over the T rows
+// (q.sample_ws: its own workspace, srgpt_llm_lookup_sample_ws_bytes; error bits go to the state's sticky word), then the accept
+// that advances the Philox counter.  The top-k-64 sampler's drawn ids go to the lookup workspace's row_ids, dead since the rows were
+// embedded.
+static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const LookupReq& q, srgpt_stream_t stream) {
+  const bool batched = q.steps != nullptr;
   LlmFormat fmt;
-  SRGPT_TRY(llm_format(w, "srgpt_llm_lookup_step_batch", &fmt));
-  const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, Hkv = w->kv_heads, D = w->head_dim;
-  const int B = st->batch, T = lk->T, R = B * T, QW = (Hq + 2 * Hkv) * D;
-  const size_t es = dtype_size(dt);
+  SRGPT_TRY(llm_format(w, batched ? "srgpt_llm_lookup_step_batch" : "srgpt_llm_lookup_step", &fmt));
+  const int dt = w->dtype, Hd = w->hidden, B = q.B, T = q.T, R = B * T;
   hipStream_t s = as_stream(stream);
   const LlmWs d = carve_llm(w, B, st->ws_tokens, st->ws);  // the state's sticky error word and embedded-token record
-  const LookupBatchWs l = carve_lookup_batch(w, B, T, lk->ws);
-  const size_t layer_kv = (size_t)B * Hkv * st->max_pos * D * es;
-  SRGPT_TRY(srgpt_lookup_draft_batch_launch(lk->prompt_ids, lk->ld_prompt, lk->n_prompt, st->out_ids, lk->steps, B, st->max_new, T - 1,
-                                            lk->max_ngram, (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
+  const LookupWs l = carve_lookup(w, B, T, q.ws);
+  if (batched)
+    SRGPT_TRY(srgpt_lookup_draft_batch_launch(q.prompt_ids, q.ld_prompt, q.n_prompt_dev, st->out_ids, q.steps, B, st->max_new, T - 1,
+                                              q.max_ngram, (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
+  else
+    SRGPT_TRY(srgpt_lookup_draft_launch(q.prompt_ids, q.n_prompt, st->out_ids, st->step, st->max_new, T - 1, q.max_ngram,
+                                        (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
   SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, R, Hd, dt, stream));
-  const DecodeStep ds = DecodeStep::make(w, fmt, R, stream);
-  float* const ss_attn = l.rowss;
-  float* const ss_mlp = l.rowss + (size_t)R * SRGPT_ROWSS_STRIDE;
-  for (int i = 0; i < w->layers; ++i) {
-    char* kc = reinterpret_cast<char*>(st->kcache) + (size_t)i * layer_kv;
-    char* vc = reinterpret_cast<char*>(st->vcache) + (size_t)i * layer_kv;
-    const LayerMats m = layer_mats(w, fmt, i);
-    SRGPT_TRY(ds.gemv(m.qkv, l.xd, w->attn_norm[i], nullptr, l.qkvd, QW, Hd, 0, 0, i > 0 ? ss_mlp : nullptr, nullptr));
-    SRGPT_TRY(srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, B, T, Hq, Hkv, D,
-                                           st->max_pos, dt, stream));
-    SRGPT_TRY(ds.gemv(m.o, l.attnd, nullptr, l.xd, l.xd, Hd, Hq * D, 0, 0, nullptr, ss_attn));
-    SRGPT_TRY(ds.gemv(m.gu, l.xd, w->mlp_norm[i], nullptr, l.actd, I, Hd, 1, 0, ss_attn, nullptr));
-    SRGPT_TRY(ds.gemv(m.down, l.actd, nullptr, l.xd, l.xd, Hd, I, 0, 0, nullptr, ss_mlp));
+  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(l.xd, l.qkvd, l.attnd, l.actd, l.rowss, R), stream);
+  SRGPT_TRY(ds.layers_lm_head(st, q.logits, [&](int, const LayerMats&, void* kc, void* vc) {
+    return srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, B, T, w->heads, w->kv_heads,
+                                        w->head_dim, st->max_pos, dt, stream);
+  }));
+  if (st->sampling) {
+    if (q.sampler == SRGPT_SAMPLER_FULL) {
+      const SampleFullWs c = carve_sample_full_ws(q.sample_ws, T, w->vocab);
+      SRGPT_TRY(srgpt_sample_full_rows_launch(q.logits, st->sampling, q.sample_ws, c.pv, c.pi, nullptr, T, w->vocab, s));
+      return srgpt_lookup_accept_sampled_launch(st->sampling, 0, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
+                                                st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
+    }
+    const SampleWs c = carve_sample_ws(q.sample_ws, T);
+    SRGPT_TRY(srgpt_sample_rows_launch(q.logits, st->sampling, l.row_ids, q.sample_ws, c.pv, c.pi, d.err, T, w->vocab, s));
+    return srgpt_lookup_accept_sampled_launch(st->sampling, 1, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
+                                              st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
   }
-  SRGPT_TRY(ds.gemv(Mat{w->lm_head, w->lm_head8, w->lm_head_scale, nullptr, 0, nullptr, nullptr}, l.xd, w->final_norm, nullptr, lk->logits, w->vocab, Hd,
-                    0, 1, w->layers > 0 ? ss_mlp : nullptr, nullptr));
-  hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, R), dim3(256), 0, s, lk->logits, l.amax_v, l.amax_i, w->vocab);
+  hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, R), dim3(256), 0, s, q.logits, l.amax_v, l.amax_i, w->vocab);
   SRGPT_LAUNCH_CHECK();
-  return srgpt_lookup_accept_batch_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, B, T, st->tok, st->out_ids, st->pos, lk->steps,
-                                          st->step, st->max_new, st->max_pos, d.tok_emb, lk->stats, s);
+  if (batched)
+    return srgpt_lookup_accept_batch_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, B, T, st->tok, st->out_ids, st->pos, q.steps,
+                                            st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
+  return srgpt_lookup_accept_launch(nullptr, l.amax_v, l.amax_i, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos, st->step,
+                                    st->max_new, st->max_pos, d.tok_emb, q.stats, s);
+}
+
+extern "C" int srgpt_llm_lookup_step(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_step"));
+  return lookup_step_impl(w, st, lookup_req(lk), stream);
+}
+
+extern "C" int srgpt_llm_lookup_step_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
+                                        void* sample_ws, srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_step_ex"));
+  return lookup_step_impl(w, st, lookup_req(lk, sampler, sample_ws), stream);
 }
 
 extern "C" int srgpt_llm_lookup_step_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
                                            srgpt_stream_t stream) {
   SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_step_batch"));
-  return lookup_step_batch_impl(w, st, lk, stream);
+  return lookup_step_impl(w, st, lookup_req(lk, st->batch), stream);
 }
 
-// srgpt_llm_lookup_sync_state for the batched step: the (B, T) lookup workspace's tickets, then the state's own check
+// srgpt_llm_decode_sync_state for a state a lookup step ran on: the (B, T) lookup workspace's own arrival tickets first, then
+// everything the plain check reads (the state's tickets, its sticky error word)
+static int lookup_sync_impl(const srgpt_llm_weights* w, const srgpt_llm_state* st, int B, int T, void* ws, srgpt_stream_t stream,
+                            const char* fn, const char* what) {
+  const LookupWs l = carve_lookup(w, B, T, ws);
+  size_t bytes = 0;
+  void* sync = srgpt_decode_attn_multi_sync_words(l.dws, B, T, w->heads, w->head_dim, &bytes);
+  SRGPT_TRY(check_tickets(sync, bytes, stream, fn, what));
+  return srgpt_llm_decode_sync_state(w, st, stream);
+}
+
+extern "C" int srgpt_llm_lookup_sync_state(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup* lk,
+                                           srgpt_stream_t stream) {
+  SRGPT_CHECK(lk && lk->ws && lk->T >= 2 && lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state: bad lookup block");
+  SRGPT_TRY(check_llm(w, st));
+  return lookup_sync_impl(w, st, 1, lk->T, lk->ws, stream, "srgpt_llm_lookup_sync_state", "lookup step");
+}
+
 extern "C" int srgpt_llm_lookup_sync_state_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk,
                                                  srgpt_stream_t stream) {
   SRGPT_CHECK(lk && lk->ws && lk->T >= 2, SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state_batch: bad lookup block");
   SRGPT_TRY(check_llm(w, st));
   SRGPT_CHECK((int64_t)st->batch * lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_ARG, "srgpt_llm_lookup_sync_state_batch: bad lookup block");
-  const LookupBatchWs l = carve_lookup_batch(w, st->batch, lk->T, lk->ws);
-  size_t bytes = 0;
-  void* sync = srgpt_decode_attn_multi_sync_words(l.dws, st->batch, lk->T, w->heads, w->head_dim, &bytes);
-  std::vector<int> host(bytes / sizeof(int));
-  SRGPT_HIP_TRY(hipMemcpyAsync(host.data(), sync, bytes, hipMemcpyDeviceToHost, as_stream(stream)), "srgpt_llm_lookup_sync_state_batch: copy");
-  SRGPT_HIP_TRY(hipStreamSynchronize(as_stream(stream)), "srgpt_llm_lookup_sync_state_batch: synchronize");
-  for (size_t i = 0; i < host.size(); ++i)
-    SRGPT_CHECK(host[i] == 0, SRGPT_ERR_STATE, "batched lookup step: arrival ticket %zu of %zu is %d between steps (expected 0)", i,
-                host.size(), host[i]);
-  return srgpt_llm_decode_sync_state(w, st, stream);
+  return lookup_sync_impl(w, st, st->batch, lk->T, lk->ws, stream, "srgpt_llm_lookup_sync_state_batch", "batched lookup step");
 }
 
 // ================================================================================================
@@ -1221,21 +1194,21 @@ extern "C" int srgpt_llm_lookup_graph_create(const srgpt_llm_weights* w, srgpt_l
                                              srgpt_stream_t stream, srgpt_graph** out) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create: null out");
   SRGPT_TRY(check_lookup(w, st, lk, "srgpt_llm_lookup_graph_create"));
-  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream); });
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lookup_req(lk), stream); });
 }
 
 extern "C" int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup* lk, int sampler,
                                                 void* sample_ws, srgpt_stream_t stream, srgpt_graph** out) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_ex: null out");
   SRGPT_TRY(check_lookup_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_graph_create_ex"));
-  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lk, stream, sampler, sample_ws); });
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lookup_req(lk, sampler, sample_ws), stream); });
 }
 
 extern "C" int srgpt_llm_lookup_graph_create_batch(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
                                                    srgpt_stream_t stream, srgpt_graph** out) {
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_batch: null out");
   SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_graph_create_batch"));
-  return capture_graph(stream, out, [&] { return lookup_step_batch_impl(w, st, lk, stream); });
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lookup_req(lk, st->batch), stream); });
 }
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,

@@ -101,6 +101,46 @@ def test_draft_rule_equals_the_python_restatement():
     assert draft[:int(nd)].tolist() == draft_ref(long, 5, 3, V) and int(nd) == 5
 
 
+def test_batched_draft_of_one_sequence_is_the_single_draft():
+    """srgpt_lookup_draft_batch with B = 1 against srgpt_lookup_draft, element for element: the two kernels find their history and
+    call ONE draft body.  Every history above, at its own count, at max_new and beyond it (both clamp to the max_new ids of out_ids)"""
+    from spatialrgpt_amd import ops
+
+    max_new = 8
+    for prompt, gen, k, ng in DRAFT_CASES:
+        out_ids = torch.full((max_new,), 77, dtype=torch.int64)
+        out_ids[:len(gen)] = torch.tensor(gen, dtype=torch.int64)
+        out_ids = out_ids.to(DEV)
+        p = torch.tensor(prompt, dtype=torch.int64, device=DEV) if prompt else None
+        for count in (len(gen), max_new, max_new + 3):
+            step = torch.tensor([count], dtype=torch.int32, device=DEV)
+            one, n_one = ops.lookup_draft(p, out_ids, step, k, ng, V)
+            many, n_many = ops.lookup_draft_batch(None if p is None else p[None], torch.tensor([len(prompt)], dtype=torch.int32, device=DEV),
+                                                  out_ids[None], step, k, ng, V)
+            assert torch.equal(many[0], one) and torch.equal(n_many, n_one), (prompt, gen, count, one.tolist(), many.tolist())
+
+
+def test_accept_leaves_a_negative_count_alone():
+    """srgpt_lookup_accept with *step = -1 (no state of a request): the sequence is frozen, as a row of the batched accept is -- no
+    id is written in front of out_ids (a sentinel row on either side), nothing advances, nothing is counted"""
+    from spatialrgpt_amd import ops
+
+    T, max_new = 4, 8
+    big = torch.full((3, max_new), SENT, dtype=torch.int64, device=DEV)
+    big[1] = torch.arange(100, 100 + max_new, device=DEV)
+    bufs = dict(big=big, tok=torch.tensor([41], dtype=torch.int64, device=DEV), pos=torch.tensor([9], dtype=torch.int32, device=DEV),
+                step=torch.tensor([-1], dtype=torch.int32, device=DEV), tok_emb=torch.tensor([41], dtype=torch.int64, device=DEV),
+                stats=torch.tensor([3, 7, 5], dtype=torch.int32, device=DEV))
+    before = {k: v.clone() for k, v in bufs.items()}
+    picks = torch.tensor([11, 12, 13, 14], dtype=torch.int64, device=DEV)
+    draft = torch.tensor([11, 12, 99], dtype=torch.int64, device=DEV)  # two would be accepted, three ids emitted
+    ops.lookup_accept(picks, draft, torch.tensor([T - 1], dtype=torch.int32, device=DEV), bufs["tok"], big[1], bufs["pos"], bufs["step"],
+                      64, tok_emb=bufs["tok_emb"], stats=bufs["stats"])
+    torch.cuda.synchronize()
+    for k in bufs:
+        assert torch.equal(bufs[k], before[k]), (k, bufs[k].tolist(), before[k].tolist())
+
+
 # ------------------------------------------------------------------------------------------------ the peaked bundle
 @functools.lru_cache(maxsize=None)
 def _bundle():

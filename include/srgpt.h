@@ -206,6 +206,41 @@ int srgpt_pack_decode_weights(const void* W, void* out, int N, int K, int elem_b
 int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float norm_eps, const void* residual,
                   void* out, int batch, int N, int K, int swiglu, int out_f32, srgpt_stream_t stream);
 int srgpt_dequant_mxfp4(const void* W4, const void* wscale8, void* out_bf16, int N, int K, srgpt_stream_t stream);
+/* Additions under ABI 9: bf16 weights as LOSSLESS 13-bit codes for the batch-1 decode step -- 0.8125 of the bytes per streamed
+ * matrix and bit for bit the results of srgpt_gemv.  Not a quantisation: a bf16 weight is s | e8 | m7, the exponents of a weight row
+ * lie within a few dozen values below the row's largest, so a row stores an even base exponent b = max(emax - 31, 1) rounded up to
+ * even, and each weight s | c5 | m7 with c = e - b in [0, 31].  A row holding a weight that does not fit -- exponent field 0 (zero,
+ * denormal), 255 (Inf, NaN), or below b -- is an EXCEPTION ROW: flagged, and read from the raw matrix instead, so every bf16 matrix
+ * round-trips exactly.  The matrix [N, K] row-major bf16, K % 512 == 0 (a SwiGLU matrix: its 2 N rows as one matrix):
+ *   packed  srgpt_pack13_bytes(N, K, &flag_bytes) bytes: per row ceil(K / 2048) groups of 3328 bytes (K = 4096: 6656 per row against
+ *           8192); a group holds 4 x 64 x 8 weights as a plane of sign bits (256 B), of c >> 1 nibbles (1 KiB) and of low bytes
+ *           e0 | m7 (2 KiB), each ordered [lane][bytes] so that a wave loads it with one instruction and lane l receives the
+ *           weights k = ((4 g + t) * 64 + l) * 8 + i of the raw kernel's loads (csrc/pack13.h has the bit positions)
+ *   flags   flag_bytes bytes: one 32-bit word per row -- b / 2 replicated into its four bytes, or 0xffffffff for an exception row
+ *           -- and one more word, the number of exception rows
+ * srgpt_pack13 runs on the device, synchronises the stream and returns the number of exception rows (>= 0) or an error (< 0);
+ * srgpt_unpack13 writes the exact bf16 matrix back (coded rows from the planes, exception rows from W_raw): tests and debugging.
+ * srgpt_gemv_p13: srgpt_gemv's product for ONE bf16 row of x over such a copy, same fusions (RMSNorm prologue, SwiGLU, residual,
+ * fp32 out) and the same bits: per row the same fp32 accumulation order, reduction and rounding points; exception rows are streamed
+ * from W_raw, which must be the matrix the copy was packed from.
+ * The binding table: srgpt_llm_weights has no field for these copies; srgpt_pack13_bind(W_raw, packed, flags, N, K) records, on the
+ * host, that the raw matrix at address W_raw has this packed copy.  srgpt_llm_decode_step (and its _ex / _proc / graph forms), in a
+ * bf16 engine without fp8 / MXFP4 copies and with ONE row per step, looks up wqkv[i], wgu[i] (2 inter rows), wdown[i] and lm_head
+ * at launch / capture time and streams the packed copy of each matrix bound with exactly its shape; everything else -- 2+ rows,
+ * lookup steps, prefill, srgpt_gemv itself -- reads the raw matrices.  Unbind (srgpt_pack13_unbind: 1 if there was a binding)
+ * BEFORE the raw or the packed buffer is freed or overwritten; a graph captured while bound keeps reading the packed copy.
+ * srgpt_pack13_bound: 1 / 0.  The table is mutex-protected and GLOBAL TO THE PROCESS, one binding per raw address: a second bind of
+ * an address replaces the first, and an unbind removes whichever is there -- two owners of one raw matrix (two engines over the
+ * same device tensors) must not both bind it; check srgpt_pack13_bound first, or bind a matrix of your own (the Python loader
+ * clones a shared matrix before it binds).  o_proj (wo[i]) is never looked up: the attention launch prefetches its raw bytes. */
+size_t srgpt_pack13_bytes(int N, int K, size_t* flag_bytes);
+int srgpt_pack13(const void* W, int N, int K, void* packed, void* flags, srgpt_stream_t stream);
+int srgpt_unpack13(const void* packed, const void* flags, const void* W_raw, int N, int K, void* out, srgpt_stream_t stream);
+int srgpt_gemv_p13(const void* x, const void* packed, const void* flags, const void* W_raw, const void* norm_w, float norm_eps,
+                   const void* residual, void* out, int N, int K, int swiglu, int out_f32, srgpt_stream_t stream);
+int srgpt_pack13_bind(const void* W_raw, const void* packed, const void* flags, int N, int K);
+int srgpt_pack13_unbind(const void* W_raw);
+int srgpt_pack13_bound(const void* W_raw);
 
 /* ---------------------------------------------------------------------------------------------
  * Normalisations.

@@ -117,6 +117,13 @@ _SIGNATURES = {
     "srgpt_gemv_w8": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemv_w4": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_dequant_mxfp4": (i32, [vp, vp, vp, i32, i32, vp]),
+    "srgpt_pack13_bytes": (C.c_size_t, [i32, i32, C.POINTER(C.c_size_t)]),
+    "srgpt_pack13": (i32, [vp, i32, i32, vp, vp, vp]),
+    "srgpt_unpack13": (i32, [vp, vp, vp, i32, i32, vp, vp]),
+    "srgpt_gemv_p13": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, vp]),
+    "srgpt_pack13_bind": (i32, [vp, vp, vp, i32, i32]),
+    "srgpt_pack13_unbind": (i32, [vp]),
+    "srgpt_pack13_bound": (i32, [vp]),
     "srgpt_splice_scratch_ints": (i64, [i32, i32]),
     "srgpt_splice_plan": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
     "srgpt_splice_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i64, vp, vp, vp, vp]),

@@ -4,6 +4,7 @@
 // step (tests/golden/gemv_routes.json) -- every threshold below was calibrated on the MI355X, and all routes compute the same bits,
 // so nothing else notices a slipped comparison.
 #pragma once
+#include "pack13.h"  // the packed format's group size, for gemv_p13_launch
 
 enum GemvFamily {
   GEMV_LDS,     // gemv_kernel<T, B, SWIGLU, NX, UB> (gemv.hip): VALU, 1 - 4 rows staged in LDS
@@ -11,6 +12,7 @@ enum GemvFamily {
   GEMV_W8,      // gemv_w8_kernel<1, SWIGLU, NX> (gemv_w8.hip): VALU, one bf16 row, fp8 weights
   GEMV_SKINNY,  // skinny_kernel<SWIGLU, NI, NW, W8, PUB, PK> (skinny.hip): MFMA, up to 16 bf16 rows
   GEMV_W4,      // gemv_w4_kernel<B, SWIGLU, NX> (gemv_w4.hip): VALU, 1 - 4 bf16 rows, MXFP4 weights (its own route functions below)
+  GEMV_P13,     // gemv_p13_kernel<SWIGLU, NX> (gemv_p13.hip): VALU, one bf16 row, 13-bit packed bf16 weights (route functions below)
 };
 
 // How a call is cut: ceil(rows / chunk) launches of up to `chunk` rows, each streaming the weights once, ALL on `family` -- a
@@ -179,5 +181,25 @@ inline GemvValuLaunch gemv_w4_launch(int B, int N, int K, bool swiglu, int cus) 
   l.NX = valu_nx(B * (K / 8));
   l.NIT = ceil_div(K / 32, 64);
   l.grid = valu_grid(ceil_div(N, W4_UNIT_COLS), l.lds, cus);
+  return l;
+}
+
+// ---- srgpt_gemv_p13 (gemv_p13.hip): bf16 weights in the lossless 13-bit code of pack13.h, one bf16 activation row.  The same
+// unit / wave / grid decomposition as GEMV_LDS (a unit is one output row, or a gate and an up row), and the same bits.  A row is
+// streamed in groups of 2048 weights = 4 wave loads (3328 bytes), and a batch is ONE group of each of the unit's rows (4 loads in
+// flight per wave, SwiGLU 8).  Measured per product at one row on the MI355X (profiles/pack13.txt, us per launch, raw kernel first;
+// g = groups per batch): lm_head 163.4 | g 1: 136.5, g 2: 138.8; gate/up 37.1 | g 1: 33.7, g 2: 34.3; q/k/v 10.3 | g 1: 11.8, g 2: 12.1;
+// down_proj 21.1 | g 1: 26.6, g 7 (the whole row, 256 VGPRs): 30.3 -- the last two products stay on the raw kernels.
+inline bool gemv_p13_eligible(int rows, int K) { return rows == 1 && p13_eligible(1, K); }
+inline GemvRoute gemv_p13_route() { return GemvRoute{GEMV_P13, 1}; }  // one row per launch, and no call of more
+
+// one launch: NIT = groups per row, UB = loads per batch and row, lds = the activation row padded to whole groups
+inline GemvValuLaunch gemv_p13_launch(int N, int K, int cus) {
+  using namespace gemv_route_detail;
+  const int groups = p13_groups(K);
+  GemvValuLaunch l{1, 0, 4, groups, 0, (long long)groups * P13_GROUP_WEIGHTS * 2, false};
+  l.raise_lds_limit = l.lds > 48 * 1024;
+  l.NX = valu_nx(K / 8);
+  l.grid = valu_grid(N, l.lds, cus);
   return l;
 }

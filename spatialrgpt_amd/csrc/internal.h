@@ -41,6 +41,11 @@ int srgpt_decode_product(const DecodeProduct& p, hipStream_t s);
 int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s);  // skinny.hip: MFMA, up to 16 bf16 rows, bf16 or fp8 weights
 int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s);   // gemv_w8.hip: VALU, one row, fp8 weights (K % 16 == 0)
 
+// ---- pack13.hip: the binding table of the 13-bit packed copies (pack13_bind.h), for the decode-layer sequence of model.hip: the
+//      binding srgpt_pack13_bind made for the raw matrix at W_raw, if it has exactly this shape ----
+struct Pack13Binding;
+bool srgpt_pack13_lookup(const void* W_raw, int rows, int K, Pack13Binding* out);
+
 // ---- attn.hip: the decode attention with the L2 prefetch of the next GEMV's weights, and its arrival tickets, for model.hip ----
 int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,
                               const void* sin_tab, void* out, float* ws, int B, int Hq, int Hkv, int D, int max_pos, int dtype,

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "gemv_route.h"
 #include "internal.h"
+#include "pack13_bind.h"
 #include "pick.h"
 
 namespace {
@@ -773,23 +774,32 @@ struct DecodeStep {
   LlmFormat fmt;
   StepRows r;
   bool fp8, pub;
+  bool p13;  // the plain one-row step of a bf16 engine in its dtype format: a matrix with a bound 13-bit copy is streamed from it
   srgpt_stream_t stream;
 
-  // fp8: the matrices that are not MXFP4 (under FMT_W4A16: lm_head) are fp8
-  static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, const StepRows& r, srgpt_stream_t stream) {
+  // fp8: the matrices that are not MXFP4 (under FMT_W4A16: lm_head) are fp8.  plain_step: srgpt_llm_decode_step and its forms (the
+  // lookup steps read the raw matrices whatever is bound)
+  static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, const StepRows& r, srgpt_stream_t stream, bool plain_step) {
     const bool fp8 = fmt != FMT_DTYPE;
     const bool pub = fmt != FMT_W4A16 && gemv_rowss_supported(r.rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
-    return DecodeStep{w, fmt, r, fp8, pub, stream};
+    const bool p13 = plain_step && fmt == FMT_DTYPE && w->dtype == SRGPT_BF16 && r.rows == 1;
+    return DecodeStep{w, fmt, r, fp8, pub, p13, stream};
   }
 
+  // packable: q/k/v, gate/up, down_proj and lm_head; o_proj is not -- the attention launch prefetches its RAW matrix into L2
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
-           const float* ss_in, float* ss_out) const {
+           const float* ss_in, float* ss_out, bool packable = true) const {
     if (m.w4)  // MXFP4 layer matrix (pub is false under the format: its kernel neither reads nor publishes row statistics)
       return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
     if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
       return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out,
                               m.pk ? m.pk_rows : 0, stream);
     if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
+    if (p13 && packable) {  // consulted on the host, at eager launch and at graph capture; srgpt_gemv itself never looks (it is the raw reference)
+      Pack13Binding b;
+      if (gemv_p13_eligible(r.rows, K) && srgpt_pack13_lookup(m.w, swiglu ? 2 * N : N, K, &b))
+        return srgpt_gemv_p13(x, b.packed, b.meta, m.w, norm, w->rms_eps, res, out, N, K, swiglu, f32, stream);
+    }
     return srgpt_gemv(x, m.w, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, w->dtype, stream);
   }
 
@@ -807,7 +817,7 @@ struct DecodeStep {
       const LayerMats m = layer_mats(w, fmt, i);
       SRGPT_TRY(gemv(m.qkv, r.xd, w->attn_norm[i], nullptr, r.qkvd, QW, Hd, 0, 0, i > 0 ? r.ss_mlp : nullptr, nullptr));
       SRGPT_TRY(attention(i, m, kc, vc));
-      SRGPT_TRY(gemv(m.o, r.attnd, nullptr, r.xd, r.xd, Hd, HqD, 0, 0, nullptr, r.ss_attn));
+      SRGPT_TRY(gemv(m.o, r.attnd, nullptr, r.xd, r.xd, Hd, HqD, 0, 0, nullptr, r.ss_attn, false));
       SRGPT_TRY(gemv(m.gu, r.xd, w->mlp_norm[i], nullptr, r.actd, I, Hd, 1, 0, r.ss_attn, nullptr));
       SRGPT_TRY(gemv(m.down, r.actd, nullptr, r.xd, r.xd, Hd, I, 0, 0, nullptr, r.ss_mlp));
     }
@@ -836,7 +846,7 @@ static int decode_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, srg
     SRGPT_LAUNCH_CHECK();
   }
   const bool fp8 = fmt != FMT_DTYPE, w4 = fmt == FMT_W4A16;
-  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(d.xd, d.qkvd, d.attnd, d.actd, d.rowss, B), stream);
+  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(d.xd, d.qkvd, d.attnd, d.actd, d.rowss, B), stream, true);
   // the attention launch also pulls o_proj's weights into L2 (HBM is idle while it runs).  Round 3 built the next step -- o_proj
   // itself inside this launch, weights in registers, agent-scope hand-off -- bit-exact and 3 us per layer SLOWER
   // (profiles/r03_fused_attention_oproj.txt)
@@ -1074,7 +1084,7 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
     SRGPT_TRY(srgpt_lookup_draft_launch(q.prompt_ids, q.n_prompt, st->out_ids, st->step, st->max_new, T - 1, q.max_ngram,
                                         (int64_t)w->vocab, l.draft, l.n_draft, st->tok, l.row_ids, d.err, s));
   SRGPT_TRY(srgpt_embed_rows(w->embed, l.row_ids, l.xd, R, Hd, dt, stream));
-  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(l.xd, l.qkvd, l.attnd, l.actd, l.rowss, R), stream);
+  const DecodeStep ds = DecodeStep::make(w, fmt, step_rows(l.xd, l.qkvd, l.attnd, l.actd, l.rowss, R), stream, false);
   SRGPT_TRY(ds.layers_lm_head(st, q.logits, [&](int, const LayerMats&, void* kc, void* vc) {
     return srgpt_decode_attention_multi(l.qkvd, kc, vc, st->pos, w->rope_cos, w->rope_sin, l.attnd, l.dws, B, T, w->heads, w->kv_heads,
                                         w->head_dim, st->max_pos, dt, stream);

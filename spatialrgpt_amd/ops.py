@@ -261,6 +261,68 @@ def pack_decode_weights(w, rows: int):
     return out
 
 
+def pack13_eligible(w) -> bool:
+    """can this matrix be held as lossless 13-bit codes (include/srgpt.h, srgpt_pack13)?  bf16 [N, K] with K % 512 == 0."""
+    return w is not None and w.dim() == 2 and w.dtype == torch.bfloat16 and w.is_contiguous() and w.shape[1] % 512 == 0
+
+
+def pack13(w):
+    """srgpt_pack13: the lossless 13-bit code of a contiguous bf16 matrix [N, K], K % 512 == 0 (a SwiGLU matrix [gate; up] as the one
+    matrix of 2 N rows it is).  Returns (packed uint8, flags int32 [N + 1], number of exception rows); synchronises the stream."""
+    _dev(w)
+    if not pack13_eligible(w):
+        raise ValueError("pack13: a contiguous bf16 matrix [N, K] with K % 512 == 0")
+    N, K = w.shape
+    lib = L.load()
+    fb = C.c_size_t(0)
+    nbytes = int(lib.srgpt_pack13_bytes(N, K, C.byref(fb)))
+    packed = torch.empty((nbytes,), device=w.device, dtype=torch.uint8)
+    flags = torch.empty((fb.value // 4,), device=w.device, dtype=torch.int32)
+    n_exc = lib.srgpt_pack13(_p(w), N, K, _p(packed), _p(flags), _stream())
+    if n_exc < 0:
+        L.check(n_exc)
+    return packed, flags, int(n_exc)
+
+
+def unpack13(packed, flags, w_raw, out=None):
+    """srgpt_unpack13: the exact bf16 matrix of a packed copy (exception rows are copied from w_raw, the matrix it was packed from)."""
+    _dev(packed, flags, w_raw)
+    N, K = w_raw.shape
+    if out is None:
+        out = torch.empty((N, K), device=w_raw.device, dtype=torch.bfloat16)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.shape == (N, K)
+    L.check(L.load().srgpt_unpack13(_p(packed), _p(flags), _p(w_raw), N, K, _p(out), _stream()))
+    return out
+
+
+def gemv_p13(x, packed, flags, w_raw, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False):
+    """srgpt_gemv_p13: gemv() for ONE bf16 row over the 13-bit packed copy (pack13) of w_raw, bit for bit gemv(x, w_raw, ...)."""
+    _dev(x, packed, flags, w_raw, norm_w, residual)
+    _same_dtype("gemv_p13", x, weight=w_raw, norm_weight=norm_w, residual=residual)
+    B, K = x.shape
+    if B != 1 or x.dtype != torch.bfloat16 or w_raw.shape[1] != K or not w_raw.is_contiguous():
+        raise ValueError("gemv_p13: one bf16 row of x [1, K] and the contiguous raw matrix [rows, K]")
+    N = w_raw.shape[0] // 2 if swiglu else w_raw.shape[0]
+    if out is None:
+        out = torch.empty((B, N), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    L.check(L.load().srgpt_gemv_p13(_p(_c(x)), _p(packed), _p(flags), _p(w_raw), _p(norm_w), float(eps), _p(residual), _p(out), N, K,
+                                    int(swiglu), int(out_f32), _stream()))
+    return out
+
+
+def pack13_bind(w_raw, packed, flags) -> None:
+    """srgpt_pack13_bind: from now on the batch-1 decode step of a bf16 engine streams `packed` where its weights point at w_raw."""
+    L.check(L.load().srgpt_pack13_bind(_p(w_raw), _p(packed), _p(flags), int(w_raw.shape[0]), int(w_raw.shape[1])))
+
+
+def pack13_unbind(w_raw) -> bool:
+    return bool(L.load().srgpt_pack13_unbind(_p(w_raw)))
+
+
+def pack13_bound(w_raw) -> bool:
+    return bool(L.load().srgpt_pack13_bound(_p(w_raw)))
+
+
 def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False,
                rowss_in=None, publish=False, packed_rows=0, n_rows=None, table=None):
     """srgpt_gemv_rowss: the decode product of 2+ bf16 rows as the batched decode step runs it.  `rowss_in`: the statistics

@@ -24,6 +24,13 @@ RE = "region_extractor."
 MP = "mm_projector.layers."
 LM = "llm."
 
+# Lossless 13-bit packed copies (include/srgpt.h, srgpt_pack13) of the matrices the batch-1 bf16 decode step streams: which products
+# get one, by the per-product measurement of profiles/pack13.txt -- a product is listed only where its packed kernel's median beat
+# the raw kernel's minimum: gate/up (37.1 -> 33.7 us) and lm_head (163 -> 137 us); q/k/v (10.3 -> 11.8) and down_proj (21.1 ->
+# 26.6) stay raw.  o_proj was never a candidate: its raw register kernel reads weights the attention launch prefetched into L2.
+PACK13_PRODUCTS = ("wgu", "lm_head")
+PACK13_DEFAULT = True
+
 
 def _ptr_array(tensors: List[torch.Tensor]):
     arr = (L.vp * len(tensors))()
@@ -51,7 +58,8 @@ class PreparedWeights:
     ALL_PARTS = ("vit", "region", "projector", "llm")
 
     def __init__(self, cfg: SrgptConfig, sd: Dict[str, torch.Tensor], device, dtype, rope_positions: int = 0,
-                 consume: bool = False, llm_weight_format: str = "native", parts=None, decode_layout: str = "packed"):
+                 consume: bool = False, llm_weight_format: str = "native", parts=None, decode_layout: str = "packed",
+                 pack13=None):
         """llm_weight_format: "native" (the engine dtype) or "fp8" -- weight-only OCP e4m3fn quantisation of the five
         streamed LLM matrices with one fp32 (power-of-two) scale per output row (BASELINE config 5; bf16 engines only).  The
         fp8 bytes are the ONLY copy of those matrices in HBM: decode streams them (srgpt_gemv_w8), prefill multiplies them
@@ -59,7 +67,17 @@ class PreparedWeights:
         "mxfp4": the 4-bit option (bf16 engines only) -- the four per-layer matrices as OCP e2m1 codes with one E8M0 scale per 32
         values (ops.quantize_mxfp4_rows; include/srgpt.h, srgpt_gemv_w4), a quarter of the bf16 bytes and the only copy in HBM;
         lm_head is held as under "fp8".  Decode streams the codes (srgpt_gemv_w4); prefill expands each matrix into a bf16 scratch
-        just before its product.  Opt-in, it changes the numbers; its accuracy cost on a trained checkpoint is unmeasured."""
+        just before its product.  Opt-in, it changes the numbers; its accuracy cost on a trained checkpoint is unmeasured.
+        pack13 (bf16 engines, "native" only): also hold the PACK13_PRODUCTS as lossless 13-bit codes and bind them, so that the
+        batch-1 decode step streams 0.8125 of their bytes and computes the same bits.  None: PACK13_DEFAULT; True / False: on /
+        off.  On packs the matrices whose copy is smaller than the matrix (K % 2048 == 0).  "all" is for tests: q/k/v and
+        down_proj too (measured slower) and every K % 512 == 0 (a padded copy can be larger than the matrix).  The raw matrices
+        stay (prefill, batched rows, lookup steps and exception rows read them), so the copies are additional HBM: 0.8125 of
+        the packed matrices' bytes, +7.0 GB for the 8B model (32 gate/up matrices of 190.8 MB and lm_head of 853.7 MB: 16.1 ->
+        23.1 GB of weights; pack13_bytes()).  The binding table is global to the process and keyed by the raw matrix's address, so a
+        matrix this object binds is always its own: where the state dict's tensor would be used as it is (already on the device in
+        the engine dtype), it is cloned first -- otherwise a second engine built from the same tensors would share, replace and
+        tear down this one's binding."""
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         # parts: which components to materialise -- all of them for the model, ONE for the module-level factories
         # (spatialrgpt_amd/factories.py: the reference's build_vision_tower / build_mm_projector / build_region_extractor /
@@ -92,11 +110,20 @@ class PreparedWeights:
             raise ValueError(f"unknown decode_layout {decode_layout!r}")
         self.decode_layout = decode_layout  # fp8 weights: also keep the MFMA-operand-order copies the batched decode step streams
         self._keep: List[object] = []
+        if pack13 not in (None, True, False, "all"):
+            raise ValueError(f"unknown pack13 {pack13!r}")
+        self.pack13_mode = PACK13_DEFAULT if pack13 is None else bool(pack13)
+        self.pack13_all = isinstance(pack13, str)  # "all"
+        self._aliased = set()  # data_ptr of every tensor get() handed out without a copy: the caller's own storage
+        self.p13: Dict[str, list] = {}  # name -> per layer (raw, packed, flags, exception rows) of a bound matrix, or None
         code = {torch.float32: L.F32, torch.bfloat16: L.BF16}[dtype]
 
         def get(name):
             t = sd.pop(name) if consume else sd[name]
-            return t.to(device=self.device, dtype=dtype).contiguous()
+            out = t.to(device=self.device, dtype=dtype).contiguous()
+            if out.data_ptr() == t.data_ptr():
+                self._aliased.add(out.data_ptr())
+            return out
 
         if "vit" in self.parts:
             self._prepare_vit(cfg, get, code)
@@ -279,6 +306,59 @@ class PreparedWeights:
         lw.fp8_act = 1 if self.fp8_act else 0
         self.llm = lw
         self.vocab = self.embed.shape[0]
+        if self.pack13_mode and llm_weight_format == "native" and dtype == torch.bfloat16:
+            for k in ("wqkv", "wgu", "wdown", "lm_head") if self.pack13_all else PACK13_PRODUCTS:
+                ts = [self.lm_head] if k == "lm_head" else lt[k]
+                for i, t in enumerate(ts):
+                    if self._pack13_wanted(t) and t.data_ptr() in self._aliased:  # the caller's tensor: bind a matrix of our own
+                        ts[i] = t.clone()
+                        if k == "lm_head":
+                            self.lm_head, lw.lm_head = ts[i], ts[i].data_ptr()
+                        else:
+                            getattr(lw, k)[i] = ts[i].data_ptr()
+                self.p13[k] = [self._pack13_bind(t) for t in ts]
+
+    # ---- the 13-bit packed copies: packed, bound and unbound HERE and nowhere else (a stale binding is a silent wrong answer: the
+    # step would stream the copy of a matrix that is gone) ----
+    def _pack13_wanted(self, raw) -> bool:
+        from . import ops  # local import: ops needs the loaded library
+
+        return ops.pack13_eligible(raw) and (self.pack13_all or raw.shape[1] % 2048 == 0)
+
+    def _pack13_bind(self, raw):
+        from . import ops
+
+        if not self._pack13_wanted(raw):
+            return None
+        if ops.pack13_bound(raw):
+            # somebody else's binding (a C caller's, or another object's on storage we share after all): theirs to unbind, and
+            # replacing it would leave them streaming a copy we free -- this matrix runs the raw kernel here
+            return None
+        packed, flags, n_exc = ops.pack13(raw)
+        ops.pack13_bind(raw, packed, flags)
+        return (raw, packed, flags, n_exc)
+
+    def pack13_unbind(self, names=None) -> None:
+        """drop the bindings (and the copies) of the named products, default all: before a raw matrix is replaced, and at teardown"""
+        from . import ops
+
+        for k in list(self.p13) if names is None else names:
+            for ent in self.p13.pop(k, []):
+                if ent is not None:
+                    ops.pack13_unbind(ent[0])
+
+    def pack13_bytes(self) -> int:
+        """HBM the packed copies and their flags take, on top of the raw matrices"""
+        return sum(ent[1].numel() + 4 * ent[2].numel() for ents in self.p13.values() for ent in ents if ent is not None)
+
+    def pack13_exception_rows(self) -> int:
+        return sum(ent[3] for ents in self.p13.values() for ent in ents if ent is not None)
+
+    def __del__(self):
+        try:
+            self.pack13_unbind()
+        except Exception:
+            pass
 
     def resize_vocab(self, n: int) -> None:
         """HF `resize_token_embeddings` on the live weights (the reference's loader calls it after adding `<mask>` / `<depth>`,
@@ -303,8 +383,12 @@ class PreparedWeights:
         self.embed = resized(self.embed)
         lw = self.llm
         if self.llm_q is None:
+            repack = "lm_head" in self.p13
+            self.pack13_unbind(["lm_head"])  # before the raw matrix goes
             self.lm_head = resized(self.lm_head)
             lw.lm_head = self.lm_head.data_ptr()
+            if repack:
+                self.p13["lm_head"] = [self._pack13_bind(self.lm_head)]
         else:
             from . import ops
             q8, sc = self.lm_head8[:keep], self.lm_head_scale[:keep]
@@ -328,13 +412,20 @@ class PreparedWeights:
         return (q8.view(torch.float8_e4m3fn).float() * sc[:, None]).to(self.dtype)
 
     def llm_weight_bytes(self) -> int:
-        """bytes streamed from HBM per decoded token at batch 1 (everything but embed_tokens)."""
+        """bytes streamed from HBM per decoded token AT BATCH 1 (everything but embed_tokens): of a matrix with a bound 13-bit copy,
+        the copy and its flags (exception rows, read from the raw matrix besides, are not counted).  Steps of 2+ rows, lookup steps
+        and the prefill read the raw matrices whatever is bound: for them the figure is low by pack13_bytes() * 3 / 13."""
         es = self.embed.element_size()
         if self.llm_q is None:
             n = self.final_norm.numel() + self.lm_head.numel()
             for ts in self.llm_t.values():
                 n += sum(t.numel() for t in ts)
-            return n * es
+            n *= es
+            for ents in self.p13.values():
+                for ent in ents:
+                    if ent is not None:
+                        n += ent[1].numel() + 4 * (ent[2].numel() - 1) - ent[0].numel() * es
+            return n
         n = (self.final_norm.numel() + sum(t.numel() for k in ("attn_norm", "mlp_norm") for t in self.llm_t[k])) * es
         n += self.lm_head8.numel() + 4 * self.lm_head_scale.numel()
         for qs, scs in self.llm_q.values():

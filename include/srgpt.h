@@ -206,6 +206,42 @@ int srgpt_pack_decode_weights(const void* W, void* out, int N, int K, int elem_b
 int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float norm_eps, const void* residual,
                   void* out, int batch, int N, int K, int swiglu, int out_f32, srgpt_stream_t stream);
 int srgpt_dequant_mxfp4(const void* W4, const void* wscale8, void* out_bf16, int N, int K, srgpt_stream_t stream);
+/* Additions under ABI 9: the PACKED MXFP4 decode layout and the MFMA product over it, for 2+ rows per weight pass (W4A16: bf16
+ * activations; the codes are widened to bf16 in registers with the block scale applied, v_cvt_scalef32_pk_bf16_fp4, exactly, and fed
+ * to the bf16 MFMA of srgpt_gemv_rowss).  srgpt_gemv_w4 stays the format's raw reference; this is an opt-in second copy of a matrix.
+ * One array holds the codes AND their E8M0 bytes in granules of SRGPT_MXFP4_GRANULE weight rows; a cell is one granule x 128 k:
+ * G * 64 code bytes in MFMA-operand order followed by G * 4 scale bytes (G = SRGPT_MXFP4_GRANULE, a cell = 68 G bytes).  With
+ * rows = 2 N if swiglu else N, cell(n, k) = (n / G) * (K / 128) + k / 128:
+ *   code of (n, k)        : byte  cell * 68 G + ((k % 32) / 8 * G + n % G) * 16 + (k % 128) / 32 * 4 + (k % 8) / 2, nibble k & 1
+ *   scale byte of (n, k)  : byte  cell * 68 G + 64 G + (n % G) * 4 + (k % 128) / 32
+ * so ONE coalesced 16-byte load of lane (c = lane & 15, g = lane >> 4) is row c, k = 32 s + 8 g .. + 8 for the four MFMA k steps
+ * s = 0 .. 3 of the cell (dword s), and the dword beside the codes holds the four scale bytes of those steps; k is not permuted.
+ * Domain: K % 128 == 0, N >= 1; rows past the matrix in its last granule hold code 0 and scale byte 127; with swiglu the N gate
+ * rows are followed by the N up rows as ONE matrix of 2 N rows and N % G == 0; anything else is SRGPT_ERR_ARG before any launch
+ * (srgpt_mxfp4_packed_bytes: 0).  Size: ceil(rows / G) * (K / 128) * 68 G bytes -- the codes, the scales and the padding.
+ * srgpt_unpack_mxfp4 writes W4 / wscale8 back (tests): the round trip is exact.
+ * srgpt_gemv_w4p: srgpt_gemv_rowss's contract over such an array (RMSNorm prologue, SwiGLU, residual, fp32 out, rowss_in /
+ * rowss_out), any batch >= 1 in passes of 16 rows, all on the MFMA kernel.  With a bf16 W = srgpt_dequant_mxfp4 of the same codes,
+ * out equals srgpt_gemv_rowss(x, W, ...) BIT FOR BIT for every fusion and row count (same K split, accumulation and reduction order,
+ * same rounding points).  Scale-byte domain of THIS kernel: 2 .. 252 -- every value code * 2^(byte - 127) is then a normal finite
+ * bf16 (byte 1 makes 0.5 * 2^-126 a denormal, 253 / 254 overflow bf16 at code 6 / 4); other bytes give unspecified values, never a
+ * fault.  Argument errors as srgpt_gemv_rowss; rowss tables need 2 * CUs <= SRGPT_ROWSS_STRIDE (SRGPT_ERR_UNSUPPORTED otherwise).
+ * The binding table (the rules of srgpt_pack13_bind): srgpt_mxfp4_bind(W4, packed, N, K, swiglu) records on the host that the code
+ * array at address W4 has this packed copy; process-global, mutex-protected, keyed by the address, a lookup matches only the exact
+ * (N, K, swiglu); a second bind replaces the first; srgpt_mxfp4_unbind returns 1 if there was a binding and must be called BEFORE
+ * either buffer is freed; srgpt_mxfp4_bound: 1 / 0.  Every decode-shaped step of an MXFP4 engine (plain, batched, lookup, their
+ * graphs) looks wqkv4[i], wo4[i], wgu4[i], wdown4[i] up at launch / capture time: with 2+ rows and ALL of them bound with their
+ * shapes the layer products run srgpt_gemv_w4p with the row-statistics hand-off and lm_head srgpt_gemv_rowss; otherwise (one row, or
+ * any matrix unbound) every launch is srgpt_gemv_w4's, as without bindings. */
+#define SRGPT_MXFP4_GRANULE 16
+size_t srgpt_mxfp4_packed_bytes(int N, int K, int swiglu);
+int srgpt_pack_mxfp4(const void* W4, const void* wscale8, void* packed, int N, int K, int swiglu, srgpt_stream_t stream);
+int srgpt_unpack_mxfp4(const void* packed, void* W4, void* wscale8, int N, int K, int swiglu, srgpt_stream_t stream);
+int srgpt_gemv_w4p(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out, int batch,
+                   int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out, srgpt_stream_t stream);
+int srgpt_mxfp4_bind(const void* W4, const void* packed, int N, int K, int swiglu);
+int srgpt_mxfp4_unbind(const void* W4);
+int srgpt_mxfp4_bound(const void* W4);
 /* Additions under ABI 9: bf16 weights as LOSSLESS 13-bit codes for the batch-1 decode step -- 0.8125 of the bytes per streamed
  * matrix and bit for bit the results of srgpt_gemv.  Not a quantisation: a bf16 weight is s | e8 | m7, the exponents of a weight row
  * lie within a few dozen values below the row's largest, so a row stores an even base exponent b = max(emax - 31, 1) rounded up to

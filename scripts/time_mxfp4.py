@@ -15,6 +15,13 @@ the min .. max of all calls -- the run-to-run spread a ratio has to clear.
   prefill   the 259-row prefill and a 32-row append over it, eager calls: fp8 against mxfp4 (which expands every matrix to bf16 first)
   bytes     llm_weight_bytes() of the three engines
 
+--only packed  (-> profiles/mxfp4_mfma.txt) the packed MXFP4 copies (mxfp4_packed=True: srgpt_gemv_w4p, the MFMA product) against the
+default mxfp4 engine and fp8, three engines in one process:
+  one row   the captured batch-1 step: the packed engine takes the default engine's launches
+  steps     the captured lookup step at K = 1 / 2 / 3, the batch-4 and batch-8 step, the batched lookup step at (2, 4) and (4, 4)
+  products  the four products at 1 .. 4, 8 and 16 rows: srgpt_gemv_w4 (VALU), srgpt_gemv_w4p, fp8 srgpt_gemv_rowss over its packed copy
+  HBM       what the engines hold, and mxfp4_packed_bytes()
+
 --only steps: the bf16 and fp8 steps alone -- what a tree without the format has; --tree DIR imports the package from another
 checkout (the parent commit), so the same lines can be taken on both in turn.  --only products: the fp8 and mxfp4 steps and the
 products section alone (how a build with another W4_UNIT_COLS in csrc/gemv_route.h was compared)."""
@@ -81,14 +88,16 @@ def report(title, reps, base, unit=1.0, what="ms"):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mxfp4.txt"))
+    ap.add_argument("--out", default=None, help="default profiles/mxfp4.txt (--only packed: profiles/mxfp4_mfma.txt)")
     ap.add_argument("--rows", type=int, default=259)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--per-block", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", default="all", choices=["all", "steps", "products"])
+    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed"])
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mxfp4_mfma.txt" if args.only == "packed" else "mxfp4.txt")
     sys.path.insert(0, os.path.abspath(args.tree))
     sys.path.insert(1, ROOT)
     assert torch.cuda.is_available(), "a timing needs the MI355X"
@@ -101,13 +110,18 @@ def main():
     cfg = bench.make_cfg("vila15_8b")
     lib = L.load()
     have4 = hasattr(lib, "srgpt_gemv_w4")
-    formats = ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only == "all" else [])
-    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4"}
-    eng = {}
+    formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only == "all" else [])
+    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed"}
+    eng, held = {}, {}
     for f in formats:
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
         sd = synth_state_dict(cfg, seed=0, dtype=dt, device=dev)
-        eng[f] = SrgptEngine(cfg, sd, device=dev, dtype=dt, rope_positions=1024, consume_state_dict=True, llm_weight_format=f)
+        kw = dict(llm_weight_format="mxfp4", mxfp4_packed=True) if f == "mxfp4p" else dict(llm_weight_format=f)
+        eng[f] = SrgptEngine(cfg, sd, device=dev, dtype=dt, rope_positions=1024, consume_state_dict=True, **kw)
         del sd
+        torch.cuda.synchronize()
+        held[f] = torch.cuda.memory_allocated() - before
     say("scripts/time_mxfp4.py --only %s, tree %s: VILA1.5-8B geometry (hidden %d, inter %d, %d layers, heads %d / %d, vocab %d), "
         "synthetic weights, %s, %d CUs" % (args.only, os.path.relpath(os.path.abspath(args.tree), ROOT), cfg.hidden, cfg.inter, cfg.layers, cfg.heads, cfg.kv_heads,
                                            cfg.vocab, torch.cuda.get_device_name(0), lib.srgpt_device_cus()))
@@ -125,13 +139,20 @@ def main():
             if T is None:
                 graph = st.ensure_graph()
             else:
-                st.ensure_lookup(T - 1, 2, None)
-                graph = st.ensure_lookup_graph()
+                if B == 1:
+                    st.ensure_lookup(T - 1, 2, None)
+                    graph = st.ensure_lookup_graph()
+                else:  # the batched lookup step: B sequences of T rows
+                    st.ensure_lookup_batch(T - 1, 2, None)
+                    st.lookup_b["steps"].fill_(1)
+                    graph = st.ensure_lookup_batch_graph()
         torch.cuda.synchronize()
 
         def reset():
             st.pos.fill_(args.rows)
             st.step.fill_(1)
+            if T is not None and B > 1:
+                st.lookup_b["steps"].fill_(1)
 
         def fn():
             L.check(lib.srgpt_graph_launch(graph, 1, ops._stream()))
@@ -158,6 +179,15 @@ def main():
     shared = torch.cuda.Stream()  # the product graphs' stream
 
     section("captured batch-1 decode step, %d cached rows" % args.rows, {name[f]: (f, 1, None) for f in formats}, "fp8")
+    if args.only == "packed":
+        assert eng["mxfp4p"].w.mxfp4_packed
+        three = lambda B, T: {name[f]: (f, B, T) for f in ("mxfp4", "mxfp4p", "fp8")}
+        for K in (1, 2, 3):
+            section("captured lookup step, K = %d (T = %d rows), batch 1" % (K, K + 1), three(1, K + 1), "mxfp4")
+        for B in (4, 8):
+            section("captured batch-%d decode step" % B, three(B, None), "mxfp4")
+        for B in (2, 4):
+            section("captured batched lookup step, (%d, 4): %d rows" % (B, 4 * B), three(B, 4), "mxfp4")
     if args.only == "all" and have4:
         section("captured lookup step, K = 3 (T = 4 rows), batch 1", {"fp8": ("fp8", 1, 4), "mxfp4": ("mxfp4", 1, 4)}, "fp8")
         section("captured batch-8 decode step (fp8: one MFMA pass of 8 rows; mxfp4: two VALU passes of 4)",
@@ -165,6 +195,57 @@ def main():
     for c in checks:
         c()
     keep.clear()
+    if args.only == "packed":
+        # ---- the four products alone: the VALU kernel, the MFMA product over the packed copy, fp8 on the MFMA kernel (its packed copy)
+        w8, w4 = eng["fp8"].w, eng["mxfp4p"].w
+        Hd, I, HqD, QW = cfg.hidden, cfg.inter, cfg.heads * cfg.head_dim, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim
+        shapes = {"q/k/v   [%d, %d] norm" % (QW, Hd): ("wqkv", QW, Hd, True, False, False),
+                  "o_proj  [%d, %d] residual" % (Hd, HqD): ("wo", Hd, HqD, False, True, False),
+                  "gate/up [2 x %d, %d] norm, SwiGLU" % (I, Hd): ("wgu", I, Hd, True, False, True),
+                  "down    [%d, %d] residual" % (Hd, I): ("wdown", Hd, I, False, True, False)}
+        say("the four products alone, one launch per layer (%d matrices) in a captured graph: us per launch (min .. max of all calls)" % cfg.layers)
+        with torch.cuda.stream(shared):
+            for title, (k, N, K, norm, res, sw) in shapes.items():
+                for rows in (1, 2, 3, 4, 8, 16):
+                    x = (torch.randn((rows, K), device=dev, generator=g) * 0.5).to(dt)
+                    nw = torch.ones((K,), device=dev, dtype=dt) if norm else None
+                    r = (torch.randn((rows, N), device=dev, generator=g) * 0.5).to(dt) if res else None
+                    out = torch.empty((rows, N), device=dev, dtype=dt)
+                    R = 2 * N if sw else N
+
+                    def launches(fmt):
+                        for i in range(cfg.layers):
+                            if fmt == "w4":
+                                ops.gemv_w4(x, w4.llm_q4[k][0][i], w4.llm_q4[k][1][i], nw, 1e-5, r, sw, out=out)
+                            elif fmt == "w4p":
+                                ops.gemv_w4p(x, w4.p4[k][i][1], R, nw, 1e-5, r, sw, out=out)
+                            elif k in w8.llm_pk:
+                                ops.gemv_rowss(x, w8=w8.llm_pk[k][i], wscale=w8.llm_q[k][1][i], norm_w=nw, eps=1e-5, residual=r, swiglu=sw,
+                                               out=out, packed_rows=w8.pk_rows[k], n_rows=R)
+                            else:
+                                ops.gemv_rowss(x, w8=w8.llm_q[k][0][i], wscale=w8.llm_q[k][1][i], norm_w=nw, eps=1e-5, residual=r, swiglu=sw, out=out)
+
+                    lines = {}
+                    for fmt in ("w4", "w4p") + (("fp8",) if rows >= 2 else ()):  # (one fp8 row takes a kernel without the hand-off)
+                        launches(fmt)  # first use of an instance outside the capture
+                        torch.cuda.synchronize()
+                        gr = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(gr, stream=shared):
+                            launches(fmt)
+                        lines[fmt] = (gr.replay, None, shared)
+                    reps = interleaved(lines, args)
+                    us = lambda f: "%7.2f (%7.2f .. %7.2f)" % (mid(reps[f]) * 1e3 / cfg.layers, min(map(min, reps[f])) * 1e3 / cfg.layers,
+                                                             max(map(max, reps[f])) * 1e3 / cfg.layers)
+                    say("  %-36s %2d row%s   gemv_w4 %s   gemv_w4p %s   fp8 %s   w4p / w4 %.3f" % (
+                        title, rows, " " if rows == 1 else "s", us("w4"), us("w4p"), us("fp8") if "fp8" in reps else "      -" + " " * 21,
+                        mid(reps["w4p"]) / mid(reps["w4"])))
+        say()
+        say("HBM held per engine (torch.cuda.memory_allocated around its construction):")
+        for f in formats:
+            say("  %-13s %7.3f GB" % (name[f], held[f] / 1e9))
+        say("  mxfp4_packed_bytes() %.3f GB: the packed copies, on top of the row-major codes and scales" % (eng["mxfp4p"].w.mxfp4_packed_bytes() / 1e9))
+        say()
+
     if args.only in ("all", "products") and have4:
         # ---- the four products alone
         w8, w4 = eng["fp8"].w, eng["mxfp4"].w

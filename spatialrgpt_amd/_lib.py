@@ -117,6 +117,13 @@ _SIGNATURES = {
     "srgpt_gemv_w8": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemv_w4": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_dequant_mxfp4": (i32, [vp, vp, vp, i32, i32, vp]),
+    "srgpt_mxfp4_packed_bytes": (C.c_size_t, [i32, i32, i32]),
+    "srgpt_pack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "srgpt_unpack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "srgpt_gemv_w4p": (i32, [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "srgpt_mxfp4_bind": (i32, [vp, vp, i32, i32, i32]),
+    "srgpt_mxfp4_unbind": (i32, [vp]),
+    "srgpt_mxfp4_bound": (i32, [vp]),
     "srgpt_pack13_bytes": (C.c_size_t, [i32, i32, C.POINTER(C.c_size_t)]),
     "srgpt_pack13": (i32, [vp, i32, i32, vp, vp, vp]),
     "srgpt_unpack13": (i32, [vp, vp, vp, i32, i32, vp, vp]),

@@ -13,6 +13,7 @@ enum GemvFamily {
   GEMV_SKINNY,  // skinny_kernel<SWIGLU, NI, NW, W8, PUB, PK> (skinny.hip): MFMA, up to 16 bf16 rows
   GEMV_W4,      // gemv_w4_kernel<B, SWIGLU, NX> (gemv_w4.hip): VALU, 1 - 4 bf16 rows, MXFP4 weights (its own route functions below)
   GEMV_P13,     // gemv_p13_kernel<SWIGLU, NX> (gemv_p13.hip): VALU, one bf16 row, 13-bit packed bf16 weights (route functions below)
+  GEMV_W4_MFMA, // skinny_kernel<SWIGLU, NI, NW, false, PUB, true, W4 = true> (skinny.hip): MFMA, up to 16 bf16 rows, packed MXFP4 weights
 };
 
 // How a call is cut: ceil(rows / chunk) launches of up to `chunk` rows, each streaming the weights once, ALL on `family` -- a
@@ -182,6 +183,33 @@ inline GemvValuLaunch gemv_w4_launch(int B, int N, int K, bool swiglu, int cus) 
   l.NIT = ceil_div(K / 32, 64);
   l.grid = valu_grid(ceil_div(N, W4_UNIT_COLS), l.lds, cus);
   return l;
+}
+
+// ---- srgpt_gemv_w4p (gemv_w4p.hip -> skinny.hip) and the decode-shaped steps of an MXFP4 engine (model.hip): the MFMA product over
+// the packed copy of a code array (srgpt_pack_mxfp4), where the step's matrices are bound (mxfp4_bind.h).  `bound`: every layer
+// matrix of the engine has a packed copy of its shape.  Unbound, or below W4_MFMA_MIN_ROWS rows, the route is gemv_w4_route's; from
+// the threshold on every pass is up to 16 rows on the MFMA kernel, launched as gemv_skinny_launch(rows, N, norm, ss_in,
+// W4_GRANULE_ROWS, cus) says: the bf16 kernel's NI / NW rule, cw rounded to whole granules.
+// W4_MFMA_MIN_ROWS = 2, measured per product at the 8B geometry on the MI355X (profiles/mxfp4_mfma.txt, us per launch, VALU kernel |
+// MFMA product): 1 row q/k/v 6.1 | 8.3, o_proj 5.0 | 5.0, gate/up 13.6 | 15.0, down_proj 11.1 | 8.4; 2 rows 8.8 | 8.2, 6.9 | 5.0,
+// 19.3 | 15.1, 14.4 | 8.5; 4 rows 12.6 | 8.3, 9.3 | 5.2, 28.1 | 15.3, 24.4 | 8.9; 16 rows 48.4 | 10.8, 35.7 | 5.8, 109.9 | 20.9, 96.2 | 13.0
+// (the spread of a line's calls is under 3 %, between two processes under 1 %).  From 2 rows on the MFMA product wins EVERY product,
+// so the threshold is one constant and the route takes no shape; at one row it wins down_proj alone and the step keeps the VALU kernel
+// (whole steps: lookup K = 1 1.99 -> 1.53 ms, batch 8 5.27 -> 1.63).
+constexpr int W4_MFMA_MIN_ROWS = 2;
+constexpr int W4_GRANULE_ROWS = 16;  // SRGPT_MXFP4_GRANULE (include/srgpt.h): weight rows per granule of the packed array
+constexpr int W4_CELL_K = 128;       // k per cell: one 16-byte load per lane = the B fragments of four MFMA k steps
+
+inline GemvRoute gemv_w4_step_route(int rows, bool bound) {
+  if (!bound || rows < W4_MFMA_MIN_ROWS) return gemv_w4_route(rows);
+  return GemvRoute{GEMV_W4_MFMA, 16};
+}
+
+// bytes of the packed array of a [rows_total, K] code matrix (K % W4_CELL_K == 0): per granule and cell 64 code bytes and 4 scale
+// bytes per row
+inline long long gemv_w4p_packed_bytes(long long rows_total, int K) {
+  const long long gran = (rows_total + W4_GRANULE_ROWS - 1) / W4_GRANULE_ROWS;
+  return gran * (K / W4_CELL_K) * (68LL * W4_GRANULE_ROWS);
 }
 
 // ---- srgpt_gemv_p13 (gemv_p13.hip): bf16 weights in the lossless 13-bit code of pack13.h, one bf16 activation row.  The same

@@ -34,6 +34,7 @@ struct DecodeProduct {
   const float* ss_in;
   float* ss_out;
   int packed;
+  int w4;  // W is a packed MXFP4 array (srgpt_pack_mxfp4) of `packed` rows per granule: srgpt_skinny_launch only (gemv_w4p.hip)
 };
 // gemv.hip: the way in for the validated arguments of srgpt_gemv, srgpt_gemv_w8 and srgpt_gemv_rowss -- asks gemv_route.h for the
 // kernel family and the rows per weight pass, and hands every pass (`batch` = its rows) to that family's launcher:
@@ -45,6 +46,11 @@ int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s);   // gemv_w8.hip:
 //      binding srgpt_pack13_bind made for the raw matrix at W_raw, if it has exactly this shape ----
 struct Pack13Binding;
 bool srgpt_pack13_lookup(const void* W_raw, int rows, int K, Pack13Binding* out);
+
+// ---- gemv_w4p.hip: the binding table of the packed MXFP4 copies (mxfp4_bind.h), for the decode steps of model.hip: the binding
+//      srgpt_mxfp4_bind made for the code array at W4, if it has exactly this shape ----
+struct Mxfp4Binding;
+bool srgpt_mxfp4_lookup(const void* W4, int N, int K, int swiglu, Mxfp4Binding* out);
 
 // ---- attn.hip: the decode attention with the L2 prefetch of the next GEMV's weights, and its arrival tickets, for model.hip ----
 int srgpt_decode_attention_pf(const void* qkv, void* kcache, void* vcache, const int* pos, const void* cos_tab,

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "gemv_route.h"
 #include "internal.h"
+#include "mxfp4_bind.h"
 #include "pack13_bind.h"
 #include "pick.h"
 
@@ -775,21 +776,43 @@ struct DecodeStep {
   StepRows r;
   bool fp8, pub;
   bool p13;  // the plain one-row step of a bf16 engine in its dtype format: a matrix with a bound 13-bit copy is streamed from it
+  bool w4p;  // MXFP4 engine, gemv_w4_step_route's MFMA leg: the layer products multiply the bound packed copies (then pub is true)
   srgpt_stream_t stream;
 
   // fp8: the matrices that are not MXFP4 (under FMT_W4A16: lm_head) are fp8.  plain_step: srgpt_llm_decode_step and its forms (the
   // lookup steps read the raw matrices whatever is bound)
   static DecodeStep make(const srgpt_llm_weights* w, LlmFormat fmt, const StepRows& r, srgpt_stream_t stream, bool plain_step) {
     const bool fp8 = fmt != FMT_DTYPE;
-    const bool pub = fmt != FMT_W4A16 && gemv_rowss_supported(r.rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
+    const bool rowss = gemv_rowss_supported(r.rows, w->dtype == SRGPT_BF16, fp8, srgpt_device_cus());
+    // MXFP4: all or nothing -- the MFMA leg only where the step has the rows for it, the statistics hand-off exists (lm_head is fp8)
+    // and EVERY layer matrix has a packed copy of its shape; looked up on the host, at eager launch and at graph capture
+    const bool w4p = fmt == FMT_W4A16 && rowss && r.rows >= W4_MFMA_MIN_ROWS &&
+                     gemv_w4_step_route(r.rows, mxfp4_all_bound(w)).family == GEMV_W4_MFMA;
+    const bool pub = fmt == FMT_W4A16 ? w4p : rowss;
     const bool p13 = plain_step && fmt == FMT_DTYPE && w->dtype == SRGPT_BF16 && r.rows == 1;
-    return DecodeStep{w, fmt, r, fp8, pub, p13, stream};
+    return DecodeStep{w, fmt, r, fp8, pub, p13, w4p, stream};
+  }
+
+  // has every MXFP4 layer matrix of `w` a bound packed copy (srgpt_mxfp4_bind) of exactly its shape?
+  static bool mxfp4_all_bound(const srgpt_llm_weights* w) {
+    const int Hd = w->hidden, I = w->inter, HqD = w->heads * w->head_dim, QW = (w->heads + 2 * w->kv_heads) * w->head_dim;
+    Mxfp4Binding b;
+    for (int i = 0; i < w->layers; ++i)
+      if (!srgpt_mxfp4_lookup(w->wqkv4[i], QW, Hd, 0, &b) || !srgpt_mxfp4_lookup(w->wo4[i], Hd, HqD, 0, &b) ||
+          !srgpt_mxfp4_lookup(w->wgu4[i], I, Hd, 1, &b) || !srgpt_mxfp4_lookup(w->wdown4[i], Hd, I, 0, &b))
+        return false;
+    return w->layers > 0;
   }
 
   // packable: q/k/v, gate/up, down_proj and lm_head; o_proj is not -- the attention launch prefetches its RAW matrix into L2
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
            const float* ss_in, float* ss_out, bool packable = true) const {
-    if (m.w4)  // MXFP4 layer matrix (pub is false under the format: its kernel neither reads nor publishes row statistics)
+    if (m.w4 && w4p) {  // MXFP4 layer matrix on the MFMA leg: its packed copy, with the statistics hand-off of the other formats
+      Mxfp4Binding b;
+      SRGPT_CHECK(srgpt_mxfp4_lookup(m.w4, N, K, swiglu, &b), SRGPT_ERR_STATE, "decode step: an MXFP4 matrix was unbound while the step was being launched");
+      return srgpt_gemv_w4p(x, b.packed, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out, stream);
+    }
+    if (m.w4)  // MXFP4 layer matrix on the VALU kernel, which neither reads nor publishes row statistics (pub is false)
       return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
     if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
       return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out,

@@ -42,7 +42,7 @@ constexpr int WSTAGEB = 16 * WROWB;    // weight stage per wave
 constexpr int MAXSU = 4;               // sub-units (16-row weight tiles) accumulated per pass (8 for one 8-wave SwiGLU block per CU that
                                        // walks K once: measured equal, profiles/r06_skinny_gateup_8wave.txt)
 
-constexpr int DEPTH = 2;               // register ring depth of weight stages, bf16 and fp8 weights alike (an fp8 stage is half the
+constexpr int STAGE_DEPTH = 2;         // register ring depth of weight stages, bf16 and fp8 weights alike (an fp8 stage is half the
                                        // registers and half the bytes in flight; 3 / 4: profiles/r06_skinny_inflight.txt)
 constexpr int FS_MAX = 4;              // MFMA k steps per fragment batch (8 LDS reads in flight per batch)
 
@@ -70,7 +70,16 @@ constexpr int FS_MAX = 4;              // MFMA k steps per fragment batch (8 LDS
 // round 5 priced them at 4 - 7 % of the fp8 layer, profiles/r05_skinny_probes.txt) and a block needs LDS only for its activation
 // slices.  4-row granules keep every column split of the row-major kernel (24 q/k/v columns or 28 gate / up pairs per block);
 // 16-row granules (1 KiB contiguous per instruction) stream the single-tile products faster (profiles/r06_skinny_packed_gr.txt).
-template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK>
+// W4: the weights are MXFP4 codes in THEIR packed layout (srgpt_pack_mxfp4, include/srgpt.h; implies PK, excludes W8): a cell of a
+// granule is 128 k = one 16-byte load per lane, dword s of which holds the lane's 8 codes of k step s, and a dword beside the codes
+// holds the four E8M0 bytes of the lane's row.  A stage (256 k) is two such pairs -- an eighth of a bf16 stage's registers -- so the
+// ring holds W4_DEPTH stages (3 with 8 staged rows, 2 with 16: the activation ring's registers are not there -- the deeper
+// rings spilled 5 - 49 VGPRs in the o_proj / down_proj instances); a fragment is four v_cvt_scalef32_pk_bf16_fp4 (two codes each, the block scale `byte << 23` applied on
+// the way: exact, code * 2^e has one mantissa bit) in front of the MFMA.  Everything that decides a bit -- NI / NW, the K range of a
+// wave, the k of a step, the accumulator a step adds to, the reduction, the epilogues -- is the bf16 instance's: the same bits as
+// that kernel over the dequantised matrix.
+constexpr int W4_DEPTH = 4;
+template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK, bool W4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const bf16_t* __restrict__ x, const void* __restrict__ Wv,
                                                                           const float* __restrict__ wscale,
                                                                           const bf16_t* __restrict__ norm_w, float norm_eps,
@@ -78,6 +87,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
                                                                           int B, int N, int K, int out_f32, int cw,
                                                                           const float* __restrict__ ss_in, float* __restrict__ ss_out,
                                                                           int gr_shift) {
+  static_assert(!W4 || (PK && !W8), "MXFP4 weights are read from their packed layout only");
+  constexpr int DEPTH = !W4 || NI == 8 ? STAGE_DEPTH : NI == 4 ? W4_DEPTH - 1 : W4_DEPTH;  // register ring depth of weight stages
   constexpr int SK = 256;                   // k per wave slice
   constexpr int XROWB = WROWB;              // bytes per staged activation row
   constexpr int XL = NI;                    // activation loads per slice: 2 rows x 512 B each
@@ -90,7 +101,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   using WReg = typename std::conditional<W8 && !PK, u32x2, u32x4>::type;  // one weight load per lane
   constexpr int WEB = W8 ? 1 : 2;                                       // bytes per weight element
   constexpr int WEPL = 8;                                               // weight elements per lane-load (row-major layout)
-  constexpr int NWL = PK && W8 ? 4 : 8;                                 // loads per weight stage (packed fp8: 64 k per load)
+  constexpr int NWL = W4 ? 3 : PK && W8 ? 4 : 8;                        // registers of a weight stage in lane loads (packed fp8: 64 k
+                                                                        // per load; MXFP4: two cells of codes + one of scale dwords)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // per wave: [x stage | w stage]; reused for the reduction
   __shared__ float rs_s[16];
   __shared__ float ss_s[16][NW / 2];
@@ -193,7 +205,29 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   auto issue_w = [&](WReg* w, int pass, int sl, int su, bool ok) {
     const int cb = c0 + (pass * MAXU + su / R) * CPT;  // first column of the tile
     const int nrow = min(c0 + cwb - cb, 16);  // valid rows of the tile (16 except in the block's last tile)
-    if constexpr (PK) {
+    if constexpr (W4) {
+      // cell (granule, 128 k) of the packed MXFP4 array: [g][row in granule][16 code bytes] | [row in granule][4 scale bytes]; lane
+      // (c, g) reads row c % gr of the tile's granule c / gr.  Loads pushed out of the descriptor's range return code 0, scale 0: +0
+      const unsigned cellb = 68u << gr_shift;                      // bytes of a cell
+      const unsigned gstride = (unsigned)(K / W4_CELL_K) * cellb;  // bytes of a granule
+      const unsigned char* base = reinterpret_cast<const unsigned char*>(Wv) + (size_t)((cb + (su % R) * N) >> gr_shift) * gstride;
+      const int ngran = (nrow + (1 << gr_shift) - 1) >> gr_shift;
+      const __amdgpu_buffer_rsrc_t rs =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(base), 0, nrow > 0 ? ngran * (int)gstride : 0, 0x00020000);
+      const unsigned c = lane & 15, g = lane >> 4, cg = c & ((1u << gr_shift) - 1), goff = (c >> gr_shift) * gstride;
+      const unsigned code_off = goff + ((g << gr_shift) + cg) * 16u, sc_off = goff + (64u << gr_shift) + cg * 4u;
+      const unsigned so = ok ? (unsigned)(sl * (SK / W4_CELL_K)) * cellb : W_OUT_OF_RANGE;
+      unsigned int sc[SK / W4_CELL_K];
+#pragma unroll
+      for (int j = 0; j < SK / W4_CELL_K; ++j) {
+        // cells past K (last slice of a K that is no multiple of 256) leave the range
+        const unsigned oj = sl * SK + j * W4_CELL_K < K ? so + j * cellb : W_OUT_OF_RANGE;
+        sc[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)(sc_off + oj), 0, 2);
+        w[j] = __builtin_bit_cast(WReg, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(code_off + oj), 0, 2));  // aux 2 = nt
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      w[2] = WReg{sc[0], sc[1], 0u, 0u};
+    } else if constexpr (PK) {
       // granule (cb + (su % R) N) / gr of the packed array (tile starts, block widths and the stacked half's row count are multiples
       // of gr; rows past the matrix inside its last granule are zeros in the array).  Lane (c = lane & 15, g = lane >> 4) reads row
       // c % gr of the tile's granule c / gr: 16 bytes per k block, the k blocks of a granule gr x 64 bytes apart
@@ -245,7 +279,17 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   // packed layout: the B fragment of k step s of a stage, straight from the stage's registers
   auto pk_frag = [&](const WReg* w, int s) -> bf16x8 {
     if constexpr (!PK) return bf16x8{};
-    else if constexpr (W8) return __builtin_bit_cast(bf16x8, widen(u32x2{w[s >> 1][2 * (s & 1)], w[s >> 1][2 * (s & 1) + 1]}));
+    else if constexpr (W4) {
+      // k step s: dword s % 4 of cell s / 4, scaled by 2^(byte s % 4 of the cell's scale dword - 127) as the fp32 `byte << 23`
+      const unsigned int word = w[s >> 2][s & 3];
+      const float sc = __uint_as_float(((w[2][s >> 2] >> (8 * (s & 3))) & 0xffu) << 23);
+      u32x4 o;
+      o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 0));
+      o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 1));
+      o[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 2));
+      o[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 3));
+      return __builtin_bit_cast(bf16x8, o);
+    } else if constexpr (W8) return __builtin_bit_cast(bf16x8, widen(u32x2{w[s >> 1][2 * (s & 1)], w[s >> 1][2 * (s & 1) + 1]}));
     else return __builtin_bit_cast(bf16x8, w[s]);
   };
 
@@ -352,7 +396,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
     // slots of the activation ring (see load_x): as many slices ahead as the weight ring reaches
     // (fp8 only: with bf16 weights a stage is twice the registers and the 8-row single-tile kernel spills under a second slot --
     //  o / down 9.2 / 22.6 -> 9.9 / 24.4 us at 8 bf16 rows, profiles/r06_skinny_norm_staging.txt)
-    constexpr int XS = !W8 ? 1 : NSU == 1 ? DEPTH : (NSU == 2 && DEPTH == 4 ? 2 : 1);
+    // (MXFP4: a stage is 10 registers, the slots are there)
+    constexpr int XS = !W8 && !W4 ? 1 : NSU == 1 ? DEPTH : (NSU == 2 && DEPTH == 4 ? 2 : 1);
     static_assert(DEPTH % XS == 0, "the slot of a slice must be a compile-time function of its place in the trip");
     if (!x0_ready) load_x(std::integral_constant<int, 0>{}, sl_of(0));
     if constexpr (XS > 1) load_x(std::integral_constant<int, 1>{}, sl_of(min(1, max(cnt - 1, 0))));
@@ -572,9 +617,12 @@ static_assert(GEMV_SKINNY_ROW_BYTES == WROWB && 16 * GEMV_SKINNY_ROW_BYTES == WS
 
 // One weight pass of up to 16 rows on the MFMA kernel (GEMV_SKINNY of gemv_route.h), entered from srgpt_decode_product (gemv.hip);
 // bf16 or fp8 weights.  packed: 0 = row-major W [N][K]; 4 / 8 / 16 = the packed decode layout with granules of that many rows
-// (srgpt_pack_decode_weights); ss_in / ss_out: the rows' statistics tables (see skinny_kernel)
+// (srgpt_pack_decode_weights); ss_in / ss_out: the rows' statistics tables (see skinny_kernel).  w4 (from srgpt_gemv_w4p,
+// gemv_w4p.hip): W is a packed MXFP4 array (srgpt_pack_mxfp4), packed = its granule rows
 int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s) {
-  const int packed = p.packed, kblock = p.fp8 ? 64 : 32;
+  const int packed = p.packed, kblock = p.w4 ? W4_CELL_K : p.fp8 ? 64 : 32;
+  SRGPT_CHECK(!p.w4 || (packed == W4_GRANULE_ROWS && !p.fp8), SRGPT_ERR_ARG, "skinny: MXFP4 weights come in packed granules of %d rows",
+              W4_GRANULE_ROWS);
   SRGPT_CHECK(packed == 0 || packed == 4 || packed == 8 || packed == 16, SRGPT_ERR_ARG, "skinny: packed layout granule %d (0, 4, 8 or 16)", packed);
   SRGPT_CHECK(p.batch >= 1 && p.batch <= 16, SRGPT_ERR_ARG, "skinny: batch %d outside 1..16", p.batch);
   SRGPT_CHECK(p.K % 8 == 0 && p.K >= 8, SRGPT_ERR_ARG, "skinny: K=%d must be a multiple of 8", p.K);
@@ -592,14 +640,20 @@ int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s) {
         return flag(p.fp8 != 0, "W8", [&](auto w8_c) {
           return flag(l.PUB, "PUB", [&](auto pub_c) {
             return flag(l.PK, "PK", [&](auto pk_c) {
-              constexpr int NI = decltype(ni_c)::value, NW = decltype(nw_c)::value;
-              constexpr bool PK = decltype(pk_c)::value;
-              static_assert(gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "LDS");
-              static_assert(NW == 8 || 2 * gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "two 4-wave blocks per CU");
-              constexpr auto kfn = &skinny_kernel<decltype(sw_c)::value, NI, NW, decltype(w8_c)::value, decltype(pub_c)::value, PK>;
-              return srgpt_launch_dyn_lds<kfn>(l.lds, dim3(l.grid), dim3(64 * NW), (size_t)l.lds, s, (const bf16_t*)p.x, p.W, p.wscale,
-                                               (const bf16_t*)p.norm_w, p.eps, (const bf16_t*)p.residual, p.out, p.batch, p.N, p.K,
-                                               p.out_f32, l.cw, p.ss_in, p.ss_out, l.gr_shift);
+              return flag(p.w4 != 0, "W4", [&](auto w4_c) {
+                constexpr int NI = decltype(ni_c)::value, NW = decltype(nw_c)::value;
+                constexpr bool PK = decltype(pk_c)::value, W8 = decltype(w8_c)::value, W4 = decltype(w4_c)::value;
+                static_assert(gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "LDS");
+                static_assert(NW == 8 || 2 * gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "two 4-wave blocks per CU");
+                if constexpr (W4 && (!PK || W8)) {
+                  return (int)SRGPT_ERR_ARG;  // (checked above: MXFP4 weights are packed and not fp8)
+                } else {
+                  constexpr auto kfn = &skinny_kernel<decltype(sw_c)::value, NI, NW, W8, decltype(pub_c)::value, PK, W4>;
+                  return srgpt_launch_dyn_lds<kfn>(l.lds, dim3(l.grid), dim3(64 * NW), (size_t)l.lds, s, (const bf16_t*)p.x, p.W, p.wscale,
+                                                   (const bf16_t*)p.norm_w, p.eps, (const bf16_t*)p.residual, p.out, p.batch, p.N, p.K,
+                                                   p.out_f32, l.cw, p.ss_in, p.ss_out, l.gr_shift);
+                }
+              });
             });
           });
         });

@@ -360,6 +360,96 @@ def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=N
     return (out, table) if publish else out
 
 
+MXFP4_GRANULE = 16  # SRGPT_MXFP4_GRANULE: weight rows per granule of the packed MXFP4 layout
+
+
+def mxfp4_packed_bytes(n: int, k: int, swiglu: bool = False) -> int:
+    """srgpt_mxfp4_packed_bytes: bytes of the packed copy of an MXFP4 matrix of n rows (a SwiGLU matrix: n gate + n up rows);
+    0 outside the layout's domain (K % 128 == 0; swiglu: n % 16 == 0)."""
+    return int(L.load().srgpt_mxfp4_packed_bytes(int(n), int(k), int(swiglu)))
+
+
+def _mxfp4_shape(op: str, w4, wscale8, swiglu: bool):
+    _check_mxfp4(op, w4, wscale8)
+    rows, K = w4.shape[0], w4.shape[1] * 2
+    if swiglu and rows % 2:
+        raise ValueError(f"{op}: a SwiGLU matrix has gate rows followed by as many up rows, got {rows} rows")
+    return (rows // 2 if swiglu else rows), K
+
+
+def pack_mxfp4(w4, wscale8, swiglu: bool = False):
+    """srgpt_pack_mxfp4: the packed decode layout (codes in MFMA-operand order with their E8M0 bytes beside them, granules of 16
+    rows; include/srgpt.h) of codes [rows, K / 2] and scales [rows, K / 32], K % 128 == 0.  Returns a flat uint8 tensor."""
+    _dev(w4, wscale8)
+    N, K = _mxfp4_shape("pack_mxfp4", w4, wscale8, swiglu)
+    nbytes = mxfp4_packed_bytes(N, K, swiglu)
+    if nbytes == 0:
+        raise ValueError(f"pack_mxfp4: K = {K} must be a multiple of 128, and a SwiGLU half ({N} rows) whole granules of {MXFP4_GRANULE}")
+    packed = torch.empty((nbytes,), device=w4.device, dtype=torch.uint8)
+    L.check(L.load().srgpt_pack_mxfp4(_p(w4), _p(wscale8), _p(packed), N, K, int(swiglu), _stream()))
+    return packed
+
+
+def unpack_mxfp4(packed, n: int, k: int, swiglu: bool = False, out=None):
+    """srgpt_unpack_mxfp4: (codes, scales) of a packed copy, exactly what pack_mxfp4 was given.  out: (codes, scales) to write into."""
+    _dev(packed)
+    rows = 2 * int(n) if swiglu else int(n)
+    if out is None:
+        out = (torch.empty((rows, k // 2), device=packed.device, dtype=torch.uint8),
+               torch.empty((rows, k // 32), device=packed.device, dtype=torch.uint8))
+    w4, wscale8 = out
+    _check_mxfp4("unpack_mxfp4", w4, wscale8)
+    if tuple(w4.shape) != (rows, k // 2) or packed.numel() < mxfp4_packed_bytes(n, k, swiglu):
+        raise ValueError("unpack_mxfp4: the outputs or the packed array do not have the shape's size")
+    L.check(L.load().srgpt_unpack_mxfp4(_p(packed), _p(w4), _p(wscale8), int(n), int(k), int(swiglu), _stream()))
+    return w4, wscale8
+
+
+def gemv_w4p(x, packed, n_rows: int, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False, rowss_in=None,
+             publish=False, table=None):
+    """srgpt_gemv_w4p: gemv_rowss's product over the packed copy (pack_mxfp4) of an MXFP4 matrix of `n_rows` rows (2 N for SwiGLU),
+    any batch >= 1, on the MFMA kernel; bit for bit gemv_rowss(x, w=dequant_mxfp4(codes, scales), ...).  rowss_in / publish / table
+    as for gemv_rowss.  Returns out, or (out, table)."""
+    _dev(x, packed, norm_w, residual, rowss_in)
+    _same_dtype("gemv_w4p", x, norm_weight=norm_w, residual=residual)
+    if x.dtype != torch.bfloat16 or packed.dtype != torch.uint8 or not packed.is_contiguous():
+        raise ValueError("gemv_w4p: bf16 activations and a contiguous uint8 packed array")
+    B, K = x.shape
+    N = int(n_rows) // 2 if swiglu else int(n_rows)
+    need = mxfp4_packed_bytes(N, K, swiglu)
+    if need and packed.numel() < need:
+        raise ValueError(f"gemv_w4p: the packed array holds {packed.numel()} bytes, the shape needs {need}")
+    if out is None:
+        out = torch.empty((B, N), device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    if table is not None:
+        _dev(table)
+        if not publish or table.dtype != torch.float32 or tuple(table.shape) != (B, L.ROWSS_STRIDE) or not table.is_contiguous():
+            raise ValueError("gemv_w4p: table must be a contiguous fp32 [batch, 512] tensor, with publish=True")
+    elif publish:
+        table = torch.empty((B, L.ROWSS_STRIDE), device=x.device, dtype=torch.float32)
+    if rowss_in is not None and (rowss_in.dtype != torch.float32 or tuple(rowss_in.shape) != (B, L.ROWSS_STRIDE)
+                                 or not rowss_in.is_contiguous()):
+        raise ValueError("gemv_w4p: rowss_in must be a contiguous fp32 [batch, 512] table")
+    L.check(L.load().srgpt_gemv_w4p(_p(_c(x)), _p(packed), _p(norm_w), float(eps), _p(residual), _p(out), B, N, K, int(swiglu),
+                                    int(out_f32), _p(rowss_in), _p(table), _stream()))
+    return (out, table) if publish else out
+
+
+def mxfp4_bind(w4, packed, swiglu: bool = False) -> None:
+    """srgpt_mxfp4_bind: from now on a decode-shaped step of 2+ rows of an MXFP4 engine multiplies `packed` where its weights point
+    at the code array w4 [rows, K / 2] -- once every layer matrix of the engine is bound."""
+    rows, K = int(w4.shape[0]), int(w4.shape[1]) * 2
+    L.check(L.load().srgpt_mxfp4_bind(_p(w4), _p(packed), rows // 2 if swiglu else rows, K, int(swiglu)))
+
+
+def mxfp4_unbind(w4) -> bool:
+    return bool(L.load().srgpt_mxfp4_unbind(_p(w4)))
+
+
+def mxfp4_bound(w4) -> bool:
+    return bool(L.load().srgpt_mxfp4_bound(_p(w4)))
+
+
 def gemm_w8(a, w8, wscale, bias=None, residual=None, act=L.ACT_NONE, out=None, out_f32=False, ws=None):
     """act((a @ fp8(w8).T) * wscale + bias) + residual: a [M,K] bf16 (row stride may exceed K), w8 uint8 [N,K] (OCP e4m3fn),
     wscale fp32 [N].  ws: as for gemm."""

@@ -59,7 +59,7 @@ class PreparedWeights:
 
     def __init__(self, cfg: SrgptConfig, sd: Dict[str, torch.Tensor], device, dtype, rope_positions: int = 0,
                  consume: bool = False, llm_weight_format: str = "native", parts=None, decode_layout: str = "packed",
-                 pack13=None):
+                 pack13=None, mxfp4_packed: bool = False):
         """llm_weight_format: "native" (the engine dtype) or "fp8" -- weight-only OCP e4m3fn quantisation of the five
         streamed LLM matrices with one fp32 (power-of-two) scale per output row (BASELINE config 5; bf16 engines only).  The
         fp8 bytes are the ONLY copy of those matrices in HBM: decode streams them (srgpt_gemv_w8), prefill multiplies them
@@ -77,7 +77,13 @@ class PreparedWeights:
         23.1 GB of weights; pack13_bytes()).  The binding table is global to the process and keyed by the raw matrix's address, so a
         matrix this object binds is always its own: where the state dict's tensor would be used as it is (already on the device in
         the engine dtype), it is cloned first -- otherwise a second engine built from the same tensors would share, replace and
-        tear down this one's binding."""
+        tear down this one's binding.
+        mxfp4_packed ("mxfp4" only; default off): also hold every layer matrix's codes and scale bytes in the packed decode layout
+        (ops.pack_mxfp4: MFMA-operand order) and bind the copies (srgpt_mxfp4_bind), so that every decode-shaped step of 2+ rows --
+        batches, lookup steps, their graphs -- runs the MFMA product srgpt_gemv_w4p instead of passes of the 4-row VALU kernel.  All
+        four matrices of all layers, or none where a shape is outside the layout's domain (K % 128 == 0, inter % 16 == 0):
+        `self.mxfp4_packed` reports the outcome.  The row-major codes stay (the one-row kernel and the prefill expansion read them),
+        so the copies are additional HBM: 0.53125 bytes per weight, +3.7 GB for the 8B model (mxfp4_packed_bytes())."""
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         # parts: which components to materialise -- all of them for the model, ONE for the module-level factories
         # (spatialrgpt_amd/factories.py: the reference's build_vision_tower / build_mm_projector / build_region_extractor /
@@ -114,6 +120,9 @@ class PreparedWeights:
             raise ValueError(f"unknown pack13 {pack13!r}")
         self.pack13_mode = PACK13_DEFAULT if pack13 is None else bool(pack13)
         self.pack13_all = isinstance(pack13, str)  # "all"
+        self.mxfp4_packed = False  # set by _prepare_llm: are all MXFP4 layer matrices packed and bound?
+        self._mxfp4_want = bool(mxfp4_packed)
+        self.p4: Dict[str, list] = {}  # name -> per layer (codes, packed) of a bound MXFP4 matrix
         self._aliased = set()  # data_ptr of every tensor get() handed out without a copy: the caller's own storage
         self.p13: Dict[str, list] = {}  # name -> per layer (raw, packed, flags, exception rows) of a bound matrix, or None
         code = {torch.float32: L.F32, torch.bfloat16: L.BF16}[dtype]
@@ -241,6 +250,8 @@ class PreparedWeights:
             self.lm_head = None
             self.llm_q4, self.llm_q = q4, {}
             self.llm_pk, self.pk_rows = {}, {}
+            if self._mxfp4_want:
+                self._mxfp4_pack_bind()
         if llm_weight_format == "fp8":
             from . import ops  # local import: ops needs the loaded library
 
@@ -347,6 +358,38 @@ class PreparedWeights:
                 if ent is not None:
                     ops.pack13_unbind(ent[0])
 
+    # ---- the packed MXFP4 copies: packed, bound and unbound here and nowhere else, like the 13-bit copies ----
+    def _mxfp4_pack_bind(self) -> None:
+        from . import ops
+
+        shapes = {k: (cs[0].shape[0] // 2 if k == "wgu" else cs[0].shape[0], cs[0].shape[1] * 2, k == "wgu")
+                  for k, (cs, _) in self.llm_q4.items() if cs}
+        if not shapes or any(ops.mxfp4_packed_bytes(n, K, sw) == 0 for n, K, sw in shapes.values()):
+            return  # all or nothing: the step takes the MFMA product only with every matrix bound
+        if any(ops.mxfp4_bound(c) for cs, _ in self.llm_q4.values() for c in cs):
+            return  # somebody else's binding on storage we share: theirs to unbind (see _pack13_bind)
+        for k, (cs, scs) in self.llm_q4.items():
+            ents = []
+            for c, sc in zip(cs, scs):
+                packed = ops.pack_mxfp4(c, sc, swiglu=shapes[k][2])
+                ops.mxfp4_bind(c, packed, swiglu=shapes[k][2])
+                ents.append((c, packed))
+            self.p4[k] = ents
+        self.mxfp4_packed = True
+
+    def mxfp4_unbind(self) -> None:
+        """drop the bindings (and the packed copies) of the MXFP4 matrices: every step is again the unbound engine's"""
+        from . import ops
+
+        for k in list(self.p4):
+            for c, _ in self.p4.pop(k):
+                ops.mxfp4_unbind(c)
+        self.mxfp4_packed = False
+
+    def mxfp4_packed_bytes(self) -> int:
+        """HBM the packed MXFP4 copies take, on top of the row-major codes and scales"""
+        return sum(packed.numel() for ents in self.p4.values() for _, packed in ents)
+
     def pack13_bytes(self) -> int:
         """HBM the packed copies and their flags take, on top of the raw matrices"""
         return sum(ent[1].numel() + 4 * ent[2].numel() for ents in self.p13.values() for ent in ents if ent is not None)
@@ -357,6 +400,10 @@ class PreparedWeights:
     def __del__(self):
         try:
             self.pack13_unbind()
+        except Exception:
+            pass
+        try:
+            self.mxfp4_unbind()
         except Exception:
             pass
 

@@ -12,13 +12,16 @@
 // drift apart so that some stream while others multiply.  Grid = 2 blocks per CU.
 //
 // Fusions (include/srgpt.h): RMSNorm prologue (LlamaRMSNorm), SwiGLU epilogue, residual add, fp32 logits.
-// Rounding points mirror PyTorch's bf16 materialisation of each intermediate.
+// Rounding points mirror PyTorch's bf16 materialisation of each intermediate.  The prologue and the epilogue are the ones of
+// gemv_valu.h, shared with the other VALU products (gemv_w8.hip, gemv_w4.hip, gemv_p13.hip); this file also holds the one pass loop
+// of every decode product (srgpt_decode_product).
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
 #include "gemv_route.h"
+#include "gemv_valu.h"
 #include "internal.h"
 
 namespace {
@@ -58,8 +61,7 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* xs = reinterpret_cast<T*>(smem);  // [B][K]
   __shared__ float red[16];
-  constexpr int RES_MAXU = 4;  // residual elements of a wave's first 4 units are staged through LDS by the prologue
-  __shared__ float res_s[B][4][RES_MAXU];
+  __shared__ float res_s[B][4][GEMV_RES_MAXU];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = K / VEC;          // 16-byte chunks per row
@@ -75,109 +77,14 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         w[r][j] = __builtin_nontemporal_load(p + min((it0 + j) * 64 + lane, nchunks - 1));
-        // pin ISSUE order == CONSUMPTION order: left alone, the scheduler issued the first-consumed chunk last,
-        // which turns the counted waits below into a full vmcnt(0) drain before the first FMA
-        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);  // issue order == consumption order (see gemv_valu.h)
       }
     }
   };
 
-  // ---- prologue: stage x (and RMSNorm it) into LDS ----
-  // All global loads of the prologue (activation chunks AND norm gains) are issued up front, branch-free, so the
-  // block pays one L2 latency.  NXMAX (2 or 8, picked by the host) = chunks per thread held in registers; unused
-  // slots wrap around to valid chunks (a clamped address would hot-spot one cache line from every thread of the
-  // grid); chunks beyond NXMAX*256 (B*K > 16384 elements) take the generic loop.
-  {
-    const int total = B * nchunks;
-    const bool do_norm = norm_w != nullptr;
-    Vec16<T> xr[NXMAX], gr[NXMAX];
-    // residual elements this block will need: fetched with the prologue's loads (a load placed next to its use at
-    // the end of a row gets sunk behind the weight stream by the compiler and exposes a full memory latency per row)
-    // Round 5: the load is UNCONDITIONAL and its value is not touched until the LDS store below.  Written as
-    // `if (residual) r = to_f(residual[i])` the compiler emitted branch -> load -> s_waitcnt vmcnt(0) -> convert at the very top of
-    // the kernel: o_proj and down_proj spent a whole memory round trip (the row was just written by the launch before: an L2 miss)
-    // before requesting their first activation or weight byte.
-    const int rb = tid / (4 * RES_MAXU), rw = (tid / RES_MAXU) & 3, rk = tid % RES_MAXU;
-    const int runit = (int)blockIdx.x * 4 + rw + rk * (int)gridDim.x * 4;
-    const bool rok = !SWIGLU && residual != nullptr && tid < B * 4 * RES_MAXU && runit < N;
-    const T res_raw = (residual != nullptr ? residual : x)[rok ? (size_t)rb * N + runit : 0];
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = (tid + 256 * j) % total;
-      xr[j] = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      gr[j] = *reinterpret_cast<const Vec16<T>*>((do_norm ? norm_w : x) + (size_t)(c % nchunks) * VEC);
-    }
-    // the wave's first weight batch goes out BEHIND the prologue's own loads (in-order return: the statistics below wait for the
-    // activations only) and its HBM latency overlaps the RMSNorm, the LDS staging and the barrier
-    __builtin_amdgcn_sched_barrier(0);
-    issue(min((int)blockIdx.x * 4 + wave, N - 1), 0);
-    __builtin_amdgcn_sched_barrier(0);
-    float ss[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) ss[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      const bool ok = c < total;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += xr[j].get(i) * xr[j].get(i);
-      const int b = (B == 1) ? 0 : (c % total) / nchunks;
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb) ss[bb] += (ok && bb == b) ? sq : 0.f;
-    }
-    for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare
-      const Vec16<T> v = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      const int b = c / nchunks;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += v.get(i) * v.get(i);
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb)
-        if (bb == b) ss[bb] += sq;
-    }
-    if (rok) res_s[rb][rw][rk] = to_f(res_raw);
-    float rs[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) rs[b] = 1.f;
-    if (do_norm) {
-#pragma unroll
-      for (int b = 0; b < B; ++b) rs[b] = rsqrtf(block_sum(ss[b], red) / (float)K + norm_eps);
-    }
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      if (c < total) {
-        Vec16<T> v = xr[j];
-        if (do_norm) {
-          const int b = (B == 1) ? 0 : c / nchunks;
-          float r = rs[0];
-#pragma unroll
-          for (int bb = 1; bb < B; ++bb)
-            if (bb == b) r = rs[bb];
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) v.set(i, gr[j].get(i) * rnd<T>(xr[j].get(i) * r));  // weight * h.to(dtype)
-        }
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    if (do_norm) {
-      for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare; each thread re-reads the chunks it wrote itself
-        const int b = c / nchunks, kc = c - b * nchunks;
-        Vec16<T> v = *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC);
-        const Vec16<T> g = *reinterpret_cast<const Vec16<T>*>(norm_w + (size_t)kc * VEC);
-        float r = rs[0];
-#pragma unroll
-        for (int bb = 1; bb < B; ++bb)
-          if (bb == b) r = rs[bb];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v.set(i, g.get(i) * rnd<T>(v.get(i) * r));
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    __syncthreads();
-  }
+  // x (RMSNormed) into LDS, the residual elements of the wave's first units, the first weight batch behind the prologue's loads
+  gemv_valu_prologue<T, B, NXMAX, 1, SWIGLU>(x, norm_w, norm_eps, residual, N, K, xs, red, res_s,
+                                             [&] { issue(min((int)blockIdx.x * 4 + wave, N - 1), 0); });
 
   int uk = 0;
   for (int unit = blockIdx.x * 4 + wave; unit < N; unit += gridDim.x * 4, ++uk) {
@@ -229,19 +136,9 @@ __global__ __launch_bounds__(256, 2) void gemv_kernel(const T* __restrict__ x, c
       float a[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) a[r] = wave_sum(acc[r][b]);
-      if (lane == 0) {
-        if (SWIGLU) {
-          const float g = rnd<T>(a[0]), u = rnd<T>(a[R - 1]);
-          reinterpret_cast<T*>(out)[(size_t)b * N + unit] = from_f<T>(rnd<T>(silu(g)) * u);
-        } else {
-          float v = rnd<T>(a[0]);
-          if (residual) v = rnd<T>((uk < RES_MAXU ? res_s[b][wave][uk] : to_f(residual[(size_t)b * N + unit])) + v);
-          if (out_f32)
-            reinterpret_cast<float*>(out)[(size_t)b * N + unit] = v;
-          else
-            reinterpret_cast<T*>(out)[(size_t)b * N + unit] = from_f<T>(v);
-        }
-      }
+      if (lane == 0)
+        gemv_valu_epilogue<T, SWIGLU>(a[0], a[R - 1], residual, uk < GEMV_RES_MAXU ? &res_s[b][wave][uk] : nullptr, out, (size_t)b * N + unit,
+                                      out_f32);
     }
   }
 }
@@ -264,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
   constexpr int VEC = 8;
   constexpr int R = SWIGLU ? 2 : 1;
   constexpr int U = UB / R;
-  constexpr int RES_MAXU = 4;
+  constexpr int RES_MAXU = GEMV_RES_MAXU;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunks = K / VEC;
 
@@ -371,19 +268,8 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
     for (int r = 0; r < R; ++r) a[r] = wave_sum(acc[r]);
     // lane uk of res_pre holds the residual element of this unit (uniform index: v_readlane, not a ds_bpermute)
     const float res_b = __uint_as_float((unsigned int)__builtin_amdgcn_readlane((int)res_raw, uk < RES_MAXU ? uk : 0) << 16);
-    if (lane == 0) {
-      if (SWIGLU) {
-        const float g = rnd<T>(a[0]), u = rnd<T>(a[R - 1]);
-        reinterpret_cast<T*>(out)[unit] = from_f<T>(rnd<T>(silu(g)) * u);
-      } else {
-        float v = rnd<T>(a[0]);
-        if (residual) v = rnd<T>((uk < RES_MAXU ? res_b : to_f(residual[unit])) + v);
-        if (out_f32)
-          reinterpret_cast<float*>(out)[unit] = v;
-        else
-          reinterpret_cast<T*>(out)[unit] = from_f<T>(v);
-      }
-    }
+    if (lane == 0)
+      gemv_valu_epilogue<T, SWIGLU>(a[0], a[R - 1], residual, uk < RES_MAXU ? &res_b : nullptr, out, (size_t)unit, out_f32);
   }
 }
 
@@ -391,7 +277,6 @@ __global__ __launch_bounds__(256, 2) void gemv_reg_kernel(const bf16_t* __restri
 template <typename T>
 int launch_gemv(GemvFamily family, const DecodeProduct& p, hipStream_t s) {
   const GemvValuLaunch l = gemv_valu_launch(family, p.batch, p.N, p.K, sizeof(T) == 2, p.swiglu != 0, srgpt_device_cus());
-  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv: batch*K too large for LDS (%zu bytes)", (size_t)l.lds);
   const T *x = (const T*)p.x, *W = (const T*)p.W, *norm_w = (const T*)p.norm_w, *residual = (const T*)p.residual;
   SRGPT_TRY((srgpt_switch<false, true>(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
     constexpr bool SW = decltype(sw_c)::value;
@@ -408,8 +293,7 @@ int launch_gemv(GemvFamily family, const DecodeProduct& p, hipStream_t s) {
         constexpr int B = decltype(b_c)::value, NX = decltype(nx_c)::value;
         const auto go = [&](auto ub_c) {
           constexpr auto kfn = &gemv_kernel<T, B, SW, NX, decltype(ub_c)::value>;
-          return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, x, W, norm_w,
-                                           p.eps, residual, p.out, p.N, p.K, p.out_f32);
+          return gemv_valu_run<kfn>(l, "srgpt_gemv: batch*K", s, x, W, norm_w, p.eps, residual, p.out, p.N, p.K, p.out_f32);
         };
         if constexpr (!SW && NX == 8) {  // the only instances with batches of 7 loads (scripts/compare_isa.py guards the instance set)
           if (l.UB == 7) return go(std::integral_constant<int, 7>{});
@@ -424,12 +308,11 @@ int launch_gemv(GemvFamily family, const DecodeProduct& p, hipStream_t s) {
 
 }  // namespace
 
-// The decode products' one way in: srgpt_gemv, srgpt_gemv_w8 (skinny.hip) and srgpt_gemv_rowss validate and come here.  The route
-// (gemv_route.h) names the kernel family and the rows per weight pass; every pass takes its rows of x, residual, out and both
-// statistics tables.
-int srgpt_decode_product(const DecodeProduct& p, hipStream_t s) {
+// The decode products' one way in: every entry point validates its arguments, asks gemv_route.h for its route and comes here.  The
+// route names the kernel family and the rows per weight pass; every pass takes its rows of x, residual, out and both statistics
+// tables.
+int srgpt_decode_product(const DecodeProduct& p, const GemvRoute& r, hipStream_t s) {
   const bool bf16 = p.dtype == SRGPT_BF16;
-  const GemvRoute r = gemv_route(p.batch, p.K, bf16, p.fp8 != 0, p.norm_w != nullptr);
   const size_t es = dtype_size(p.dtype), on = p.out_f32 ? sizeof(float) : es;
   for (int b0 = 0; b0 < p.batch; b0 += r.chunk) {
     DecodeProduct c = p;
@@ -440,12 +323,19 @@ int srgpt_decode_product(const DecodeProduct& p, hipStream_t s) {
     if (p.ss_in) c.ss_in = p.ss_in + (size_t)b0 * SRGPT_ROWSS_STRIDE;
     if (p.ss_out) c.ss_out = p.ss_out + (size_t)b0 * SRGPT_ROWSS_STRIDE;
     switch (r.family) {
-      case GEMV_SKINNY: SRGPT_TRY(srgpt_skinny_launch(c, s)); break;
+      case GEMV_SKINNY:
+      case GEMV_W4_MFMA: SRGPT_TRY(srgpt_skinny_launch(c, s)); break;
       case GEMV_W8: SRGPT_TRY(srgpt_gemv_w8_valu(c, s)); break;
+      case GEMV_W4: SRGPT_TRY(srgpt_gemv_w4_valu(c, s)); break;
       default: SRGPT_TRY(bf16 ? launch_gemv<bf16_t>(r.family, c, s) : launch_gemv<float>(r.family, c, s));
     }
   }
   return SRGPT_OK;
+}
+
+// srgpt_gemv, srgpt_gemv_w8 (skinny.hip) and srgpt_gemv_rowss: the route of gemv_route
+int srgpt_decode_product(const DecodeProduct& p, hipStream_t s) {
+  return srgpt_decode_product(p, gemv_route(p.batch, p.K, p.dtype == SRGPT_BF16, p.fp8 != 0, p.norm_w != nullptr), s);
 }
 
 extern "C" int srgpt_gemv(const void* x, const void* W, const void* norm_w, float norm_eps, const void* residual,

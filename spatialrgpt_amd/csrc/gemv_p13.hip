@@ -3,7 +3,7 @@
 //   out[n] = W[n, :] . x      with W[n, k] decoded from (sign, exponent-code, low byte) planes to exactly the bf16 the raw matrix holds
 //
 // gemv_kernel<bf16, 1, ...> of gemv.hip with another weight stream: the same unit / wave / grid decomposition (a unit = one output
-// row, or a gate and an up row; a wave owns units grid-strided; 2 blocks per CU), the same prologue (x staged -- and RMSNormed -- into
+// row, or a gate and an up row; a wave owns units grid-strided; 2 blocks per CU), the same prologue (gemv_valu.h: x staged -- and RMSNormed -- into
 // LDS, the wave's first weight batch issued behind the prologue's own loads), the next batch issued before the reduction, and for
 // every row the same fp32 accumulation: lane l adds the weights k = (it * 64 + l) * 8 + i, it ascending, i = 0 .. 7, then the same
 // wave_sum and epilogue roundings.  Only how a lane comes by its 8 weights of iteration `it` differs:
@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "gemv_route.h"
+#include "gemv_valu.h"
 #include "internal.h"
 #include "pack13.h"
 
@@ -39,8 +40,7 @@ __global__ __launch_bounds__(256, 2) void gemv_p13_kernel(const T* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* xs = reinterpret_cast<T*>(smem);  // [groups * 2048]: x, then zeros
   __shared__ float red[16];
-  constexpr int RES_MAXU = 4;  // residual elements of a wave's first 4 units are staged through LDS by the prologue
-  __shared__ float res_s[4][RES_MAXU];
+  __shared__ float res_s[1][4][GEMV_RES_MAXU];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nchunks = K / VEC;         // 16-byte chunks of activations per row
@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256, 2) void gemv_p13_kernel(const T* __restrict__ 
   const size_t row_bytes = (size_t)groups * P13_GROUP_BYTES;
   const int stride = (int)gridDim.x * 4;
 
-  // one batch of the packed stream: one group of each of the unit's R rows, planes in consumption order (see gemv.hip: the
+  // one batch of the packed stream: one group of each of the unit's R rows, planes in consumption order (see gemv_valu.h: the
   // scheduling barriers pin issue order == consumption order, so the consumers get counted waits)
   uint32_t sg[R];
   u32x4 nb[R], lo[R][2];
@@ -69,75 +69,21 @@ __global__ __launch_bounds__(256, 2) void gemv_p13_kernel(const T* __restrict__ 
     }
   };
 
-  // ---- prologue: gemv_kernel's for one row, plus the meta words of the wave's units and the zero tail of the LDS row ----
-  uint32_t mw[R];  // lane l: the meta word(s) of the wave's l-th unit
+  // the meta words of the wave's units go out with the prologue's loads: lane l holds the word(s) of the wave's l-th unit
+  uint32_t mw[R];
   {
-    const bool do_norm = norm_w != nullptr;
-    Vec16<T> xr[NXMAX], gr[NXMAX];
-    const int rw = (tid / RES_MAXU) & 3, rk = tid % RES_MAXU;
-    const int runit = (int)blockIdx.x * 4 + rw + rk * stride;
-    const bool rok = !SWIGLU && residual != nullptr && tid < 4 * RES_MAXU && runit < N;
-    const T res_raw = (residual != nullptr ? residual : x)[rok ? runit : 0];
-    {
-      const long long mu = (long long)blockIdx.x * 4 + wave + (long long)lane * stride;
-      const int mi = (int)(mu < N ? mu : N - 1);
+    const long long mu = (long long)blockIdx.x * 4 + wave + (long long)lane * stride;
+    const int mi = (int)(mu < N ? mu : N - 1);
 #pragma unroll
-      for (int r = 0; r < R; ++r) mw[r] = meta[mi + r * N];
-    }
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = (tid + 256 * j) % nchunks;
-      xr[j] = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      gr[j] = *reinterpret_cast<const Vec16<T>*>((do_norm ? norm_w : x) + (size_t)c * VEC);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    issue(min((int)blockIdx.x * 4 + wave, N - 1), 0);
-    __builtin_amdgcn_sched_barrier(0);
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const bool ok = tid + 256 * j < nchunks;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += xr[j].get(i) * xr[j].get(i);
-      ss += ok ? sq : 0.f;
-    }
-    for (int c = tid + 256 * NXMAX; c < nchunks; c += 256) {  // rare
-      const Vec16<T> v = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += v.get(i) * v.get(i);
-      ss += sq;
-    }
-    for (int c = nchunks + tid; c < groups * (P13_GROUP_WEIGHTS / VEC); c += 256)  // the zero tail (no iteration when K % 2048 == 0)
-      *reinterpret_cast<u32x4*>(xs + (size_t)c * VEC) = u32x4{0u, 0u, 0u, 0u};
-    if (rok) res_s[rw][rk] = to_f(res_raw);
-    float rs = 1.f;
-    if (do_norm) rs = rsqrtf(block_sum(ss, red) / (float)K + norm_eps);
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      if (c < nchunks) {
-        Vec16<T> v = xr[j];
-        if (do_norm) {
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) v.set(i, gr[j].get(i) * rnd<T>(xr[j].get(i) * rs));  // weight * h.to(dtype)
-        }
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    if (do_norm) {
-      for (int c = tid + 256 * NXMAX; c < nchunks; c += 256) {  // rare; each thread re-reads the chunks it wrote itself
-        Vec16<T> v = *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC);
-        const Vec16<T> g = *reinterpret_cast<const Vec16<T>*>(norm_w + (size_t)c * VEC);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v.set(i, g.get(i) * rnd<T>(v.get(i) * rs));
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    __syncthreads();
+    for (int r = 0; r < R; ++r) mw[r] = meta[mi + r * N];
   }
+  // x (RMSNormed) into LDS and the residual elements of the wave's first units; behind the prologue's loads the first packed batch,
+  // then the zero tail of the LDS row (no iteration when K % 2048 == 0; nothing the statistics wait for)
+  gemv_valu_prologue<T, 1, NXMAX, 1, SWIGLU>(x, norm_w, norm_eps, residual, N, K, xs, red, res_s, [&] {
+    issue(min((int)blockIdx.x * 4 + wave, N - 1), 0);
+    for (int c = nchunks + tid; c < groups * (P13_GROUP_WEIGHTS / VEC); c += 256)
+      *reinterpret_cast<u32x4*>(xs + (size_t)c * VEC) = u32x4{0u, 0u, 0u, 0u};
+  });
 
   int uk = 0;
   for (int unit = blockIdx.x * 4 + wave; unit < N; unit += stride, ++uk) {
@@ -215,19 +161,8 @@ __global__ __launch_bounds__(256, 2) void gemv_p13_kernel(const T* __restrict__ 
     float a[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) a[r] = wave_sum(acc[r]);
-    if (lane == 0) {
-      if (SWIGLU) {
-        const float g = rnd<T>(a[0]), u = rnd<T>(a[R - 1]);
-        reinterpret_cast<T*>(out)[unit] = from_f<T>(rnd<T>(silu(g)) * u);
-      } else {
-        float v = rnd<T>(a[0]);
-        if (residual) v = rnd<T>((uk < RES_MAXU ? res_s[wave][uk] : to_f(residual[unit])) + v);
-        if (out_f32)
-          reinterpret_cast<float*>(out)[unit] = v;
-        else
-          reinterpret_cast<T*>(out)[unit] = from_f<T>(v);
-      }
-    }
+    if (lane == 0)
+      gemv_valu_epilogue<T, SWIGLU>(a[0], a[R - 1], residual, uk < GEMV_RES_MAXU ? &res_s[0][wave][uk] : nullptr, out, (size_t)unit, out_f32);
   }
 }
 
@@ -241,13 +176,11 @@ extern "C" int srgpt_gemv_p13(const void* x, const void* packed, const void* fla
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_p13: swiglu excludes residual/out_f32");
   SRGPT_CHECK((long long)N * (swiglu ? 2 : 1) <= 0x7fffffffLL / 2, SRGPT_ERR_ARG, "srgpt_gemv_p13: N=%d too large", N);
   const GemvValuLaunch l = gemv_p13_launch(N, K, srgpt_device_cus());
-  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv_p13: K too large for LDS (%zu bytes)", (size_t)l.lds);
   hipStream_t s = as_stream(stream);
   const auto go = [&](auto sw_c, auto nx_c) {
     constexpr auto kfn = &gemv_p13_kernel<decltype(sw_c)::value, decltype(nx_c)::value>;
-    return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, (const T*)x,
-                                     (const unsigned char*)packed, (const uint32_t*)flags, (const T*)W_raw, (const T*)norm_w, norm_eps,
-                                     (const T*)residual, out, N, K, out_f32);
+    return gemv_valu_run<kfn>(l, "srgpt_gemv_p13: K", s, (const T*)x, (const unsigned char*)packed, (const uint32_t*)flags, (const T*)W_raw,
+                              (const T*)norm_w, norm_eps, (const T*)residual, out, N, K, out_f32);
   };
   SRGPT_TRY((srgpt_switch<2, 8>(l.NX, "NX", [&](auto nx_c) {
     return swiglu ? go(std::true_type{}, nx_c) : go(std::false_type{}, nx_c);

@@ -3,8 +3,8 @@
 // and the exact bf16 expansion of such a matrix (srgpt_dequant_mxfp4, what the prefill multiplies).
 //
 // Same structure as gemv_w8.hip (wave per unit, 1-KiB non-temporal wave loads issued in consumption order, branch-free consumption
-// with clamped indices, x in LDS behind the fused RMSNorm prologue, residual elements and scales requested ahead of the weight
-// stream, SwiGLU / residual / fp32-logit epilogues with the header's rounding points) with these differences:
+// with clamped indices, scales requested ahead of the weight stream; the prologue -- x in LDS behind the fused RMSNorm, the residual
+// elements -- and the SwiGLU / residual / fp32-logit epilogue with the header's rounding points are gemv_valu.h's) with these differences:
 //   * a 16-byte chunk holds 32 weights = exactly ONE MX block: a lane needs one scale byte per chunk, fetched (a byte load per
 //     chunk) in front of the batch's weight loads;
 //   * a K = 4096 row is only 2 wave loads; a unit is W4_UNIT_COLS = 2 output columns like gemv_w8.hip's (plain: 2 rows x 2 chunks =
@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "gemv_route.h"
+#include "gemv_valu.h"
 #include "internal.h"
 
 namespace {
@@ -39,7 +40,6 @@ __global__ __launch_bounds__(256, 2) void gemv_w4_kernel(const T* __restrict__ x
                                                          const unsigned char* __restrict__ wscale, const T* __restrict__ norm_w,
                                                          float norm_eps, const T* __restrict__ residual,
                                                          void* __restrict__ out, int N, int K, int out_f32) {
-  constexpr int VEC = 8;    // activation elements per 16-byte chunk
   constexpr int WVEC = 32;  // weight elements per 16-byte chunk = one MX block
   constexpr int C = W4_UNIT_COLS;    // output columns per unit
   constexpr int R = SWIGLU ? 2 * C : C;  // weight rows per unit (SwiGLU: C gate + C up rows -> C outputs)
@@ -47,13 +47,9 @@ __global__ __launch_bounds__(256, 2) void gemv_w4_kernel(const T* __restrict__ x
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* xs = reinterpret_cast<T*>(smem);  // [B][K]
   __shared__ float red[16];
-  constexpr int RES_MAXU = 4;  // residual elements of a wave's first 4 units are staged through LDS by the prologue
-  constexpr int RSLOT = C * RES_MAXU;  // (unit, column-of-unit) slots per wave
-  static_assert(B * 4 * RSLOT <= 256, "one thread per staged residual element");
-  __shared__ float res_s[B][4][RSLOT];
+  __shared__ float res_s[B][4][C * GEMV_RES_MAXU];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nchunks = K / VEC;           // 16-byte activation chunks per row
   const int wchunks = K / WVEC;          // 16-byte weight chunks (= scale bytes) per row
   const int nit = (wchunks + 63) >> 6;   // weight-chunk iterations per row (64 lanes each)
   const int NUNIT = (N + C - 1) / C;
@@ -87,97 +83,14 @@ __global__ __launch_bounds__(256, 2) void gemv_w4_kernel(const T* __restrict__ x
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         w[r][j] = __builtin_nontemporal_load(p + min((it0 + j) * 64 + lane, wchunks - 1));
-        __builtin_amdgcn_sched_barrier(0);  // issue order == consumption order (see gemv.hip)
+        __builtin_amdgcn_sched_barrier(0);  // issue order == consumption order (see gemv_valu.h)
       }
     }
   };
 
-  // ---- prologue: stage x (and RMSNorm it) into LDS: gemv_w8.hip's, with the residual slots of C-column units ----
-  {
-    const int total = B * nchunks;
-    const bool do_norm = norm_w != nullptr;
-    Vec16<T> xr[NXMAX], gr[NXMAX];
-    // residual elements this block will need: fetched with the prologue's loads (see gemv_w8.hip)
-    const int rb = tid / (4 * RSLOT), rw = (tid / RSLOT) & 3, rk = tid % RSLOT;
-    const long long rcol = ((long long)blockIdx.x * 4 + rw + (long long)(rk / C) * gridDim.x * 4) * C + (rk % C);  // output column
-    const bool rok = !SWIGLU && residual != nullptr && tid < B * 4 * RSLOT && rcol < N;
-    const T res_raw = (residual != nullptr ? residual : x)[rok ? (size_t)rb * N + (size_t)rcol : 0];
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = (tid + 256 * j) % total;
-      xr[j] = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      gr[j] = *reinterpret_cast<const Vec16<T>*>((do_norm ? norm_w : x) + (size_t)(c % nchunks) * VEC);
-    }
-    // first weight batch behind the prologue's own loads: its HBM latency overlaps the RMSNorm, the LDS staging and the barrier
-    __builtin_amdgcn_sched_barrier(0);
-    issue(min((int)blockIdx.x * 4 + wave, NUNIT - 1), 0);
-    __builtin_amdgcn_sched_barrier(0);
-    float ss[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) ss[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      const bool ok = c < total;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += xr[j].get(i) * xr[j].get(i);
-      const int b = (B == 1) ? 0 : (c % total) / nchunks;
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb) ss[bb] += (ok && bb == b) ? sq : 0.f;
-    }
-    for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare
-      const Vec16<T> v = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      const int b = c / nchunks;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += v.get(i) * v.get(i);
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb)
-        if (bb == b) ss[bb] += sq;
-    }
-    if (rok) res_s[rb][rw][rk] = to_f(res_raw);
-    float rs[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) rs[b] = 1.f;
-    if (do_norm) {
-#pragma unroll
-      for (int b = 0; b < B; ++b) rs[b] = rsqrtf(block_sum(ss[b], red) / (float)K + norm_eps);
-    }
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      if (c < total) {
-        Vec16<T> v = xr[j];
-        if (do_norm) {
-          const int b = (B == 1) ? 0 : c / nchunks;
-          float r = rs[0];
-#pragma unroll
-          for (int bb = 1; bb < B; ++bb)
-            if (bb == b) r = rs[bb];
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) v.set(i, gr[j].get(i) * rnd<T>(xr[j].get(i) * r));  // weight * h.to(dtype)
-        }
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    if (do_norm) {
-      for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare; each thread re-reads the chunks it wrote itself
-        const int b = c / nchunks, kc = c - b * nchunks;
-        Vec16<T> v = *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC);
-        const Vec16<T> g = *reinterpret_cast<const Vec16<T>*>(norm_w + (size_t)kc * VEC);
-        float r = rs[0];
-#pragma unroll
-        for (int bb = 1; bb < B; ++bb)
-          if (bb == b) r = rs[bb];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v.set(i, g.get(i) * rnd<T>(v.get(i) * r));
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    __syncthreads();
-  }
+  // x (RMSNormed) into LDS, the residual elements of the wave's first units (C columns each), the first weight batch
+  gemv_valu_prologue<T, B, NXMAX, C, SWIGLU>(x, norm_w, norm_eps, residual, N, K, xs, red, res_s,
+                                             [&] { issue(min((int)blockIdx.x * 4 + wave, NUNIT - 1), 0); });
 
   int uk = 0;
   for (int unit = blockIdx.x * 4 + wave; unit < NUNIT; unit += gridDim.x * 4, ++uk) {
@@ -237,20 +150,9 @@ __global__ __launch_bounds__(256, 2) void gemv_w4_kernel(const T* __restrict__ x
 #pragma unroll
         for (int c = 0; c < C; ++c) {
           const int n = C * unit + c;
-          if (n < N) {
-            if (SWIGLU) {
-              const float g = rnd<T>(a[c]), u = rnd<T>(a[C + c]);
-              reinterpret_cast<T*>(out)[(size_t)b * N + n] = from_f<T>(rnd<T>(silu(g)) * u);
-            } else {
-              float v = rnd<T>(a[c]);
-              if (residual)
-                v = rnd<T>((uk < RES_MAXU ? res_s[b][wave][C * uk + c] : to_f(residual[(size_t)b * N + n])) + v);
-              if (out_f32)
-                reinterpret_cast<float*>(out)[(size_t)b * N + n] = v;
-              else
-                reinterpret_cast<T*>(out)[(size_t)b * N + n] = from_f<T>(v);
-            }
-          }
+          if (n < N)
+            gemv_valu_epilogue<T, SWIGLU>(a[c], a[R - C + c], residual, uk < GEMV_RES_MAXU ? &res_s[b][wave][C * uk + c] : nullptr, out,
+                                          (size_t)b * N + n, out_f32);
         }
       }
     }
@@ -278,26 +180,23 @@ __global__ __launch_bounds__(256) void dequant_mxfp4_kernel(const unsigned char*
   }
 }
 
-// one launch of up to W4_MAX_ROWS rows
-int launch_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float eps, const void* residual, void* out,
-                   int B, int N, int K, int swiglu, int out_f32, hipStream_t s) {
-  const GemvValuLaunch l = gemv_w4_launch(B, N, K, swiglu != 0, srgpt_device_cus());
-  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv_w4: batch*K too large for LDS (%zu bytes)", (size_t)l.lds);
-  SRGPT_TRY((srgpt_switch<false, true>(swiglu != 0, "SWIGLU", [&](auto sw_c) {
+}  // namespace
+
+// one launch of up to W4_MAX_ROWS rows (GEMV_W4 of gemv_route.h), entered from srgpt_decode_product (gemv.hip)
+int srgpt_gemv_w4_valu(const DecodeProduct& p, hipStream_t s) {
+  const GemvValuLaunch l = gemv_w4_launch(p.batch, p.N, p.K, p.swiglu != 0, srgpt_device_cus());
+  SRGPT_TRY((srgpt_switch<false, true>(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
     return srgpt_switch<1, 2, 3, 4>(l.B, "B", [&](auto b_c) {
       return srgpt_switch<2, 8>(l.NX, "NX", [&](auto nx_c) {
         constexpr auto kfn = &gemv_w4_kernel<decltype(b_c)::value, decltype(sw_c)::value, decltype(nx_c)::value>;
-        return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, (const T*)x,
-                                         (const unsigned char*)W4, (const unsigned char*)wscale8, (const T*)norm_w, eps,
-                                         (const T*)residual, out, N, K, out_f32);
+        return gemv_valu_run<kfn>(l, "srgpt_gemv_w4: batch*K", s, (const T*)p.x, (const unsigned char*)p.W, p.wscale8, (const T*)p.norm_w,
+                                  p.eps, (const T*)p.residual, p.out, p.N, p.K, p.out_f32);
       });
     });
   })));
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
-
-}  // namespace
 
 extern "C" int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float norm_eps,
                              const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
@@ -307,15 +206,9 @@ extern "C" int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8,
   SRGPT_CHECK(K % 32 == 0, SRGPT_ERR_ARG, "srgpt_gemv_w4: K=%d must be a multiple of 32 (one scale per 32 values)", K);
   SRGPT_CHECK(!(swiglu && (residual || out_f32)), SRGPT_ERR_ARG, "srgpt_gemv_w4: swiglu excludes residual/out_f32");
   SRGPT_CHECK((long long)N * (swiglu ? 2 : 1) <= 0x7fffffffLL / 2, SRGPT_ERR_ARG, "srgpt_gemv_w4: N=%d too large", N);
-  const GemvRoute r = gemv_w4_route(batch);
-  const size_t on = out_f32 ? sizeof(float) : sizeof(T);
-  for (int b0 = 0; b0 < batch; b0 += r.chunk) {
-    const int nb = batch - b0 < r.chunk ? batch - b0 : r.chunk;
-    SRGPT_TRY(launch_gemv_w4((const char*)x + (size_t)b0 * K * sizeof(T), W4, wscale8, norm_w, norm_eps,
-                             residual ? (const char*)residual + (size_t)b0 * N * sizeof(T) : nullptr, (char*)out + (size_t)b0 * N * on, nb,
-                             N, K, swiglu, out_f32, as_stream(stream)));
-  }
-  return SRGPT_OK;
+  return srgpt_decode_product(DecodeProduct{x, W4, nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, SRGPT_BF16, 0,
+                                            nullptr, nullptr, 0, 0, (const unsigned char*)wscale8},
+                              gemv_w4_route(batch), as_stream(stream));
 }
 
 extern "C" int srgpt_dequant_mxfp4(const void* W4, const void* wscale8, void* out_bf16, int N, int K, srgpt_stream_t stream) {

@@ -94,8 +94,8 @@ extern "C" int srgpt_unpack_mxfp4(const void* packed, void* W4, void* wscale8, i
   return repack<false>("srgpt_unpack_mxfp4", W4, wscale8, const_cast<void*>(packed), N, K, swiglu, stream);
 }
 
-// srgpt_gemv_rowss's contract over a packed MXFP4 array: passes of up to 16 rows (gemv_w4_step_route's MFMA leg), every pass with
-// its rows of x, residual, out and both statistics tables -- the loop of srgpt_decode_product
+// srgpt_gemv_rowss's contract over a packed MXFP4 array: srgpt_decode_product's passes of up to 16 rows (gemv_w4_step_route's MFMA
+// leg), every pass with its rows of x, residual, out and both statistics tables
 extern "C" int srgpt_gemv_w4p(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out,
                               int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out,
                               srgpt_stream_t stream) {
@@ -107,19 +107,10 @@ extern "C" int srgpt_gemv_w4p(const void* x, const void* packed, const void* nor
   SRGPT_CHECK(!rowss_out || (!swiglu && !out_f32), SRGPT_ERR_ARG, "srgpt_gemv_w4p: row statistics are published for plain bf16 outputs only");
   SRGPT_CHECK((!rowss_in && !rowss_out) || 2 * srgpt_device_cus() <= GEMV_ROWSS_SLOTS, SRGPT_ERR_UNSUPPORTED,
               "srgpt_gemv_w4p: %d CUs do not fit the %d row-statistics slots", srgpt_device_cus(), GEMV_ROWSS_SLOTS);
-  const int chunk = gemv_w4_step_route(W4_MFMA_MIN_ROWS, true).chunk;  // the MFMA leg's rows per pass, whatever the call holds
-  const size_t on = out_f32 ? sizeof(float) : sizeof(bf16_t);
-  for (int b0 = 0; b0 < batch; b0 += chunk) {
-    DecodeProduct c{x, packed, nullptr, norm_w, norm_eps, residual, out, batch - b0 < chunk ? batch - b0 : chunk, N, K, swiglu, out_f32,
-                    SRGPT_BF16, 0, rowss_in, rowss_out, W4_GRANULE_ROWS, 1};
-    c.x = (const char*)x + (size_t)b0 * K * sizeof(bf16_t);
-    if (residual) c.residual = (const char*)residual + (size_t)b0 * N * sizeof(bf16_t);
-    c.out = (char*)out + (size_t)b0 * N * on;
-    if (rowss_in) c.ss_in = rowss_in + (size_t)b0 * SRGPT_ROWSS_STRIDE;
-    if (rowss_out) c.ss_out = rowss_out + (size_t)b0 * SRGPT_ROWSS_STRIDE;
-    SRGPT_TRY(srgpt_skinny_launch(c, as_stream(stream)));
-  }
-  return SRGPT_OK;
+  // the MFMA leg's route, whatever the call holds
+  return srgpt_decode_product(DecodeProduct{x, packed, nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, SRGPT_BF16,
+                                            0, rowss_in, rowss_out, W4_GRANULE_ROWS, 1},
+                              gemv_w4_step_route(W4_MFMA_MIN_ROWS, true), as_stream(stream));
 }
 
 extern "C" int srgpt_mxfp4_bind(const void* W4, const void* packed, int N, int K, int swiglu) {

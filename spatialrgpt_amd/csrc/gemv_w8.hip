@@ -2,8 +2,8 @@
 //   out[b, n] = round_bf16( (sum_k x[b, k] * fp8(W8[n, k])) * wscale[n] )            (HBM-bound, half the bytes of bf16)
 //
 // Same structure as gemv.hip (wave per unit, 8 independent 1-KiB non-temporal wave loads per batch issued in consumption
-// order, branch-free consumption with counted vmcnt, x in LDS, fused RMSNorm / SwiGLU / residual / fp32-logit epilogues,
-// prologue loads issued up front) with these differences:
+// order, branch-free consumption with counted vmcnt; the prologue -- x in LDS behind the fused RMSNorm -- and the SwiGLU /
+// residual / fp32-logit epilogue are gemv_valu.h's, with two output columns per unit) with these differences:
 //   * a 16-byte chunk holds 16 weights, so a K = 4096 row is 4 wave loads: a unit is TWO output columns (plain: rows 2u,
 //     2u+1 -> 8 loads per batch; SwiGLU: gate rows 2u, 2u+1 and up rows N+2u, N+2u+1 -> 16 loads = 16 KiB per batch:
 //     at half the bytes per row the per-row latency dominates, fewer and larger rounds win here);
@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "gemv_route.h"
+#include "gemv_valu.h"
 #include "internal.h"
 
 namespace {
@@ -26,18 +27,15 @@ __global__ __launch_bounds__(256, 2) void gemv_w8_kernel(const T* __restrict__ x
                                                          const float* __restrict__ wscale, const T* __restrict__ norm_w,
                                                          float norm_eps, const T* __restrict__ residual,
                                                          void* __restrict__ out, int N, int K, int out_f32) {
-  constexpr int VEC = 8;   // activation elements per 16-byte chunk
   constexpr int WVEC = 16;  // weight elements per 16-byte chunk
   constexpr int R = SWIGLU ? 4 : 2;  // weight rows per unit (SwiGLU: 2 gate + 2 up rows -> 2 outputs; 16 KiB per wave in flight)
   constexpr int U = 4;               // K-chunks per row per batch
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* xs = reinterpret_cast<T*>(smem);  // [B][K]
   __shared__ float red[16];
-  constexpr int RES_MAXU = 4;  // residual elements of a wave's first 4 units are staged through LDS by the prologue
-  __shared__ float res_s[B][4][2 * RES_MAXU];
+  __shared__ float res_s[B][4][2 * GEMV_RES_MAXU];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nchunks = K / VEC;           // 16-byte activation chunks per row
   const int wchunks = K / WVEC;          // 16-byte weight chunks per row
   const int nit = (wchunks + 63) >> 6;   // weight-chunk iterations per row (64 lanes each)
   const int NUNIT = (N + 1) >> 1;
@@ -63,111 +61,21 @@ __global__ __launch_bounds__(256, 2) void gemv_w8_kernel(const T* __restrict__ x
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         w[r][j] = __builtin_nontemporal_load(p + min((it0 + j) * 64 + lane, wchunks - 1));
-        __builtin_amdgcn_sched_barrier(0);  // issue order == consumption order (see gemv.hip)
+        __builtin_amdgcn_sched_barrier(0);  // issue order == consumption order (see gemv_valu.h)
       }
     }
   };
 
-  // ---- prologue: stage x (and RMSNorm it) into LDS ----
-  // All global loads of the prologue (activation chunks AND norm gains) are issued up front, branch-free, so the
-  // block pays one L2 latency.  NXMAX (2 or 8, picked by the host) = chunks per thread held in registers; unused
-  // slots wrap around to valid chunks (a clamped address would hot-spot one cache line from every thread of the
-  // grid); chunks beyond NXMAX*256 (B*K > 16384 elements) take the generic loop.
-  {
-    const int total = B * nchunks;
-    const bool do_norm = norm_w != nullptr;
-    Vec16<T> xr[NXMAX], gr[NXMAX];
-    // residual elements this block will need: fetched with the prologue's loads (a load placed next to its use at
-    // the end of a row gets sunk behind the weight stream by the compiler and exposes a full memory latency per row)
-    constexpr int RSLOT = 2 * RES_MAXU;  // (unit, row-of-pair) slots per wave
-    const int rb = tid / (4 * RSLOT), rw = (tid / RSLOT) & 3, rk = tid % RSLOT;
-    const int runit = ((int)blockIdx.x * 4 + rw + (rk >> 1) * (int)gridDim.x * 4) * 2 + (rk & 1);  // output row
-    const bool rok = !SWIGLU && residual != nullptr && tid < B * 4 * RSLOT && runit < N;
-    // unconditional, untouched until the LDS store (gemv.hip: the branchy form cost a memory round trip at the top of the kernel)
-    const T res_raw = (residual != nullptr ? residual : x)[rok ? (size_t)rb * N + runit : 0];
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = (tid + 256 * j) % total;
-      xr[j] = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      gr[j] = *reinterpret_cast<const Vec16<T>*>((do_norm ? norm_w : x) + (size_t)(c % nchunks) * VEC);
-    }
-    // first weight batch behind the prologue's own loads: its HBM latency overlaps the RMSNorm, the LDS staging and the barrier
-    __builtin_amdgcn_sched_barrier(0);
-    issue(min((int)blockIdx.x * 4 + wave, NUNIT - 1), 0);
-    __builtin_amdgcn_sched_barrier(0);
-    float ss[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) ss[b] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      const bool ok = c < total;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += xr[j].get(i) * xr[j].get(i);
-      const int b = (B == 1) ? 0 : (c % total) / nchunks;
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb) ss[bb] += (ok && bb == b) ? sq : 0.f;
-    }
-    for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare
-      const Vec16<T> v = *reinterpret_cast<const Vec16<T>*>(x + (size_t)c * VEC);
-      *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      const int b = c / nchunks;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) sq += v.get(i) * v.get(i);
-#pragma unroll
-      for (int bb = 0; bb < B; ++bb)
-        if (bb == b) ss[bb] += sq;
-    }
-    if (rok) res_s[rb][rw][rk] = to_f(res_raw);
-    float rs[B];
-#pragma unroll
-    for (int b = 0; b < B; ++b) rs[b] = 1.f;
-    if (do_norm) {
-#pragma unroll
-      for (int b = 0; b < B; ++b) rs[b] = rsqrtf(block_sum(ss[b], red) / (float)K + norm_eps);
-    }
-#pragma unroll
-    for (int j = 0; j < NXMAX; ++j) {
-      const int c = tid + 256 * j;
-      if (c < total) {
-        Vec16<T> v = xr[j];
-        if (do_norm) {
-          const int b = (B == 1) ? 0 : c / nchunks;
-          float r = rs[0];
-#pragma unroll
-          for (int bb = 1; bb < B; ++bb)
-            if (bb == b) r = rs[bb];
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) v.set(i, gr[j].get(i) * rnd<T>(xr[j].get(i) * r));  // weight * h.to(dtype)
-        }
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    if (do_norm) {
-      for (int c = tid + 256 * NXMAX; c < total; c += 256) {  // rare; each thread re-reads the chunks it wrote itself
-        const int b = c / nchunks, kc = c - b * nchunks;
-        Vec16<T> v = *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC);
-        const Vec16<T> g = *reinterpret_cast<const Vec16<T>*>(norm_w + (size_t)kc * VEC);
-        float r = rs[0];
-#pragma unroll
-        for (int bb = 1; bb < B; ++bb)
-          if (bb == b) r = rs[bb];
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v.set(i, g.get(i) * rnd<T>(v.get(i) * r));
-        *reinterpret_cast<Vec16<T>*>(xs + (size_t)c * VEC) = v;
-      }
-    }
-    __syncthreads();
-  }
+  // x (RMSNormed) into LDS, the residual elements of the wave's first units (two columns each), the first weight batch
+  gemv_valu_prologue<T, B, NXMAX, 2, SWIGLU>(x, norm_w, norm_eps, residual, N, K, xs, red, res_s,
+                                             [&] { issue(min((int)blockIdx.x * 4 + wave, NUNIT - 1), 0); });
 
   int uk = 0;
   for (int unit = blockIdx.x * 4 + wave; unit < NUNIT; unit += gridDim.x * 4, ++uk) {
     int rows[R];
     unit_rows(unit, rows);
     // the row scales are requested BEFORE the weight stream (scalar loads): placed at their use they would queue behind
-    // the weight loads and expose a memory latency per unit (same trap as the residual element, see gemv.hip)
+    // the weight loads and expose a memory latency per unit (same trap as the residual element, see gemv_valu.h)
     float sc[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) sc[r] = wscale[rows[r]];
@@ -229,20 +137,9 @@ __global__ __launch_bounds__(256, 2) void gemv_w8_kernel(const T* __restrict__ x
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const int n = 2 * unit + r;
-          if (n < N) {
-            if (SWIGLU) {
-              const float g = rnd<T>(a[r]), u = rnd<T>(a[R - 2 + r]);
-              reinterpret_cast<T*>(out)[(size_t)b * N + n] = from_f<T>(rnd<T>(silu(g)) * u);
-            } else {
-              float v = rnd<T>(a[r]);
-              if (residual)
-                v = rnd<T>((uk < RES_MAXU ? res_s[b][wave][2 * uk + r] : to_f(residual[(size_t)b * N + n])) + v);
-              if (out_f32)
-                reinterpret_cast<float*>(out)[(size_t)b * N + n] = v;
-              else
-                reinterpret_cast<T*>(out)[(size_t)b * N + n] = from_f<T>(v);
-            }
-          }
+          if (n < N)
+            gemv_valu_epilogue<T, SWIGLU>(a[r], a[R - 2 + r], residual, uk < GEMV_RES_MAXU ? &res_s[b][wave][2 * uk + r] : nullptr, out,
+                                          (size_t)b * N + n, out_f32);
         }
       }
     }
@@ -254,14 +151,12 @@ __global__ __launch_bounds__(256, 2) void gemv_w8_kernel(const T* __restrict__ x
 // one row on the VALU kernel (GEMV_W8 of gemv_route.h), entered from srgpt_decode_product (gemv.hip)
 int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s) {
   const GemvValuLaunch l = gemv_valu_launch(GEMV_W8, p.batch, p.N, p.K, true, p.swiglu != 0, srgpt_device_cus());
-  SRGPT_CHECK(l.lds <= GEMV_LDS_CAP, SRGPT_ERR_UNSUPPORTED, "srgpt_gemv_w8: batch*K too large for LDS (%zu bytes)", (size_t)l.lds);
   SRGPT_TRY((srgpt_switch<false, true>(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
     return srgpt_switch<1>(l.B, "B", [&](auto b_c) {
       return srgpt_switch<2, 8>(l.NX, "NX", [&](auto nx_c) {
         constexpr auto kfn = &gemv_w8_kernel<decltype(b_c)::value, decltype(sw_c)::value, decltype(nx_c)::value>;
-        return srgpt_launch_dyn_lds<kfn>(l.raise_lds_limit ? GEMV_LDS_CAP : 0, dim3(l.grid), dim3(256), (size_t)l.lds, s, (const T*)p.x,
-                                         (const unsigned char*)p.W, p.wscale, (const T*)p.norm_w, p.eps, (const T*)p.residual, p.out,
-                                         p.N, p.K, p.out_f32);
+        return gemv_valu_run<kfn>(l, "srgpt_gemv_w8: batch*K", s, (const T*)p.x, (const unsigned char*)p.W, p.wscale, (const T*)p.norm_w,
+                                  p.eps, (const T*)p.residual, p.out, p.N, p.K, p.out_f32);
       });
     });
   })));

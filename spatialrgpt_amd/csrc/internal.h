@@ -20,9 +20,12 @@ int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Srg
 void srgpt_splitk_apply(SrgptGemmEpilogue& e, const GemmRoute& r, void* ws);
 int srgpt_splitk_finish(const SrgptGemmEpilogue& e, hipStream_t s, bool* fused);
 
-// ---- the decode products (gemv.hip, gemv_w8.hip, skinny.hip) ----
+// ---- the decode products (gemv.hip, gemv_w8.hip, gemv_w4.hip, gemv_w4p.hip, skinny.hip; gemv_p13.hip is one row, one launch) ----
+// The VALU kernels share their x-staging prologue, their lane-0 epilogue and their launch tail (gemv_valu.h); every entry point
+// validates its own arguments, takes its route from gemv_route.h and goes through the one pass loop below.
 // One product as its entry point received it.  W: dtype weights, or (fp8) e4m3 bytes with wscale, row-major or packed (`packed` rows
-// per granule); ss_in / ss_out: the rows' statistics tables of srgpt_gemv_rowss, or NULL
+// per granule), or MXFP4 codes with wscale8, or (w4) their packed array; ss_in / ss_out: the rows' statistics tables of
+// srgpt_gemv_rowss, or NULL
 struct DecodeProduct {
   const void *x, *W;
   const float* wscale;
@@ -35,12 +38,16 @@ struct DecodeProduct {
   float* ss_out;
   int packed;
   int w4;  // W is a packed MXFP4 array (srgpt_pack_mxfp4) of `packed` rows per granule: srgpt_skinny_launch only (gemv_w4p.hip)
+  const unsigned char* wscale8;  // W is a row-major MXFP4 code array, these its E8M0 block scales: srgpt_gemv_w4_valu only
 };
-// gemv.hip: the way in for the validated arguments of srgpt_gemv, srgpt_gemv_w8 and srgpt_gemv_rowss -- asks gemv_route.h for the
-// kernel family and the rows per weight pass, and hands every pass (`batch` = its rows) to that family's launcher:
+// gemv.hip: the way in for validated arguments -- cuts the call into the route's weight passes and hands every pass (`batch` = its
+// rows) to the launcher of the route's family.  Without a route: gemv_route's (srgpt_gemv, srgpt_gemv_w8, srgpt_gemv_rowss);
+// srgpt_gemv_w4 and srgpt_gemv_w4p bring gemv_w4_route's and gemv_w4_step_route's
+int srgpt_decode_product(const DecodeProduct& p, const GemvRoute& r, hipStream_t s);
 int srgpt_decode_product(const DecodeProduct& p, hipStream_t s);
-int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s);  // skinny.hip: MFMA, up to 16 bf16 rows, bf16 or fp8 weights
+int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s);  // skinny.hip: MFMA, up to 16 bf16 rows; bf16, fp8 or packed MXFP4 weights
 int srgpt_gemv_w8_valu(const DecodeProduct& p, hipStream_t s);   // gemv_w8.hip: VALU, one row, fp8 weights (K % 16 == 0)
+int srgpt_gemv_w4_valu(const DecodeProduct& p, hipStream_t s);   // gemv_w4.hip: VALU, up to W4_MAX_ROWS rows, MXFP4 weights
 
 // ---- pack13.hip: the binding table of the 13-bit packed copies (pack13_bind.h), for the decode-layer sequence of model.hip: the
 //      binding srgpt_pack13_bind made for the raw matrix at W_raw, if it has exactly this shape ----

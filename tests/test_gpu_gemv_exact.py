@@ -391,6 +391,10 @@ CASES = [
      'gemv_w8_kernel SwiGLU, odd N'),
     ('gemv_w8', 'fp8', 1, 6, 4112, 0, 1, 0, ('gemv_w8', 1, [(1, 1, 8, 8, 0)]),
      'gemv_w8_kernel SwiGLU NX 8'),
+    ('gemv_w8', 'fp8', 1, 200, 16400, 0, 0, 0, ('gemv_w8', 1, [(1, 1, 8, 8, 0)]),
+     'gemv_w8_kernel, the looping prologue: 2050 activation chunks'),
+    ('gemv_w8', 'fp8', 1, 200, 16400, 1, 0, 0, ('gemv_w8', 1, [(1, 1, 8, 8, 0)]),
+     'gemv_w8_kernel norm, the looping prologue'),
     ('gemv_w8', 'fp8', 1, 37, 264, 0, 0, 0, ('skinny', 16, [(1, 2, 4, 0, 0, 3, 16)]),
      'one fp8 row, K % 16 != 0: skinny_kernel with a batch of 1'),
     ('gemv_w8', 'fp8', 1, 37, 264, 1, 0, 0, ('skinny', 16, [(1, 2, 8, 0, 0, 3, 16)]),

@@ -156,6 +156,13 @@ def test_exact_products_more_units_than_residual_slots(B):
     exact_case(B, 40000, 32, 77 + B, variants=("plain",))
 
 
+@pytest.mark.parametrize("N", [3, 7])
+def test_exact_products_looping_prologue(N):
+    """4 rows x K = 4128: 4 * 516 = 2064 activation chunks, more than the 256 * 8 the prologue's threads hold in registers -- the
+    last 16 chunks (the tail of row 3) are staged, squared and normalised by its loops"""
+    exact_case(4, N, 4128, 500 + N, variants=("plain", "norm"))
+
+
 # ------------------------------------------------------------------------------------------------ 3. random data
 def _rand(shape, dtype, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)

@@ -28,13 +28,13 @@ def _ns():
 _cache = {}
 
 
-def _matrix(K):
-    """one gaussian matrix per K, std 0.02 like synth_state_dict, tall enough for the largest SwiGLU case, and its packed copy; a
-    product over the first rows of it reads the first rows of the copy (rows are coded independently)"""
+def _matrix(K, rows=None):
+    """one gaussian matrix per K, std 0.02 like synth_state_dict, tall enough for the largest SwiGLU case (or `rows` tall), and its
+    packed copy; a product over the first rows of it reads the first rows of the copy (rows are coded independently)"""
     if K not in _cache:
         ops = _ops()
         g = torch.Generator(device="cuda").manual_seed(1000 + K)
-        rows = 2 * max(_ns())
+        rows = rows or 2 * max(_ns())
         w = torch.randn((rows, K), device="cuda", generator=g) * 0.02
         # the device generator returns an exact 0.0 about once in 1e7 draws (and a value below 2^-30 once in 1e8): not gaussian
         # weights but an exception row each -- those have their own cases below
@@ -93,6 +93,18 @@ def test_gemv_p13_equals_gemv_bit_for_bit(K):
         for fusion in FUSIONS:
             rows = 2 * N if fusion == "norm_swiglu" else N
             ref, got = _both(ops, fusion, x, w[:rows], packed, flags, nw, res, N)
+            assert ref.dtype == got.dtype and torch.equal(ref, got), (K, N, fusion, int((ref != got).sum()))
+
+
+def test_gemv_p13_equals_gemv_bit_for_bit_looping_prologue():
+    """K = 16896 (K % 512 == 0): 2112 activation chunks, more than the 256 * 8 the prologue's threads hold in registers -- the last 64
+    are staged, squared and normalised by its loops; 33 chunk iterations = 9 groups, the last one padded with zeros in LDS"""
+    ops = _ops()
+    K, ns = 16896, (3, 4 * _grid() + 5)
+    w, packed, flags, x, nw, res = _matrix(K, rows=max(ns))
+    for N in ns:
+        for fusion in ("norm", "residual"):
+            ref, got = _both(ops, fusion, x, w[:N], packed, flags, nw, res, N)
             assert ref.dtype == got.dtype and torch.equal(ref, got), (K, N, fusion, int((ref != got).sum()))
 
 

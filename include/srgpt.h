@@ -206,6 +206,36 @@ int srgpt_pack_decode_weights(const void* W, void* out, int N, int K, int elem_b
 int srgpt_gemv_w4(const void* x, const void* W4, const void* wscale8, const void* norm_w, float norm_eps, const void* residual,
                   void* out, int batch, int N, int K, int swiglu, int out_f32, srgpt_stream_t stream);
 int srgpt_dequant_mxfp4(const void* W4, const void* wscale8, void* out_bf16, int N, int K, srgpt_stream_t stream);
+/* Additions under ABI 9: the prefill-side products over such a matrix (W4A16: bf16 activations and outputs, the ROW-MAJOR codes and
+ * scales above; the packed copies below are not involved).  Each takes the arguments of its bf16 counterpart with the operand pair
+ * (W4, wscale8) in place of W and a bf16 scratch `expand` [N, K] ([2 I, K] for _swiglu), and returns BIT FOR BIT what the counterpart
+ * returns on srgpt_dequant_mxfp4 of the same codes -- C, the norm output Y, the q/k/v buffer and both caches, the SwiGLU output: the
+ * product takes the SAME route (kernel family, tile, K splits) as the bf16 call of that (M, N, K, workspace, device), and everything
+ * that decides a bit (the k of every MFMA step, the instruction, the accumulators, the K range of a split, the slab order, every
+ * epilogue and fused reduction) is the bf16 instance's.  On the direct-to-LDS kernels with K % 64 == 0 the codes are multiplied IN
+ * the kernel: the code tile is DMA'd to LDS as bytes and widened between LDS and the MFMA operand (v_cvt_scalef32_pk_bf16_fp4, the
+ * block scale as the fp32 `byte << 23`, exact), the dequantised matrix is never written.  Every other route (the whole-M kernel of
+ * the 225 .. 272-row prefill, the 256 x 256 tiles of M >= 384, K % 64 != 0) expands the matrix into `expand` first
+ * (srgpt_dequant_mxfp4) and runs the bf16 launch on it.  srgpt_gemm_w4_in_kernel (host only; N = I with swiglu) returns 1 if the
+ * call of that shape multiplies the codes in the kernel on this device, 0 if it expands: `expand` is written and read only on the
+ * expansion path and may be NULL where the answer is 1; otherwise NULL is SRGPT_ERR_ARG before any launch.
+ *   srgpt_gemm_w4                C = A W^T + residual                 (srgpt_gemm: no bias / activation, plain rows, C fp32 if out_f32)
+ *   srgpt_gemm_w4_norm           the same (dense rows) and Y = RMSNorm(C)        (srgpt_gemm_norm with SRGPT_NORM_RMS, no bias)
+ *   srgpt_gemm_w4_swiglu         out = silu(A Wg^T) * (A Wu^T), Wgu4 = [Wg; Wu]  (srgpt_gemm_swiglu)
+ *   srgpt_gemm_w4_rope_kv_append q/k/v projection + RoPE + cache append          (srgpt_gemm_rope_kv_append)
+ * Scale-byte domain of the equality: 2 .. 252 (as srgpt_gemv_w4p below); other bytes give unspecified values, never a fault; no
+ * byte outside the code and scale arrays is read.  SRGPT_ERR_ARG: a NULL A / W4 / wscale8 / output, K % 32 != 0, A or `expand` not
+ * 16-byte aligned, codes not 4-byte aligned, and the counterpart's own argument errors.  ws / ws_bytes as for srgpt_gemm. */
+int srgpt_gemm_w4(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K, int lda,
+                  int ldc, int out_f32, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream);
+int srgpt_gemm_w4_norm(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
+                       void* expand, void* ws, int64_t ws_bytes, const void* norm_w, void* Y, float norm_eps, srgpt_stream_t stream);
+int srgpt_gemm_w4_swiglu(const void* A, const void* Wgu4, const void* wscale8, void* out, int M, int I, int K, void* gu_scratch,
+                         void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream);
+int srgpt_gemm_w4_rope_kv_append(const void* A, const void* W4, const void* wscale8, void* qkv, int K, void* expand, void* ws,
+                                 int64_t ws_bytes, void* kcache, void* vcache, const int* pos0, const void* cos_tab,
+                                 const void* sin_tab, int B, int T, int Hq, int Hkv, int D, int max_pos, srgpt_stream_t stream);
+int srgpt_gemm_w4_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes);
 /* Additions under ABI 9: the PACKED MXFP4 decode layout and the MFMA product over it, for 2+ rows per weight pass (W4A16: bf16
  * activations; the codes are widened to bf16 in registers with the block scale applied, v_cvt_scalef32_pk_bf16_fp4, exactly, and fed
  * to the bf16 MFMA of srgpt_gemv_rowss).  srgpt_gemv_w4 stays the format's raw reference; this is an opt-in second copy of a matrix.
@@ -654,9 +684,10 @@ typedef struct {
   /* ABI 9: optional MXFP4 copies (codes + E8M0 block scales, see srgpt_gemv_w4) of the four per-layer matrices; all NULL: the formats
    * above.  When wqkv4 != NULL they are the weights of those four (the dtype and fp8 arrays above are not read for them and may hold
    * NULLs): the decode step, the lookup steps included, streams them through srgpt_gemv_w4 (a batch of more than 4 rows in passes of
-   * 4); prefill and append prefill expand each matrix with srgpt_dequant_mxfp4 into a bf16 scratch in the workspace just before its
-   * product and run the bf16 launches on it -- bit-identical to a bf16 engine on the dequantised weights, at the price of one more
-   * pass over bf16-sized bytes per matrix.  lm_head stays fp8: lm_head8 + lm_head_scale are required, multiplied as under the fp8
+   * 4); prefill and append prefill run the srgpt_gemm_w4 family -- bit-identical to a bf16 engine on the dequantised weights: the
+   * direct-to-LDS kernels (every product of an append, o_proj of the bs = 1 prefill) multiply the codes themselves, the whole-M and
+   * 256 x 256 routes still expand each matrix with srgpt_dequant_mxfp4 into a bf16 scratch in the workspace just before its product,
+   * at the price of one more pass over bf16-sized bytes per such matrix.  lm_head stays fp8: lm_head8 + lm_head_scale are required, multiplied as under the fp8
    * format.  Needs dtype SRGPT_BF16, hidden, inter and heads * head_dim multiples of 32, and wqkv8 == NULL. */
   const void* const* wqkv4;
   const void* const* wqkv4_scale;

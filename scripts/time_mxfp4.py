@@ -1,6 +1,6 @@
 """What llm_weight_format="mxfp4" costs and gains against fp8 and bf16.  -> profiles/mxfp4.txt
 
-    python scripts/time_mxfp4.py [--out profiles/mxfp4.txt] [--rows 259] [--only steps|products] [--tree DIR]
+    python scripts/time_mxfp4.py [--out profiles/mxfp4.txt] [--rows 259] [--only steps|products|packed|prefill] [--tree DIR]
 
 VILA1.5-8B geometry (bench.make_cfg, synth_state_dict seed 0), one process, three engines (bf16, fp8, mxfp4) on one card.  Every
 timed call is: the state put back outside the window, device synchronise, an event, the work, an event, synchronise.  The lines of a
@@ -12,7 +12,8 @@ the min .. max of all calls -- the run-to-run spread a ratio has to clear.
   batch 8   the captured batch-8 step: fp8 (the MFMA kernel, one pass of 8 rows) against mxfp4 (two passes of 4 rows)
   products  q/k/v, o_proj, gate/up and down_proj alone at 1 .. 4 rows, srgpt_gemv_w8 against srgpt_gemv_w4: a captured graph of one
             launch per layer (32 different matrices: nothing is served from a cache), us per launch
-  prefill   the 259-row prefill and a 32-row append over it, eager calls: fp8 against mxfp4 (which expands every matrix to bf16 first)
+  prefill   the 259-row prefill and a 32-row append over it, eager calls: fp8 against mxfp4 (srgpt_gemm_w4 and its composites: the
+            direct-to-LDS kernels multiply the codes, the whole-M and 256 x 256 routes expand the matrix to bf16 first)
   bytes     llm_weight_bytes() of the three engines
 
 --only packed  (-> profiles/mxfp4_mfma.txt) the packed MXFP4 copies (mxfp4_packed=True: srgpt_gemv_w4p, the MFMA product) against the
@@ -21,6 +22,11 @@ default mxfp4 engine and fp8, three engines in one process:
   steps     the captured lookup step at K = 1 / 2 / 3, the batch-4 and batch-8 step, the batched lookup step at (2, 4) and (4, 4)
   products  the four products at 1 .. 4, 8 and 16 rows: srgpt_gemv_w4 (VALU), srgpt_gemv_w4p, fp8 srgpt_gemv_rowss over its packed copy
   HBM       what the engines hold, and mxfp4_packed_bytes()
+
+--only prefill  (-> profiles/mxfp4_prefill.txt) the prefill leg for all three formats: the captured batch-1 decode steps, then the
+259-row prefill and the 32-row append over 259 cached rows, eager, bf16 / fp8 / mxfp4.  Run on this tree and, with --tree, on the
+parent commit's checkout in alternating fresh processes: a change of the mxfp4 lines counts when it clears the min .. max of one
+process's calls, and the bf16 / fp8 lines and the decode steps have to stay inside it.
 
 --only steps: the bf16 and fp8 steps alone -- what a tree without the format has; --tree DIR imports the package from another
 checkout (the parent commit), so the same lines can be taken on both in turn.  --only products: the fp8 and mxfp4 steps and the
@@ -93,11 +99,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--per-block", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed"])
+    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed", "prefill"])
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mxfp4_mfma.txt" if args.only == "packed" else "mxfp4.txt")
+        args.out = os.path.join(ROOT, "profiles", {"packed": "mxfp4_mfma.txt", "prefill": "mxfp4_prefill.txt"}.get(args.only, "mxfp4.txt"))
     sys.path.insert(0, os.path.abspath(args.tree))
     sys.path.insert(1, ROOT)
     assert torch.cuda.is_available(), "a timing needs the MI355X"
@@ -110,7 +116,7 @@ def main():
     cfg = bench.make_cfg("vila15_8b")
     lib = L.load()
     have4 = hasattr(lib, "srgpt_gemv_w4")
-    formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only == "all" else [])
+    formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only in ("all", "prefill") else [])
     name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed"}
     eng, held = {}, {}
     for f in formats:
@@ -286,12 +292,12 @@ def main():
                         mid(reps["mxfp4"]) / mid(reps["fp8"])))
         say()
 
-    if args.only == "all" and have4:
+    if args.only in ("all", "prefill") and have4:
         # ---- prefill and append
         x = (torch.randn((1, args.rows + 32, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
         head, tail = x[:, :args.rows].contiguous(), x[:, args.rows:].contiguous()
         lines_p, lines_a = {}, {}
-        for f in ("fp8", "mxfp4"):
+        for f in (formats if args.only == "prefill" else ("fp8", "mxfp4")):
             e = eng[f]
             st = e.new_state(1, 512, 4)
             keep.append(st)
@@ -309,8 +315,8 @@ def main():
             with torch.cuda.stream(e.stream):
                 prefill()
             torch.cuda.synchronize()
-            lines_p[f] = (prefill, None, e.stream)
-            lines_a[f] = (append, back, e.stream)
+            lines_p[name[f]] = (prefill, None, e.stream)
+            lines_a[name[f]] = (append, back, e.stream)
         report("%d-row prefill, eager" % args.rows, interleaved(lines_p, args), "fp8")
         report("32-row append over %d cached rows, eager" % args.rows, interleaved(lines_a, args), "fp8")
 

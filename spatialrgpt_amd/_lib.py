@@ -117,6 +117,11 @@ _SIGNATURES = {
     "srgpt_gemv_w8": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemv_w4": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "srgpt_dequant_mxfp4": (i32, [vp, vp, vp, i32, i32, vp]),
+    "srgpt_gemm_w4": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "srgpt_gemm_w4_norm": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, f32, vp]),
+    "srgpt_gemm_w4_swiglu": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "srgpt_gemm_w4_rope_kv_append": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "srgpt_gemm_w4_in_kernel": (i32, [i32, i32, i32, i32, i32, i64]),
     "srgpt_mxfp4_packed_bytes": (C.c_size_t, [i32, i32, i32]),
     "srgpt_pack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "srgpt_unpack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),

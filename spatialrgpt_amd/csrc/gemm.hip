@@ -30,9 +30,25 @@ constexpr int BK = 64;  // bf16 elements per K tile = 8 slots of 16 B
 // NBUF = 2: the next tile's LDS-DMA is issued before the current tile is multiplied, one barrier per K tile -- for grids that
 //           leave a CU with only 1-2 blocks (the M = 259 prefill and ViT shapes), where each K step would otherwise pay a
 //           full memory latency.
-template <int BM, int BN, int NBUF>
+//
+// W4: the weight operand is row-major MXFP4 codes [N, K / 2] + E8M0 bytes [N, K / 32] (include/srgpt.h), K % 64 == 0.  The code tile
+// of a K tile is BN rows x 32 B = 8 dwords per row, a dword = the 8 codes of one MFMA fragment (k = 16 ks + 8 (lane >> 5) .. + 8):
+// LDS-DMA with 4 bytes per lane moves 8 rows x 32 B per wave-instruction (the same GW requests per wave, the same lane >> 3 /
+// lane & 7 mapping), a fragment is one ds_read_b32 + four v_cvt_scalef32_pk_bf16_fp4 with the block scale `byte << 23` (exact), and
+// the two scale bytes a row needs per K tile are loaded from global memory by the lanes that multiply the row, one tile ahead
+// when double-buffered.  Dword swizzle: slot ^ ((row >> 2) & 7) -- a ds_read_b32 resolves banks (dword address mod 32) per 32-lane
+// half, a half reads 32 consecutive rows at one slot = dword 8 row + slot', and for a fixed row & 3 the eight row >> 2 give eight
+// different slot' (SQ_LDS_BANK_CONFLICT 0; slot ^ (((row >> 3) & 3) << 1), derived for 64 banks, measured half of the W reads'
+// cycles as conflicts); the source side permutes which dword a lane fetches ((row >> 2) & 7 = ((wave & 3) << 1) | (lane >> 5) for
+// every group of a wave).  The k of every step, the MFMA, the accumulators, the split ranges and the epilogue are the bf16
+// instance's, so the product equals it on srgpt_dequant_mxfp4 of the codes bit for bit.  The mode is the presence of the trailing scale-pointer argument (a parameter pack of
+// zero or one `const unsigned char*`; W then points at the codes): the bf16 instantiation keeps its parameter list and compiles to the
+// instructions it had without this mode (a body shared through a __device__ function did not: checked on the disassembly).
+template <int BM, int BN, int NBUF, typename... Scale8>
 __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
-                                                                         int K, int lda, Epilogue e) {
+                                                                         int K, int lda, Epilogue e, Scale8... scale8) {
+  constexpr bool W4 = sizeof...(Scale8) == 1;
+  static_assert(sizeof...(Scale8) <= 1, "at most one scale pointer");
   // wave layout: 2 x 2 waves of (BM/2) x (BN/2) when BM is a multiple of 64; BM = 96 (three 32-row MFMA tiles -- 259 rows pad to
   // 288 instead of 320 and a tile step moves 17.8 instead of 23.4 bytes per kFLOP through the fill path that bounds this kernel):
   // 1 x 4 waves of 96 x (BN/4)
@@ -40,7 +56,8 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const b
   constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;  // rows / columns of a wave's sub-tile
   constexpr int TM = WTM / 32, TN = WTN / 32;
   static_assert(TM * 32 * WAVES_M == BM && TN * 32 * WAVES_N == BN && BM % 32 == 0 && BN % 32 == 0, "tile / wave layout");
-  constexpr int TILE = (BM + BN) * BK;  // elements per stage buffer
+  constexpr int WROW = W4 ? BK / 4 : BK;    // bf16-sized elements a W row takes in LDS (W4: 32 bytes of codes)
+  constexpr int TILE = BM * BK + BN * WROW;  // elements per stage buffer
   __shared__ __attribute__((aligned(1024))) bf16_t lds[NBUF * TILE];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -61,21 +78,42 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const b
 #pragma unroll
   for (int i = 0; i < GA; ++i) pa[i] = A + (size_t)min(m0 + (wave + 4 * i) * 8 + lr, e.M - 1) * lda + lc * 8;
 #pragma unroll
-  for (int i = 0; i < GW; ++i) pw[i] = W + (size_t)min(n0 + (wave + 4 * i) * 8 + lr, e.N - 1) * K + lc * 8;
+  for (int i = 0; i < GW; ++i) {
+    const size_t row = (size_t)min(n0 + (wave + 4 * i) * 8 + lr, e.N - 1);
+    // W4: byte offsets in bf16_t units -- a row is K / 2 bytes = K / 4 elements, the lane's dword is slot ^ ((row >> 2) & 7)
+    pw[i] = W4 ? W + row * (K / 4) + ((lane & 7) ^ (((wave & 3) << 1) | (lr >> 2))) * 2 : W + row * K + lc * 8;
+  }
+  // W4: the E8M0 bytes of the rows this lane multiplies (clamped like the rows themselves); sc[j] = bytes 2 kt, 2 kt + 1 of row j
+  const unsigned char* ps[TN];
+  unsigned int sc_cur[TN] = {}, sc_nxt[TN] = {};
+  if constexpr (W4) {
+    const unsigned char* wscale8 = (scale8, ...);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) ps[j] = wscale8 + (size_t)min(n0 + wn * WTN + j * 32 + (lane & 31), e.N - 1) * (K / 32);
+  }
+  auto load_scales = [&](int kt, unsigned int* sc) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j) sc[j] = (unsigned int)ps[j][2 * kt] | ((unsigned int)ps[j][2 * kt + 1] << 8);
+  };
 
   auto stage = [&](int kt, int buf) {
     bf16_t* As = lds + buf * TILE;
     bf16_t* Ws = As + BM * BK;
     const int k0 = kt * BK;
-    if (k0 + BK <= K) {
+    if (W4 || k0 + BK <= K) {  // (W4: K % 64 == 0, no ragged tile)
 #pragma unroll
       for (int i = 0; i < GA; ++i)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pa[i] + k0),
                                          (__attribute__((address_space(3))) void*)(As + (wave + 4 * i) * 8 * BK), 16, 0, 0);
 #pragma unroll
-      for (int i = 0; i < GW; ++i)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw[i] + k0),
-                                         (__attribute__((address_space(3))) void*)(Ws + (wave + 4 * i) * 8 * BK), 16, 0, 0);
+      for (int i = 0; i < GW; ++i) {
+        if constexpr (W4)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw[i] + k0 / 4),
+                                           (__attribute__((address_space(3))) void*)(Ws + (wave + 4 * i) * 8 * WROW), 4, 0, 0);
+        else
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pw[i] + k0),
+                                           (__attribute__((address_space(3))) void*)(Ws + (wave + 4 * i) * 8 * BK), 16, 0, 0);
+      }
     } else {  // ragged last tile: zero-filled through registers, same swizzled slots
       const bool ok = k0 + lc * 8 < K;
 #pragma unroll
@@ -98,7 +136,7 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const b
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = zero16;
 
-  auto compute = [&](int buf) {
+  auto compute = [&](int buf, const unsigned int* sc) {
     const bf16_t* As = lds + buf * TILE;
     const bf16_t* Ws = As + BM * BK;
 #pragma unroll
@@ -113,7 +151,18 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const b
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int r = wn * WTN + j * 32 + (lane & 31);
-        fw[j] = *reinterpret_cast<const bf16x8*>(Ws + r * BK + ((slot ^ ((r >> 1) & 7)) << 3));
+        if constexpr (W4) {
+          const unsigned int word = *reinterpret_cast<const unsigned int*>(Ws + r * WROW + ((slot ^ ((r >> 2) & 7)) << 1));
+          const float s = __uint_as_float(((sc[j] >> (8 * (ks >> 1))) & 0xffu) << 23);  // k steps 0, 1: block 2 kt; 2, 3: 2 kt + 1
+          u32x4 o;
+          o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, s, 0));
+          o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, s, 1));
+          o[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, s, 2));
+          o[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, s, 3));
+          fw[j] = __builtin_bit_cast(bf16x8, o);
+        } else {
+          fw[j] = *reinterpret_cast<const bf16x8*>(Ws + r * BK + ((slot ^ ((r >> 1) & 7)) << 3));
+        }
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -125,17 +174,26 @@ __global__ __launch_bounds__(256, NBUF == 1 ? 3 : 2) void gemm_bf16_glds(const b
   if (NBUF == 1) {
     for (int kt = kt0; kt < nk; ++kt) {
       stage(kt, 0);
+      if constexpr (W4) load_scales(kt, sc_cur);
       __syncthreads();  // carries the vmcnt(0) that lands the LDS-DMA
-      compute(0);
+      compute(0, sc_cur);
       __syncthreads();  // every wave is done reading before the next tile overwrites the buffer
     }
   } else {
     stage(kt0, 0);
+    if constexpr (W4) load_scales(kt0, sc_cur);
     for (int kt = kt0; kt < nk; ++kt) {
       const int cur = (kt - kt0) & 1;
       __syncthreads();  // tile kt has landed (vmcnt(0)); every wave has finished tile kt-1, so the other buffer is free
-      if (kt + 1 < nk) stage(kt + 1, cur ^ 1);
-      compute(cur);
+      if (kt + 1 < nk) {
+        stage(kt + 1, cur ^ 1);
+        if constexpr (W4) load_scales(kt + 1, sc_nxt);
+      }
+      compute(cur, sc_cur);
+      if constexpr (W4) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) sc_cur[j] = sc_nxt[j];
+      }
     }
   }
 
@@ -563,18 +621,41 @@ static Epilogue plain_epilogue(void* C, int M, int N, int ldc) {
   return e;
 }
 
+// The weight operand of a product: a row-major matrix of the activation dtype, or (ABI 9) row-major MXFP4 codes with their E8M0
+// bytes (include/srgpt.h) and the bf16 scratch [N, K] they are expanded into where no kernel multiplies codes (gemm_w4_in_kernel).
+struct WOperand {
+  const void* w;       // the matrix, or the codes [N, K / 2]
+  const void* scale8;  // NULL: `w` is a matrix of the dtype; else the block scales [N, K / 32]
+  void* expand;        // codes only: written and read on the expansion path alone, may be NULL otherwise
+};
+
+// the codes' checks, and their expansion where `in_kernel` is false: afterwards *W is what the bf16 launch reads
+static int w4_resolve(const char* fn, const WOperand& w, int N, int K, int dtype, bool in_kernel, srgpt_stream_t stream, const void** W) {
+  SRGPT_CHECK(dtype == SRGPT_BF16, SRGPT_ERR_ARG, "%s: MXFP4 weights need bf16 activations", fn);
+  SRGPT_CHECK(K % 32 == 0, SRGPT_ERR_ARG, "%s: K=%d must be a multiple of 32 (one scale per 32 values)", fn, K);
+  SRGPT_CHECK((uintptr_t)w.w % 4 == 0, SRGPT_ERR_ARG, "%s: the codes must be 4-byte aligned", fn);
+  *W = w.w;
+  if (in_kernel) return SRGPT_OK;
+  SRGPT_CHECK(w.expand, SRGPT_ERR_ARG, "%s: this shape expands the codes first and needs the bf16 [N, K] scratch", fn);
+  SRGPT_CHECK((uintptr_t)w.expand % 16 == 0, SRGPT_ERR_ARG, "%s: the scratch must be 16-byte aligned", fn);
+  *W = w.expand;
+  return srgpt_dequant_mxfp4(w.w, w.scale8, w.expand, N, K, stream);
+}
+
 // C = epilogue(A W^T) for the entry points below: validate, pick the route (gemm_route.h), launch its kernel, reduce the slabs.
-// *fused: see srgpt_splitk_finish.
-static int gemm_run(const void* A, const void* W, int K, int lda, int dtype, void* ws, int64_t ws_bytes, Epilogue e,
+// Codes take the route of the bf16 product and are multiplied in its kernel where gemm_w4_in_kernel says so; everywhere else they
+// are expanded and the launches are the bf16 ones.  *fused: see srgpt_splitk_finish.
+static int gemm_run(const void* A, const WOperand& w, int K, int lda, int dtype, void* ws, int64_t ws_bytes, Epilogue e,
                     srgpt_stream_t stream, bool* fused) {
   const int M = e.M, N = e.N;
-  SRGPT_CHECK(A && W && e.C, SRGPT_ERR_ARG, "srgpt_gemm: null pointer");
+  const bool w4 = w.scale8 != nullptr;
+  SRGPT_CHECK(A && w.w && e.C, SRGPT_ERR_ARG, "srgpt_gemm: null pointer");
   SRGPT_CHECK(M > 0 && N > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm: bad shape M=%d N=%d K=%d", M, N, K);
   SRGPT_CHECK(dtype == SRGPT_F32 || dtype == SRGPT_BF16, SRGPT_ERR_ARG, "srgpt_gemm: bad dtype %d", dtype);
   const int vec = dtype == SRGPT_BF16 ? 8 : 4;
   SRGPT_CHECK(K % vec == 0 && lda % vec == 0, SRGPT_ERR_ARG,
               "srgpt_gemm: K=%d and lda=%d must be multiples of %d (16-byte rows)", K, lda, vec);
-  SRGPT_CHECK(((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0), SRGPT_ERR_ARG, "srgpt_gemm: A/W must be 16-byte aligned");
+  SRGPT_CHECK(((uintptr_t)A % 16 == 0) && (w4 || (uintptr_t)w.w % 16 == 0), SRGPT_ERR_ARG, "srgpt_gemm: A/W must be 16-byte aligned");
   if (e.out_mode == SRGPT_OUT_DECONV2X) {
     SRGPT_CHECK(N % 4 == 0 && e.gw > 0 && M % (e.gw * e.gw) == 0, SRGPT_ERR_ARG, "srgpt_gemm: bad deconv geometry");
   } else {
@@ -583,6 +664,9 @@ static int gemm_run(const void* A, const void* W, int K, int lda, int dtype, voi
   }
   hipStream_t s = as_stream(stream);
   const GemmRoute r = dtype == SRGPT_F32 ? gemm_route_f32() : gemm_route(M, N, K, srgpt_device_cus(), ws != nullptr, ws_bytes);
+  const bool codes = w4 && gemm_w4_in_kernel(r, K);  // the kernel reads the codes
+  const void* W = w.w;
+  if (w4) SRGPT_TRY(w4_resolve("srgpt_gemm_w4", w, N, K, dtype, codes, stream, &W));
   srgpt_splitk_apply(e, r, ws);
   switch (r.family) {
     case GEMM_F32_SIMPLE:
@@ -593,8 +677,13 @@ static int gemm_run(const void* A, const void* W, int K, int lda, int dtype, voi
     case GEMM_TILE_256: SRGPT_TRY(srgpt_gemm256_launch(A, W, K, lda, e, s)); break;
     case GEMM_GLDS: {
       const dim3 grid(cdiv(N, 128), cdiv(M, r.bm), e.splits);
-#define SRGPT_GLDS(BM, NBUF) \
-  hipLaunchKernelGGL((gemm_bf16_glds<BM, 128, NBUF>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e)
+#define SRGPT_GLDS(BM, NBUF)                                                                                                        \
+  do {                                                                                                                              \
+    if (codes)                                                                                                                      \
+      hipLaunchKernelGGL((gemm_bf16_glds<BM, 128, NBUF, const unsigned char*>), grid, dim3(256), 0, s, (const bf16_t*)A,            \
+                         (const bf16_t*)W, K, lda, e, (const unsigned char*)w.scale8);                                              \
+    else hipLaunchKernelGGL((gemm_bf16_glds<BM, 128, NBUF>), grid, dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e); \
+  } while (0)
       if (r.bm == 128) SRGPT_GLDS(128, 1);
       else if (r.bm == 96 && r.nbuf == 2) SRGPT_GLDS(96, 2);
       else if (r.bm == 96) SRGPT_GLDS(96, 1);
@@ -614,15 +703,29 @@ extern "C" int srgpt_gemm(const void* A, const void* W, const void* bias, const 
   Epilogue e = plain_epilogue(C, M, N, ldc);
   e.bias = bias, e.residual = residual, e.act = act, e.bias_mod = bias_mod, e.res_mod = res_mod;
   e.out_f32 = out_f32, e.out_mode = out_mode, e.gw = gw;
-  return gemm_run(A, W, K, lda, dtype, ws, ws_bytes, e, stream, nullptr);
+  return gemm_run(A, WOperand{W, nullptr, nullptr}, K, lda, dtype, ws, ws_bytes, e, stream, nullptr);
+}
+
+// the W4 entry points' own pointer check (the scales make an operand a code operand, so a NULL one must not pass as a bf16 matrix)
+static int w4_args(const char* fn, const void* W4, const void* wscale8) {
+  SRGPT_CHECK(W4 && wscale8, SRGPT_ERR_ARG, "%s: null pointer", fn);
+  return SRGPT_OK;
+}
+
+extern "C" int srgpt_gemm_w4(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
+                             int lda, int ldc, int out_f32, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4", W4, wscale8));
+  Epilogue e = plain_epilogue(C, M, N, ldc);
+  e.residual = residual, e.out_f32 = out_f32;
+  return gemm_run(A, WOperand{W4, wscale8, expand}, K, lda, SRGPT_BF16, ws, ws_bytes, e, stream, nullptr);
 }
 
 // C = A W^T + bias + residual (dense rows) and Y = norm(C) in one call (include/srgpt.h; the layer loops of model.hip).  The norm
 // rides in the split-K reduction when the product is split; otherwise it is the ordinary srgpt_rmsnorm / srgpt_layernorm launch --
 // either way the two outputs are bit-identical to srgpt_gemm followed by the norm.
-extern "C" int srgpt_gemm_norm(const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K,
-                               void* ws, int64_t ws_bytes, int norm_kind, const void* norm_w, const void* norm_b, void* Y,
-                               float norm_eps, int dtype, srgpt_stream_t stream) {
+static int gemm_norm_run(const void* A, const WOperand& w, const void* bias, const void* residual, void* C, int M, int N, int K, void* ws,
+                         int64_t ws_bytes, int norm_kind, const void* norm_w, const void* norm_b, void* Y, float norm_eps, int dtype,
+                         srgpt_stream_t stream) {
   SRGPT_CHECK(norm_kind == SRGPT_NORM_RMS || norm_kind == SRGPT_NORM_LAYER, SRGPT_ERR_ARG, "srgpt_gemm_norm: unknown norm kind %d",
               norm_kind);
   SRGPT_CHECK(norm_w && Y && (norm_kind == SRGPT_NORM_RMS || norm_b), SRGPT_ERR_ARG, "srgpt_gemm_norm: null pointer");
@@ -631,7 +734,7 @@ extern "C" int srgpt_gemm_norm(const void* A, const void* W, const void* bias, c
   e.bias = bias, e.residual = residual;
   e.norm_w = norm_w, e.norm_b = norm_b, e.norm_y = Y, e.norm_eps = norm_eps, e.norm_kind = norm_kind;
   bool fused = false;
-  SRGPT_TRY(gemm_run(A, W, K, K, dtype, ws, ws_bytes, e, stream, &fused));
+  SRGPT_TRY(gemm_run(A, w, K, K, dtype, ws, ws_bytes, e, stream, &fused));
   if (!fused) {
     if (norm_kind == SRGPT_NORM_RMS) SRGPT_TRY(srgpt_rmsnorm(C, norm_w, Y, M, N, norm_eps, dtype, stream));
     else SRGPT_TRY(srgpt_layernorm(C, norm_w, norm_b, Y, M, N, norm_eps, SRGPT_ACT_NONE, dtype, stream));
@@ -639,12 +742,27 @@ extern "C" int srgpt_gemm_norm(const void* A, const void* W, const void* bias, c
   return SRGPT_OK;
 }
 
+extern "C" int srgpt_gemm_norm(const void* A, const void* W, const void* bias, const void* residual, void* C, int M, int N, int K,
+                               void* ws, int64_t ws_bytes, int norm_kind, const void* norm_w, const void* norm_b, void* Y,
+                               float norm_eps, int dtype, srgpt_stream_t stream) {
+  return gemm_norm_run(A, WOperand{W, nullptr, nullptr}, bias, residual, C, M, N, K, ws, ws_bytes, norm_kind, norm_w, norm_b, Y, norm_eps,
+                       dtype, stream);
+}
+
+extern "C" int srgpt_gemm_w4_norm(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
+                                  void* expand, void* ws, int64_t ws_bytes, const void* norm_w, void* Y, float norm_eps,
+                                  srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_norm", W4, wscale8));
+  return gemm_norm_run(A, WOperand{W4, wscale8, expand}, nullptr, residual, C, M, N, K, ws, ws_bytes, SRGPT_NORM_RMS, norm_w, nullptr, Y,
+                       norm_eps, SRGPT_BF16, stream);
+}
+
 // qkv = A W^T for the B * T token rows of a prefill, then RoPE on q (in place) and k, k and v appended to the caches -- the
 // projection and srgpt_rope_kv_append in one call (include/srgpt.h).  The rotation rides in the split-K reduction when the product is
 // split; otherwise it is the ordinary srgpt_rope_kv_append launch.  Every byte written is the same either way.
-extern "C" int srgpt_gemm_rope_kv_append(const void* A, const void* W, void* qkv, int K, void* ws, int64_t ws_bytes, void* kcache,
-                                         void* vcache, const int* pos0, const void* cos_tab, const void* sin_tab, int B, int T_,
-                                         int Hq, int Hkv, int D, int max_pos, int dtype, srgpt_stream_t stream) {
+static int gemm_rope_run(const void* A, const WOperand& w, void* qkv, int K, void* ws, int64_t ws_bytes, void* kcache, void* vcache,
+                         const int* pos0, const void* cos_tab, const void* sin_tab, int B, int T_, int Hq, int Hkv, int D, int max_pos,
+                         int dtype, srgpt_stream_t stream) {
   SRGPT_CHECK(qkv && kcache && vcache && cos_tab && sin_tab, SRGPT_ERR_ARG, "srgpt_gemm_rope_kv_append: null pointer");
   SRGPT_CHECK(B > 0 && T_ > 0 && Hq > 0 && Hkv > 0 && D > 0 && (D & 1) == 0 && T_ <= max_pos, SRGPT_ERR_ARG,
               "srgpt_gemm_rope_kv_append: bad shape");
@@ -653,30 +771,69 @@ extern "C" int srgpt_gemm_rope_kv_append(const void* A, const void* W, void* qkv
   e.rope_k = kcache, e.rope_v = vcache, e.rope_pos0 = pos0, e.rope_cos = cos_tab, e.rope_sin = sin_tab;
   e.rope_T = T_, e.rope_Hq = Hq, e.rope_Hkv = Hkv, e.rope_D = D, e.rope_max_pos = max_pos;
   bool fused = false;
-  SRGPT_TRY(gemm_run(A, W, K, K, dtype, ws, ws_bytes, e, stream, &fused));
+  SRGPT_TRY(gemm_run(A, w, K, K, dtype, ws, ws_bytes, e, stream, &fused));
   if (!fused) SRGPT_TRY(srgpt_rope_kv_append(qkv, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq, Hkv, D, max_pos, dtype, stream));
   return SRGPT_OK;
+}
+
+extern "C" int srgpt_gemm_rope_kv_append(const void* A, const void* W, void* qkv, int K, void* ws, int64_t ws_bytes, void* kcache,
+                                         void* vcache, const int* pos0, const void* cos_tab, const void* sin_tab, int B, int T_,
+                                         int Hq, int Hkv, int D, int max_pos, int dtype, srgpt_stream_t stream) {
+  return gemm_rope_run(A, WOperand{W, nullptr, nullptr}, qkv, K, ws, ws_bytes, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq, Hkv, D,
+                       max_pos, dtype, stream);
+}
+
+extern "C" int srgpt_gemm_w4_rope_kv_append(const void* A, const void* W4, const void* wscale8, void* qkv, int K, void* expand, void* ws,
+                                            int64_t ws_bytes, void* kcache, void* vcache, const int* pos0, const void* cos_tab,
+                                            const void* sin_tab, int B, int T_, int Hq, int Hkv, int D, int max_pos,
+                                            srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_rope_kv_append", W4, wscale8));
+  return gemm_rope_run(A, WOperand{W4, wscale8, expand}, qkv, K, ws, ws_bytes, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq, Hkv, D,
+                       max_pos, SRGPT_BF16, stream);
 }
 
 // out[M, I] = rnd(rnd(silu(A Wg^T)) * (A Wu^T)) for the stacked weight Wgu = [Wg; Wu] ([2 I, K]) -- LlamaMLP's gate / up products and
 // srgpt_silu_mul in one call (include/srgpt.h).  On the whole-M kernel (225 .. 272 rows: the bs = 1 prefill) a block multiplies 64
 // gate columns and the 64 matching up columns and the activation is its epilogue: the [M, 2 I] intermediate is neither written nor
-// read.  Every other shape runs srgpt_gemm into `gu_scratch` and srgpt_silu_mul -- the result is the same to the last bit.
-extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int M, int I, int K, void* gu_scratch, void* ws,
-                                 int64_t ws_bytes, int dtype, srgpt_stream_t stream) {
-  SRGPT_CHECK(A && Wgu && out, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: null pointer");
+// read.  Every other shape runs the plain product into `gu_scratch` and srgpt_silu_mul -- the result is the same to the last bit.
+// Codes: the whole-M kernel has no W4 mode, so the fused form expands them first; the plain product follows gemm_run's rule.
+static int gemm_swiglu_run(const void* A, const WOperand& w, void* out, int M, int I, int K, void* gu_scratch, void* ws, int64_t ws_bytes,
+                           int dtype, srgpt_stream_t stream) {
+  const bool w4 = w.scale8 != nullptr;
+  SRGPT_CHECK(A && w.w && out, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: null pointer");
   SRGPT_CHECK(M > 0 && I > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: bad shape M=%d I=%d K=%d", M, I, K);
   if (dtype == SRGPT_BF16 && gemm_swiglu_fused_shape(M, I, K, srgpt_device_cus()) && ((uintptr_t)A % 16 == 0) &&
-      ((uintptr_t)Wgu % 16 == 0)) {
+      (w4 || (uintptr_t)w.w % 16 == 0)) {
+    const void* W = w.w;
+    if (w4) SRGPT_TRY(w4_resolve("srgpt_gemm_w4_swiglu", w, 2 * I, K, dtype, false, stream, &W));
     Epilogue e = plain_epilogue(out, M, I, I);
     e.swiglu_inter = I;
-    SRGPT_TRY(srgpt_gemm288_launch(A, Wgu, K, K, e, as_stream(stream)));
+    SRGPT_TRY(srgpt_gemm288_launch(A, W, K, K, e, as_stream(stream)));
     return SRGPT_OK;
   }
   SRGPT_CHECK(gu_scratch, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: this shape needs the [M, 2 I] scratch buffer");
-  SRGPT_TRY(srgpt_gemm(A, Wgu, nullptr, nullptr, gu_scratch, M, 2 * I, K, K, 2 * I, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, ws,
-                       ws_bytes, dtype, stream));
+  SRGPT_TRY(gemm_run(A, w, K, K, dtype, ws, ws_bytes, plain_epilogue(gu_scratch, M, 2 * I, 2 * I), stream, nullptr));
   return srgpt_silu_mul(gu_scratch, out, M, I, dtype, stream);
+}
+
+extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int M, int I, int K, void* gu_scratch, void* ws,
+                                 int64_t ws_bytes, int dtype, srgpt_stream_t stream) {
+  return gemm_swiglu_run(A, WOperand{Wgu, nullptr, nullptr}, out, M, I, K, gu_scratch, ws, ws_bytes, dtype, stream);
+}
+
+extern "C" int srgpt_gemm_w4_swiglu(const void* A, const void* Wgu4, const void* wscale8, void* out, int M, int I, int K,
+                                    void* gu_scratch, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_swiglu", Wgu4, wscale8));
+  return gemm_swiglu_run(A, WOperand{Wgu4, wscale8, expand}, out, M, I, K, gu_scratch, ws, ws_bytes, SRGPT_BF16, stream);
+}
+
+// host only: 1 when the W4 entry point of this shape multiplies the codes in its kernel on this device, 0 when it expands them first
+// (N = I with swiglu: srgpt_gemm_w4_swiglu)
+extern "C" int srgpt_gemm_w4_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0) return 0;
+  const int cus = srgpt_device_cus();
+  if (swiglu) return gemm_swiglu_w4_in_kernel(M, N, K, cus, have_ws != 0, ws_bytes) ? 1 : 0;
+  return gemm_w4_in_kernel(gemm_route(M, N, K, cus, have_ws != 0, ws_bytes), K) ? 1 : 0;
 }
 
 // C = epilogue((A @ fp8(W8)^T) * wscale): bf16 activations, OCP e4m3fn weight bytes, one fp32 scale per weight row -- the

@@ -145,3 +145,14 @@ inline GemmRoute gemm_route_fp8(int M, int N, int nk, int min_tiles, int cus, bo
 inline bool gemm_swiglu_fused_shape(int M, int I, int K, int cus) {
   return M > 224 && M <= 272 && K % 64 == 0 && K / 64 >= 4 && I % 64 == 0 && I / 64 >= cus / 2;
 }
+
+// srgpt_gemm_w4 / _norm / _rope_kv_append (MXFP4 codes as the weight operand): the route is gemm_route's, unchanged.  Does the kernel
+// of route `r` multiply the codes itself?  Only the direct-to-LDS family has a W4 mode, and its code tile holds whole K tiles of 64;
+// every other product expands the codes into the bf16 scratch first and runs the bf16 launch.
+inline bool gemm_w4_in_kernel(const GemmRoute& r, int K) { return r.family == GEMM_GLDS && K % 64 == 0; }
+
+// srgpt_gemm_w4_swiglu: the fused form runs on the whole-M kernel, which has no W4 mode; every other shape is the plain product of
+// the stacked matrix [2 I, K]
+inline bool gemm_swiglu_w4_in_kernel(int M, int I, int K, int cus, bool have_ws, int64_t ws_bytes) {
+  return !gemm_swiglu_fused_shape(M, I, K, cus) && gemm_w4_in_kernel(gemm_route(M, 2 * I, K, cus, have_ws, ws_bytes), K);
+}

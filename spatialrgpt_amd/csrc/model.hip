@@ -396,8 +396,8 @@ namespace {
 // not touched: FMT_W8A16 (srgpt_gemm_w8 / srgpt_gemv_w8; the decode step streams half the bytes per token), or with fp8_act
 // FMT_W8A8: the prefill's per-token e4m3 activations on the fp8 matrix pipe (include/srgpt.h).  The decode step and the
 // all-position lm_head (fp32 logits, parity hook) are W8A16 under both fp8 formats.  MXFP4 copies present -> FMT_W4A16: the four
-// layer matrices are codes + block scales (srgpt_gemv_w4 in the decode steps, srgpt_dequant_mxfp4 + the bf16 launches in the
-// prefill), lm_head is fp8 and multiplied as under FMT_W8A16.
+// layer matrices are codes + block scales (srgpt_gemv_w4 in the decode steps, the srgpt_gemm_w4 family in the prefill), lm_head
+// is fp8 and multiplied as under FMT_W8A16.
 enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8, FMT_W4A16 };
 
 // the format of `w` and the check that fp8 weights are complete, on the host before any launch; `fn`: the entry point the message names
@@ -502,47 +502,41 @@ struct Prefill {
   // bit-identical to the two launches, one launch and one pass over the rows less per norm), so only layer 0 normalises l.x itself
   int layer_dtype(int i) const {
     const LayerMats m = layer_mats(w, fmt, i);
-    return layer_bf16_launches(i, [](const Mat& a, int, int, const void** W) {
-      *W = a.w;
-      return (int)SRGPT_OK;
-    }, m);
-  }
-
-  // MXFP4 matrices: each is expanded (srgpt_dequant_mxfp4, exact) into the workspace's one bf16 scratch just before its product, and
-  // the launches are layer_dtype's on the scratch: every byte the prefill writes equals a bf16 engine's on the dequantised weights.
-  // The stream orders product -> next expansion, so one scratch serves the four.  Price: one more pass over bf16-sized bytes per
-  // matrix (include/srgpt.h); a W4 operand inside the GEMM is what is left.
-  int layer_w4a16(int i) const {
-    const LayerMats m = layer_mats(w, fmt, i);
-    return layer_bf16_launches(i, [this](const Mat& a, int N, int K, const void** W) {
-      *W = l.w4;
-      return srgpt_dequant_mxfp4(a.w4, a.scale4, l.w4, N, K, stream);
-    }, m);
-  }
-
-  // the launches of a layer over row-major matrices of the engine dtype; get(mat, N, K, &W) makes matrix `mat` [N, K] available at W
-  // just before the product that reads it
-  template <typename Get>
-  int layer_bf16_launches(int i, Get&& get, const LayerMats& m) const {
-    const void* W = nullptr;
     if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
     // projection + RoPE + cache append: the rotation rides in the split-K reduction
-    SRGPT_TRY(get(m.qkv, QW, Hd, &W));
-    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, W, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
+    SRGPT_TRY(srgpt_gemm_rope_kv_append(l.h, m.qkv.w, l.qkv, Hd, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
                                         w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim, st->max_pos, dt, stream));
     SRGPT_TRY(attention(i));
-    SRGPT_TRY(get(m.o, Hd, HqD, &W));
-    SRGPT_TRY(srgpt_gemm_norm(l.attn, W, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
+    SRGPT_TRY(srgpt_gemm_norm(l.attn, m.o.w, nullptr, l.x, l.x, rows, Hd, HqD, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->mlp_norm[i], nullptr,
                               l.h, w->rms_eps, dt, stream));
     // gate / up + SiLU * up: the activation is the product's epilogue on the whole-M kernel
-    SRGPT_TRY(get(m.gu, 2 * I, Hd, &W));
-    SRGPT_TRY(srgpt_gemm_swiglu(l.h, W, l.act, rows, I, Hd, l.gu, l.gws, gws_bytes(), dt, stream));
-    SRGPT_TRY(get(m.down, Hd, I, &W));
+    SRGPT_TRY(srgpt_gemm_swiglu(l.h, m.gu.w, l.act, rows, I, Hd, l.gu, l.gws, gws_bytes(), dt, stream));
     if (i + 1 < w->layers)
-      return srgpt_gemm_norm(l.act, W, nullptr, l.x, l.x, rows, Hd, I, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->attn_norm[i + 1],
+      return srgpt_gemm_norm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, l.gws, gws_bytes(), SRGPT_NORM_RMS, w->attn_norm[i + 1],
                              nullptr, l.h, w->rms_eps, dt, stream);
-    return srgpt_gemm(l.act, W, nullptr, l.x, l.x, rows, Hd, I, I, Hd, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, l.gws,
+    return srgpt_gemm(l.act, m.down.w, nullptr, l.x, l.x, rows, Hd, I, I, Hd, SRGPT_ACT_NONE, 0, 0, 0, SRGPT_OUT_PLAIN, 0, l.gws,
                       gws_bytes(), dt, stream);
+  }
+
+  // MXFP4 matrices: layer_dtype's sequence through the W4 entry points (include/srgpt.h), which take the route of the bf16 product and
+  // return its bits on the dequantised matrix: every byte the prefill writes equals a bf16 engine's on the dequantised weights.  On the
+  // direct-to-LDS kernels (every product of an append, o_proj of the bs = 1 prefill) the codes are multiplied in the kernel; the
+  // whole-M and 256 x 256 routes still expand each matrix (srgpt_dequant_mxfp4, exact) into the workspace's one bf16 scratch l.w4
+  // just before its product -- the stream orders product -> next expansion, so one scratch serves the four.
+  int layer_w4a16(int i) const {
+    const LayerMats m = layer_mats(w, fmt, i);
+    if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
+    SRGPT_TRY(srgpt_gemm_w4_rope_kv_append(l.h, m.qkv.w4, m.qkv.scale4, l.qkv, Hd, l.w4, l.gws, gws_bytes(), cache(st->kcache, i),
+                                           cache(st->vcache, i), pos0, w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim,
+                                           st->max_pos, stream));
+    SRGPT_TRY(attention(i));
+    SRGPT_TRY(srgpt_gemm_w4_norm(l.attn, m.o.w4, m.o.scale4, l.x, l.x, rows, Hd, HqD, l.w4, l.gws, gws_bytes(), w->mlp_norm[i], l.h,
+                                 w->rms_eps, stream));
+    SRGPT_TRY(srgpt_gemm_w4_swiglu(l.h, m.gu.w4, m.gu.scale4, l.act, rows, I, Hd, l.gu, l.w4, l.gws, gws_bytes(), stream));
+    if (i + 1 < w->layers)
+      return srgpt_gemm_w4_norm(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, l.w4, l.gws, gws_bytes(), w->attn_norm[i + 1], l.h,
+                                w->rms_eps, stream);
+    return srgpt_gemm_w4(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, I, Hd, 0, l.w4, l.gws, gws_bytes(), stream);
   }
 
   int layer_w8a16(int i) const {

@@ -619,6 +619,112 @@ def gemm_rope_kv_append(a, w, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D
     return qkv
 
 
+def _w4_operand(op, a, w4, wscale8, rows=None):
+    """checks of a W4A16 product's operands -> (M, N, K): a [M, K] bf16 (dense), codes [N, K / 2], scales [N, K / 32]."""
+    _dev(a, w4, wscale8)
+    if a.dtype != torch.bfloat16:
+        raise ValueError(f"{op}: a must be bf16")
+    _check_mxfp4(op, w4, wscale8)
+    M, K = a.shape
+    if w4.shape[1] * 2 != K:
+        raise ValueError(f"{op}: a has K = {K}, the codes {w4.shape[1] * 2}")
+    if rows is not None and w4.shape[0] != rows:
+        raise ValueError(f"{op}: the codes have {w4.shape[0]} rows, the product needs {rows}")
+    return M, w4.shape[0], K
+
+
+def _w4_expand(op, expand, in_kernel, N, K, device):
+    """the bf16 scratch [N, K] the codes are expanded into where no kernel multiplies them: the caller's, or a fresh one on the
+    expansion path (None where the codes are multiplied in the kernel: it is neither written nor read there)."""
+    if expand is not None:
+        _dev(expand)
+        if expand.dtype != torch.bfloat16 or not expand.is_contiguous() or expand.numel() < N * K:
+            raise ValueError(f"{op}: expand must be a contiguous bf16 buffer of at least {N} x {K} elements")
+        return expand
+    return None if in_kernel else torch.empty((N, K), device=device, dtype=torch.bfloat16)
+
+
+def gemm_w4_in_kernel(M, N, K, swiglu=False, device=None, ws=None) -> bool:
+    """srgpt_gemm_w4_in_kernel with the split-K workspace this module passes: True when gemm_w4 / gemm_w4_norm /
+    gemm_w4_rope_kv_append of an [M, K] x [N, K] product (gemm_w4_swiglu with N = I) multiply the MXFP4 codes inside the GEMM kernel
+    on this device, False when they expand the codes into the bf16 scratch first."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    ws, ws_bytes = _ws_arg(device, M, 2 * N if swiglu else N, True, ws)
+    return _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes)
+
+
+def _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes) -> bool:
+    return bool(L.load().srgpt_gemm_w4_in_kernel(M, N, K, int(swiglu), int(ws is not None), ws_bytes))
+
+
+def gemm_w4(a, w4, wscale8, residual=None, out=None, out_f32=False, expand=None, ws=None):
+    """a @ dequant(w4, wscale8).T + residual with MXFP4 weights (codes [N, K / 2], E8M0 scales [N, K / 32]): bit for bit
+    gemm(a, dequant_mxfp4(w4, wscale8), residual=...).  a [M, K] bf16 (row stride may exceed K).  expand: the bf16 [N, K] scratch of
+    the expansion path (see gemm_w4_in_kernel; None: allocated when needed).  ws: as for gemm."""
+    M, N, K = _w4_operand("gemm_w4", a, w4, wscale8)
+    _dev(residual)
+    _same_dtype("gemm_w4", a, residual=residual)
+    assert a.stride(1) == 1
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
+    ws, ws_bytes = _ws_arg(a.device, M, N, True, ws)
+    expand = _w4_expand("gemm_w4", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
+    L.check(L.load().srgpt_gemm_w4(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, a.stride(0), out.stride(0),
+                                   int(out_f32), _p(expand), ws, ws_bytes, _stream()))
+    return out
+
+
+def gemm_w4_norm(a, w4, wscale8, residual, norm_w, eps, out=None, y=None, expand=None, ws=None):
+    """(a @ dequant(w4, wscale8).T + residual, rmsnorm(that)): gemm_norm (RMSNorm, no bias) with MXFP4 weights, bit for bit
+    gemm_norm(a, dequant_mxfp4(w4, wscale8), ...).  expand / ws: as for gemm_w4."""
+    M, N, K = _w4_operand("gemm_w4_norm", a, w4, wscale8)
+    _dev(residual, norm_w)
+    _same_dtype("gemm_w4_norm", a, residual=residual, norm_weight=norm_w)
+    assert a.is_contiguous() and (residual is None or residual.is_contiguous())
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=a.dtype)
+    if y is None:
+        y = torch.empty((M, N), device=a.device, dtype=a.dtype)
+    ws, ws_bytes = _ws_arg(a.device, M, N, True, ws)
+    expand = _w4_expand("gemm_w4_norm", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
+    L.check(L.load().srgpt_gemm_w4_norm(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, _p(expand), ws, ws_bytes,
+                                        _p(norm_w), _p(y), float(eps), _stream()))
+    return out, y
+
+
+def gemm_w4_swiglu(a, wgu4, wscale8, out=None, expand=None):
+    """silu(a @ wg.T) * (a @ wu.T) for the stacked MXFP4 matrix [2 I, K]: bit for bit gemm_swiglu(a, dequant_mxfp4(wgu4, wscale8)).
+    expand: the bf16 [2 I, K] scratch of the expansion path (None: allocated when needed)."""
+    M, N2, K = _w4_operand("gemm_w4_swiglu", a, wgu4, wscale8)
+    I = N2 // 2
+    assert N2 == 2 * I and a.is_contiguous()
+    if out is None:
+        out = torch.empty((M, I), device=a.device, dtype=a.dtype)
+    scratch = torch.empty((M, 2 * I), device=a.device, dtype=a.dtype)
+    ws, ws_bytes = _ws_arg(a.device, M, 2 * I, True)
+    expand = _w4_expand("gemm_w4_swiglu", expand, _w4_in_kernel(M, I, K, True, ws, ws_bytes), 2 * I, K, a.device)
+    L.check(L.load().srgpt_gemm_w4_swiglu(_p(a), _p(wgu4), _p(wscale8), _p(out), M, I, K, _p(scratch), _p(expand), ws, ws_bytes,
+                                          _stream()))
+    return out
+
+
+def gemm_w4_rope_kv_append(a, w4, wscale8, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D, pos0=None, qkv=None, expand=None):
+    """gemm_rope_kv_append with MXFP4 weights: bit for bit (qkv and both caches) the bf16 call on dequant_mxfp4(w4, wscale8)."""
+    N = (Hq + 2 * Hkv) * D
+    M, _, K = _w4_operand("gemm_w4_rope_kv_append", a, w4, wscale8, rows=N)
+    _dev(kcache, vcache, cos_tab, sin_tab)
+    assert M == B * T and a.is_contiguous()
+    if qkv is None:
+        qkv = torch.empty((M, N), device=a.device, dtype=a.dtype)
+    ws, ws_bytes = _ws_arg(a.device, M, N, True)
+    expand = _w4_expand("gemm_w4_rope_kv_append", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
+    max_pos = kcache.shape[-2]
+    L.check(L.load().srgpt_gemm_w4_rope_kv_append(_p(a), _p(w4), _p(wscale8), _p(qkv), K, _p(expand), ws, ws_bytes, _p(kcache),
+                                                  _p(vcache), _p(pos0), _p(cos_tab), _p(sin_tab), B, T, Hq, Hkv, D, max_pos,
+                                                  _stream()))
+    return qkv
+
+
 def rope_kv_append(qkv, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D, pos0=None):
     _dev(qkv, kcache, vcache, cos_tab, sin_tab)
     max_pos = kcache.shape[-2]

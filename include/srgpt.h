@@ -272,6 +272,24 @@ int srgpt_gemv_w4p(const void* x, const void* packed, const void* norm_w, float 
 int srgpt_mxfp4_bind(const void* W4, const void* packed, int N, int K, int swiglu);
 int srgpt_mxfp4_unbind(const void* W4);
 int srgpt_mxfp4_bound(const void* W4);
+/* Additions under ABI 9: the WIDE weight pass of the MFMA decode products -- 17 to 32 rows against ONE stream of the weights (opt-in).
+ * srgpt_gemv_rowss and srgpt_gemv_w4p cut a call into passes of 16 rows, the M side of one v_mfma_f32_16x16x32_bf16, and every pass
+ * reads the whole matrix; a wide pass carries a chunk of 17 - 32 rows as two 16-row M tiles that share each weight fragment.
+ * srgpt_gemv_rowss_wide / srgpt_gemv_w4p_wide: the arguments, argument errors and fusions of the 16-row forms.  A call is cut into
+ * chunks of 32 rows and a tail; a tail of 16 rows or fewer runs the 16-row form's launch for its row count (40 rows = 32 + 8), and a
+ * call of 16 rows or fewer IS the 16-row form.  Row r of a wide chunk has, bit for bit, the output (and the published statistics) of a
+ * 16-row pass that holds it: the column split, a wave's K range, the k order, one accumulator per weight tile and M tile, the
+ * wave-ordered reduction and the epilogues do not depend on the row count.  (The 16-row forms on a call of 17 - 31 rows end with a
+ * pass of FEWER than 9 rows, which sums even and odd k steps on two accumulators: those rows differ from the wide entry's in the
+ * last bits -- the reason the option is off by default.)  A product whose wide instance is not built or does not pay keeps passes of 16:
+ * srgpt_gemv_wide_pass_rows(batch, fp8, packed, w4, N, K, norm, swiglu) returns the rows per pass the wide entries take for such a call
+ * (bf16 activations; packed: rows per granule, 0 row-major; w4: packed MXFP4) -- 32, or 16. */
+int srgpt_gemv_rowss_wide(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
+                          const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in,
+                          float* rowss_out, int packed_rows, srgpt_stream_t stream);
+int srgpt_gemv_w4p_wide(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out, int batch,
+                        int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out, srgpt_stream_t stream);
+int srgpt_gemv_wide_pass_rows(int batch, int fp8, int packed, int w4, int N, int K, int norm, int swiglu);
 /* Additions under ABI 9: bf16 weights as LOSSLESS 13-bit codes for the batch-1 decode step -- 0.8125 of the bytes per streamed
  * matrix and bit for bit the results of srgpt_gemv.  Not a quantisation: a bf16 weight is s | e8 | m7, the exponents of a weight row
  * lie within a few dozen values below the row's largest, so a row stores an even base exponent b = max(emax - 31, 1) rounded up to
@@ -674,6 +692,11 @@ typedef struct {
    * 1: prefill quantises each GEMM's input per token (srgpt_quant_rows_e4m3) and multiplies on the fp8 matrix pipe
    * (srgpt_gemm_w8a8); decode and the all-position lm_head stay W8A16.  Needs hidden, inter and heads * head_dim % 128 == 0. */
   int fp8_act;
+  /* ABI 9: rows per weight pass of the decode step's MFMA products.  0 or 16: passes of 16 rows.  32: the wide pass above (the step
+   * calls srgpt_gemv_rowss_wide / srgpt_gemv_w4p_wide) -- a step of 17 - 32 rows reads every weight byte once.  Any other value:
+   * SRGPT_ERR_ARG from every LLM entry point.  The field sits in the four bytes that padded fp8_act in front of the pointer below: no
+   * offset and no size of the struct changed, and a zero-initialised struct is the behaviour before the field. */
+  int decode_pass_rows;
   /* ABI 9: optional PACKED copies (srgpt_pack_decode_weights) of the fp8 layer matrices for the batched decode step (2+ rows per GPU);
    * NULL (array or entry): that product streams the row-major copy.  pk_rows_*: rows per granule of the matrix' packed copies. */
   const void* const* wqkv8p;

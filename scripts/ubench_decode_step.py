@@ -1,7 +1,9 @@
 """decode ms/token of the whole graph-captured step for several (weights, batch) configurations in one process.
   SRGPT_LIB=<path of a libsrgpt_hip*.so build> python scripts/ubench_decode_step.py fp8:8 fp8:4 bf16:4 bf16:1:2048
 (weights:batch[:T] -- T = cached prompt positions, default 259)
-Every line echoes the run's SRGPT_* / UBENCH_* environment (UBENCH_DECODE_LAYOUT = packed / rowmajor: the fp8 decode copies).
+weights = bf16, fp8 or mxfp4 (MXFP4 with the packed, bound copies).
+Every line echoes the run's SRGPT_* / UBENCH_* environment (UBENCH_DECODE_LAYOUT = packed / rowmajor: the fp8 decode copies;
+UBENCH_PASS_ROWS = 16 / 32: the engine's decode_pass_rows, where the library under test has the option).
 A kernel change is A/B'd by running this on two builds of the library (ab_libs_decode_step.sh)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -9,6 +11,10 @@ import torch
 from spatialrgpt_amd import _lib
 if os.environ.get("SRGPT_LIB"):
     _lib.LIB_PATH = os.path.abspath(os.environ["SRGPT_LIB"])
+    import ctypes
+    have = ctypes.CDLL(_lib.LIB_PATH)  # an older build (the parent commit's) lacks the newest entries: the step does not call them
+    for name in [n for n in _lib._SIGNATURES if not hasattr(have, n)]:
+        del _lib._SIGNATURES[name]
 from spatialrgpt_amd.config import SrgptConfig
 from spatialrgpt_amd.engine import SrgptEngine
 from spatialrgpt_amd.weights import synth_state_dict
@@ -21,7 +27,9 @@ rope = max(1024, max(int(t) for _, _, t in wanted) + G + 128)
 for fmt in sorted({w for w, _, _ in wanted}):
     sd = synth_state_dict(cfg, seed=0, dtype=torch.bfloat16, device="cuda")
     eng = SrgptEngine(cfg, sd, device="cuda", dtype=torch.bfloat16, rope_positions=rope, consume_state_dict=True,
-                      llm_weight_format="fp8" if fmt == "fp8" else "native", decode_layout=os.environ.get("UBENCH_DECODE_LAYOUT", "packed"))
+                      llm_weight_format={"fp8": "fp8", "mxfp4": "mxfp4"}.get(fmt, "native"), mxfp4_packed=fmt == "mxfp4",
+                      decode_layout=os.environ.get("UBENCH_DECODE_LAYOUT", "packed"),
+                      **({"decode_pass_rows": int(os.environ["UBENCH_PASS_ROWS"])} if os.environ.get("UBENCH_PASS_ROWS") else {}))
     del sd
     for w, b, t_ in wanted:
         if w != fmt:

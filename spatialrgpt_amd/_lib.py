@@ -45,7 +45,7 @@ class LlmWeights(C.Structure):
         ("lm_head8", vp), ("lm_head_scale", vp),
         ("wqkv8", C.POINTER(vp)), ("wqkv_scale", C.POINTER(vp)), ("wo8", C.POINTER(vp)), ("wo_scale", C.POINTER(vp)),
         ("wgu8", C.POINTER(vp)), ("wgu_scale", C.POINTER(vp)), ("wdown8", C.POINTER(vp)), ("wdown_scale", C.POINTER(vp)),
-        ("fp8_act", i32),
+        ("fp8_act", i32), ("decode_pass_rows", i32),  # (the new int fills fp8_act's padding: no offset moved)
         ("wqkv8p", C.POINTER(vp)), ("wo8p", C.POINTER(vp)), ("wgu8p", C.POINTER(vp)), ("wdown8p", C.POINTER(vp)),
         ("pk_rows_qkv", i32), ("pk_rows_o", i32), ("pk_rows_gu", i32), ("pk_rows_down", i32),
         ("wqkv4", C.POINTER(vp)), ("wqkv4_scale", C.POINTER(vp)), ("wo4", C.POINTER(vp)), ("wo4_scale", C.POINTER(vp)),
@@ -126,6 +126,9 @@ _SIGNATURES = {
     "srgpt_pack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "srgpt_unpack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "srgpt_gemv_w4p": (i32, [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "srgpt_gemv_rowss_wide": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
+    "srgpt_gemv_w4p_wide": (i32, [vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "srgpt_gemv_wide_pass_rows": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
     "srgpt_mxfp4_bind": (i32, [vp, vp, i32, i32, i32]),
     "srgpt_mxfp4_unbind": (i32, [vp]),
     "srgpt_mxfp4_bound": (i32, [vp]),

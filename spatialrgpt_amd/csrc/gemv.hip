@@ -310,7 +310,8 @@ int launch_gemv(GemvFamily family, const DecodeProduct& p, hipStream_t s) {
 
 // The decode products' one way in: every entry point validates its arguments, asks gemv_route.h for its route and comes here.  The
 // route names the kernel family and the rows per weight pass; every pass takes its rows of x, residual, out and both statistics
-// tables.
+// tables.  A wide route (chunk 32, gemv_wide_route): a chunk of 17 - 32 rows is one wide launch, a tail of 16 rows or fewer the
+// 16-row launch of its row count (srgpt_skinny_launch picks by the chunk's rows).
 int srgpt_decode_product(const DecodeProduct& p, const GemvRoute& r, hipStream_t s) {
   const bool bf16 = p.dtype == SRGPT_BF16;
   const size_t es = dtype_size(p.dtype), on = p.out_f32 ? sizeof(float) : es;
@@ -360,9 +361,10 @@ extern "C" int srgpt_gemv_rowss_supported(int batch, int dtype, int fp8) {
   return gemv_rowss_supported(batch, dtype == SRGPT_BF16, fp8 != 0, srgpt_device_cus()) ? 1 : 0;
 }
 
-extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,
-                                float norm_eps, const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
-                                const float* rowss_in, float* rowss_out, int packed_rows, srgpt_stream_t stream) {
+// srgpt_gemv_rowss (pass_rows = 16: gemv_route's own route) and srgpt_gemv_rowss_wide (32: gemv_wide_route's)
+static int gemv_rowss_impl(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w, float norm_eps,
+                           const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in,
+                           float* rowss_out, int packed_rows, int pass_rows, srgpt_stream_t stream) {
   SRGPT_CHECK(x && (W || W8) && out, SRGPT_ERR_ARG, "srgpt_gemv_rowss: null pointer");
   SRGPT_CHECK(packed_rows == 0 || packed_rows == 4 || packed_rows == 8 || packed_rows == 16, SRGPT_ERR_ARG,
               "srgpt_gemv_rowss: packed_rows = %d (0: row-major; 4, 8 or 16 rows per granule)", packed_rows);
@@ -375,5 +377,27 @@ extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, co
               "srgpt_gemv_rowss: %d row(s) of %s weights take a kernel without the statistics hand-off", batch, W8 ? "fp8" : "bf16");
   return srgpt_decode_product(DecodeProduct{x, W8 ? W8 : W, W8 ? wscale : nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu,
                                             out_f32, SRGPT_BF16, W8 != nullptr, rowss_in, rowss_out, packed_rows},
+                              gemv_wide_route(batch, K, W8 != nullptr, packed_rows, false, norm_w != nullptr, swiglu != 0, pass_rows),
                               as_stream(stream));
+}
+
+extern "C" int srgpt_gemv_rowss(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,
+                                float norm_eps, const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
+                                const float* rowss_in, float* rowss_out, int packed_rows, srgpt_stream_t stream) {
+  return gemv_rowss_impl(x, W, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, rowss_in, rowss_out, packed_rows,
+                         16, stream);
+}
+
+// The same product with chunks of 17 - 32 rows in ONE weight pass (gemv_wide_route); 16 rows or fewer: srgpt_gemv_rowss itself
+extern "C" int srgpt_gemv_rowss_wide(const void* x, const void* W, const void* W8, const float* wscale, const void* norm_w,
+                                     float norm_eps, const void* residual, void* out, int batch, int N, int K, int swiglu, int out_f32,
+                                     const float* rowss_in, float* rowss_out, int packed_rows, srgpt_stream_t stream) {
+  return gemv_rowss_impl(x, W, W8, wscale, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, rowss_in, rowss_out, packed_rows,
+                         GEMV_WIDE_ROWS, stream);
+}
+
+// rows per weight pass gemv_wide_route picks for a call of `batch` rows (16 or 32; a VALU route: its chunk), for tests and callers
+extern "C" int srgpt_gemv_wide_pass_rows(int batch, int fp8, int packed, int w4, int N, int K, int norm, int swiglu) {
+  (void)N;
+  return gemv_wide_route(batch, K, fp8 != 0, packed, w4 != 0, norm != 0, swiglu != 0, GEMV_WIDE_ROWS).chunk;
 }

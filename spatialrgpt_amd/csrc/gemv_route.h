@@ -205,6 +205,52 @@ inline GemvRoute gemv_w4_step_route(int rows, bool bound) {
   return GemvRoute{GEMV_W4_MFMA, 16};
 }
 
+// ---- the wide pass (opt-in: srgpt_gemv_rowss_wide, srgpt_gemv_w4p_wide, srgpt_llm_weights::decode_pass_rows = 32): a chunk of 17 - 32
+// rows on the NI = 16 instances of skinny_kernel, two 16-row M tiles against one stream of the weights.  pass_rows: 32 asks for it;
+// anything else, or a call of 16 rows or fewer, is the route above for the same call (w4: the MFMA leg srgpt_gemv_w4p always takes).
+// A call is cut into chunks of 32 and a tail; a tail of 16 rows or fewer takes the 16-row launch of its row count (40 = 32 + 8,
+// 33 = 32 + 1).  This function is the one place that decides which products run wide.
+constexpr int GEMV_WIDE_ROWS = 32;
+// is there a wide instance of skinny_kernel for these weights?  (all but packed bf16: see gemv_wide_route)
+constexpr bool gemv_wide_has_instance(bool fp8, int packed, bool w4) { return fp8 || w4 || packed == 0; }
+
+inline GemvRoute gemv_wide_route(int rows, int K, bool fp8, int packed, bool w4, bool norm, bool swiglu, int pass_rows) {
+  const GemvRoute base = w4 ? gemv_w4_step_route(W4_MFMA_MIN_ROWS, true) : gemv_route(rows, K, true, fp8, norm);
+  if (pass_rows != GEMV_WIDE_ROWS || rows <= 16) return base;
+  if (base.family != GEMV_SKINNY && base.family != GEMV_W4_MFMA) return base;
+  (void)swiglu;
+  // Measured on the MI355X at the 8B geometry (profiles/wide_decode.txt; us per launch at 17 / 32 rows, two 16-row passes -> wide; the
+  // min .. max of a line's calls is under 0.6 us, lm_head under 10): EVERY product of the three engine formats beats its two passes by
+  // more than that spread, so no measured entry keeps a product at 16 --
+  //   bf16 row-major   q/k/v 24.7 -> 15.4 / 28.1 -> 16.0, o 17.2 -> 10.5 / 18.7 -> 11.1, gate/up 74.1 -> 41.4 / 75.2 -> 42.9,
+  //                    down 43.3 -> 26.8 / 46.4 -> 29.3, lm_head 342.9 -> 180.2 / 360.8 -> 189.3
+  //   fp8 packed       q/k/v 16.8 -> 13.8 / 19.0 -> 14.2, o 12.4 -> 8.9 / 13.7 -> 9.2, gate/up 45.7 -> 30.3 / 47.0 -> 31.7,
+  //                    down 26.9 -> 22.5 / 31.6 -> 23.5, lm_head (fp8 row-major) 177.1 -> 124.9 / 200.8 -> 136.5
+  //   MXFP4 packed     q/k/v 15.8 -> 13.4 / 18.6 -> 13.8, o 11.1 -> 8.7 / 12.1 -> 8.8, gate/up 31.4 -> 28.1 / 37.3 -> 28.9,
+  //                    down 22.0 -> 21.4 / 26.4 -> 21.9 (the closest: 21.31 .. 21.58 against 21.84 .. 22.14 at 17 rows)
+  // Products kept at passes of 16 rows, one line per entry with its reason (gemv_wide_has_instance is the launcher's side of it):
+  // bf16 weights in the packed layout: skinny_kernel<false, 16, 8, false, true, true, false> spills 2 VGPRs (12 bytes of scratch), not built
+  if (!gemv_wide_has_instance(fp8, packed, w4)) return base;
+  return GemvRoute{base.family, GEMV_WIDE_ROWS};
+}
+
+// dynamic LDS of a wide block: stages of half a slice -- per wave 32 activation rows and (row-major weights) 16 weight rows of 128 k,
+// padded to 288 bytes.  The reduction buffer holds both M tiles.
+constexpr int GEMV_WIDE_ROW_BYTES = 256 + 32;
+constexpr int gemv_wide_lds(int NW, bool PK) {
+  const int stages = NW * (32 + (PK ? 0 : 16)) * GEMV_WIDE_ROW_BYTES, reduction = NW * 2 * GEMV_SKINNY_SUBUNITS * 64 * 4 * 4;
+  return stages > reduction ? stages : reduction;
+}
+
+// one wide launch: 17 - 32 rows.  NW, cw, the grid and the granule are gemv_skinny_launch's for the same N and norm (they do not depend
+// on the row count), so every row keeps the columns, the K range and the reduction order of its 16-row pass
+inline GemvSkinnyLaunch gemv_wide_launch(int rows, int N, bool norm, bool ss_in, int packed, int cus) {
+  GemvSkinnyLaunch l = gemv_skinny_launch(rows > 16 ? 16 : rows, N, norm, ss_in, packed, cus);
+  l.NI = 16;
+  l.lds = gemv_wide_lds(l.NW, l.PK);
+  return l;
+}
+
 // bytes of the packed array of a [rows_total, K] code matrix (K % W4_CELL_K == 0): per granule and cell 64 code bytes and 4 scale
 // bytes per row
 inline long long gemv_w4p_packed_bytes(long long rows_total, int K) {

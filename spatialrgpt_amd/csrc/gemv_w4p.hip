@@ -96,9 +96,9 @@ extern "C" int srgpt_unpack_mxfp4(const void* packed, void* W4, void* wscale8, i
 
 // srgpt_gemv_rowss's contract over a packed MXFP4 array: srgpt_decode_product's passes of up to 16 rows (gemv_w4_step_route's MFMA
 // leg), every pass with its rows of x, residual, out and both statistics tables
-extern "C" int srgpt_gemv_w4p(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out,
-                              int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out,
-                              srgpt_stream_t stream) {
+static int gemv_w4p_impl(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out,
+                         int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out, int pass_rows,
+                         srgpt_stream_t stream) {
   SRGPT_CHECK(x && packed && out, SRGPT_ERR_ARG, "srgpt_gemv_w4p: null pointer");
   SRGPT_CHECK(batch > 0, SRGPT_ERR_ARG, "srgpt_gemv_w4p: bad shape");
   SRGPT_TRY(check_shape("srgpt_gemv_w4p", N, K, swiglu));
@@ -110,7 +110,22 @@ extern "C" int srgpt_gemv_w4p(const void* x, const void* packed, const void* nor
   // the MFMA leg's route, whatever the call holds
   return srgpt_decode_product(DecodeProduct{x, packed, nullptr, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, SRGPT_BF16,
                                             0, rowss_in, rowss_out, W4_GRANULE_ROWS, 1},
-                              gemv_w4_step_route(W4_MFMA_MIN_ROWS, true), as_stream(stream));
+                              gemv_wide_route(batch, K, false, W4_GRANULE_ROWS, true, norm_w != nullptr, swiglu != 0, pass_rows),
+                              as_stream(stream));
+}
+
+extern "C" int srgpt_gemv_w4p(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out,
+                              int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out,
+                              srgpt_stream_t stream) {
+  return gemv_w4p_impl(x, packed, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, rowss_in, rowss_out, 16, stream);
+}
+
+// The same product with chunks of 17 - 32 rows in ONE weight pass (gemv_wide_route); 16 rows or fewer: srgpt_gemv_w4p itself
+extern "C" int srgpt_gemv_w4p_wide(const void* x, const void* packed, const void* norm_w, float norm_eps, const void* residual, void* out,
+                                   int batch, int N, int K, int swiglu, int out_f32, const float* rowss_in, float* rowss_out,
+                                   srgpt_stream_t stream) {
+  return gemv_w4p_impl(x, packed, norm_w, norm_eps, residual, out, batch, N, K, swiglu, out_f32, rowss_in, rowss_out, GEMV_WIDE_ROWS,
+                       stream);
 }
 
 extern "C" int srgpt_mxfp4_bind(const void* W4, const void* packed, int N, int K, int swiglu) {

@@ -403,6 +403,8 @@ enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8, FMT_W4A16 };
 // the format of `w` and the check that fp8 weights are complete, on the host before any launch; `fn`: the entry point the message names
 int llm_format(const srgpt_llm_weights* w, const char* fn, LlmFormat* fmt) {
   *fmt = FMT_DTYPE;
+  SRGPT_CHECK(w->decode_pass_rows == 0 || w->decode_pass_rows == 16 || w->decode_pass_rows == GEMV_WIDE_ROWS, SRGPT_ERR_ARG,
+              "%s: decode_pass_rows = %d (0 or 16: passes of 16 rows; %d: the wide pass)", fn, w->decode_pass_rows, GEMV_WIDE_ROWS);
   if (w->wqkv4) {
     SRGPT_CHECK(w->dtype == SRGPT_BF16 && w->wo4 && w->wgu4 && w->wdown4 && w->wqkv4_scale && w->wo4_scale && w->wgu4_scale &&
                     w->wdown4_scale && w->lm_head8 && w->lm_head_scale,
@@ -801,16 +803,18 @@ struct DecodeStep {
   // packable: q/k/v, gate/up, down_proj and lm_head; o_proj is not -- the attention launch prefetches its RAW matrix into L2
   int gemv(const Mat& m, const void* x, const void* norm, const void* res, void* out, int N, int K, int swiglu, int f32,
            const float* ss_in, float* ss_out, bool packable = true) const {
+    const bool wide = w->decode_pass_rows == GEMV_WIDE_ROWS;  // srgpt_llm_weights::decode_pass_rows: the wide entries (gemv_wide_route)
     if (m.w4 && w4p) {  // MXFP4 layer matrix on the MFMA leg: its packed copy, with the statistics hand-off of the other formats
       Mxfp4Binding b;
       SRGPT_CHECK(srgpt_mxfp4_lookup(m.w4, N, K, swiglu, &b), SRGPT_ERR_STATE, "decode step: an MXFP4 matrix was unbound while the step was being launched");
-      return srgpt_gemv_w4p(x, b.packed, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out, stream);
+      return (wide ? srgpt_gemv_w4p_wide : srgpt_gemv_w4p)(x, b.packed, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out,
+                                                           stream);
     }
     if (m.w4)  // MXFP4 layer matrix on the VALU kernel, which neither reads nor publishes row statistics (pub is false)
       return srgpt_gemv_w4(x, m.w4, m.scale4, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
     if (pub)  // the MFMA kernel reads the packed copy of the fp8 bytes where there is one
-      return srgpt_gemv_rowss(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, ss_in, ss_out,
-                              m.pk ? m.pk_rows : 0, stream);
+      return (wide ? srgpt_gemv_rowss_wide : srgpt_gemv_rowss)(x, m.w, m.pk ? m.pk : m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K,
+                                                               swiglu, f32, ss_in, ss_out, m.pk ? m.pk_rows : 0, stream);
     if (fp8) return srgpt_gemv_w8(x, m.w8, m.scale, norm, w->rms_eps, res, out, r.rows, N, K, swiglu, f32, stream);
     if (p13 && packable) {  // consulted on the host, at eager launch and at graph capture; srgpt_gemv itself never looks (it is the raw reference)
       Pack13Binding b;

@@ -78,6 +78,14 @@ constexpr int FS_MAX = 4;              // MFMA k steps per fragment batch (8 LDS
 // the way: exact, code * 2^e has one mantissa bit) in front of the MFMA.  Everything that decides a bit -- NI / NW, the K range of a
 // wave, the k of a step, the accumulator a step adds to, the reduction, the epilogues -- is the bf16 instance's: the same bits as
 // that kernel over the dequantised matrix.
+// WIDE (NI == 16, gemv_wide_launch of gemv_route.h): 17 - 32 rows in one weight pass, as TWO 16-row M tiles.  Every k step of a
+// weight tile issues two v_mfma_f32_16x16x32_bf16 that share the weight fragment; each has its own activation fragment and its own
+// accumulator (one per sub-unit and M tile, as in the NI == 8 instance).  NW, cw, the grid, a wave's K range, the k order, the
+// wave-ordered reduction, the statistics and the epilogues are the NI == 8 instance's, so row r of a wide pass has the bits of a
+// 16-row pass that holds it.  A slice of 32 activation rows is 64 registers per lane on its way into LDS, and beside a row-major weight
+// stage the LDS for it is not there either (8 waves: 208 896 B), so a wide stage is HALF a slice: 128 k of 32 activation rows and of the
+// 16 weight rows, staged rows padded to 288 B (72 dwords = 8 mod 64 banks, as 544 B).  A wave walks its 256-wide slices as pairs of such
+// stages, in k order; a row-major wave load is then 4 rows x 256 bytes, a packed stage half the lane loads.
 constexpr int W4_DEPTH = 4;
 template <bool SWIGLU, int NI, int NW, bool W8, bool PUB, bool PK, bool W4>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const bf16_t* __restrict__ x, const void* __restrict__ Wv,
@@ -88,10 +96,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
                                                                           const float* __restrict__ ss_in, float* __restrict__ ss_out,
                                                                           int gr_shift) {
   static_assert(!W4 || (PK && !W8), "MXFP4 weights are read from their packed layout only");
-  constexpr int DEPTH = !W4 || NI == 8 ? STAGE_DEPTH : NI == 4 ? W4_DEPTH - 1 : W4_DEPTH;  // register ring depth of weight stages
-  constexpr int SK = 256;                   // k per wave slice
-  constexpr int XROWB = WROWB;              // bytes per staged activation row
-  constexpr int XL = NI;                    // activation loads per slice: 2 rows x 512 B each
+  constexpr int MT = NI == 16 ? 2 : 1;      // 16-row M tiles per pass
+  constexpr int SK = MT == 2 ? 128 : 256;  // k per stage: a slice, or half of one (wide instances)
+  constexpr int HS = 256 / SK;              // stages per slice
+  // register ring depth of weight stages (half slices: half the bytes in flight -- deeper rings spilled 4 - 83 VGPRs in the wide instances)
+  constexpr int DEPTH = !W4 || NI >= 8 ? STAGE_DEPTH : NI == 4 ? W4_DEPTH - 1 : W4_DEPTH;
+  constexpr int XROWB = 2 * SK + 32;        // bytes per staged row (activations and weights)
+  constexpr int RPL = 512 / SK;             // rows per wave load of a stage
+  constexpr int XL = 2 * NI / RPL;          // activation loads per stage: 2 rows x 512 B each (half slices: 4 rows x 256 B)
+  constexpr int WL = 16 / RPL;              // weight loads per stage (row-major layout)
+  constexpr int WSTGB = 16 * XROWB;         // weight stage per wave (row-major layout)
   constexpr int R = SWIGLU ? 2 : 1;  // weight tiles (sub-units) per 16-column output tile
   constexpr int MAXU = MAXSU / R;
   constexpr int CPT = 16;            // output columns per tile
@@ -101,25 +115,26 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   using WReg = typename std::conditional<W8 && !PK, u32x2, u32x4>::type;  // one weight load per lane
   constexpr int WEB = W8 ? 1 : 2;                                       // bytes per weight element
   constexpr int WEPL = 8;                                               // weight elements per lane-load (row-major layout)
-  constexpr int NWL = W4 ? 3 : PK && W8 ? 4 : 8;                        // registers of a weight stage in lane loads (packed fp8: 64 k
-                                                                        // per load; MXFP4: two cells of codes + one of scale dwords)
+  // registers of a weight stage in lane loads (packed bf16: 32 k per load, packed fp8: 64 k; MXFP4: a cell of codes per 128 k + one
+  // of scale dwords; row-major: WL)
+  constexpr int NWL = W4 ? SK / W4_CELL_K + 1 : PK ? SK / (W8 ? 64 : 32) : WL;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // per wave: [x stage | w stage]; reused for the reduction
-  __shared__ float rs_s[16];
-  __shared__ float ss_s[16][NW / 2];
-  __shared__ float pub_s[NW][4];
+  __shared__ float rs_s[16 * MT];
+  __shared__ float ss_s[16 * MT][NW / 2];
+  __shared__ float pub_s[MT][NW][4];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned char* xst = smem + wave * (XSTAGEB + (PK ? 0 : WSTAGEB));
+  unsigned char* xst = smem + wave * (XSTAGEB + (PK ? 0 : WSTGB));
   unsigned char* wst = xst + XSTAGEB;  // (row-major layout only)
-  const int nsl = (K + SK - 1) / SK;  // K slices; wave w takes w, w + NW, ...
+  const int nsl = (K + 255) / 256;  // 256-wide K slices; a wave takes one contiguous range of them (first_sl below)
   const int c0 = (int)blockIdx.x * cw;                 // first output column of this block
   const int cwb = min(cw, N - c0);                     // its column count (the last block may own fewer)
   const int ntile = (cwb + CPT - 1) / CPT;             // tiles, the last one possibly partial
   const int npass = (ntile + MAXU - 1) / MAXU;
   const bool do_norm = PUB || norm_w != nullptr;  // (published statistics are the RMSNorm's: a compile-time fact for those instances)
-  const int lrow = lane >> 5, lchunk = lane & 31;  // staging loads: lane -> (row parity, 16-byte chunk of the 512-byte row piece)
+  const int lrow = lane >> (SK == 256 ? 5 : 4), lchunk = lane & (SK / 8 - 1);  // staging loads: lane -> (row of the RPL a wave load covers, 16-byte chunk of the row's 2 SK bytes)
   const int xchunk = lchunk;
-  auto xrow_of = [&](int j) { return 2 * j + lrow; };
+  auto xrow_of = [&](int j) { return RPL * j + lrow; };
 
   // activation slice: XL loads covering 2*NI rows x SK k (rows past the batch re-read row B-1: their outputs are never
   // stored), plus the RMSNorm gains of the lane's chunk
@@ -154,7 +169,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
       for (int j = 0; j < XL; ++j) rsr[j] = rs_s[xrow_of(j)];
     }
   };
-  auto stage_x = [&](auto slot_c, int sl, bool valid) {
+  auto stage_x = [&](auto slot_c, int sl, bool valid) __attribute__((always_inline)) {
     constexpr int slot = decltype(slot_c)::value;
     const bool kvalid = valid && sl * SK + xchunk * 8 < K;
 #pragma unroll
@@ -198,9 +213,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   // range and comes back as zeros without a memory access -- no per-load select, and the per-lane part of the address is eight
   // kernel-constant offsets (row 2j + lrow, chunk lchunk) plus one slice offset per stage: 12 VALU per stage where the
   // flat-address form spent 45 (the ISA of round 2's kernel: 126 v_cndmask + 104 shifts / adds per 8 stages).
-  unsigned wrow_off[8];
+  unsigned wrow_off[WL];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) wrow_off[j] = ((unsigned)(2 * j + lrow) * (unsigned)K + (unsigned)lchunk * WEPL) * WEB;
+  for (int j = 0; j < WL; ++j) wrow_off[j] = ((unsigned)(RPL * j + lrow) * (unsigned)K + (unsigned)lchunk * WEPL) * WEB;
   constexpr unsigned W_OUT_OF_RANGE = 0x10000000u;  // > any descriptor range (16 rows x K x 2 bytes), no 32-bit wrap when added
   auto issue_w = [&](WReg* w, int pass, int sl, int su, bool ok) {
     const int cb = c0 + (pass * MAXU + su / R) * CPT;  // first column of the tile
@@ -226,7 +241,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
         w[j] = __builtin_bit_cast(WReg, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(code_off + oj), 0, 2));  // aux 2 = nt
         __builtin_amdgcn_sched_barrier(0);
       }
-      w[2] = WReg{sc[0], sc[1], 0u, 0u};
+      w[SK / W4_CELL_K] = WReg{sc[0], sc[SK / W4_CELL_K - 1], 0u, 0u};  // (one cell per stage: the second dword is unused)
     } else if constexpr (PK) {
       // granule (cb + (su % R) N) / gr of the packed array (tile starts, block widths and the stacked half's row count are multiples
       // of gr; rows past the matrix inside its last granule are zeros in the array).  Lane (c = lane & 15, g = lane >> 4) reads row
@@ -254,7 +269,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
       // slice offset; lanes whose k lies past K (last slice of a K that is no multiple of 256) leave the range too
       const unsigned so = (ok ? (unsigned)(sl * SK) * WEB : W_OUT_OF_RANGE) + (sl * SK + lchunk * WEPL < K ? 0u : W_OUT_OF_RANGE);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
+      for (int j = 0; j < WL; ++j) {
         if constexpr (W8) w[j] = __builtin_bit_cast(WReg, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(wrow_off[j] + so), 0, 2));
         else w[j] = __builtin_bit_cast(WReg, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(wrow_off[j] + so), 0, 2));  // aux 2 = nt
         __builtin_amdgcn_sched_barrier(0);
@@ -282,7 +297,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
     else if constexpr (W4) {
       // k step s: dword s % 4 of cell s / 4, scaled by 2^(byte s % 4 of the cell's scale dword - 127) as the fp32 `byte << 23`
       const unsigned int word = w[s >> 2][s & 3];
-      const float sc = __uint_as_float(((w[2][s >> 2] >> (8 * (s & 3))) & 0xffu) << 23);
+      const float sc = __uint_as_float(((w[SK / W4_CELL_K][s >> 2] >> (8 * (s & 3))) & 0xffu) << 23);
       u32x4 o;
       o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 0));
       o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 1));
@@ -298,8 +313,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   // opened again and again; contiguous ranges stream 5 - 6 % faster at 4 / 8 bf16 rows, 2.5 % at 8 fp8 rows
   // (profiles/r03_skinny_contig.txt).
   const int per_wave = (nsl + NW - 1) / NW, first_sl = wave * per_wave;
-  const int cnt = max(0, min(per_wave, nsl - first_sl));  // slices of this wave: [first_sl, first_sl + cnt)
-  auto sl_of = [&](int i) { return first_sl + i; };
+  const int cnt = HS * max(0, min(per_wave, nsl - first_sl));  // stages of this wave: its slices [first_sl, first_sl + cnt / HS)
+  auto sl_of = [&](int i) { return HS * first_sl + i; };
   load_x(std::integral_constant<int, 0>{}, sl_of(0));
   bool x0_ready = true;  // slot 0 holds (a request for) the first slice of the pass about to start
 
@@ -367,46 +382,55 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
   // wave w owns rows w, w + NW, ...; `between` runs after the loads have been requested (the first weight stage queues behind them)
   auto pub_stats = [&](auto&& between) {
     constexpr int RPW = (2 * NI + NW - 1) / NW;
-    f32x4 sv[RPW][2];
+    constexpr int RG = RPW > 4 ? 4 : RPW;  // rows in flight per wave (a wide pass of a 4-wave block: two groups of 4)
+    static_assert(RPW % RG == 0, "row groups");
 #pragma unroll
-    for (int j = 0; j < RPW; ++j) {
-      const float* p = ss_in + (size_t)min(wave + j * NW, B - 1) * SRGPT_ROWSS_STRIDE + lane * 8;
-      sv[j][0] = *reinterpret_cast<const f32x4*>(p);
-      sv[j][1] = *reinterpret_cast<const f32x4*>(p + 4);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    between();
-    __builtin_amdgcn_sched_barrier(0);
+    for (int j0 = 0; j0 < RPW; j0 += RG) {
+      f32x4 sv[RG][2];
 #pragma unroll
-    for (int j = 0; j < RPW; ++j) {
-      float t = ((sv[j][0][0] + sv[j][0][1]) + (sv[j][0][2] + sv[j][0][3])) + ((sv[j][1][0] + sv[j][1][1]) + (sv[j][1][2] + sv[j][1][3]));
-      t = wave_sum(t);
-      if (lane == 0 && wave + j * NW < 2 * NI) rs_s[wave + j * NW] = rsqrtf(t / (float)K + norm_eps);
+      for (int j = 0; j < RG; ++j) {
+        const float* p = ss_in + (size_t)min(wave + (j0 + j) * NW, B - 1) * SRGPT_ROWSS_STRIDE + lane * 8;
+        sv[j][0] = *reinterpret_cast<const f32x4*>(p);
+        sv[j][1] = *reinterpret_cast<const f32x4*>(p + 4);
+      }
+      if (j0 == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        between();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int j = 0; j < RG; ++j) {
+        float t = ((sv[j][0][0] + sv[j][0][1]) + (sv[j][0][2] + sv[j][0][3])) + ((sv[j][1][0] + sv[j][1][1]) + (sv[j][1][2] + sv[j][1][3]));
+        t = wave_sum(t);
+        if (lane == 0 && wave + (j0 + j) * NW < 2 * NI) rs_s[wave + (j0 + j) * NW] = rsqrtf(t / (float)K + norm_eps);
+      }
     }
     __syncthreads();
   };
   float pub_acc = 0.f;  // ss_out: sum of squares of this thread's output elements (all of one batch row: see the epilogue)
+  float pub_acc1 = 0.f;  // ... in the second M tile of a wide pass
 
   // one pass over K for NSU sub-units
   auto run_pass = [&](auto nsu_c, int pass, int nu) {
     constexpr int NSU = decltype(nsu_c)::value;
     constexpr int NS = SK / 32;           // MFMA k steps per stage
-    constexpr int FS = NI == 8 ? 2 : FS_MAX;  // k steps whose fragments are read together (16 staged rows: fewer, registers)
+    constexpr int FS = NI >= 8 ? 2 : FS_MAX;  // k steps whose fragments are read together (16 staged rows: fewer, registers)
     constexpr bool TWO_ACC = NI < 8;  // even / odd k steps on separate accumulators (16 staged rows: the registers are not there)
     // slots of the activation ring (see load_x): as many slices ahead as the weight ring reaches
     // (fp8 only: with bf16 weights a stage is twice the registers and the 8-row single-tile kernel spills under a second slot --
     //  o / down 9.2 / 22.6 -> 9.9 / 24.4 us at 8 bf16 rows, profiles/r06_skinny_norm_staging.txt)
     // (MXFP4: a stage is 10 registers, the slots are there)
-    constexpr int XS = !W8 && !W4 ? 1 : NSU == 1 ? DEPTH : (NSU == 2 && DEPTH == 4 ? 2 : 1);
+    // (32 staged rows: a slot is 64 registers, one slot)
+    constexpr int XS = (!W8 && !W4) || MT == 2 ? 1 : NSU == 1 ? DEPTH : (NSU == 2 && DEPTH == 4 ? 2 : 1);
     static_assert(DEPTH % XS == 0, "the slot of a slice must be a compile-time function of its place in the trip");
     if (!x0_ready) load_x(std::integral_constant<int, 0>{}, sl_of(0));
     if constexpr (XS > 1) load_x(std::integral_constant<int, 1>{}, sl_of(min(1, max(cnt - 1, 0))));
     if constexpr (XS > 2) load_x(std::integral_constant<int, 2>{}, sl_of(min(2, max(cnt - 1, 0))));
     if constexpr (XS > 3) load_x(std::integral_constant<int, 3>{}, sl_of(min(3, max(cnt - 1, 0))));
     x0_ready = XS == 1;  // a one-slot pass leaves the next pass's first slice requested
-    f32x4 acc[NSU], acc2[TWO_ACC ? NSU : 1];
+    f32x4 acc[NSU * MT], acc2[TWO_ACC ? NSU : 1];  // acc[mt NSU + su]: one accumulator per (sub-unit, M tile)
 #pragma unroll
-    for (int su = 0; su < NSU; ++su) acc[su] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int su = 0; su < NSU * MT; ++su) acc[su] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int su = 0; su < (TWO_ACC ? NSU : 1); ++su) acc2[su] = f32x4{0.f, 0.f, 0.f, 0.f};
     // register ring of DEPTH weight stages with static slot indices (a trip = DEPTH slices x NSU stages, a multiple of
@@ -420,7 +444,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
     constexpr int EIT0 = ((NSU / R) * 256 + NT - 1) / NT;  // epilogue iterations per thread
     constexpr int EIT = EIT0 > 0 ? EIT0 : 1;               // (odd NSU never occurs with SwiGLU; keep the type valid)
     float pre_sc[EIT][RS];
-    unsigned short pre_res[EIT];  // bf16 bits
+    unsigned short pre_res[MT * EIT];  // bf16 bits
     auto load_epilogue_operands = [&]() {
       const bool has_res = !SWIGLU && residual != nullptr;
       const bf16_t* rp = has_res ? residual : x;
@@ -433,6 +457,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
 #pragma unroll
         for (int r = 0; r < RS; ++r) pre_sc[i][r] = W8 ? wscale[n + r * N] : 1.f;
         pre_res[i] = *reinterpret_cast<const unsigned short*>(rp + (has_res ? (size_t)b * N + n : (size_t)0));
+        if constexpr (MT == 2)
+          pre_res[EIT + i] = *reinterpret_cast<const unsigned short*>(rp + (has_res ? (size_t)min(b + 16, B - 1) * N + n : (size_t)0));
       }
     };
     // pass 0: the first weight stage goes out behind the statistics' own loads (in-order return: the reduction waits for its
@@ -473,13 +499,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
             }
             if constexpr (!PK) {
 #pragma unroll
-              for (int j = 0; j < 8; ++j) *reinterpret_cast<u32x4*>(wst + (2 * j + lrow) * WROWB + lchunk * 16) = staged(wb[cur][j]);
+              for (int j = 0; j < WL; ++j) *reinterpret_cast<u32x4*>(wst + (RPL * j + lrow) * XROWB + lchunk * 16) = staged(wb[cur][j]);
             }
             __builtin_amdgcn_wave_barrier();
             // The fragment reads of FS k steps are issued together in front of their MFMAs, which alternate between two
             // accumulators.  Left to the compiler the unrolled loop became read -> wait -> MFMA per k step on ONE accumulator: a
             // full LDS latency per step, ~1.5k cycles per stage and sub-unit -- the kernel was bound by that, not by HBM.
-            const int xrow = lane & (2 * NI - 1);  // rows past the staged ones alias valid rows: their outputs are never stored
+            const int xrow = MT == 2 ? (lane & 15) : lane & (2 * NI - 1);  // rows past the staged ones alias valid rows: their outputs are never stored
             if constexpr (XREUSE) {
               // the activation fragments of the slice are the same for all of its sub-units: read once, kept in registers
               if (su == 0) {
@@ -490,14 +516,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
 #pragma unroll
             for (int s0 = 0; s0 < NS; s0 += FS) {
               bf16x8 xf[FS];
+              bf16x8 xf1[MT == 2 ? FS : 1];  // the second M tile's
               bf16x8 wfr[FS];
 #pragma unroll
               for (int t = 0; t < FS; ++t) {
                 const int s = s0 + t;
                 if constexpr (XREUSE) xf[t] = xall[s];
                 else xf[t] = *reinterpret_cast<const bf16x8*>(xst + xrow * XROWB + (4 * s + (lane >> 4)) * 16);
+                if constexpr (MT == 2) xf1[t] = *reinterpret_cast<const bf16x8*>(xst + (xrow + 16) * XROWB + (4 * s + (lane >> 4)) * 16);
                 if constexpr (PK) wfr[t] = pk_frag(wb[cur], s);
-                else wfr[t] = *reinterpret_cast<const bf16x8*>(wst + (lane & 15) * WROWB + (4 * s + (lane >> 4)) * 16);
+                else wfr[t] = *reinterpret_cast<const bf16x8*>(wst + (lane & 15) * XROWB + (4 * s + (lane >> 4)) * 16);
               }
               __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -506,6 +534,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
                 // D[batch row][weight row] += x[batch row][k] * W[weight row][k]
                 if (TWO_ACC && (t & 1)) acc2[TWO_ACC ? su : 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[t], wf, acc2[TWO_ACC ? su : 0], 0, 0, 0);
                 else acc[su] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[t], wf, acc[su], 0, 0, 0);
+                if constexpr (MT == 2) acc[NSU + su] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf1[t], wf, acc[NSU + su], 0, 0, 0);
               }
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -531,23 +560,32 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
 
     // ---- cross-wave reduction (fixed order) + epilogue ----
     __syncthreads();
-    float* redf = reinterpret_cast<float*>(smem);  // [NW waves][MAXSU][64 lanes][4]
+    float* redf = reinterpret_cast<float*>(smem);  // [NW waves][MT M tiles][MAXSU][64 lanes][4]
 #pragma unroll
-    for (int su = 0; su < NSU; ++su) *reinterpret_cast<f32x4*>(redf + ((wave * MAXSU + su) * 64 + lane) * 4) = TWO_ACC ? acc[su] + acc2[TWO_ACC ? su : 0] : acc[su];
+    for (int su = 0; su < NSU; ++su) *reinterpret_cast<f32x4*>(redf + ((wave * MT * MAXSU + su) * 64 + lane) * 4) = TWO_ACC ? acc[su] + acc2[TWO_ACC ? su : 0] : acc[su];
+    if constexpr (MT == 2) {
+#pragma unroll
+      for (int su = 0; su < NSU; ++su) *reinterpret_cast<f32x4*>(redf + (((wave * MT + 1) * MAXSU + su) * 64 + lane) * 4) = acc[NSU + su];
+    }
     __syncthreads();
+    // (a wide pass: the iterations of M tile 0, rows 0 .. 15, then those of M tile 1)
 #pragma unroll
-    for (int i = 0; i < EIT; ++i) {
+    for (int im = 0; im < MT * EIT; ++im) {
+      const int mt = im / EIT, i = im % EIT;
       const int e = tid + i * NT;
-      if (e >= (NSU / R) * 256) break;
+      if (e >= (NSU / R) * 256) {
+        if constexpr (MT == 1) break;
+        else continue;
+      }
       const int u = e >> 8, l2 = e & 63, q = (e >> 6) & 3;
-      const int b = 4 * (l2 >> 4) + q;
+      const int b = 16 * mt + 4 * (l2 >> 4) + q;
       const int n = c0 + (pass * MAXU + u) * CPT + (l2 & 15);
       float a[RS];
 #pragma unroll
       for (int r = 0; r < RS; ++r) {
         float t = 0.f;
 #pragma unroll
-        for (int wv = 0; wv < NW; ++wv) t += redf[((wv * MAXSU + u * R + r) * 64 + l2) * 4 + q];
+        for (int wv = 0; wv < NW; ++wv) t += redf[(((wv * MT + mt) * MAXSU + u * R + r) * 64 + l2) * 4 + q];
         if (W8) t *= pre_sc[i][r];
         a[r] = t;
       }
@@ -557,8 +595,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
           reinterpret_cast<bf16_t*>(out)[(size_t)b * N + n] = (bf16_t)(rnd<bf16_t>(silu(g)) * up);
         } else {
           float v = rnd<bf16_t>(a[0]);
-          if (residual) v = rnd<bf16_t>(__uint_as_float((unsigned int)pre_res[i] << 16) + v);
-          pub_acc = fmaf(v, v, pub_acc);
+          if (residual) v = rnd<bf16_t>(__uint_as_float((unsigned int)pre_res[mt * EIT + i] << 16) + v);
+          if (MT == 2 && mt == 1) pub_acc1 = fmaf(v, v, pub_acc1);
+          else pub_acc = fmaf(v, v, pub_acc);
           if (out_f32)
             reinterpret_cast<float*>(out)[(size_t)b * N + n] = v;
           else
@@ -592,12 +631,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
       // hold different tiles of the same rows: added in wave order through LDS
       float tot = lanes_sum<16>(pub_acc);
       if constexpr (NW > 4) {
-        if ((lane & 15) == 0) pub_s[wave][lane >> 4] = tot;
+        if ((lane & 15) == 0) pub_s[0][wave][lane >> 4] = tot;
         __syncthreads();
         if (wave < 4) {
           tot = 0.f;
 #pragma unroll
-          for (int wv = 0; wv < NW; wv += 4) tot += pub_s[wave + wv][lane >> 4];
+          for (int wv = 0; wv < NW; wv += 4) tot += pub_s[0][wave + wv][lane >> 4];
         }
       }
       const int b = 4 * (lane >> 4) + wave;
@@ -605,6 +644,23 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_kernel(const 
         float* row = ss_out + (size_t)b * SRGPT_ROWSS_STRIDE;
         row[blockIdx.x] = tot;
         for (int sidx = (int)blockIdx.x + (int)gridDim.x; sidx < SRGPT_ROWSS_STRIDE; sidx += (int)gridDim.x) row[sidx] = 0.f;
+      }
+      if constexpr (MT == 2) {  // the second M tile of a wide pass: rows 16 + ..., the same sums in the same order
+        float tot1 = lanes_sum<16>(pub_acc1);
+        if constexpr (NW > 4) {
+          if ((lane & 15) == 0) pub_s[1][wave][lane >> 4] = tot1;
+          __syncthreads();
+          if (wave < 4) {
+            tot1 = 0.f;
+#pragma unroll
+            for (int wv = 0; wv < NW; wv += 4) tot1 += pub_s[1][wave + wv][lane >> 4];
+          }
+        }
+        if (wave < 4 && (lane & 15) == 0 && b + 16 < B) {
+          float* row = ss_out + (size_t)(b + 16) * SRGPT_ROWSS_STRIDE;
+          row[blockIdx.x] = tot1;
+          for (int sidx = (int)blockIdx.x + (int)gridDim.x; sidx < SRGPT_ROWSS_STRIDE; sidx += (int)gridDim.x) row[sidx] = 0.f;
+        }
       }
     }
   }
@@ -615,7 +671,7 @@ static_assert(GEMV_SKINNY_ROW_BYTES == WROWB && 16 * GEMV_SKINNY_ROW_BYTES == WS
 
 }  // namespace
 
-// One weight pass of up to 16 rows on the MFMA kernel (GEMV_SKINNY of gemv_route.h), entered from srgpt_decode_product (gemv.hip);
+// One weight pass of up to 16 rows (a wide chunk: 17 - 32) on the MFMA kernel (GEMV_SKINNY of gemv_route.h), entered from srgpt_decode_product (gemv.hip);
 // bf16 or fp8 weights.  packed: 0 = row-major W [N][K]; 4 / 8 / 16 = the packed decode layout with granules of that many rows
 // (srgpt_pack_decode_weights); ss_in / ss_out: the rows' statistics tables (see skinny_kernel).  w4 (from srgpt_gemv_w4p,
 // gemv_w4p.hip): W is a packed MXFP4 array (srgpt_pack_mxfp4), packed = its granule rows
@@ -624,18 +680,20 @@ int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s) {
   SRGPT_CHECK(!p.w4 || (packed == W4_GRANULE_ROWS && !p.fp8), SRGPT_ERR_ARG, "skinny: MXFP4 weights come in packed granules of %d rows",
               W4_GRANULE_ROWS);
   SRGPT_CHECK(packed == 0 || packed == 4 || packed == 8 || packed == 16, SRGPT_ERR_ARG, "skinny: packed layout granule %d (0, 4, 8 or 16)", packed);
-  SRGPT_CHECK(p.batch >= 1 && p.batch <= 16, SRGPT_ERR_ARG, "skinny: batch %d outside 1..16", p.batch);
+  SRGPT_CHECK(p.batch >= 1 && p.batch <= GEMV_WIDE_ROWS, SRGPT_ERR_ARG, "skinny: batch %d outside 1..%d", p.batch, GEMV_WIDE_ROWS);
   SRGPT_CHECK(p.K % 8 == 0 && p.K >= 8, SRGPT_ERR_ARG, "skinny: K=%d must be a multiple of 8", p.K);
   SRGPT_CHECK(!p.ss_in || p.norm_w, SRGPT_ERR_ARG, "skinny: published row statistics are the RMSNorm's input (norm_w is NULL)");
   SRGPT_CHECK(!p.ss_out || (!p.swiglu && !p.out_f32), SRGPT_ERR_ARG, "skinny: row statistics are published for plain bf16 outputs only");
-  const GemvSkinnyLaunch l = gemv_skinny_launch(p.batch, p.N, p.norm_w != nullptr, p.ss_in != nullptr, packed, srgpt_device_cus());
+  // 17 - 32 rows: a chunk of gemv_wide_route (the other routes cut a call into passes of 16)
+  const GemvSkinnyLaunch l = p.batch > 16 ? gemv_wide_launch(p.batch, p.N, p.norm_w != nullptr, p.ss_in != nullptr, packed, srgpt_device_cus())
+                                          : gemv_skinny_launch(p.batch, p.N, p.norm_w != nullptr, p.ss_in != nullptr, packed, srgpt_device_cus());
   SRGPT_CHECK(!p.ss_out || l.grid <= SRGPT_ROWSS_STRIDE, SRGPT_ERR_UNSUPPORTED, "skinny: %d blocks do not fit the %d row-statistics slots",
               l.grid, SRGPT_ROWSS_STRIDE);
   SRGPT_CHECK(!packed || (p.K % kblock == 0 && (!p.swiglu || p.N % packed == 0)), SRGPT_ERR_UNSUPPORTED,
               "skinny: the packed weight layout needs K %% %d == 0 (K = %d)%s", kblock, p.K, p.swiglu ? " and whole granules per half" : "");
   const auto flag = [](bool v, const char* what, auto&& f) { return srgpt_switch<false, true>(v, what, f); };
   SRGPT_TRY((flag(p.swiglu != 0, "SWIGLU", [&](auto sw_c) {
-    return srgpt_switch<2, 4, 8>(l.NI, "NI", [&](auto ni_c) {
+    return srgpt_switch<2, 4, 8, 16>(l.NI, "NI", [&](auto ni_c) {
       return srgpt_switch<4, 8>(l.NW, "NW", [&](auto nw_c) {
         return flag(p.fp8 != 0, "W8", [&](auto w8_c) {
           return flag(l.PUB, "PUB", [&](auto pub_c) {
@@ -643,10 +701,14 @@ int srgpt_skinny_launch(const DecodeProduct& p, hipStream_t s) {
               return flag(p.w4 != 0, "W4", [&](auto w4_c) {
                 constexpr int NI = decltype(ni_c)::value, NW = decltype(nw_c)::value;
                 constexpr bool PK = decltype(pk_c)::value, W8 = decltype(w8_c)::value, W4 = decltype(w4_c)::value;
-                static_assert(gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "LDS");
-                static_assert(NW == 8 || 2 * gemv_skinny_lds(NI, NW, PK) <= 160 * 1024, "two 4-wave blocks per CU");
+                constexpr int LDS = NI == 16 ? gemv_wide_lds(NW, PK) : gemv_skinny_lds(NI, NW, PK);
+                static_assert(LDS <= 160 * 1024, "LDS");
+                static_assert(NW == 8 || 2 * LDS <= 160 * 1024, "two 4-wave blocks per CU");
                 if constexpr (W4 && (!PK || W8)) {
                   return (int)SRGPT_ERR_ARG;  // (checked above: MXFP4 weights are packed and not fp8)
+                } else if constexpr (NI == 16 && !gemv_wide_has_instance(W8, PK ? 16 : 0, W4)) {
+                  srgpt_set_error("skinny: no wide instance for these weights (gemv_wide_route keeps them at 16 rows)");
+                  return (int)SRGPT_ERR_UNSUPPORTED;
                 } else {
                   constexpr auto kfn = &skinny_kernel<decltype(sw_c)::value, NI, NW, W8, decltype(pub_c)::value, PK, W4>;
                   return srgpt_launch_dyn_lds<kfn>(l.lds, dim3(l.grid), dim3(64 * NW), (size_t)l.lds, s, (const bf16_t*)p.x, p.W, p.wscale,

@@ -249,7 +249,7 @@ class SplicePlan:
 class SrgptEngine:
     def __init__(self, cfg: SrgptConfig, state_dict: Dict[str, torch.Tensor], device="cuda", dtype=torch.bfloat16,
                  rope_positions: int = 0, consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None,
-                 decode_layout: str = "packed", pack13=None, mxfp4_packed: bool = False):
+                 decode_layout: str = "packed", pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16):
         L.load()  # fail loudly if the HIP extension is missing
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         if self.device.type != "cuda":
@@ -262,15 +262,21 @@ class SrgptEngine:
             raise ValueError(f"Unexpected select feature: {cfg.select_feature}")
         # decode_layout "packed": fp8 LLM weights also get MFMA-operand-order copies for the batched decode step (weights.py)
         # pack13: bf16 weights also get lossless 13-bit copies the batch-1 decode step streams (weights.py; None: its default, True / False, "all" for tests)
+        # decode_pass_rows: 16, or 32 = steps of 17 - 32 rows stream every weight matrix once (weights.py; read-only afterwards)
         # mxfp4_packed: "mxfp4" weights also get packed copies, bound, for the MFMA product of every step of 2+ rows (weights.py; default off)
         self.w = PreparedWeights(cfg, state_dict, self.device, dtype, rope_positions, consume=consume_state_dict,
                                  llm_weight_format=llm_weight_format, parts=parts, decode_layout=decode_layout, pack13=pack13,
-                                 mxfp4_packed=mxfp4_packed)
+                                 mxfp4_packed=mxfp4_packed, decode_pass_rows=decode_pass_rows)
         self._state: Optional[DecodeState] = None
         self._vit_ws: Optional[torch.Tensor] = None
         self.use_graph = True
         # the decode loop runs on its own stream: hipGraph capture is illegal on the legacy default stream
         self.stream = torch.cuda.Stream(device=self.device)
+
+    @property
+    def decode_pass_rows(self) -> int:
+        """rows per weight pass of the decode step's MFMA products (16, or 32: the wide pass); set at construction"""
+        return self.w.decode_pass_rows
 
     # ------------------------------------------------------------------ A1
     def vit(self, images: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:

@@ -323,13 +323,21 @@ def pack13_bound(w_raw) -> bool:
     return bool(L.load().srgpt_pack13_bound(_p(w_raw)))
 
 
+def gemv_wide_pass_rows(batch: int, n: int, k: int, fp8: bool = False, packed_rows: int = 0, w4: bool = False, norm: bool = False,
+                        swiglu: bool = False) -> int:
+    """srgpt_gemv_wide_pass_rows: rows per weight pass the `wide=True` products take for such a call -- 32, or 16 for a product
+    (or a call of 16 rows or fewer) that keeps passes of 16."""
+    return int(L.load().srgpt_gemv_wide_pass_rows(int(batch), int(fp8), int(packed_rows), int(w4), int(n), int(k), int(norm), int(swiglu)))
+
+
 def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False,
-               rowss_in=None, publish=False, packed_rows=0, n_rows=None, table=None):
+               rowss_in=None, publish=False, packed_rows=0, n_rows=None, table=None, wide=False):
     """srgpt_gemv_rowss: the decode product of 2+ bf16 rows as the batched decode step runs it.  `rowss_in`: the statistics
     table of x's rows ([B, 512] fp32, from the call that produced x) replaces the RMSNorm's own reduction; `publish`: also
     return the table of the output rows.  `packed_rows` > 0: w / w8 is the flat packed array of pack_decode_weights (n_rows = the
     matrix' row count, 2 N for SwiGLU).  `table`: with `publish`, the caller's contiguous fp32 [B, 512] tensor to publish into (None: a
-    new one).  Returns out, or (out, table)."""
+    new one).  `wide`: srgpt_gemv_rowss_wide -- chunks of 17 - 32 rows in one weight pass (every row the bits of a 16-row pass holding it).
+    Returns out, or (out, table)."""
     wt = w8 if w8 is not None else w
     _dev(x, wt, wscale, norm_w, residual, rowss_in)
     _same_dtype("gemv_rowss", x, norm_weight=norm_w, residual=residual)
@@ -354,9 +362,9 @@ def gemv_rowss(x, w=None, w8=None, wscale=None, norm_w=None, eps=0.0, residual=N
     if rowss_in is not None and (rowss_in.dtype != torch.float32 or tuple(rowss_in.shape) != (B, L.ROWSS_STRIDE)
                                  or not rowss_in.is_contiguous()):
         raise ValueError("gemv_rowss: rowss_in must be a contiguous fp32 [batch, 512] table")
-    L.check(L.load().srgpt_gemv_rowss(_p(_c(x)), _p(w) if w8 is None else None, _p(w8), _p(wscale), _p(norm_w), float(eps),
-                                      _p(residual), _p(out), B, N, K, int(swiglu), int(out_f32), _p(rowss_in), _p(table),
-                                      int(packed_rows), _stream()))
+    fn = L.load().srgpt_gemv_rowss_wide if wide else L.load().srgpt_gemv_rowss
+    L.check(fn(_p(_c(x)), _p(w) if w8 is None else None, _p(w8), _p(wscale), _p(norm_w), float(eps),
+               _p(residual), _p(out), B, N, K, int(swiglu), int(out_f32), _p(rowss_in), _p(table), int(packed_rows), _stream()))
     return (out, table) if publish else out
 
 
@@ -406,10 +414,10 @@ def unpack_mxfp4(packed, n: int, k: int, swiglu: bool = False, out=None):
 
 
 def gemv_w4p(x, packed, n_rows: int, norm_w=None, eps=0.0, residual=None, swiglu=False, out=None, out_f32=False, rowss_in=None,
-             publish=False, table=None):
+             publish=False, table=None, wide=False):
     """srgpt_gemv_w4p: gemv_rowss's product over the packed copy (pack_mxfp4) of an MXFP4 matrix of `n_rows` rows (2 N for SwiGLU),
     any batch >= 1, on the MFMA kernel; bit for bit gemv_rowss(x, w=dequant_mxfp4(codes, scales), ...).  rowss_in / publish / table
-    as for gemv_rowss.  Returns out, or (out, table)."""
+    as for gemv_rowss; `wide`: srgpt_gemv_w4p_wide.  Returns out, or (out, table)."""
     _dev(x, packed, norm_w, residual, rowss_in)
     _same_dtype("gemv_w4p", x, norm_weight=norm_w, residual=residual)
     if x.dtype != torch.bfloat16 or packed.dtype != torch.uint8 or not packed.is_contiguous():
@@ -430,8 +438,9 @@ def gemv_w4p(x, packed, n_rows: int, norm_w=None, eps=0.0, residual=None, swiglu
     if rowss_in is not None and (rowss_in.dtype != torch.float32 or tuple(rowss_in.shape) != (B, L.ROWSS_STRIDE)
                                  or not rowss_in.is_contiguous()):
         raise ValueError("gemv_w4p: rowss_in must be a contiguous fp32 [batch, 512] table")
-    L.check(L.load().srgpt_gemv_w4p(_p(_c(x)), _p(packed), _p(norm_w), float(eps), _p(residual), _p(out), B, N, K, int(swiglu),
-                                    int(out_f32), _p(rowss_in), _p(table), _stream()))
+    fn = L.load().srgpt_gemv_w4p_wide if wide else L.load().srgpt_gemv_w4p
+    L.check(fn(_p(_c(x)), _p(packed), _p(norm_w), float(eps), _p(residual), _p(out), B, N, K, int(swiglu), int(out_f32), _p(rowss_in),
+               _p(table), _stream()))
     return (out, table) if publish else out
 
 

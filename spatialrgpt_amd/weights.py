@@ -59,7 +59,7 @@ class PreparedWeights:
 
     def __init__(self, cfg: SrgptConfig, sd: Dict[str, torch.Tensor], device, dtype, rope_positions: int = 0,
                  consume: bool = False, llm_weight_format: str = "native", parts=None, decode_layout: str = "packed",
-                 pack13=None, mxfp4_packed: bool = False):
+                 pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16):
         """llm_weight_format: "native" (the engine dtype) or "fp8" -- weight-only OCP e4m3fn quantisation of the five
         streamed LLM matrices with one fp32 (power-of-two) scale per output row (BASELINE config 5; bf16 engines only).  The
         fp8 bytes are the ONLY copy of those matrices in HBM: decode streams them (srgpt_gemv_w8), prefill multiplies them
@@ -83,7 +83,14 @@ class PreparedWeights:
         batches, lookup steps, their graphs -- runs the MFMA product srgpt_gemv_w4p instead of passes of the 4-row VALU kernel.  All
         four matrices of all layers, or none where a shape is outside the layout's domain (K % 128 == 0, inter % 16 == 0):
         `self.mxfp4_packed` reports the outcome.  The row-major codes stay (the one-row kernel and the prefill expansion read them),
-        so the copies are additional HBM: 0.53125 bytes per weight, +3.7 GB for the 8B model (mxfp4_packed_bytes())."""
+        so the copies are additional HBM: 0.53125 bytes per weight, +3.7 GB for the 8B model (mxfp4_packed_bytes()).
+        decode_pass_rows (16 or 32; default 16): rows per weight pass of the decode step's MFMA products.  32: a step of 17 - 32 rows
+        streams every matrix once instead of twice (srgpt_gemv_rowss_wide / srgpt_gemv_w4p_wide) for the products gemv_route.h's
+        gemv_wide_route runs wide; rows 16 and up of a step of 17 - 31 rows then differ in the last bits from the default's (there
+        they are a pass of fewer than 9 rows, which sums on two accumulators).  Fixed at construction: captured graphs hold launches."""
+        if decode_pass_rows not in (16, 32) or isinstance(decode_pass_rows, bool):
+            raise ValueError(f"decode_pass_rows must be 16 or 32, got {decode_pass_rows!r}")
+        self._decode_pass_rows = int(decode_pass_rows)
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         # parts: which components to materialise -- all of them for the model, ONE for the module-level factories
         # (spatialrgpt_amd/factories.py: the reference's build_vision_tower / build_mm_projector / build_region_extractor /
@@ -315,6 +322,7 @@ class PreparedWeights:
                 setattr(lw, k + "4", a4)
                 setattr(lw, k + "4_scale", asc)
         lw.fp8_act = 1 if self.fp8_act else 0
+        lw.decode_pass_rows = self._decode_pass_rows
         self.llm = lw
         self.vocab = self.embed.shape[0]
         if self.pack13_mode and llm_weight_format == "native" and dtype == torch.bfloat16:
@@ -389,6 +397,10 @@ class PreparedWeights:
     def mxfp4_packed_bytes(self) -> int:
         """HBM the packed MXFP4 copies take, on top of the row-major codes and scales"""
         return sum(packed.numel() for ents in self.p4.values() for _, packed in ents)
+
+    @property
+    def decode_pass_rows(self) -> int:
+        return self._decode_pass_rows
 
     def pack13_bytes(self) -> int:
         """HBM the packed copies and their flags take, on top of the raw matrices"""

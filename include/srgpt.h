@@ -236,6 +236,29 @@ int srgpt_gemm_w4_rope_kv_append(const void* A, const void* W4, const void* wsca
                                  int64_t ws_bytes, void* kcache, void* vcache, const int* pos0, const void* cos_tab,
                                  const void* sin_tab, int B, int T, int Hq, int Hkv, int D, int max_pos, srgpt_stream_t stream);
 int srgpt_gemm_w4_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes);
+/* Additions under ABI 9: the `_direct` forms of those four (opt-in) -- the whole-M kernel multiplies the codes too.  Each has the
+ * signature, the argument errors, the route and the bits of its plain counterpart above (equal to the bf16 counterpart on
+ * srgpt_dequant_mxfp4 of the codes, scale-byte domain 2 .. 252; no byte outside the code and scale arrays is read).  They differ in
+ * WHERE the codes are expanded: in the kernel wherever the plain entry does so, and also on the whole-M kernel (q/k/v, gate/up and
+ * down_proj of a 225 .. 272-row prefill; the fused SwiGLU form included) when K % 64 == 0, there are at least 4 K tiles and the scale
+ * bytes of a block's K range (128 rows x 2 bytes per K tile of the block's split) fit the LDS the three stages leave: at most 181
+ * K tiles per block.  There the code tile is DMA'd to LDS as bytes (4 KiB instead of 16 per K tile) and the dequantised matrix is
+ * neither written nor read.  The 256 x 256 tiles, K % 64 == 32 and a range that does not fit still expand.
+ * srgpt_gemm_w4_direct_in_kernel (host only; N = I with swiglu) answers for these entries what srgpt_gemm_w4_in_kernel answers for
+ * the plain ones: 1 -- `expand` is neither written nor read and may be NULL; 0 -- the call IS the plain entry's expansion path, and
+ * a NULL `expand` is SRGPT_ERR_ARG before any launch. */
+int srgpt_gemm_w4_direct(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
+                         int lda, int ldc, int out_f32, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream);
+int srgpt_gemm_w4_norm_direct(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
+                              void* expand, void* ws, int64_t ws_bytes, const void* norm_w, void* Y, float norm_eps,
+                              srgpt_stream_t stream);
+int srgpt_gemm_w4_swiglu_direct(const void* A, const void* Wgu4, const void* wscale8, void* out, int M, int I, int K,
+                                void* gu_scratch, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream);
+int srgpt_gemm_w4_rope_kv_append_direct(const void* A, const void* W4, const void* wscale8, void* qkv, int K, void* expand, void* ws,
+                                        int64_t ws_bytes, void* kcache, void* vcache, const int* pos0, const void* cos_tab,
+                                        const void* sin_tab, int B, int T, int Hq, int Hkv, int D, int max_pos,
+                                        srgpt_stream_t stream);
+int srgpt_gemm_w4_direct_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes);
 /* Additions under ABI 9: the PACKED MXFP4 decode layout and the MFMA product over it, for 2+ rows per weight pass (W4A16: bf16
  * activations; the codes are widened to bf16 in registers with the block scale applied, v_cvt_scalef32_pk_bf16_fp4, exactly, and fed
  * to the bf16 MFMA of srgpt_gemv_rowss).  srgpt_gemv_w4 stays the format's raw reference; this is an opt-in second copy of a matrix.
@@ -663,6 +686,12 @@ int srgpt_mask_pad_resize(const void* src_u8, int K, int H, int W, const int* hb
 typedef struct {
   int dtype, hidden, inter, layers, heads, kv_heads, head_dim, vocab;
   float rms_eps;
+  /* ABI 9: MXFP4 weights only (wqkv4 below).  0: srgpt_llm_prefill, _ragged and _append run the plain srgpt_gemm_w4 entries.  1: they
+   * run the `_direct` entries -- q/k/v, gate/up and down_proj of a 225 .. 272-row prefill multiply the codes in the whole-M kernel, no
+   * bf16 expansion; every byte written is the same.  Any other value, or 1 without wqkv4: SRGPT_ERR_ARG from every LLM entry point.
+   * The field sits in the four bytes that padded rms_eps in front of the pointer below: no offset and no size of the struct changed,
+   * and a zero-initialised struct is the behaviour before the field. */
+  int mxfp4_direct;
   const void* rope_cos;    /* [max_pos, head_dim/2] (see srgpt_rope_kv_append) */
   const void* rope_sin;
   const void* embed;       /* [vocab, hidden] */

@@ -28,6 +28,13 @@ default mxfp4 engine and fp8, three engines in one process:
 parent commit's checkout in alternating fresh processes: a change of the mxfp4 lines counts when it clears the min .. max of one
 process's calls, and the bf16 / fp8 lines and the decode steps have to stay inside it.
 
+--only whole_m  (-> profiles/mxfp4_whole_m.txt) --only prefill's lines with a fourth engine, "mxfp4 direct" (mxfp4_prefill_direct=True:
+the whole-M kernel multiplies the codes of q/k/v, gate/up and down_proj itself), where the timed tree has the option; then those
+three products alone at `rows` rows, one launch per layer (32 different matrices) in a captured graph, us per launch: the W4 instance
+(direct=True), the expansion plus the bf16 launch (the plain entry) and the bf16 launch alone (the bf16 engine's matrix).  Same
+protocol as --only prefill: this tree and, with --tree, the parent commit's checkout (three engines, no products section) in
+alternating fresh processes of one job.
+
 --only steps: the bf16 and fp8 steps alone -- what a tree without the format has; --tree DIR imports the package from another
 checkout (the parent commit), so the same lines can be taken on both in turn.  --only products: the fp8 and mxfp4 steps and the
 products section alone (how a build with another W4_UNIT_COLS in csrc/gemv_route.h was compared)."""
@@ -99,11 +106,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--per-block", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed", "prefill"])
+    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed", "prefill", "whole_m"])
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", {"packed": "mxfp4_mfma.txt", "prefill": "mxfp4_prefill.txt"}.get(args.only, "mxfp4.txt"))
+        args.out = os.path.join(ROOT, "profiles", {"packed": "mxfp4_mfma.txt", "prefill": "mxfp4_prefill.txt", "whole_m": "mxfp4_whole_m.txt"}.get(args.only, "mxfp4.txt"))
     sys.path.insert(0, os.path.abspath(args.tree))
     sys.path.insert(1, ROOT)
     assert torch.cuda.is_available(), "a timing needs the MI355X"
@@ -116,14 +123,18 @@ def main():
     cfg = bench.make_cfg("vila15_8b")
     lib = L.load()
     have4 = hasattr(lib, "srgpt_gemv_w4")
-    formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only in ("all", "prefill") else [])
-    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed"}
+    have_direct = hasattr(lib, "srgpt_gemm_w4_direct")  # (the parent commit's tree has neither the entries nor the engine's option)
+    formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only in ("all", "prefill", "whole_m") else [])
+    if args.only == "whole_m" and have_direct:
+        formats.append("mxfp4d")
+    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed", "mxfp4d": "mxfp4 direct"}
     eng, held = {}, {}
     for f in formats:
         torch.cuda.synchronize()
         before = torch.cuda.memory_allocated()
         sd = synth_state_dict(cfg, seed=0, dtype=dt, device=dev)
-        kw = dict(llm_weight_format="mxfp4", mxfp4_packed=True) if f == "mxfp4p" else dict(llm_weight_format=f)
+        kw = dict(llm_weight_format="mxfp4", mxfp4_packed=True) if f == "mxfp4p" else \
+            dict(llm_weight_format="mxfp4", mxfp4_prefill_direct=True) if f == "mxfp4d" else dict(llm_weight_format=f)
         eng[f] = SrgptEngine(cfg, sd, device=dev, dtype=dt, rope_positions=1024, consume_state_dict=True, **kw)
         del sd
         torch.cuda.synchronize()
@@ -292,12 +303,12 @@ def main():
                         mid(reps["mxfp4"]) / mid(reps["fp8"])))
         say()
 
-    if args.only in ("all", "prefill") and have4:
+    if args.only in ("all", "prefill", "whole_m") and have4:
         # ---- prefill and append
         x = (torch.randn((1, args.rows + 32, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
         head, tail = x[:, :args.rows].contiguous(), x[:, args.rows:].contiguous()
         lines_p, lines_a = {}, {}
-        for f in (formats if args.only == "prefill" else ("fp8", "mxfp4")):
+        for f in (formats if args.only in ("prefill", "whole_m") else ("fp8", "mxfp4")):
             e = eng[f]
             st = e.new_state(1, 512, 4)
             keep.append(st)
@@ -319,6 +330,48 @@ def main():
             lines_a[name[f]] = (append, back, e.stream)
         report("%d-row prefill, eager" % args.rows, interleaved(lines_p, args), "fp8")
         report("32-row append over %d cached rows, eager" % args.rows, interleaved(lines_a, args), "fp8")
+
+    if args.only == "whole_m" and have_direct:
+        # ---- the three whole-M products alone: codes in the kernel, expansion + bf16 launch, bf16 launch alone
+        w4, wn = eng["mxfp4"].w, eng["native"].w
+        Hd, I, QW, M = cfg.hidden, cfg.inter, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim, args.rows
+        shapes = {"q/k/v   [%d, %d]" % (QW, Hd): ("wqkv", QW, Hd, False, False),
+                  "gate/up [2 x %d, %d] SwiGLU" % (I, Hd): ("wgu", I, Hd, False, True),
+                  "down    [%d, %d] residual" % (Hd, I): ("wdown", Hd, I, True, False)}
+        say("the whole-M products alone at %d rows, one launch per layer (%d matrices) in a captured graph: us per launch, median "
+            "(min .. max of all calls)" % (M, cfg.layers))
+        with torch.cuda.stream(shared):
+            for title, (k, N, K, res, sw) in shapes.items():
+                x = (torch.randn((M, K), device=dev, generator=g) * 0.5).to(dt)
+                r = (torch.randn((M, N), device=dev, generator=g) * 0.5).to(dt) if res else None
+                out = torch.empty((M, N), device=dev, dtype=dt)
+                expand = torch.empty(((2 * N if sw else N), K), device=dev, dtype=dt)
+                assert ops.gemm_w4_in_kernel(M, N, K, swiglu=sw, direct=True) and not ops.gemm_w4_in_kernel(M, N, K, swiglu=sw)
+
+                def launches(fmt):
+                    for i in range(cfg.layers):
+                        c, s = w4.llm_q4[k][0][i], w4.llm_q4[k][1][i]
+                        if fmt == "bf16":
+                            ops.gemm_swiglu(x, wn.llm_t[k][i], out=out) if sw else ops.gemm(x, wn.llm_t[k][i], residual=r, out=out)
+                        elif sw:
+                            ops.gemm_w4_swiglu(x, c, s, out=out, expand=expand, direct=fmt == "w4")
+                        else:
+                            ops.gemm_w4(x, c, s, residual=r, out=out, expand=expand, direct=fmt == "w4")
+
+                lines = {}
+                for fmt in ("w4", "expand", "bf16"):
+                    launches(fmt)  # first use of an instance outside the capture
+                    torch.cuda.synchronize()
+                    gr = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gr, stream=shared):
+                        launches(fmt)
+                    lines[fmt] = (gr.replay, None, shared)
+                reps = interleaved(lines, args)
+                us = lambda f: "%7.2f (%7.2f .. %7.2f)" % (mid(reps[f]) * 1e3 / cfg.layers, min(map(min, reps[f])) * 1e3 / cfg.layers,
+                                                         max(map(max, reps[f])) * 1e3 / cfg.layers)
+                say("  %-34s W4 instance %s   expansion + bf16 %s   bf16 alone %s   W4 / expansion %.3f   W4 / bf16 %.3f" % (
+                    title, us("w4"), us("expand"), us("bf16"), mid(reps["w4"]) / mid(reps["expand"]), mid(reps["w4"]) / mid(reps["bf16"])))
+        say()
 
     say("llm_weight_bytes() (streamed per decoded token at batch 1):")
     base = eng[formats[0]].w.llm_weight_bytes()

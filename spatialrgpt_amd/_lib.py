@@ -39,6 +39,7 @@ class LlmWeights(C.Structure):
     _fields_ = [
         ("dtype", i32), ("hidden", i32), ("inter", i32), ("layers", i32), ("heads", i32), ("kv_heads", i32),
         ("head_dim", i32), ("vocab", i32), ("rms_eps", f32),
+        ("mxfp4_direct", i32),  # (fills rms_eps's padding in front of the pointer: no offset moved)
         ("rope_cos", vp), ("rope_sin", vp), ("embed", vp), ("final_norm", vp), ("lm_head", vp),
         ("attn_norm", C.POINTER(vp)), ("wqkv", C.POINTER(vp)), ("wo", C.POINTER(vp)),
         ("mlp_norm", C.POINTER(vp)), ("wgu", C.POINTER(vp)), ("wdown", C.POINTER(vp)),
@@ -122,6 +123,12 @@ _SIGNATURES = {
     "srgpt_gemm_w4_swiglu": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
     "srgpt_gemm_w4_rope_kv_append": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemm_w4_in_kernel": (i32, [i32, i32, i32, i32, i32, i64]),
+    "srgpt_gemm_w4_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
+    "srgpt_gemm_w4_norm_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, f32, vp]),
+    "srgpt_gemm_w4_swiglu_direct": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
+    "srgpt_gemm_w4_rope_kv_append_direct": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32,
+                                                  vp]),
+    "srgpt_gemm_w4_direct_in_kernel": (i32, [i32, i32, i32, i32, i32, i64]),
     "srgpt_mxfp4_packed_bytes": (C.c_size_t, [i32, i32, i32]),
     "srgpt_pack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "srgpt_unpack_mxfp4": (i32, [vp, vp, vp, i32, i32, i32, vp]),

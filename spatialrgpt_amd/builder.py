@@ -236,7 +236,7 @@ def load_image_processor(model_path: str, cfg: SrgptConfig, tower_dir: str = Non
 
 
 def load_model(model_path, device="cuda", dtype=torch.bfloat16, llm_weight_format="native", vision_resolution=-1,
-               interpolate_mode="linear", mxfp4_packed=False, decode_pass_rows=16):
+               interpolate_mode="linear", mxfp4_packed=False, decode_pass_rows=16, mxfp4_prefill_direct=False):
     """-> (tokenizer, LlavaLlamaModel, image_processor): everything `load_pretrained_model` and the HF-registry entry points
     (`AutoModel.from_pretrained`, `LlavaLlamaModel(config=...)`) share."""
     from .model import LlavaLlamaModel
@@ -246,13 +246,13 @@ def load_model(model_path, device="cuda", dtype=torch.bfloat16, llm_weight_forma
     image_processor = load_image_processor(model_path, cfg)
     model = LlavaLlamaModel(cfg, sd, device=device, dtype=dtype, tokenizer=tokenizer, image_processor=image_processor,
                             consume_state_dict=True, llm_weight_format=llm_weight_format, mxfp4_packed=mxfp4_packed,
-                            decode_pass_rows=decode_pass_rows)
+                            decode_pass_rows=decode_pass_rows, mxfp4_prefill_direct=mxfp4_prefill_direct)
     return tokenizer, model, image_processor
 
 
 def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", dtype=torch.bfloat16, prefix_reuse=False, lookup_sampling=False,
-                          lookup_batch=False, mxfp4_packed=False, decode_pass_rows=16, **kwargs):
+                          lookup_batch=False, mxfp4_packed=False, decode_pass_rows=16, mxfp4_prefill_direct=False, **kwargs):
     if load_4bit:
         raise NotImplementedError("bitsandbytes 4-bit loading is out of scope (builder.py:40-60); the engine's own 4-bit option is "
                                   "llm_weight_format=\"mxfp4\" (INTEGRATION.md)")
@@ -265,7 +265,9 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
                                                    vision_resolution=kwargs.pop("vision_resolution", -1),
                                                    interpolate_mode=kwargs.pop("interpolate_mode", "linear"),
                                                    mxfp4_packed=mxfp4_packed,  # opt-in under "mxfp4": packed copies for 2+ row steps
-                                                   decode_pass_rows=decode_pass_rows)  # 32: steps of 17 - 32 rows in one weight pass
+                                                   decode_pass_rows=decode_pass_rows,  # 32: steps of 17 - 32 rows in one weight pass
+                                                   # opt-in under "mxfp4": the whole-M prefill kernel multiplies the codes itself
+                                                   mxfp4_prefill_direct=mxfp4_prefill_direct)
     model.prefix_reuse = bool(prefix_reuse)  # opt-in: unchanged callers continue the last request's cache (spatialrgpt_amd/reuse.py)
     model.lookup_sampling = bool(lookup_sampling)  # opt-in: sampled requests with prompt_lookup_num_tokens run sampled lookup steps
     model.lookup_batch = bool(lookup_batch)  # opt-in: greedy batches with prompt_lookup_num_tokens run batched lookup steps

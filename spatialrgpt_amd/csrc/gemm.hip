@@ -627,6 +627,7 @@ struct WOperand {
   const void* w;       // the matrix, or the codes [N, K / 2]
   const void* scale8;  // NULL: `w` is a matrix of the dtype; else the block scales [N, K / 32]
   void* expand;        // codes only: written and read on the expansion path alone, may be NULL otherwise
+  bool direct;         // codes only: the `_direct` entry points -- the whole-M kernel multiplies the codes too (gemm_w4_direct_in_kernel)
 };
 
 // the codes' checks, and their expansion where `in_kernel` is false: afterwards *W is what the bf16 launch reads
@@ -643,8 +644,8 @@ static int w4_resolve(const char* fn, const WOperand& w, int N, int K, int dtype
 }
 
 // C = epilogue(A W^T) for the entry points below: validate, pick the route (gemm_route.h), launch its kernel, reduce the slabs.
-// Codes take the route of the bf16 product and are multiplied in its kernel where gemm_w4_in_kernel says so; everywhere else they
-// are expanded and the launches are the bf16 ones.  *fused: see srgpt_splitk_finish.
+// Codes take the route of the bf16 product and are multiplied in its kernel where gemm_w4_in_kernel (a `direct` operand:
+// gemm_w4_direct_in_kernel) says so; everywhere else they are expanded and the launches are the bf16 ones.  *fused: see srgpt_splitk_finish.
 static int gemm_run(const void* A, const WOperand& w, int K, int lda, int dtype, void* ws, int64_t ws_bytes, Epilogue e,
                     srgpt_stream_t stream, bool* fused) {
   const int M = e.M, N = e.N;
@@ -664,7 +665,7 @@ static int gemm_run(const void* A, const WOperand& w, int K, int lda, int dtype,
   }
   hipStream_t s = as_stream(stream);
   const GemmRoute r = dtype == SRGPT_F32 ? gemm_route_f32() : gemm_route(M, N, K, srgpt_device_cus(), ws != nullptr, ws_bytes);
-  const bool codes = w4 && gemm_w4_in_kernel(r, K);  // the kernel reads the codes
+  const bool codes = w4 && (w.direct ? gemm_w4_direct_in_kernel(r, K) : gemm_w4_in_kernel(r, K));  // the kernel reads the codes
   const void* W = w.w;
   if (w4) SRGPT_TRY(w4_resolve("srgpt_gemm_w4", w, N, K, dtype, codes, stream, &W));
   srgpt_splitk_apply(e, r, ws);
@@ -673,7 +674,10 @@ static int gemm_run(const void* A, const WOperand& w, int K, int lda, int dtype,
       hipLaunchKernelGGL(gemm_f32_simple, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, s, (const float*)A, (const float*)W, K, lda, e);
       SRGPT_LAUNCH_CHECK();
       break;
-    case GEMM_WHOLE_M_288: SRGPT_TRY(srgpt_gemm288_launch(A, W, K, lda, e, s)); break;
+    case GEMM_WHOLE_M_288:
+      if (codes) SRGPT_TRY(srgpt_gemm288_w4_launch(A, W, w.scale8, K, lda, e, s));
+      else SRGPT_TRY(srgpt_gemm288_launch(A, W, K, lda, e, s));
+      break;
     case GEMM_TILE_256: SRGPT_TRY(srgpt_gemm256_launch(A, W, K, lda, e, s)); break;
     case GEMM_GLDS: {
       const dim3 grid(cdiv(N, 128), cdiv(M, r.bm), e.splits);
@@ -712,12 +716,22 @@ static int w4_args(const char* fn, const void* W4, const void* wscale8) {
   return SRGPT_OK;
 }
 
+// Each W4 entry point and its `_direct` form (include/srgpt.h) are one call with WOperand::direct off / on.
 extern "C" int srgpt_gemm_w4(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N, int K,
                              int lda, int ldc, int out_f32, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
   SRGPT_TRY(w4_args("srgpt_gemm_w4", W4, wscale8));
   Epilogue e = plain_epilogue(C, M, N, ldc);
   e.residual = residual, e.out_f32 = out_f32;
-  return gemm_run(A, WOperand{W4, wscale8, expand}, K, lda, SRGPT_BF16, ws, ws_bytes, e, stream, nullptr);
+  return gemm_run(A, WOperand{W4, wscale8, expand, false}, K, lda, SRGPT_BF16, ws, ws_bytes, e, stream, nullptr);
+}
+
+extern "C" int srgpt_gemm_w4_direct(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N,
+                                    int K, int lda, int ldc, int out_f32, void* expand, void* ws, int64_t ws_bytes,
+                                    srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_direct", W4, wscale8));
+  Epilogue e = plain_epilogue(C, M, N, ldc);
+  e.residual = residual, e.out_f32 = out_f32;
+  return gemm_run(A, WOperand{W4, wscale8, expand, true}, K, lda, SRGPT_BF16, ws, ws_bytes, e, stream, nullptr);
 }
 
 // C = A W^T + bias + residual (dense rows) and Y = norm(C) in one call (include/srgpt.h; the layer loops of model.hip).  The norm
@@ -753,8 +767,16 @@ extern "C" int srgpt_gemm_w4_norm(const void* A, const void* W4, const void* wsc
                                   void* expand, void* ws, int64_t ws_bytes, const void* norm_w, void* Y, float norm_eps,
                                   srgpt_stream_t stream) {
   SRGPT_TRY(w4_args("srgpt_gemm_w4_norm", W4, wscale8));
-  return gemm_norm_run(A, WOperand{W4, wscale8, expand}, nullptr, residual, C, M, N, K, ws, ws_bytes, SRGPT_NORM_RMS, norm_w, nullptr, Y,
-                       norm_eps, SRGPT_BF16, stream);
+  return gemm_norm_run(A, WOperand{W4, wscale8, expand, false}, nullptr, residual, C, M, N, K, ws, ws_bytes, SRGPT_NORM_RMS, norm_w,
+                       nullptr, Y, norm_eps, SRGPT_BF16, stream);
+}
+
+extern "C" int srgpt_gemm_w4_norm_direct(const void* A, const void* W4, const void* wscale8, const void* residual, void* C, int M, int N,
+                                         int K, void* expand, void* ws, int64_t ws_bytes, const void* norm_w, void* Y, float norm_eps,
+                                         srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_norm_direct", W4, wscale8));
+  return gemm_norm_run(A, WOperand{W4, wscale8, expand, true}, nullptr, residual, C, M, N, K, ws, ws_bytes, SRGPT_NORM_RMS, norm_w,
+                       nullptr, Y, norm_eps, SRGPT_BF16, stream);
 }
 
 // qkv = A W^T for the B * T token rows of a prefill, then RoPE on q (in place) and k, k and v appended to the caches -- the
@@ -788,15 +810,25 @@ extern "C" int srgpt_gemm_w4_rope_kv_append(const void* A, const void* W4, const
                                             const void* sin_tab, int B, int T_, int Hq, int Hkv, int D, int max_pos,
                                             srgpt_stream_t stream) {
   SRGPT_TRY(w4_args("srgpt_gemm_w4_rope_kv_append", W4, wscale8));
-  return gemm_rope_run(A, WOperand{W4, wscale8, expand}, qkv, K, ws, ws_bytes, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq, Hkv, D,
-                       max_pos, SRGPT_BF16, stream);
+  return gemm_rope_run(A, WOperand{W4, wscale8, expand, false}, qkv, K, ws, ws_bytes, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq,
+                       Hkv, D, max_pos, SRGPT_BF16, stream);
+}
+
+extern "C" int srgpt_gemm_w4_rope_kv_append_direct(const void* A, const void* W4, const void* wscale8, void* qkv, int K, void* expand,
+                                                   void* ws, int64_t ws_bytes, void* kcache, void* vcache, const int* pos0,
+                                                   const void* cos_tab, const void* sin_tab, int B, int T_, int Hq, int Hkv, int D,
+                                                   int max_pos, srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_rope_kv_append_direct", W4, wscale8));
+  return gemm_rope_run(A, WOperand{W4, wscale8, expand, true}, qkv, K, ws, ws_bytes, kcache, vcache, pos0, cos_tab, sin_tab, B, T_, Hq,
+                       Hkv, D, max_pos, SRGPT_BF16, stream);
 }
 
 // out[M, I] = rnd(rnd(silu(A Wg^T)) * (A Wu^T)) for the stacked weight Wgu = [Wg; Wu] ([2 I, K]) -- LlamaMLP's gate / up products and
 // srgpt_silu_mul in one call (include/srgpt.h).  On the whole-M kernel (225 .. 272 rows: the bs = 1 prefill) a block multiplies 64
 // gate columns and the 64 matching up columns and the activation is its epilogue: the [M, 2 I] intermediate is neither written nor
 // read.  Every other shape runs the plain product into `gu_scratch` and srgpt_silu_mul -- the result is the same to the last bit.
-// Codes: the whole-M kernel has no W4 mode, so the fused form expands them first; the plain product follows gemm_run's rule.
+// Codes: the fused form expands them first, unless the operand is `direct` and the scale table fits (the whole-M kernel's W4
+// instance, gemm288.hip); the plain product follows gemm_run's rule.
 static int gemm_swiglu_run(const void* A, const WOperand& w, void* out, int M, int I, int K, void* gu_scratch, void* ws, int64_t ws_bytes,
                            int dtype, srgpt_stream_t stream) {
   const bool w4 = w.scale8 != nullptr;
@@ -805,10 +837,12 @@ static int gemm_swiglu_run(const void* A, const WOperand& w, void* out, int M, i
   if (dtype == SRGPT_BF16 && gemm_swiglu_fused_shape(M, I, K, srgpt_device_cus()) && ((uintptr_t)A % 16 == 0) &&
       (w4 || (uintptr_t)w.w % 16 == 0)) {
     const void* W = w.w;
-    if (w4) SRGPT_TRY(w4_resolve("srgpt_gemm_w4_swiglu", w, 2 * I, K, dtype, false, stream, &W));
+    const bool codes = w4 && w.direct && gemm288_w4_scales_fit(K / 64);  // gemm_swiglu_w4_direct_in_kernel on the fused shape
+    if (w4) SRGPT_TRY(w4_resolve("srgpt_gemm_w4_swiglu", w, 2 * I, K, dtype, codes, stream, &W));
     Epilogue e = plain_epilogue(out, M, I, I);
     e.swiglu_inter = I;
-    SRGPT_TRY(srgpt_gemm288_launch(A, W, K, K, e, as_stream(stream)));
+    if (codes) SRGPT_TRY(srgpt_gemm288_w4_launch(A, W, w.scale8, K, K, e, as_stream(stream)));
+    else SRGPT_TRY(srgpt_gemm288_launch(A, W, K, K, e, as_stream(stream)));
     return SRGPT_OK;
   }
   SRGPT_CHECK(gu_scratch, SRGPT_ERR_ARG, "srgpt_gemm_swiglu: this shape needs the [M, 2 I] scratch buffer");
@@ -824,7 +858,13 @@ extern "C" int srgpt_gemm_swiglu(const void* A, const void* Wgu, void* out, int 
 extern "C" int srgpt_gemm_w4_swiglu(const void* A, const void* Wgu4, const void* wscale8, void* out, int M, int I, int K,
                                     void* gu_scratch, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
   SRGPT_TRY(w4_args("srgpt_gemm_w4_swiglu", Wgu4, wscale8));
-  return gemm_swiglu_run(A, WOperand{Wgu4, wscale8, expand}, out, M, I, K, gu_scratch, ws, ws_bytes, SRGPT_BF16, stream);
+  return gemm_swiglu_run(A, WOperand{Wgu4, wscale8, expand, false}, out, M, I, K, gu_scratch, ws, ws_bytes, SRGPT_BF16, stream);
+}
+
+extern "C" int srgpt_gemm_w4_swiglu_direct(const void* A, const void* Wgu4, const void* wscale8, void* out, int M, int I, int K,
+                                           void* gu_scratch, void* expand, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
+  SRGPT_TRY(w4_args("srgpt_gemm_w4_swiglu_direct", Wgu4, wscale8));
+  return gemm_swiglu_run(A, WOperand{Wgu4, wscale8, expand, true}, out, M, I, K, gu_scratch, ws, ws_bytes, SRGPT_BF16, stream);
 }
 
 // host only: 1 when the W4 entry point of this shape multiplies the codes in its kernel on this device, 0 when it expands them first
@@ -834,6 +874,14 @@ extern "C" int srgpt_gemm_w4_in_kernel(int M, int N, int K, int swiglu, int have
   const int cus = srgpt_device_cus();
   if (swiglu) return gemm_swiglu_w4_in_kernel(M, N, K, cus, have_ws != 0, ws_bytes) ? 1 : 0;
   return gemm_w4_in_kernel(gemm_route(M, N, K, cus, have_ws != 0, ws_bytes), K) ? 1 : 0;
+}
+
+// the same question for the `_direct` entry points
+extern "C" int srgpt_gemm_w4_direct_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0) return 0;
+  const int cus = srgpt_device_cus();
+  if (swiglu) return gemm_swiglu_w4_direct_in_kernel(M, N, K, cus, have_ws != 0, ws_bytes) ? 1 : 0;
+  return gemm_w4_direct_in_kernel(gemm_route(M, N, K, cus, have_ws != 0, ws_bytes), K) ? 1 : 0;
 }
 
 // C = epilogue((A @ fp8(W8)^T) * wscale): bf16 activations, OCP e4m3fn weight bytes, one fp32 scale per weight row -- the

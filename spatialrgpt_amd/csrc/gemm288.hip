@@ -22,10 +22,36 @@
 //     also carry the norm / RoPE that follows); SwiGLU mode for the stacked gate / up weight (srgpt_gemm_swiglu): the block's 128 W
 //     rows are 64 gate rows and the 64 matching up rows, the activation is the epilogue
 // Requirements (checked by the callers in gemm.hip): K % 64 == 0, at least 4 K tiles, M <= 272 per row tile.
+//
+// W4 instance (srgpt_gemm288_w4_launch; the `_direct` W4 entry points of include/srgpt.h): the weight operand is row-major MXFP4
+// codes [N, K / 2] + E8M0 bytes [N, K / 32].  The mode is the presence of a trailing scale-pointer argument (a parameter pack of zero
+// or one `const unsigned char*`, as gemm_bf16_glds): the bf16 instantiation keeps its parameter list and compiles to the
+// instructions it had without the mode (compared on the disassembly of the two builds: identical but for the kernel's name).
+//   * W side of a K tile: 128 rows x 32 B of codes = 4 KiB instead of 16, 16 groups of 8 rows x 32 B moved by
+//     global_load_lds_dword (4 bytes per lane, one wave-instruction = one group): a wave still issues TWO W requests per K tile and
+//     the A side is untouched, so every vmcnt immediate of the protocol (6 / 7 / 12) stays valid.  Dword swizzle slot ^ ((row >> 2)
+//     & 7) on the source side and in the fragment read (gemm.hip's W4 instances: conflict-free ds_read_b32)
+//   * a main W fragment is one ds_read_b32 (the 8 codes at k = 16 ks + 8 (lane >> 5)) + four v_cvt_scalef32_pk_bf16_fp4 with the
+//     block scale `byte << 23` (exact), in the LOAD part; the tail fragments (16x16x32 layout: row lane & 15, k group lane >> 4) are
+//     one dword each, widened the same way.  SwiGLU mode, row clamping: the code and scale rows are addressed as the bf16 rows
+//   * scale bytes: a table in LDS behind the three stages (3 x 38 = 114 KiB; the table from there to 160 KiB) holds bytes 2 kt,
+//     2 kt + 1 of the block's 128 W rows for the block's OWN K tiles kt0 .. nk - 1, [kt - kt0][row] as 16-bit pairs, 260 bytes per
+//     tile (the staging writes of consecutive tiles fall into different banks).  It is staged in the prologue with plain loads
+//     issued AFTER the prologue's requests, ds_write_b16, and one full wait (s_waitcnt vmcnt(0) lgkmcnt(0)) in front of the first
+//     barrier, which publishes it; the prologue's own waits then pass at once.  The loop issues no plain vector load, so its
+//     counts are the bf16 instance's; the LOAD part reads a row's pair with ds_read_u16 (ks 0, 1: the low byte; 2, 3: the high one).
+//     gemm_route.h's gemm288_w4_scales_fit is the fit rule (at most 181 K tiles per block: 16.25 KiB at K = 4096, down_proj's
+//     K = 14336 is split into 28 tiles per block); a range that does not fit keeps the expansion
+//   * the SwiGLU hand-over writes LDS 0 .. 136 KiB, over the table: only behind the barriers after the loop, when no LOAD part
+//     reads it any more.  The k of every MFMA step, the instructions, the accumulators, the split ranges, the slab layout and both
+//     epilogues are the bf16 instance's: the product equals it on srgpt_dequant_mxfp4 of the codes bit for bit
+//   * resources (compiler remarks, gfx950): 177 VGPRs (bf16: 176), 0 AGPRs, no VGPR spill and no scratch, 60 SGPRs spilled to VGPR
+//     lanes (bf16: 16), 160 KiB of dynamic LDS (bf16: 150), 2 waves per SIMD = the one block of 8 waves per CU of both instances
 #include <type_traits>
 
 #include "common.h"
 #include "gemm_epilogue.h"
+#include "gemm_route.h"
 #include "internal.h"
 
 namespace {
@@ -36,6 +62,11 @@ constexpr int T_A = T_BM * T_BK * 2;         // 34 KiB
 constexpr int T_W = T_BN * T_BK * 2;         // 16 KiB
 constexpr int T_STAGE = T_A + T_W;           // 50 KiB
 constexpr int T_LDS = T_NS * T_STAGE;        // 150 KiB
+// W4 instance: a W stage is 128 rows x 32 B of codes; behind the three stages the block's table of scale bytes (gemm_route.h)
+constexpr int T_W4 = T_BN * T_BK / 2;        // 4 KiB
+constexpr int T_STAGE4 = T_A + T_W4;         // 38 KiB
+constexpr int T_TBL = T_NS * T_STAGE4;       // 114 KiB: where the scale table starts
+static_assert(T_TBL == GEMM288_W4_STAGES, "gemm_route.h's fit rule counts these stages");
 
 #define T_BARRIER()                       \
   do {                                    \
@@ -50,8 +81,13 @@ constexpr int T_LDS = T_NS * T_STAGE;        // 150 KiB
     __builtin_amdgcn_sched_barrier(0);                        \
   } while (0)
 
+template <typename... Scale8>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_288_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, int K,
-                                                               int lda, Epilogue e) {
+                                                               int lda, Epilogue e, Scale8... scale8) {
+  constexpr bool W4 = sizeof...(Scale8) == 1;
+  static_assert(sizeof...(Scale8) <= 1, "at most one scale pointer");
+  constexpr int S_STAGE = W4 ? T_STAGE4 : T_STAGE;  // bytes of a stage
+  constexpr int S_GROUP = W4 ? 256 : 1024;          // bytes of an 8-row W group
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -79,28 +115,39 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_288_kernel(const bf16_t* __r
   for (int i = 0; i < 2; ++i) {  // W groups 0 .. 15
     const int r = (wave + 8 * i) * 8 + lr;  // row of the W tile
     const int wrow = swi ? (r < 64 ? n0 + r : swi + n0 + r - 64) : min(n0 + r, e.N - 1);
-    pw[i] = W + (size_t)wrow * K + lc * 8;
+    // W4: byte offsets in bf16_t units -- a row is K / 2 bytes = K / 4 elements, the lane's dword is slot ^ ((row >> 2) & 7), and
+    // (row >> 2) & 7 = ((wave & 3) << 1) | (lr >> 2) for both groups of a wave (gemm.hip's W4 instances)
+    pw[i] = W4 ? W + (size_t)wrow * (K / 4) + ((lane & 7) ^ (((wave & 3) << 1) | (lr >> 2))) * 2 : W + (size_t)wrow * K + lc * 8;
   }
   const bf16_t* ptl = A + (size_t)min(m0 + T_MAIN + wave * 8 + lr, e.M - 1) * lda + lc * 8;                    // A group 32 + wave
   auto dma = [&](const void* s_, int lds_off) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s_,
                                      (__attribute__((address_space(3))) void*)(lds + lds_off), 16, 0, 0);
   };
+  auto dma4 = [&](const void* s_, int lds_off) {  // W4: 4 bytes per lane, one wave-instruction = 8 rows x 32 B of codes
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)s_,
+                                     (__attribute__((address_space(3))) void*)(lds + lds_off), 4, 0, 0);
+  };
+  auto request_w = [&](int k0, int soff) {  // the wave's two W groups: the same two requests in either mode
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if constexpr (W4) dma4(pw[i] + k0 / 4, soff + T_A + (wave + 8 * i) * S_GROUP);
+      else dma(pw[i] + k0, soff + T_A + (wave + 8 * i) * S_GROUP);
+    }
+  };
   auto request = [&](int kt) {  // the wave's groups of K tile kt into stage kt % 3
     const int k0 = kt * T_BK;
-    const int soff = (kt % T_NS) * T_STAGE;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) dma(pw[i] + k0, soff + T_A + (wave + 8 * i) * 1024);
+    const int soff = (kt % T_NS) * S_STAGE;
+    request_w(k0, soff);
 #pragma unroll
     for (int i = 0; i < 4; ++i) dma(pa[i] + k0, soff + (wave + 8 * i) * 1024);
     if (tail_wave) dma(ptl + k0, soff + (32 + wave) * 1024);
   };
   auto request_part = [&](int kt, int part) {  // the same requests in three portions (issued between the MFMAs of a multiply part)
     const int k0 = kt * T_BK;
-    const int soff = (kt % T_NS) * T_STAGE;
+    const int soff = (kt % T_NS) * S_STAGE;
     if (part == 0) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) dma(pw[i] + k0, soff + T_A + (wave + 8 * i) * 1024);
+      request_w(k0, soff);
     } else if (part == 1) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) dma(pa[i] + k0, soff + (wave + 8 * i) * 1024);
@@ -119,6 +166,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_288_kernel(const bf16_t* __r
   for (int s2 = 0; s2 < 2; ++s2) {
     toff[s2] = T_A + trow * 128 + (((4 * s2 + g4) ^ ((trow >> 1) & 7)) << 4);
     taoff[s2] = (T_MAIN + l15) * 128 + (((4 * s2 + g4) ^ ((l15 >> 1) & 7)) << 4);
+    // W4: the same k group is dword 4 s2 + g4 of the row's 32 B of codes
+    if constexpr (W4) toff[s2] = T_A + trow * 32 + (((4 * s2 + g4) ^ ((trow >> 2) & 7)) << 2);
   }
 
   // ---- fragment addresses (gemm256): row = tile row + (lane & 31), slot = (2 ks + (lane >> 5)) ^ ((row >> 1) & 7) ----
@@ -127,7 +176,21 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_288_kernel(const bf16_t* __r
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) koff[ks] = l31 * 128 + ((hi ^ (sw & 1)) << 4) + ((ks ^ (sw >> 1)) << 5);
   const int wm = wave >> 1, wn = wave & 1;  // waves 4 (M) x 2 (N): 64 x 64 of C each = 2 x 2 MFMA tiles (8 A + 8 W fragment reads per K tile)
-  const int a_base = wm * 64 * 128, w_base = T_A + wn * 64 * 128;
+  const int a_base = wm * 64 * 128, w_base = T_A + wn * 64 * (W4 ? 32 : 128);
+  // W4: a main W fragment is the dword (2 ks + hi) ^ ((row >> 2) & 7) of its row, row & 31 = l31
+  int koff4[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) koff4[ks] = l31 * 32 + (((2 * ks + hi) ^ ((l31 >> 2) & 7)) << 2);
+  // MXFP4 codes -> bf16 with the block scale `byte << 23` (exact): the 8 codes of a dword are one MFMA fragment
+  auto widen = [](unsigned int word, unsigned int byte) {
+    const float sc = __uint_as_float(byte << 23);
+    u32x4 o;
+    o[0] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 0));
+    o[1] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 1));
+    o[2] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 2));
+    o[3] = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 3));
+    return __builtin_bit_cast(bf16x8, o);
+  };
 
   f32x16 acc[4];
   {
@@ -158,6 +221,29 @@ do {                                  \
   request(kt0);
   if (kt0 + 1 < nk) request(kt0 + 1);
   if (late && kt0 + 2 < nk) request(kt0 + 2);
+  if constexpr (W4) {
+    // The scale table: bytes 2 kt, 2 kt + 1 of the block's 128 W rows for its own K tiles kt0 .. nk - 1, as 16-bit pairs at
+    // [kt - kt0][row] with GEMM288_W4_SCALE_TILE bytes per tile.  Plain loads AFTER the prologue's requests (their latency overlaps
+    // the first tiles'), so the compiler's wait for them also lands every request issued so far and the waits below pass at once;
+    // no plain vector load remains in flight when the loop starts, and the loop issues none: its counts are the bf16 instance's.
+    // Wave w stages rows w + 8 j, a lane one tile of each: a wave-instruction reads up to 128 contiguous bytes of a row.
+    const unsigned char* sc8 = (scale8, ...);
+    const int nt = nk - kt0;
+    for (int t = lane; t < nt; t += 64) {
+      unsigned int v[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int r = wave + 8 * j;
+        const int wrow = swi ? (r < 64 ? n0 + r : swi + n0 + r - 64) : min(n0 + r, e.N - 1);
+        const unsigned char* p = sc8 + (size_t)wrow * (K / 32) + 2 * (kt0 + t);
+        v[j] = (unsigned int)p[0] | ((unsigned int)p[1] << 8);
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        *reinterpret_cast<unsigned short*>(lds + T_TBL + t * GEMM288_W4_SCALE_TILE + (wave + 8 * j) * 2) = (unsigned short)v[j];
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the table is written before the barrier below publishes it
+  }
   if (!late) {
     T_WAIT_SHARE(kt0 + 1 < nk);
   } else {  // late waves carry no tail group: 6 requests per tile
@@ -170,20 +256,53 @@ do {                                  \
   if (late) T_BARRIER();
   for (int kt = kt0; kt < nk; ++kt) {
     // ---- LOAD part ----
-    const char* buf = lds + (kt % T_NS) * T_STAGE;
+    const char* buf = lds + (kt % T_NS) * S_STAGE;
     bf16x8 fa[4][2], fw[4][2], fta[2], ftw[2];
+    if constexpr (W4) {
+      // the code dwords and the rows' scale pairs first, the A fragments behind them, then the widening: ks 0, 1 are block 2 kt
+      const char* tbl = lds + T_TBL + (kt - kt0) * GEMM288_W4_SCALE_TILE;
+      unsigned int cw[4][2], ctw[2] = {0u, 0u}, sc[2], sct = 0u;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
+      for (int i = 0; i < 2; ++i) sc[i] = *reinterpret_cast<const unsigned short*>(tbl + (wn * 64 + i * 32 + l31) * 2);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        fa[ks][i] = *reinterpret_cast<const bf16x8*>(buf + a_base + i * 32 * 128 + koff[ks]);
-        fw[ks][i] = *reinterpret_cast<const bf16x8*>(buf + w_base + i * 32 * 128 + koff[ks]);
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) cw[ks][i] = *reinterpret_cast<const unsigned int*>(buf + w_base + i * 32 * 32 + koff4[ks]);
+      if (has_tail) {
+        sct = *reinterpret_cast<const unsigned short*>(tbl + trow * 2);
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) ctw[s2] = *reinterpret_cast<const unsigned int*>(buf + toff[s2]);
       }
-    if (has_tail) {
 #pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        fta[s2] = *reinterpret_cast<const bf16x8*>(buf + taoff[s2]);
-        ftw[s2] = *reinterpret_cast<const bf16x8*>(buf + toff[s2]);
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fa[ks][i] = *reinterpret_cast<const bf16x8*>(buf + a_base + i * 32 * 128 + koff[ks]);
+      if (has_tail) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) fta[s2] = *reinterpret_cast<const bf16x8*>(buf + taoff[s2]);
+      }
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fw[ks][i] = widen(cw[ks][i], (sc[i] >> (8 * (ks >> 1))) & 0xffu);
+      if (has_tail) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) ftw[s2] = widen(ctw[s2], (sct >> (8 * s2)) & 0xffu);
+      }
+    } else {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          fa[ks][i] = *reinterpret_cast<const bf16x8*>(buf + a_base + i * 32 * 128 + koff[ks]);
+          fw[ks][i] = *reinterpret_cast<const bf16x8*>(buf + w_base + i * 32 * 128 + koff[ks]);
+        }
+      if (has_tail) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          fta[s2] = *reinterpret_cast<const bf16x8*>(buf + taoff[s2]);
+          ftw[s2] = *reinterpret_cast<const bf16x8*>(buf + toff[s2]);
+        }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -298,12 +417,29 @@ do {                                  \
 
 // e.splits / e.tiles_per_split / e.partial are set by the caller (srgpt_splitk_apply) when it wants split-K; the deterministic slab
 // reduction (srgpt_splitk_finish, gemm.hip) follows there.
+static dim3 grid288(const Epilogue& e) {
+  return dim3(e.swiglu_inter ? e.swiglu_inter / (T_BN / 2) : cdiv(e.N, T_BN), e.splits > 1 ? e.splits : 1, cdiv(e.M, T_BM));
+}
+
 int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const Epilogue& e, hipStream_t s) {
   static std::atomic<uint64_t> attr_done{0};
-  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_bf16_288_kernel, T_LDS));
-  hipLaunchKernelGGL(gemm_bf16_288_kernel,
-                     dim3(e.swiglu_inter ? e.swiglu_inter / (T_BN / 2) : cdiv(e.N, T_BN), e.splits > 1 ? e.splits : 1, cdiv(e.M, T_BM)),
-                     dim3(512), T_LDS, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
+  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_bf16_288_kernel<>, T_LDS));
+  hipLaunchKernelGGL(gemm_bf16_288_kernel<>, grid288(e), dim3(512), T_LDS, s, (const bf16_t*)A, (const bf16_t*)W, K, lda, e);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+// The W4 instance: W4 / wscale8 are the row-major MXFP4 codes [N, K / 2] and E8M0 bytes [N, K / 32] (include/srgpt.h).  The caller
+// has asked gemm_w4_direct_in_kernel / gemm_swiglu_w4_direct_in_kernel (gemm_route.h); the fit rule is checked again here because an
+// oversized scale table would be written past the block's LDS.
+int srgpt_gemm288_w4_launch(const void* A, const void* W4, const void* wscale8, int K, int lda, const Epilogue& e, hipStream_t s) {
+  const int tiles = e.splits > 1 ? e.tiles_per_split : K / T_BK;
+  SRGPT_CHECK(K % T_BK == 0 && K / T_BK >= 4 && gemm288_w4_scales_fit(tiles), SRGPT_ERR_ARG,
+              "gemm288 (W4): K=%d with %d K tiles per block does not fit the kernel", K, tiles);
+  static std::atomic<uint64_t> attr_done{0};
+  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_bf16_288_kernel<const unsigned char*>, GEMM288_LDS_MAX));
+  hipLaunchKernelGGL((gemm_bf16_288_kernel<const unsigned char*>), grid288(e), dim3(512), GEMM288_LDS_MAX, s, (const bf16_t*)A,
+                     (const bf16_t*)W4, K, lda, e, (const unsigned char*)wscale8);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }

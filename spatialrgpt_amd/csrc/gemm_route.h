@@ -156,3 +156,31 @@ inline bool gemm_w4_in_kernel(const GemmRoute& r, int K) { return r.family == GE
 inline bool gemm_swiglu_w4_in_kernel(int M, int I, int K, int cus, bool have_ws, int64_t ws_bytes) {
   return !gemm_swiglu_fused_shape(M, I, K, cus) && gemm_w4_in_kernel(gemm_route(M, 2 * I, K, cus, have_ws, ws_bytes), K);
 }
+
+// ---- the opt-in `_direct` forms of the four W4 entry points (srgpt_gemm_w4_direct ...): the whole-M kernel multiplies the codes too ----
+// LDS of gemm_bf16_288_kernel's W4 instance (gemm288.hip): three stages of A 272 x 64 bf16 + W 128 x 32 B of codes, and behind them the
+// E8M0 bytes of the block's 128 W rows over the block's own K tiles, [tile][row] as 16-bit pairs, a tile 4 bytes past 256 so that the
+// staging writes of consecutive tiles fall into different banks.  The table has to fit what the stages leave of a CU's 160 KiB.
+constexpr int GEMM288_LDS_MAX = 160 * 1024;
+constexpr int GEMM288_W4_STAGES = 3 * (272 * 64 * 2 + 128 * 32);  // 114 KiB
+constexpr int GEMM288_W4_SCALE_TILE = 128 * 2 + 4;                // bytes of the table per K tile
+// the fit rule, shared by the route below and the kernel's launcher: `tiles` K tiles in a block's range
+inline bool gemm288_w4_scales_fit(int tiles) {
+  return tiles > 0 && (int64_t)tiles * GEMM288_W4_SCALE_TILE <= GEMM288_LDS_MAX - GEMM288_W4_STAGES;
+}
+
+// srgpt_gemm_w4_direct / _norm_direct / _rope_kv_append_direct: does the kernel of route `r` multiply the codes itself?  Wherever
+// gemm_w4_in_kernel says so, and on the whole-M family (whose requirements K % 64 == 0 and >= 4 K tiles gemm_route has checked; they
+// are repeated here because the kernel's W4 mode depends on them) when the scale bytes of a block's K range fit the LDS left over.
+// The 256 x 256 tiles and K % 64 == 32 still expand.
+inline bool gemm_w4_direct_in_kernel(const GemmRoute& r, int K) {
+  if (gemm_w4_in_kernel(r, K)) return true;
+  return r.family == GEMM_WHOLE_M_288 && K % 64 == 0 && K / 64 >= 4 && gemm288_w4_scales_fit(r.tiles_per_split);
+}
+
+// srgpt_gemm_w4_swiglu_direct: the fused whole-M shape (never split: a block's range is all of K) under the same conditions; every
+// other shape is the plain product of the stacked matrix [2 I, K]
+inline bool gemm_swiglu_w4_direct_in_kernel(int M, int I, int K, int cus, bool have_ws, int64_t ws_bytes) {
+  if (gemm_swiglu_fused_shape(M, I, K, cus)) return gemm288_w4_scales_fit(K / 64);  // (the shape has K % 64 == 0 and >= 4 tiles)
+  return gemm_w4_direct_in_kernel(gemm_route(M, 2 * I, K, cus, have_ws, ws_bytes), K);
+}

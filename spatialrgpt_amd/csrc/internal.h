@@ -13,6 +13,10 @@ struct AttnPrefillRoute;   // attn_route.h
 // ---- gemm256.hip / gemm288.hip: the 256 x 256 and the whole-M (up to 272 rows) bf16 MFMA tiles, dispatched by gemm.hip ----
 int srgpt_gemm256_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
 int srgpt_gemm288_launch(const void* A, const void* W, int K, int lda, const SrgptGemmEpilogue& e, hipStream_t s);
+// its W4 instance: MXFP4 codes [N, K / 2] + E8M0 bytes [N, K / 32] as the weight operand, where gemm_route.h's
+// gemm_w4_direct_in_kernel / gemm_swiglu_w4_direct_in_kernel say so (SRGPT_ERR_ARG before any launch otherwise)
+int srgpt_gemm288_w4_launch(const void* A, const void* W4, const void* wscale8, int K, int lda, const SrgptGemmEpilogue& e,
+                            hipStream_t s);
 
 // ---- gemm.hip: split-K around a product's launch, for every GEMM launcher (gemm.hip, gemm_f8.hip): the route's split into the
 //      epilogue in front of it, the slab reduction + epilogue (when K was split) behind it; *fused (may be NULL) = the norm / RoPE

@@ -405,6 +405,8 @@ int llm_format(const srgpt_llm_weights* w, const char* fn, LlmFormat* fmt) {
   *fmt = FMT_DTYPE;
   SRGPT_CHECK(w->decode_pass_rows == 0 || w->decode_pass_rows == 16 || w->decode_pass_rows == GEMV_WIDE_ROWS, SRGPT_ERR_ARG,
               "%s: decode_pass_rows = %d (0 or 16: passes of 16 rows; %d: the wide pass)", fn, w->decode_pass_rows, GEMV_WIDE_ROWS);
+  SRGPT_CHECK(w->mxfp4_direct == 0 || (w->mxfp4_direct == 1 && w->wqkv4), SRGPT_ERR_ARG,
+              "%s: mxfp4_direct = %d (0: the plain W4 entries; 1: the _direct entries, MXFP4 weights only)", fn, w->mxfp4_direct);
   if (w->wqkv4) {
     SRGPT_CHECK(w->dtype == SRGPT_BF16 && w->wo4 && w->wgu4 && w->wdown4 && w->wqkv4_scale && w->wo4_scale && w->wgu4_scale &&
                     w->wdown4_scale && w->lm_head8 && w->lm_head_scale,
@@ -525,20 +527,26 @@ struct Prefill {
   // direct-to-LDS kernels (every product of an append, o_proj of the bs = 1 prefill) the codes are multiplied in the kernel; the
   // whole-M and 256 x 256 routes still expand each matrix (srgpt_dequant_mxfp4, exact) into the workspace's one bf16 scratch l.w4
   // just before its product -- the stream orders product -> next expansion, so one scratch serves the four.
+  // srgpt_llm_weights::mxfp4_direct = 1: the same sequence through the `_direct` entries, where the whole-M kernel multiplies the
+  // codes too (q/k/v, gate/up and down_proj of the 225 .. 272-row prefill); the scratch stays for the routes that still expand.
   int layer_w4a16(int i) const {
     const LayerMats m = layer_mats(w, fmt, i);
+    const bool direct = w->mxfp4_direct == 1;
+    const auto gemm_rope = direct ? srgpt_gemm_w4_rope_kv_append_direct : srgpt_gemm_w4_rope_kv_append;
+    const auto gemm_norm = direct ? srgpt_gemm_w4_norm_direct : srgpt_gemm_w4_norm;
+    const auto gemm_swiglu = direct ? srgpt_gemm_w4_swiglu_direct : srgpt_gemm_w4_swiglu;
+    const auto gemm = direct ? srgpt_gemm_w4_direct : srgpt_gemm_w4;
     if (i == 0) SRGPT_TRY(norm(w->attn_norm[i]));
-    SRGPT_TRY(srgpt_gemm_w4_rope_kv_append(l.h, m.qkv.w4, m.qkv.scale4, l.qkv, Hd, l.w4, l.gws, gws_bytes(), cache(st->kcache, i),
-                                           cache(st->vcache, i), pos0, w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim,
-                                           st->max_pos, stream));
+    SRGPT_TRY(gemm_rope(l.h, m.qkv.w4, m.qkv.scale4, l.qkv, Hd, l.w4, l.gws, gws_bytes(), cache(st->kcache, i), cache(st->vcache, i), pos0,
+                        w->rope_cos, w->rope_sin, B, T, w->heads, w->kv_heads, w->head_dim, st->max_pos, stream));
     SRGPT_TRY(attention(i));
-    SRGPT_TRY(srgpt_gemm_w4_norm(l.attn, m.o.w4, m.o.scale4, l.x, l.x, rows, Hd, HqD, l.w4, l.gws, gws_bytes(), w->mlp_norm[i], l.h,
-                                 w->rms_eps, stream));
-    SRGPT_TRY(srgpt_gemm_w4_swiglu(l.h, m.gu.w4, m.gu.scale4, l.act, rows, I, Hd, l.gu, l.w4, l.gws, gws_bytes(), stream));
+    SRGPT_TRY(gemm_norm(l.attn, m.o.w4, m.o.scale4, l.x, l.x, rows, Hd, HqD, l.w4, l.gws, gws_bytes(), w->mlp_norm[i], l.h, w->rms_eps,
+                        stream));
+    SRGPT_TRY(gemm_swiglu(l.h, m.gu.w4, m.gu.scale4, l.act, rows, I, Hd, l.gu, l.w4, l.gws, gws_bytes(), stream));
     if (i + 1 < w->layers)
-      return srgpt_gemm_w4_norm(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, l.w4, l.gws, gws_bytes(), w->attn_norm[i + 1], l.h,
-                                w->rms_eps, stream);
-    return srgpt_gemm_w4(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, I, Hd, 0, l.w4, l.gws, gws_bytes(), stream);
+      return gemm_norm(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, l.w4, l.gws, gws_bytes(), w->attn_norm[i + 1], l.h,
+                       w->rms_eps, stream);
+    return gemm(l.act, m.down.w4, m.down.scale4, l.x, l.x, rows, Hd, I, I, Hd, 0, l.w4, l.gws, gws_bytes(), stream);
   }
 
   int layer_w8a16(int i) const {

@@ -249,7 +249,8 @@ class SplicePlan:
 class SrgptEngine:
     def __init__(self, cfg: SrgptConfig, state_dict: Dict[str, torch.Tensor], device="cuda", dtype=torch.bfloat16,
                  rope_positions: int = 0, consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None,
-                 decode_layout: str = "packed", pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16):
+                 decode_layout: str = "packed", pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16,
+                 mxfp4_prefill_direct: bool = False):
         L.load()  # fail loudly if the HIP extension is missing
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         if self.device.type != "cuda":
@@ -266,7 +267,8 @@ class SrgptEngine:
         # mxfp4_packed: "mxfp4" weights also get packed copies, bound, for the MFMA product of every step of 2+ rows (weights.py; default off)
         self.w = PreparedWeights(cfg, state_dict, self.device, dtype, rope_positions, consume=consume_state_dict,
                                  llm_weight_format=llm_weight_format, parts=parts, decode_layout=decode_layout, pack13=pack13,
-                                 mxfp4_packed=mxfp4_packed, decode_pass_rows=decode_pass_rows)
+                                 mxfp4_packed=mxfp4_packed, decode_pass_rows=decode_pass_rows,
+                                 mxfp4_prefill_direct=mxfp4_prefill_direct)
         self._state: Optional[DecodeState] = None
         self._vit_ws: Optional[torch.Tensor] = None
         self.use_graph = True
@@ -277,6 +279,11 @@ class SrgptEngine:
     def decode_pass_rows(self) -> int:
         """rows per weight pass of the decode step's MFMA products (16, or 32: the wide pass); set at construction"""
         return self.w.decode_pass_rows
+
+    @property
+    def mxfp4_prefill_direct(self) -> bool:
+        """"mxfp4" weights: the prefill multiplies the codes inside the whole-M kernel too (weights.py); set at construction"""
+        return self.w.mxfp4_prefill_direct
 
     # ------------------------------------------------------------------ A1
     def vit(self, images: torch.Tensor, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:

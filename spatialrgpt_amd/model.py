@@ -185,7 +185,7 @@ class LlavaLlamaModel:
                  dtype=torch.bfloat16, tokenizer=None, image_processor=None, rope_positions: int = 0,
                  consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, prefix_reuse: bool = False,
                  lookup_sampling: bool = False, lookup_batch: bool = False, pack13=None, mxfp4_packed: bool = False,
-                 decode_pass_rows: int = 16, **hf_kwargs):
+                 decode_pass_rows: int = 16, mxfp4_prefill_direct: bool = False, **hf_kwargs):
         self.hf_config = None
         if isinstance(config, LlavaConfig):
             # the reference's construction path: config carries the checkpoint location
@@ -210,7 +210,8 @@ class LlavaLlamaModel:
         self.config = config
         self.engine = SrgptEngine(config, state_dict, device=device, dtype=dtype, rope_positions=rope_positions,
                                   consume_state_dict=consume_state_dict, llm_weight_format=llm_weight_format, parts=parts,
-                                  pack13=pack13, mxfp4_packed=mxfp4_packed, decode_pass_rows=decode_pass_rows)
+                                  pack13=pack13, mxfp4_packed=mxfp4_packed, decode_pass_rows=decode_pass_rows,
+                                  mxfp4_prefill_direct=mxfp4_prefill_direct)
         self.tokenizer = tokenizer
         self.vision_tower = _VisionTower(self.engine, image_processor)
         self.region_extractor = _RegionExtractor(self.engine) if config.enable_region else None
@@ -242,6 +243,12 @@ class LlavaLlamaModel:
         """rows per weight pass of the decode step's MFMA products: 16, or 32 (steps of 17 - 32 rows stream every weight matrix once);
         set at construction and read-only, because captured graphs hold launches"""
         return self.engine.decode_pass_rows
+
+    @property
+    def mxfp4_prefill_direct(self) -> bool:
+        """llm_weight_format="mxfp4": the 225 .. 272-row prefill multiplies the codes inside the whole-M kernel instead of expanding
+        q/k/v, gate/up and down_proj to bf16 first (same bits); set at construction and read-only"""
+        return self.engine.mxfp4_prefill_direct
 
     @property
     def last_reuse(self):

@@ -653,23 +653,31 @@ def _w4_expand(op, expand, in_kernel, N, K, device):
     return None if in_kernel else torch.empty((N, K), device=device, dtype=torch.bfloat16)
 
 
-def gemm_w4_in_kernel(M, N, K, swiglu=False, device=None, ws=None) -> bool:
+def gemm_w4_in_kernel(M, N, K, swiglu=False, device=None, ws=None, direct=False) -> bool:
     """srgpt_gemm_w4_in_kernel with the split-K workspace this module passes: True when gemm_w4 / gemm_w4_norm /
     gemm_w4_rope_kv_append of an [M, K] x [N, K] product (gemm_w4_swiglu with N = I) multiply the MXFP4 codes inside the GEMM kernel
-    on this device, False when they expand the codes into the bf16 scratch first."""
+    on this device, False when they expand the codes into the bf16 scratch first.  direct: the answer for the same calls with
+    direct=True (srgpt_gemm_w4_direct_in_kernel)."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     ws, ws_bytes = _ws_arg(device, M, 2 * N if swiglu else N, True, ws)
-    return _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes)
+    return _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes, direct)
 
 
-def _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes) -> bool:
-    return bool(L.load().srgpt_gemm_w4_in_kernel(M, N, K, int(swiglu), int(ws is not None), ws_bytes))
+def _w4_in_kernel(M, N, K, swiglu, ws, ws_bytes, direct=False) -> bool:
+    fn = L.load().srgpt_gemm_w4_direct_in_kernel if direct else L.load().srgpt_gemm_w4_in_kernel
+    return bool(fn(M, N, K, int(swiglu), int(ws is not None), ws_bytes))
 
 
-def gemm_w4(a, w4, wscale8, residual=None, out=None, out_f32=False, expand=None, ws=None):
+def _w4_entry(name, direct):
+    """the C entry point `name`, or its `_direct` form (include/srgpt.h): the whole-M kernel multiplies the codes too"""
+    return getattr(L.load(), name + "_direct" if direct else name)
+
+
+def gemm_w4(a, w4, wscale8, residual=None, out=None, out_f32=False, expand=None, ws=None, direct=False):
     """a @ dequant(w4, wscale8).T + residual with MXFP4 weights (codes [N, K / 2], E8M0 scales [N, K / 32]): bit for bit
     gemm(a, dequant_mxfp4(w4, wscale8), residual=...).  a [M, K] bf16 (row stride may exceed K).  expand: the bf16 [N, K] scratch of
-    the expansion path (see gemm_w4_in_kernel; None: allocated when needed).  ws: as for gemm."""
+    the expansion path (see gemm_w4_in_kernel; None: allocated when needed).  ws: as for gemm.  direct (here and on the three
+    products below): the `_direct` entry point -- the same bits, the codes multiplied in the whole-M kernel too (opt-in)."""
     M, N, K = _w4_operand("gemm_w4", a, w4, wscale8)
     _dev(residual)
     _same_dtype("gemm_w4", a, residual=residual)
@@ -677,13 +685,13 @@ def gemm_w4(a, w4, wscale8, residual=None, out=None, out_f32=False, expand=None,
     if out is None:
         out = torch.empty((M, N), device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
     ws, ws_bytes = _ws_arg(a.device, M, N, True, ws)
-    expand = _w4_expand("gemm_w4", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
-    L.check(L.load().srgpt_gemm_w4(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, a.stride(0), out.stride(0),
+    expand = _w4_expand("gemm_w4", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes, direct), N, K, a.device)
+    L.check(_w4_entry("srgpt_gemm_w4", direct)(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, a.stride(0), out.stride(0),
                                    int(out_f32), _p(expand), ws, ws_bytes, _stream()))
     return out
 
 
-def gemm_w4_norm(a, w4, wscale8, residual, norm_w, eps, out=None, y=None, expand=None, ws=None):
+def gemm_w4_norm(a, w4, wscale8, residual, norm_w, eps, out=None, y=None, expand=None, ws=None, direct=False):
     """(a @ dequant(w4, wscale8).T + residual, rmsnorm(that)): gemm_norm (RMSNorm, no bias) with MXFP4 weights, bit for bit
     gemm_norm(a, dequant_mxfp4(w4, wscale8), ...).  expand / ws: as for gemm_w4."""
     M, N, K = _w4_operand("gemm_w4_norm", a, w4, wscale8)
@@ -695,13 +703,13 @@ def gemm_w4_norm(a, w4, wscale8, residual, norm_w, eps, out=None, y=None, expand
     if y is None:
         y = torch.empty((M, N), device=a.device, dtype=a.dtype)
     ws, ws_bytes = _ws_arg(a.device, M, N, True, ws)
-    expand = _w4_expand("gemm_w4_norm", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
-    L.check(L.load().srgpt_gemm_w4_norm(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, _p(expand), ws, ws_bytes,
+    expand = _w4_expand("gemm_w4_norm", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes, direct), N, K, a.device)
+    L.check(_w4_entry("srgpt_gemm_w4_norm", direct)(_p(a), _p(w4), _p(wscale8), _p(residual), _p(out), M, N, K, _p(expand), ws, ws_bytes,
                                         _p(norm_w), _p(y), float(eps), _stream()))
     return out, y
 
 
-def gemm_w4_swiglu(a, wgu4, wscale8, out=None, expand=None):
+def gemm_w4_swiglu(a, wgu4, wscale8, out=None, expand=None, direct=False):
     """silu(a @ wg.T) * (a @ wu.T) for the stacked MXFP4 matrix [2 I, K]: bit for bit gemm_swiglu(a, dequant_mxfp4(wgu4, wscale8)).
     expand: the bf16 [2 I, K] scratch of the expansion path (None: allocated when needed)."""
     M, N2, K = _w4_operand("gemm_w4_swiglu", a, wgu4, wscale8)
@@ -711,13 +719,14 @@ def gemm_w4_swiglu(a, wgu4, wscale8, out=None, expand=None):
         out = torch.empty((M, I), device=a.device, dtype=a.dtype)
     scratch = torch.empty((M, 2 * I), device=a.device, dtype=a.dtype)
     ws, ws_bytes = _ws_arg(a.device, M, 2 * I, True)
-    expand = _w4_expand("gemm_w4_swiglu", expand, _w4_in_kernel(M, I, K, True, ws, ws_bytes), 2 * I, K, a.device)
-    L.check(L.load().srgpt_gemm_w4_swiglu(_p(a), _p(wgu4), _p(wscale8), _p(out), M, I, K, _p(scratch), _p(expand), ws, ws_bytes,
+    expand = _w4_expand("gemm_w4_swiglu", expand, _w4_in_kernel(M, I, K, True, ws, ws_bytes, direct), 2 * I, K, a.device)
+    L.check(_w4_entry("srgpt_gemm_w4_swiglu", direct)(_p(a), _p(wgu4), _p(wscale8), _p(out), M, I, K, _p(scratch), _p(expand), ws, ws_bytes,
                                           _stream()))
     return out
 
 
-def gemm_w4_rope_kv_append(a, w4, wscale8, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D, pos0=None, qkv=None, expand=None):
+def gemm_w4_rope_kv_append(a, w4, wscale8, kcache, vcache, cos_tab, sin_tab, B, T, Hq, Hkv, D, pos0=None, qkv=None, expand=None,
+                           direct=False):
     """gemm_rope_kv_append with MXFP4 weights: bit for bit (qkv and both caches) the bf16 call on dequant_mxfp4(w4, wscale8)."""
     N = (Hq + 2 * Hkv) * D
     M, _, K = _w4_operand("gemm_w4_rope_kv_append", a, w4, wscale8, rows=N)
@@ -726,9 +735,9 @@ def gemm_w4_rope_kv_append(a, w4, wscale8, kcache, vcache, cos_tab, sin_tab, B, 
     if qkv is None:
         qkv = torch.empty((M, N), device=a.device, dtype=a.dtype)
     ws, ws_bytes = _ws_arg(a.device, M, N, True)
-    expand = _w4_expand("gemm_w4_rope_kv_append", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes), N, K, a.device)
+    expand = _w4_expand("gemm_w4_rope_kv_append", expand, _w4_in_kernel(M, N, K, False, ws, ws_bytes, direct), N, K, a.device)
     max_pos = kcache.shape[-2]
-    L.check(L.load().srgpt_gemm_w4_rope_kv_append(_p(a), _p(w4), _p(wscale8), _p(qkv), K, _p(expand), ws, ws_bytes, _p(kcache),
+    L.check(_w4_entry("srgpt_gemm_w4_rope_kv_append", direct)(_p(a), _p(w4), _p(wscale8), _p(qkv), K, _p(expand), ws, ws_bytes, _p(kcache),
                                                   _p(vcache), _p(pos0), _p(cos_tab), _p(sin_tab), B, T, Hq, Hkv, D, max_pos,
                                                   _stream()))
     return qkv

@@ -59,7 +59,7 @@ class PreparedWeights:
 
     def __init__(self, cfg: SrgptConfig, sd: Dict[str, torch.Tensor], device, dtype, rope_positions: int = 0,
                  consume: bool = False, llm_weight_format: str = "native", parts=None, decode_layout: str = "packed",
-                 pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16):
+                 pack13=None, mxfp4_packed: bool = False, decode_pass_rows: int = 16, mxfp4_prefill_direct: bool = False):
         """llm_weight_format: "native" (the engine dtype) or "fp8" -- weight-only OCP e4m3fn quantisation of the five
         streamed LLM matrices with one fp32 (power-of-two) scale per output row (BASELINE config 5; bf16 engines only).  The
         fp8 bytes are the ONLY copy of those matrices in HBM: decode streams them (srgpt_gemv_w8), prefill multiplies them
@@ -87,10 +87,16 @@ class PreparedWeights:
         decode_pass_rows (16 or 32; default 16): rows per weight pass of the decode step's MFMA products.  32: a step of 17 - 32 rows
         streams every matrix once instead of twice (srgpt_gemv_rowss_wide / srgpt_gemv_w4p_wide) for the products gemv_route.h's
         gemv_wide_route runs wide; rows 16 and up of a step of 17 - 31 rows then differ in the last bits from the default's (there
-        they are a pass of fewer than 9 rows, which sums on two accumulators).  Fixed at construction: captured graphs hold launches."""
+        they are a pass of fewer than 9 rows, which sums on two accumulators).  Fixed at construction: captured graphs hold launches.
+        mxfp4_prefill_direct ("mxfp4" only; default off): prefill and append prefill call the `_direct` W4 entry points
+        (srgpt_llm_weights::mxfp4_direct = 1) -- q/k/v, gate/up and down_proj of a 225 .. 272-row prefill multiply the codes inside the
+        whole-M kernel instead of expanding each matrix to bf16 first.  Every byte the prefill writes is the same."""
         if decode_pass_rows not in (16, 32) or isinstance(decode_pass_rows, bool):
             raise ValueError(f"decode_pass_rows must be 16 or 32, got {decode_pass_rows!r}")
         self._decode_pass_rows = int(decode_pass_rows)
+        if mxfp4_prefill_direct and llm_weight_format != "mxfp4":
+            raise ValueError(f"mxfp4_prefill_direct needs llm_weight_format='mxfp4', got {llm_weight_format!r}")
+        self._mxfp4_prefill_direct = bool(mxfp4_prefill_direct)
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
         # parts: which components to materialise -- all of them for the model, ONE for the module-level factories
         # (spatialrgpt_amd/factories.py: the reference's build_vision_tower / build_mm_projector / build_region_extractor /
@@ -323,6 +329,7 @@ class PreparedWeights:
                 setattr(lw, k + "4_scale", asc)
         lw.fp8_act = 1 if self.fp8_act else 0
         lw.decode_pass_rows = self._decode_pass_rows
+        lw.mxfp4_direct = 1 if self._mxfp4_prefill_direct else 0
         self.llm = lw
         self.vocab = self.embed.shape[0]
         if self.pack13_mode and llm_weight_format == "native" and dtype == torch.bfloat16:
@@ -401,6 +408,10 @@ class PreparedWeights:
     @property
     def decode_pass_rows(self) -> int:
         return self._decode_pass_rows
+
+    @property
+    def mxfp4_prefill_direct(self) -> bool:
+        return self._mxfp4_prefill_direct
 
     def pack13_bytes(self) -> int:
         """HBM the packed copies and their flags take, on top of the raw matrices"""

@@ -236,6 +236,20 @@ int srgpt_gemm_w4_rope_kv_append(const void* A, const void* W4, const void* wsca
                                  int64_t ws_bytes, void* kcache, void* vcache, const int* pos0, const void* cos_tab,
                                  const void* sin_tab, int B, int T, int Hq, int Hkv, int D, int max_pos, srgpt_stream_t stream);
 int srgpt_gemm_w4_in_kernel(int M, int N, int K, int swiglu, int have_ws, int64_t ws_bytes);
+/* Addition under ABI 9: W4A8 -- srgpt_gemm_w8a8 (above) with such a matrix as the weight operand, on the block-scaled form of the
+ * same instruction (v_mfma_scale_f32_16x16x128_f8f6f4 with B as e2m1): a lane's 32 k of one MFMA are one MX block, so the E8M0 bytes
+ * as stored are the instruction's scale operand and the matrix is NOT expanded, on any route and at any M.
+ *   C[M,N] = ( (A8[M,K] @ value[N,K]^T) * ascale[m] + bias[n] ) + residual[M,N]
+ * A8 / ascale from srgpt_quant_rows_e4m3 (or its fused forms), (W4, wscale8) the ROW-MAJOR codes and scales; bias / residual / C,
+ * the rounding points, the route (256 x 256 tiles, deterministic K slabs: srgpt_gemm_w8a8's for that M, N, K, workspace, device) and
+ * the remark on power-of-two scales are srgpt_gemm_w8a8's.  Products e4m3 x e2m1 x 2^(byte - 127) are exact; the instruction adds the
+ * 128 products of a step in a fixed-width window below the largest one (as under unit scales), so with block scales that differ
+ * inside a row's K tile the small blocks lose low bits the fp32 sum of srgpt_gemm_w4 would keep (tests/test_gpu_gemm_w4a8.py states
+ * the bound).  Opt-in like W8A8: the activations are quantised, the numbers change.  K % 128 == 0, K >= 256, lda % 16 == 0, A8 and W4
+ * 16-byte and wscale8 4-byte aligned; anything else returns SRGPT_ERR_UNSUPPORTED (no fallback), a NULL operand or lda < K / ldc < N
+ * SRGPT_ERR_ARG, before any launch.  Scale bytes 1 .. 254; no byte outside the code and scale arrays is read. */
+int srgpt_gemm_w4a8(const void* A8, const float* ascale, const void* W4, const void* wscale8, const void* bias, const void* residual,
+                    void* C, int M, int N, int K, int lda, int ldc, int out_f32, void* ws, int64_t ws_bytes, srgpt_stream_t stream);
 /* Additions under ABI 9: the `_direct` forms of those four (opt-in) -- the whole-M kernel multiplies the codes too.  Each has the
  * signature, the argument errors, the route and the bits of its plain counterpart above (equal to the bf16 counterpart on
  * srgpt_dequant_mxfp4 of the codes, scale-byte domain 2 .. 252; no byte outside the code and scale arrays is read).  They differ in
@@ -717,9 +731,12 @@ typedef struct {
   const float* const* wgu_scale;
   const void* const* wdown8;
   const float* const* wdown_scale;
-  /* fp8 weights only.  0: W8A16 everywhere (exact weights x bf16 activations -- the default, what the parity tests pin).
-   * 1: prefill quantises each GEMM's input per token (srgpt_quant_rows_e4m3) and multiplies on the fp8 matrix pipe
-   * (srgpt_gemm_w8a8); decode and the all-position lm_head stay W8A16.  Needs hidden, inter and heads * head_dim % 128 == 0. */
+  /* fp8 or MXFP4 weights.  0: bf16 activations everywhere (W8A16 / W4A16: exact weights x bf16 activations -- the default, what the
+   * parity tests pin).  1: prefill, ragged prefill and append prefill quantise each GEMM's input per token (srgpt_quant_rows_e4m3) and
+   * multiply on the fp8 matrix pipe -- srgpt_gemm_w8a8 with fp8 weights, srgpt_gemm_w4a8 with MXFP4 weights (wqkv4 below: W4A8, the
+   * codes times the block scales in the instruction, no bf16 expansion at any row count; mxfp4_direct is then not consulted and the
+   * workspace holds no expansion scratch).  Decode steps and the all-position lm_head keep bf16 activations.  Needs hidden, inter and
+   * heads * head_dim % 128 == 0 (>= 256), else the prefill entries return SRGPT_ERR_UNSUPPORTED. */
   int fp8_act;
   /* ABI 9: rows per weight pass of the decode step's MFMA products.  0 or 16: passes of 16 rows.  32: the wide pass above (the step
    * calls srgpt_gemv_rowss_wide / srgpt_gemv_w4p_wide) -- a step of 17 - 32 rows reads every weight byte once.  Any other value:
@@ -739,7 +756,9 @@ typedef struct {
    * 4); prefill and append prefill run the srgpt_gemm_w4 family -- bit-identical to a bf16 engine on the dequantised weights: the
    * direct-to-LDS kernels (every product of an append, o_proj of the bs = 1 prefill) multiply the codes themselves, the whole-M and
    * 256 x 256 routes still expand each matrix with srgpt_dequant_mxfp4 into a bf16 scratch in the workspace just before its product,
-   * at the price of one more pass over bf16-sized bytes per such matrix.  lm_head stays fp8: lm_head8 + lm_head_scale are required, multiplied as under the fp8
+   * at the price of one more pass over bf16-sized bytes per such matrix.  With fp8_act = 1 (above) the prefill entries are W4A8
+   * instead: per-token e4m3 activations x the codes on the block-scaled MFMA (srgpt_gemm_w4a8), nothing expanded; the decode steps are
+   * the same W4A16 ones.  lm_head stays fp8: lm_head8 + lm_head_scale are required, multiplied as under the fp8
    * format.  Needs dtype SRGPT_BF16, hidden, inter and heads * head_dim multiples of 32, and wqkv8 == NULL. */
   const void* const* wqkv4;
   const void* const* wqkv4_scale;

@@ -1,6 +1,6 @@
 """What llm_weight_format="mxfp4" costs and gains against fp8 and bf16.  -> profiles/mxfp4.txt
 
-    python scripts/time_mxfp4.py [--out profiles/mxfp4.txt] [--rows 259] [--only steps|products|packed|prefill] [--tree DIR]
+    python scripts/time_mxfp4.py [--out profiles/mxfp4.txt] [--rows 259] [--only steps|products|packed|prefill|whole_m|w4a8] [--tree DIR]
 
 VILA1.5-8B geometry (bench.make_cfg, synth_state_dict seed 0), one process, three engines (bf16, fp8, mxfp4) on one card.  Every
 timed call is: the state put back outside the window, device synchronise, an event, the work, an event, synchronise.  The lines of a
@@ -34,6 +34,13 @@ three products alone at `rows` rows, one launch per layer (32 different matrices
 (direct=True), the expansion plus the bf16 launch (the plain entry) and the bf16 launch alone (the bf16 engine's matrix).  Same
 protocol as --only prefill: this tree and, with --tree, the parent commit's checkout (three engines, no products section) in
 alternating fresh processes of one job.
+
+--only w4a8  (-> profiles/mxfp4_w4a8.txt) llm_weight_format="mxfp4_w4a8" (per-token e4m3 activations x the codes on the block-scaled
+MFMA, srgpt_gemm_w4a8) next to bf16, "fp8_w8a8" and "mxfp4" with mxfp4_prefill_direct=True, four engines in one process (three where
+the timed tree does not have the format): the captured batch-1 decode step; the prefill at 1 x, 4 x and 8 x `rows` rows; the 32-row
+append over `rows` cached rows; then the four layer products alone at 8 x `rows` rows, one launch per layer (32 different matrices)
+in a captured graph, us per launch: srgpt_gemm_w4a8, srgpt_gemm_w8a8 and the expansion + srgpt_gemm (srgpt_gemm_w4).  Same protocol
+as --only whole_m; with --tree the parent commit's checkout gives the lines that must not move.
 
 --only steps: the bf16 and fp8 steps alone -- what a tree without the format has; --tree DIR imports the package from another
 checkout (the parent commit), so the same lines can be taken on both in turn.  --only products: the fp8 and mxfp4 steps and the
@@ -106,11 +113,11 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--per-block", type=int, default=10)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed", "prefill", "whole_m"])
+    ap.add_argument("--only", default="all", choices=["all", "steps", "products", "packed", "prefill", "whole_m", "w4a8"])
     ap.add_argument("--tree", default=ROOT, help="the checkout whose package is timed")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", {"packed": "mxfp4_mfma.txt", "prefill": "mxfp4_prefill.txt", "whole_m": "mxfp4_whole_m.txt"}.get(args.only, "mxfp4.txt"))
+        args.out = os.path.join(ROOT, "profiles", {"packed": "mxfp4_mfma.txt", "prefill": "mxfp4_prefill.txt", "whole_m": "mxfp4_whole_m.txt", "w4a8": "mxfp4_w4a8.txt"}.get(args.only, "mxfp4.txt"))
     sys.path.insert(0, os.path.abspath(args.tree))
     sys.path.insert(1, ROOT)
     assert torch.cuda.is_available(), "a timing needs the MI355X"
@@ -127,7 +134,12 @@ def main():
     formats = ["fp8", "mxfp4", "mxfp4p"] if args.only == "packed" else ["fp8", "mxfp4"] if args.only == "products" else ["native", "fp8"] + (["mxfp4"] if have4 and args.only in ("all", "prefill", "whole_m") else [])
     if args.only == "whole_m" and have_direct:
         formats.append("mxfp4d")
-    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed", "mxfp4d": "mxfp4 direct"}
+    have_w4a8 = hasattr(lib, "srgpt_gemm_w4a8")
+    if args.only == "w4a8":
+        formats = ["native", "fp8_w8a8", "mxfp4d"] + (["mxfp4_w4a8"] if have_w4a8 else [])
+    name = {"native": "bf16", "fp8": "fp8", "mxfp4": "mxfp4", "mxfp4p": "mxfp4 packed", "mxfp4d": "mxfp4 direct", "fp8_w8a8": "fp8_w8a8",
+            "mxfp4_w4a8": "mxfp4_w4a8"}
+    base_fmt = "fp8_w8a8" if args.only == "w4a8" else "fp8"
     eng, held = {}, {}
     for f in formats:
         torch.cuda.synchronize()
@@ -195,7 +207,7 @@ def main():
 
     shared = torch.cuda.Stream()  # the product graphs' stream
 
-    section("captured batch-1 decode step, %d cached rows" % args.rows, {name[f]: (f, 1, None) for f in formats}, "fp8")
+    section("captured batch-1 decode step, %d cached rows" % args.rows, {name[f]: (f, 1, None) for f in formats}, base_fmt)
     if args.only == "packed":
         assert eng["mxfp4p"].w.mxfp4_packed
         three = lambda B, T: {name[f]: (f, B, T) for f in ("mxfp4", "mxfp4p", "fp8")}
@@ -330,6 +342,86 @@ def main():
             lines_a[name[f]] = (append, back, e.stream)
         report("%d-row prefill, eager" % args.rows, interleaved(lines_p, args), "fp8")
         report("32-row append over %d cached rows, eager" % args.rows, interleaved(lines_a, args), "fp8")
+
+    if args.only == "w4a8":
+        # ---- prefill at 1 x, 4 x and 8 x rows; the append
+        for B in (1, 4, 8):
+            x = (torch.randn((B, args.rows, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
+            lines_p = {}
+            for f in formats:
+                e = eng[f]
+                st = e.new_state(B, args.rows + 8, 4, ws_tokens=args.rows)
+
+                def prefill(e=e, st=st, x=x):
+                    e.prefill(x, max_new=4, state=st)
+
+                with torch.cuda.stream(e.stream):
+                    prefill()
+                torch.cuda.synchronize()
+                lines_p[name[f]] = (prefill, None, e.stream)
+            report("%d x %d-row prefill (%d rows), eager" % (B, args.rows, B * args.rows), interleaved(lines_p, args), base_fmt)
+            del lines_p, st
+        x = (torch.randn((1, args.rows + 32, cfg.hidden), device=dev, generator=g) * 0.5).to(dt)
+        head, tail = x[:, :args.rows].contiguous(), x[:, args.rows:].contiguous()
+        lines_a = {}
+        for f in formats:
+            e = eng[f]
+            st = e.new_state(1, 512, 4)
+            keep.append(st)
+
+            def append(e=e, st=st):
+                e.append(st, tail)
+
+            def back(st=st):
+                st.pos.fill_(args.rows)
+                st.host_len = [args.rows]
+
+            with torch.cuda.stream(e.stream):
+                e.prefill(head, max_new=4, state=st)
+            torch.cuda.synchronize()
+            lines_a[name[f]] = (append, back, e.stream)
+        report("32-row append over %d cached rows, eager" % args.rows, interleaved(lines_a, args), base_fmt)
+
+    if args.only == "w4a8" and have_w4a8:
+        # ---- the four layer products alone at 8 x rows: W4A8, W8A8, expansion + bf16
+        w4, w8 = eng["mxfp4_w4a8"].w, eng["fp8_w8a8"].w
+        Hd, I, HqD, QW, M = cfg.hidden, cfg.inter, cfg.heads * cfg.head_dim, (cfg.heads + 2 * cfg.kv_heads) * cfg.head_dim, 8 * args.rows
+        shapes = {"q/k/v   [%d, %d]" % (QW, Hd): ("wqkv", QW, Hd, False), "o_proj  [%d, %d] residual" % (Hd, HqD): ("wo", Hd, HqD, True),
+                  "gate/up [%d, %d]" % (2 * I, Hd): ("wgu", 2 * I, Hd, False), "down    [%d, %d] residual" % (Hd, I): ("wdown", Hd, I, True)}
+        say("the four layer products alone at %d rows, one launch per layer (%d matrices) in a captured graph: us per launch, median "
+            "(min .. max of all calls)" % (M, cfg.layers))
+        with torch.cuda.stream(shared):
+            for title, (k, N, K, res) in shapes.items():
+                x = (torch.randn((M, K), device=dev, generator=g) * 0.5).to(dt)
+                a8, asc = ops.quant_rows_e4m3(x)
+                r = (torch.randn((M, N), device=dev, generator=g) * 0.5).to(dt) if res else None
+                out = torch.empty((M, N), device=dev, dtype=dt)
+                expand = torch.empty((N, K), device=dev, dtype=dt)
+                assert not ops.gemm_w4_in_kernel(M, N, K)
+
+                def launches(fmt):
+                    for i in range(cfg.layers):
+                        if fmt == "w4a8":
+                            ops.gemm_w4a8(a8, asc, w4.llm_q4[k][0][i], w4.llm_q4[k][1][i], residual=r, out=out)
+                        elif fmt == "w8a8":
+                            ops.gemm_w8a8(a8, asc, w8.llm_q[k][0][i], w8.llm_q[k][1][i], residual=r, out=out)
+                        else:
+                            ops.gemm_w4(x, w4.llm_q4[k][0][i], w4.llm_q4[k][1][i], residual=r, out=out, expand=expand)
+
+                lines = {}
+                for fmt in ("w4a8", "w8a8", "expand"):
+                    launches(fmt)  # first use of an instance outside the capture
+                    torch.cuda.synchronize()
+                    gr = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(gr, stream=shared):
+                        launches(fmt)
+                    lines[fmt] = (gr.replay, None, shared)
+                reps = interleaved(lines, args)
+                us = lambda f: "%7.2f (%7.2f .. %7.2f)" % (mid(reps[f]) * 1e3 / cfg.layers, min(map(min, reps[f])) * 1e3 / cfg.layers,
+                                                         max(map(max, reps[f])) * 1e3 / cfg.layers)
+                say("  %-34s gemm_w4a8 %s   gemm_w8a8 %s   expansion + bf16 gemm %s   w4a8 / w8a8 %.3f   w4a8 / expansion %.3f" % (
+                    title, us("w4a8"), us("w8a8"), us("expand"), mid(reps["w4a8"]) / mid(reps["w8a8"]), mid(reps["w4a8"]) / mid(reps["expand"])))
+        say()
 
     if args.only == "whole_m" and have_direct:
         # ---- the three whole-M products alone: codes in the kernel, expansion + bf16 launch, bf16 launch alone

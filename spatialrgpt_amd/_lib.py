@@ -123,6 +123,7 @@ _SIGNATURES = {
     "srgpt_gemm_w4_swiglu": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
     "srgpt_gemm_w4_rope_kv_append": (i32, [vp, vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "srgpt_gemm_w4_in_kernel": (i32, [i32, i32, i32, i32, i32, i64]),
+    "srgpt_gemm_w4a8": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "srgpt_gemm_w4_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i64, vp]),
     "srgpt_gemm_w4_norm_direct": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, vp, f32, vp]),
     "srgpt_gemm_w4_swiglu_direct": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),

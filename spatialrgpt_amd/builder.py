@@ -258,6 +258,7 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
                                   "llm_weight_format=\"mxfp4\" (INTEGRATION.md)")
     # load_8bit (bitsandbytes int8 in the reference, builder.py:51-52) maps to the engine's 8-bit option: weight-only OCP
     # fp8 (e4m3fn, one scale per output row) for the LLM matrices the decode step streams
+    # llm_weight_format=: "native", "fp8", "fp8_w8a8", "mxfp4", "mxfp4_w4a8" (PreparedWeights validates the name and the geometry)
     llm_weight_format = "fp8" if load_8bit else kwargs.pop("llm_weight_format", "native")
     if model_base is not None or "lora" in model_name.lower():
         raise NotImplementedError("LoRA / delta checkpoints are out of scope (builder.py:64-139)")

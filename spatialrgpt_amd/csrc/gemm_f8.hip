@@ -14,6 +14,38 @@
 //     2g + 1 of the row: two ds_read_b128 at slot ^ f(row), f chosen for the instruction's 16-lane service groups (see below)
 //   * phase P of a K tile = rows 64 P .. 64 P + 63 of the wave's A panel (4 fragments) x the 4 W fragments of the tile
 // Requirements (checked by the launcher): K % 128 == 0, K >= 256, 16-byte aligned rows.
+//
+// The W4 instance (srgpt_gemm_w4a8: e4m3 activations x MXFP4 weights, W4A8) is the same kernel with the weight operand as the
+// instruction's e2m1 form (blgp:4) and its E8M0 block scale: in the 16x16x128 form lane (r, g) multiplies k = 32 g .. 32 g + 31 of
+// row r, which is exactly one MX block, so the scale bytes as stored ([N, K / 32], 2^(byte - 127)) are the operand and nothing is
+// dequantised anywhere.  What differs from the fp8 instance:
+//   * K order of the mixed form (measured with identity rows, tests/test_gpu_gemm_w4a8.py pins it): the instruction numbers the
+//     128 k of a step by REGISTER HALF first for an 8-register (fp8) operand -- lane g, registers 0 - 3 are k = 16 g .. 16 g + 15,
+//     registers 4 - 7 are k = 64 + 16 g .. 64 + 16 g + 15 -- and plainly for a 4-register (fp4) one: lane g is k = 32 g .. 32 g + 31.
+//     Between two fp8 operands any common order gives the same dot product (the fp8 instance loads slots 2 g and 2 g + 1 on both
+//     sides); against codes the A fragment has to be the instruction's own: 16-byte slots g and 4 + g of the row.
+//   * W tile: 128 codes = 64 bytes per row, 256 rows = 16 KiB per stage.  One 16-byte DMA wave-instruction stages 16 rows = one
+//     MFMA fragment; a thread issues 2 for the whole tile (slot 0) instead of 4 (slots 0 and 1).
+//   * fragment: lane (r, g) reads the 16 bytes of chunk g of its row with one ds_read_b128 = the low four registers of B.
+//     Swizzle: physical chunk = g ^ s(r), s(r) = (4 - (r >> 2)) & 3.  Derivation: a 16-lane service group of ds_read_b128 (the
+//     groups below) covers 256 bytes = all banks once iff its lanes hit 16 different 16-byte slots mod 256, and the slot of lane
+//     (r, g) is 4 (r & 3) + (g ^ s(r)).  Group {0-3, 12-15, 20-27} holds, per residue r & 3, the row quarters q = r >> 2 = 0 and 3
+//     at chunk g and q = 1, 2 at chunk g + 1; group {4-11, 16-19, 28-31} q = 1, 2 at g and q = 0, 3 at g + 1.  So {s(0), s(3),
+//     1 ^ s(1), 1 ^ s(2)} and {s(1), s(2), 1 ^ s(0), 1 ^ s(3)} must each be {0, 1, 2, 3}: s = 0, 3, 2, 1 for q = 0 .. 3 does it
+//     (lanes 32 - 63: the same with every chunk ^ 2).  Applied on the global side of the DMA (the LDS side of a wave-instruction
+//     is linear).  PMC (profiles/mxfp4_w4a8.txt): SQ_LDS_BANK_CONFLICT = 0 at both shapes counted.
+//   * block scales: per K tile a W row has 4 E8M0 bytes = one dword, lane (r, g) needs byte g: the dword is shifted right by 8 g and
+//     passed with opsel 0.  The 256 dwords of a K tile are staged by LDS-DMA of 4 bytes per lane next to the W tile (slot 1, one
+//     instruction per thread): waves 0 - 3 stage the 256 rows, waves 4 - 7 stage them again into a second copy, so that every
+//     wave has the same number of requests in flight (the counted waits are per wave) -- 1 KiB per tile more from L2.  Wave
+//     (wr, wc) reads copy wr.  No ordinary global load in the main loop.
+//   * counted waits, re-derived: per K tile a thread issues W 2 + scales 1 + A 4 = 7 requests (fp8: 8).  Phase 1 of tile kt
+//     issues slots 0, 1, 2 of tile kt + 2 = 2 + 1 + 2 = 5 (fp8: 6), phase 0 of tile kt issues slot 3 of tile kt + 1 = 2.  Phase 0
+//     needs slot 3 of ITS tile (issued a tile ago, read one phase later) with the 5 of the previous phase 1 still flying:
+//     vmcnt(5) (fp8: 6).  Phase 1 needs those 5 (W, scales, A rows of phase 0 of the next tile, read one phase later) with the
+//     2 of this tile's phase 0 flying: vmcnt(2), unchanged.  The prologue leaves the 5 of tile kt0 + 1 flying: vmcnt(5).
+//   * LDS: A 32 KiB + W 16 KiB + scales 2 KiB = 50 KiB per stage, 100 KiB.
+//   * epilogue: unchanged, without the per-column scale (the block scales are in the product).
 #include <type_traits>
 
 #include "common.h"
@@ -31,6 +63,10 @@ constexpr int F_OPER = F_BM * F_BK;                // bytes of one operand tile 
 constexpr int F_BUF = 2 * F_OPER;                  // one K-tile buffer: A then W (64 KiB)
 constexpr int F_LDS = 2 * F_BUF;                   // 128 KiB
 constexpr int F_UNIT = 0x7f7f7f7f;                 // E8M0 block scale 2^0 in every byte
+constexpr int F4_W = F_BN * F_BK / 2;              // W4 instance: bytes of the W code tile (16 KiB)
+constexpr int F4_S = 2 * F_BN * 4;                 // ... and of the two copies of its block scales (2 KiB)
+constexpr int F4_BUF = F_OPER + F4_W + F4_S;       // one K-tile buffer: A, W codes, scales (50 KiB)
+constexpr int F4_LDS = 2 * F4_BUF;                 // 100 KiB
 
 #define F_BARRIER()                      \
   do {                                   \
@@ -45,9 +81,14 @@ constexpr int F_UNIT = 0x7f7f7f7f;                 // E8M0 block scale 2^0 in ev
     __builtin_amdgcn_sched_barrier(0);                        \
   } while (0)
 
+// W4 = false: W is e4m3 bytes [N, K]; no further argument (the instance is the kernel this file had before the W4 one, instruction
+// for instruction).  W4 = true: W is MXFP4 codes [N, K / 2] and the one further argument their E8M0 bytes [N, K / 32].
+template <bool W4, typename... Scales>
 __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char* __restrict__ A, const unsigned char* __restrict__ W,
                                                              const float* __restrict__ ascale, int K, int lda, Epilogue e, int gx,
-                                                             int gy) {
+                                                             int gy, Scales... scales) {
+  static_assert(sizeof...(Scales) == (W4 ? 1 : 0), "the block-scale array is an argument of the W4 instance only");
+  constexpr int BUF = W4 ? F4_BUF : F_BUF;
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -81,19 +122,38 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
   for (int i = 0; i < 4; ++i) {
     const int gw_ = wave + 8 * i;
     const int ga_ = (i & 1) * 16 + (i >> 1) * 8 + wave;
-    pw[i] = W + (size_t)min(n0 + gw_ * 8 + lr, e.N - 1) * K + lc * 16;
+    if constexpr (!W4) pw[i] = W + (size_t)min(n0 + gw_ * 8 + lr, e.N - 1) * K + lc * 16;
     pa[i] = A + (size_t)min(m0 + ga_ * 8 + lr, e.M - 1) * lda + lc * 16;
+  }
+  // W4: one wave-instruction stages 16 rows x 64 B (groups w, w + 8); lane -> row lane >> 2 of the group, physical chunk lane & 3,
+  // which holds logical chunk ^ s(row), s(row) = (4 - (row >> 2)) & 3 (header).  Scales: thread -> row tid & 255, copy tid >> 8
+  const unsigned char* ps = nullptr;
+  if constexpr (W4) {
+    const unsigned char* S = (scales, ...);
+    const int lc4 = (lane & 3) ^ ((4 - (lane >> 4)) & 3);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) pw[i] = W + (size_t)min(n0 + (wave + 8 * i) * 16 + (lane >> 2), e.N - 1) * (K >> 1) + lc4 * 16;
+    ps = S + (size_t)min(n0 + (wave & 3) * 64 + lane, e.N - 1) * (K >> 5);
   }
   auto dma = [&](const void* src, int lds_off) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                      (__attribute__((address_space(3))) void*)(lds + lds_off), 16, 0, 0);
   };
+  auto dma4 = [&](const void* src, int lds_off) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)(lds + lds_off), 4, 0, 0);
+  };
   // stage slot `sl` (compile-time) of K tile kt into buffer kt & 1; which = 0 / 1: first / second instruction of the slot, 2: both
   auto stage = [&](auto sl_c, int kt, int which = 2) {
     constexpr int sl = decltype(sl_c)::value;
     const int k0 = kt * F_BK;
-    const int boff = (kt & 1) * F_BUF;
-    if constexpr (sl == 0) {
+    const int boff = (kt & 1) * BUF;
+    if constexpr (sl == 0 && W4) {  // the whole code tile
+      if (which != 1) dma(pw[0] + (k0 >> 1), boff + F_OPER + (wave + 0) * 1024);
+      if (which != 0) dma(pw[1] + (k0 >> 1), boff + F_OPER + (wave + 8) * 1024);
+    } else if constexpr (sl == 1 && W4) {  // its block scales: one instruction, `which` is 2
+      dma4(ps + (k0 >> 5), boff + F_OPER + F4_W + wave * 256);
+    } else if constexpr (sl == 0) {
       if (which != 1) dma(pw[0] + k0, boff + F_OPER + (wave + 0) * 1024);
       if (which != 0) dma(pw[1] + k0, boff + F_OPER + (wave + 8) * 1024);
     } else if constexpr (sl == 1) {
@@ -118,10 +178,15 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
   // rows 4-11 of the next: with the plain swizzle both land on the same slots (PMC: SQ_LDS_BANK_CONFLICT = 50 % of the LDS
   // cycles); f sends row pairs 2-5 to slots 0-3 and pairs 0, 1, 6, 7 to slots 4-7, each set closed under ^ 2 (and ^ 4, ^ 6)
   const int r16 = lane & 15, g = lane >> 4, sw = ((r16 >> 1) + 6) & 7;
-  const int fo_lo = r16 * 128 + (((2 * g) ^ sw) << 4);      // k = 32 g .. 32 g + 15
-  const int fo_hi = r16 * 128 + (((2 * g + 1) ^ sw) << 4);  // k = 32 g + 16 .. 32 g + 31
+  // W4 (only A is read this way): the A bytes that meet the codes of block g are slots g and 4 + g -- see the header; the same f
+  // is conflict-free for this pair of slots too (every service group still covers the 16 slots of 256 bytes once)
+  const int fo_lo = r16 * 128 + (((W4 ? g : 2 * g) ^ sw) << 4);          // k = 32 g .. 32 g + 15      (W4: 16 g .. 16 g + 15)
+  const int fo_hi = r16 * 128 + (((W4 ? 4 + g : 2 * g + 1) ^ sw) << 4);  // k = 32 g + 16 .. 32 g + 31 (W4: 64 + 16 g .. + 15)
   const int a_base = wr * 128 * 128;                        // + (4 P + mi) * 16 rows
-  const int w_base = F_OPER + wc * 64 * 128;                // + jn * 16 rows
+  const int w_base = F_OPER + wc * 64 * (W4 ? 64 : 128);    // + jn * 16 rows
+  // W4: the 16 bytes of chunk g of row r16 (64-byte rows), and the row's scale dword in copy wr
+  const int fo4 = r16 * 64 + ((g ^ ((4 - (r16 >> 2)) & 3)) << 4);
+  const int so4 = F_OPER + F4_W + wr * 1024 + (wc * 64 + r16) * 4;  // + jn * 16 rows
   auto frag = [&](const char* p) -> i32x8 {
     const i32x4 lo = *reinterpret_cast<const i32x4*>(p + fo_lo);
     const i32x4 hi = *reinterpret_cast<const i32x4*>(p + fo_hi);
@@ -134,6 +199,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   i32x8 fw[4], fa[4];
+  i32x4 fw4[4];       // W4: the code fragments ...
+  unsigned int fs[4];  // ... and their rows' scale dwords, then >> 8 g: byte 0 is the lane's block scale
 
   // ---- prologue: tile kt0 complete, W + A rows 0..63 / 128..191 of tile kt0+1 (the rest is staged in phase 0 of tile kt0) ----
   stage(S0{}, kt0);
@@ -144,7 +211,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
     stage(S0{}, kt0 + 1);
     stage(S1{}, kt0 + 1);
     stage(S2{}, kt0 + 1);
-    F_VMCNT(6);
+    if constexpr (W4) F_VMCNT(5); else F_VMCNT(6);
   } else {
     F_VMCNT(0);
   }
@@ -155,8 +222,14 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
 
   auto phase = [&](auto p_c, int kt, bool more1, bool more2) {
     constexpr int P = decltype(p_c)::value;
-    const char* buf = lds + (kt & 1) * F_BUF;
-    if constexpr (P == 0) {
+    const char* buf = lds + (kt & 1) * BUF;
+    if constexpr (P == 0 && W4) {
+#pragma unroll
+      for (int jn = 0; jn < 4; ++jn) {
+        fw4[jn] = *reinterpret_cast<const i32x4*>(buf + w_base + jn * 16 * 64 + fo4);
+        fs[jn] = *reinterpret_cast<const unsigned int*>(buf + so4 + jn * 16 * 4);
+      }
+    } else if constexpr (P == 0) {
 #pragma unroll
       for (int jn = 0; jn < 4; ++jn) fw[jn] = frag(buf + w_base + jn * 16 * 128);
     }
@@ -164,7 +237,11 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
     for (int mi = 0; mi < 4; ++mi) fa[mi] = frag(buf + a_base + (4 * P + mi) * 16 * 128);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (P == 0) {
-      if (more1) F_VMCNT(6); else F_VMCNT(0);
+      if constexpr (W4) {
+        if (more1) F_VMCNT(5); else F_VMCNT(0);
+      } else {
+        if (more1) F_VMCNT(6); else F_VMCNT(0);
+      }
     } else {
       if (more2) F_VMCNT(2); else F_VMCNT(0);
     }
@@ -173,12 +250,22 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
     F_BARRIER();
     // -------- multiply part: 16 MFMAs on 16 accumulators, this phase's DMA instructions in their shadow --------
     __builtin_amdgcn_s_setprio(1);
+    if constexpr (P == 0 && W4) {
+#pragma unroll
+      for (int jn = 0; jn < 4; ++jn) fs[jn] >>= 8 * g;
+    }
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
-      for (int jn = 0; jn < 4; ++jn)
-        acc[4 * P + mi][jn] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[mi], fw[jn], acc[4 * P + mi][jn], 0, 0, 0, F_UNIT,
-                                                                               0, F_UNIT);
+      for (int jn = 0; jn < 4; ++jn) {
+        if constexpr (W4)  // blgp 4: B is e2m1, its low four registers; A's block scale stays unit
+          acc[4 * P + mi][jn] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              fa[mi], __builtin_shufflevector(fw4[jn], fw4[jn], 0, 1, 2, 3, -1, -1, -1, -1), acc[4 * P + mi][jn], 0, 4, 0, F_UNIT, 0,
+              (int)fs[jn]);
+        else
+          acc[4 * P + mi][jn] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fa[mi], fw[jn], acc[4 * P + mi][jn], 0, 0, 0, F_UNIT,
+                                                                                 0, F_UNIT);
+      }
       // anchor: the MFMA intrinsic has no side effects, and without a use here the compiler sinks all 32 of a K tile below the
       // phase's closing barrier (seen in the ISA) -- the schedule above exists to keep them between the barriers
       asm volatile("" : "+v"(acc[4 * P + mi][0]), "+v"(acc[4 * P + mi][1]), "+v"(acc[4 * P + mi][2]), "+v"(acc[4 * P + mi][3]));
@@ -242,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
 #pragma unroll
   for (int jn = 0; jn < 4; ++jn) {
     ncl[jn] = min(n0 + wc * 64 + jn * 16 + r16, e.N - 1);
-    sc[jn] = e.wscale[ncl[jn]];
+    sc[jn] = W4 ? 1.f : e.wscale[ncl[jn]];
   }
   {
     const bf16_t* bp = bias ? bias : reinterpret_cast<const bf16_t*>(ascale);
@@ -272,7 +359,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f8_256_kernel(const unsigned char
     for (int jn = 0; jn < 4; ++jn)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const float y = rnd<bf16_t>(acc[i][jn][q] * as[i & 1][q] * sc[jn] + bs[jn]);  // the Linear's output is materialised in bf16
+        // the Linear's output is materialised in bf16 (W4: no per-column scale, the block scales are in the product)
+        const float y = W4 ? rnd<bf16_t>(acc[i][jn][q] * as[i & 1][q] + bs[jn]) : rnd<bf16_t>(acc[i][jn][q] * as[i & 1][q] * sc[jn] + bs[jn]);
         v[jn][q] = has_res ? rnd<bf16_t>(y + res[i & 1][jn][q]) : y;
       }
     if (e.out_f32) {
@@ -483,9 +571,37 @@ int srgpt_gemm_w8a8(const void* A8, const float* ascale, const void* W8, const f
   const int gx = cdiv(N, F_BN), gy = cdiv(M, F_BM);
   srgpt_splitk_apply(e, gemm_route_fp8(M, N, K / F_BK, 4, srgpt_device_cus(), ws != nullptr, ws_bytes), ws);
   static std::atomic<uint64_t> attr_done{0};
-  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_f8_256_kernel, F_LDS));
-  hipLaunchKernelGGL(gemm_f8_256_kernel, dim3(gx * gy, e.splits > 1 ? e.splits : 1), dim3(512), F_LDS, s,
+  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_f8_256_kernel<false>, F_LDS));
+  hipLaunchKernelGGL(gemm_f8_256_kernel<false>, dim3(gx * gy, e.splits > 1 ? e.splits : 1), dim3(512), F_LDS, s,
                      (const unsigned char*)A8, (const unsigned char*)W8, ascale, K, lda, e, gx, gy);
+  SRGPT_LAUNCH_CHECK();
+  return srgpt_splitk_finish(e, s, nullptr);
+}
+
+// W4A8: the same product with MXFP4 weights -- codes W4 [N, K / 2] + E8M0 block scales wscale8 [N, K / 32] (include/srgpt.h) in
+// place of (W8, wscale); the block scales are operands of the MFMA, the matrix is not expanded on any route.  Route, slabs and
+// reduction are srgpt_gemm_w8a8's.
+int srgpt_gemm_w4a8(const void* A8, const float* ascale, const void* W4, const void* wscale8, const void* bias, const void* residual,
+                    void* C, int M, int N, int K, int lda, int ldc, int out_f32, void* ws, int64_t ws_bytes, srgpt_stream_t stream) {
+  SRGPT_CHECK(A8 && ascale && W4 && wscale8 && C, SRGPT_ERR_ARG, "srgpt_gemm_w4a8: null pointer");
+  SRGPT_CHECK(M > 0 && N > 0 && K > 0, SRGPT_ERR_ARG, "srgpt_gemm_w4a8: bad shape M=%d N=%d K=%d", M, N, K);
+  SRGPT_CHECK(lda >= K, SRGPT_ERR_ARG, "srgpt_gemm_w4a8: lda < K");
+  SRGPT_CHECK(ldc >= N, SRGPT_ERR_ARG, "srgpt_gemm_w4a8: ldc < N");
+  SRGPT_CHECK(K % F_BK == 0 && K >= 2 * F_BK && lda % 16 == 0 && ((uintptr_t)A8 % 16) == 0 && ((uintptr_t)W4 % 16) == 0 &&
+                  ((uintptr_t)wscale8 % 4) == 0,
+              SRGPT_ERR_UNSUPPORTED,
+              "srgpt_gemm_w4a8: K must be a multiple of 128 (>= 256), the rows of A8 and W4 16-byte and wscale8 4-byte aligned (K=%d lda=%d)",
+              K, lda);
+  Epilogue e{};
+  e.bias = bias, e.residual = residual, e.C = C, e.M = M, e.N = N, e.ldc = ldc, e.act = SRGPT_ACT_NONE, e.out_f32 = out_f32;
+  e.out_mode = SRGPT_OUT_PLAIN, e.splits = 1, e.wscale = nullptr;
+  hipStream_t s = as_stream(stream);
+  const int gx = cdiv(N, F_BN), gy = cdiv(M, F_BM);
+  srgpt_splitk_apply(e, gemm_route_fp8(M, N, K / F_BK, 4, srgpt_device_cus(), ws != nullptr, ws_bytes), ws);
+  static std::atomic<uint64_t> attr_done{0};
+  SRGPT_TRY(srgpt_ensure_dyn_lds(attr_done, (const void*)gemm_f8_256_kernel<true, const unsigned char*>, F4_LDS));
+  hipLaunchKernelGGL((gemm_f8_256_kernel<true, const unsigned char*>), dim3(gx * gy, e.splits > 1 ? e.splits : 1), dim3(512), F4_LDS, s,
+                     (const unsigned char*)A8, (const unsigned char*)W4, ascale, K, lda, e, gx, gy, (const unsigned char*)wscale8);
   SRGPT_LAUNCH_CHECK();
   return srgpt_splitk_finish(e, s, nullptr);
 }

@@ -61,13 +61,14 @@ struct LlmWs {
   void* smpf;        // full sampler: the row's keys and threshold pair (the head of SampleFullWs)
   int* err;          // sticky error word of the decode step (bit 0: a caller-written st->tok outside the table), read by srgpt_llm_decode_sync_state
   float* rowss;   // decode, 2+ rows: two row-statistics tables [batch][SRGPT_ROWSS_STRIDE] (o_proj's and down_proj's output rows)
-  void* a8;       // fp8_act: the e4m3 bytes of the current GEMM input [rows, max K]
+  void* a8;       // fp8_act (W8A8 and W4A8 prefill): the e4m3 bytes of the current GEMM input [rows, max K]
   float* a8s;     // fp8_act: their per-row scales [rows]
   // srgpt_llm_prefill_append: [batch] the validated position every row's segment starts at, and [batch] that + the rows it appends
   // (the keys the row may see, its pos after the call).  They LIVE IN qkvd: the decode step's q/k/v scratch is dead between steps
   // (every step writes it before reading it) and holds >= 12 bytes per row, so the workspace does not grow
   int *app_pos0, *app_kvlen;
-  void* w4;  // MXFP4 weights: the bf16 expansion of the matrix the prefill multiplies next (sized for the largest of the four)
+  void* w4;  // MXFP4 weights, bf16 activations: the bf16 expansion of the matrix the prefill multiplies next (sized for the largest
+             // of the four); NULL with fp8_act (W4A8: nothing expands)
   size_t total;
 };
 LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws) {
@@ -110,7 +111,7 @@ LlmWs carve_llm(const srgpt_llm_weights* w, int batch, int max_tokens, void* ws)
   l.app_pos0 = reinterpret_cast<int*>(l.qkvd);
   l.app_kvlen = l.qkvd ? l.app_pos0 + batch : nullptr;
   l.w4 = nullptr;
-  if (w->wqkv4) {  // last: the layout of every other format is untouched
+  if (w->wqkv4 && !w->fp8_act) {  // last: the layout of every other format is untouched
     const size_t hqd = (size_t)w->heads * w->head_dim;
     size_t n = qkvw * w->hidden;
     if (hqd * w->hidden > n) n = hqd * w->hidden;
@@ -397,8 +398,9 @@ namespace {
 // FMT_W8A8: the prefill's per-token e4m3 activations on the fp8 matrix pipe (include/srgpt.h).  The decode step and the
 // all-position lm_head (fp32 logits, parity hook) are W8A16 under both fp8 formats.  MXFP4 copies present -> FMT_W4A16: the four
 // layer matrices are codes + block scales (srgpt_gemv_w4 in the decode steps, the srgpt_gemm_w4 family in the prefill), lm_head
-// is fp8 and multiplied as under FMT_W8A16.
-enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8, FMT_W4A16 };
+// is fp8 and multiplied as under FMT_W8A16.  FMT_W4A8 (MXFP4 copies and fp8_act) exists in prefill_impl only: the prefill's products
+// are srgpt_gemm_w4a8 on per-token e4m3 activations; llm_format() reports FMT_W4A16 for such weights and every step entry runs that.
+enum LlmFormat { FMT_DTYPE, FMT_W8A16, FMT_W8A8, FMT_W4A16, FMT_W4A8 };
 
 // the format of `w` and the check that fp8 weights are complete, on the host before any launch; `fn`: the entry point the message names
 int llm_format(const srgpt_llm_weights* w, const char* fn, LlmFormat* fmt) {
@@ -432,14 +434,14 @@ struct Mat {
   const float* scale;  // their row scales
   const void* pk;      // packed copy of the fp8 bytes for the MFMA decode kernel, or NULL: stream the row-major ones
   int pk_rows;         // its rows per granule
-  const void* w4;      // MXFP4 codes (FMT_W4A16 only; then w / w8 are not read)
+  const void* w4;      // MXFP4 codes (FMT_W4A16 / FMT_W4A8 only; then w / w8 are not read)
   const void* scale4;  // their E8M0 block scales
 };
 struct LayerMats {
   Mat qkv, o, gu, down;
 };
 LayerMats layer_mats(const srgpt_llm_weights* w, LlmFormat fmt, int i) {
-  if (fmt == FMT_W4A16) {
+  if (fmt == FMT_W4A16 || fmt == FMT_W4A8) {
     auto mat4 = [&](const void* const* W4, const void* const* sc4) { return Mat{nullptr, nullptr, nullptr, nullptr, 0, W4[i], sc4[i]}; };
     return LayerMats{mat4(w->wqkv4, w->wqkv4_scale), mat4(w->wo4, w->wo4_scale), mat4(w->wgu4, w->wgu4_scale),
                      mat4(w->wdown4, w->wdown4_scale)};
@@ -496,9 +498,12 @@ struct Prefill {
   int gemm_w8(const void* a, const Mat& m, const void* res, void* out, int N, int K) const {
     return srgpt_gemm_w8(a, m.w8, m.scale, nullptr, res, out, rows, N, K, K, N, SRGPT_ACT_NONE, 0, l.gws, gws_bytes(), stream);
   }
-  // W8A8: the rows of `a` -> e4m3 bytes + per-token scales (l.a8, l.a8s), and the product of the rows quantised last
+  // W8A8 / W4A8: the rows of `a` -> e4m3 bytes + per-token scales (l.a8, l.a8s), and the product of the rows quantised last with the
+  // format's weights (fp8 bytes + row scales, or MXFP4 codes + block scales)
   int quant(const void* a, int K) const { return srgpt_quant_rows_e4m3(a, l.a8, l.a8s, rows, K, K, stream); }
   int gemm_w8a8(const Mat& m, const void* res, void* out, int N, int K) const {
+    if (fmt == FMT_W4A8)
+      return srgpt_gemm_w4a8(l.a8, l.a8s, m.w4, m.scale4, nullptr, res, out, rows, N, K, K, N, 0, l.gws, gws_bytes(), stream);
     return srgpt_gemm_w8a8(l.a8, l.a8s, m.w8, m.scale, nullptr, res, out, rows, N, K, K, N, 0, l.gws, gws_bytes(), stream);
   }
 
@@ -562,7 +567,7 @@ struct Prefill {
     return gemm_w8(l.act, m.down, l.x, l.x, Hd, I);
   }
 
-  // W8A8, rows of up to 16384 columns: the producer of a GEMM's input rows (RMSNorm, SwiGLU) is fused into their per-token
+  // W8A8 and W4A8 (one sequence: gemm_w8a8 takes the format's weights), rows of up to 16384 columns: the producer of a GEMM's input rows (RMSNorm, SwiGLU) is fused into their per-token
   // quantisation -- the bf16 intermediate is neither written nor read (bit-identical to the two launches: tests/test_gpu_fp8_mfma.py)
   int layer_w8a8(int i) const {
     const LayerMats m = layer_mats(w, fmt, i);
@@ -578,7 +583,7 @@ struct Prefill {
     return gemm_w8a8(m.down, l.x, l.x, Hd, I);
   }
 
-  // W8A8, wider rows (Llama-3-70B: inter 28672): the W8A16 sequence with every product's input quantised by a launch of its own
+  // W8A8 and W4A8, wider rows (Llama-3-70B: inter 28672): the W8A16 sequence with every product's input quantised by a launch of its own
   int layer_w8a8_wide(int i) const {
     const LayerMats m = layer_mats(w, fmt, i);
     SRGPT_TRY(norm(w->attn_norm[i]));
@@ -620,7 +625,8 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
   SRGPT_TRY(llm_format(w, append ? "srgpt_llm_prefill_append" : "srgpt_llm_prefill", &fmt));
   const int dt = w->dtype, Hd = w->hidden, I = w->inter, Hq = w->heads, D = w->head_dim;
   const int B = st->batch, rows = B * T;
-  if (fmt == FMT_W8A8)
+  if (fmt == FMT_W4A16 && w->fp8_act != 0) fmt = FMT_W4A8;  // mxfp4_direct (checked by llm_format) is not consulted
+  if (fmt == FMT_W8A8 || fmt == FMT_W4A8)
     SRGPT_CHECK(Hd % 128 == 0 && I % 128 == 0 && (Hq * D) % 128 == 0 && Hd >= 256 && I >= 256 && Hq * D >= 256,
                 SRGPT_ERR_UNSUPPORTED, "srgpt_llm_prefill: fp8_act needs hidden, inter and heads * head_dim to be multiples of 128");
   const bool wide = Hd > 16384 || I > 16384;  // the fused quantisation kernels hold rows of up to 16384 columns
@@ -656,7 +662,8 @@ static int prefill_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const v
     switch (fmt) {
       case FMT_DTYPE: SRGPT_TRY(p.layer_dtype(i)); break;
       case FMT_W8A16: SRGPT_TRY(p.layer_w8a16(i)); break;
-      case FMT_W8A8: SRGPT_TRY(wide ? p.layer_w8a8_wide(i) : p.layer_w8a8(i)); break;
+      case FMT_W8A8:
+      case FMT_W4A8: SRGPT_TRY(wide ? p.layer_w8a8_wide(i) : p.layer_w8a8(i)); break;
       case FMT_W4A16: SRGPT_TRY(p.layer_w4a16(i)); break;
     }
     if (hidden_out)

@@ -261,6 +261,8 @@ class SrgptEngine:
             raise NotImplementedError(f"{cfg.region_extractor_type} not implemented")  # base_extractor.py:160-161
         if cfg.select_feature not in ("cls_patch", "patch"):
             raise ValueError(f"Unexpected select feature: {cfg.select_feature}")
+        # llm_weight_format: "native", "fp8", "fp8_w8a8", "mxfp4" or "mxfp4_w4a8" (= "mxfp4" whose prefill multiplies per-token e4m3
+        # activations with the codes on the block-scaled MFMA, nothing expanded; the batched choice) -- weights.py
         # decode_layout "packed": fp8 LLM weights also get MFMA-operand-order copies for the batched decode step (weights.py)
         # pack13: bf16 weights also get lossless 13-bit copies the batch-1 decode step streams (weights.py; None: its default, True / False, "all" for tests)
         # decode_pass_rows: 16, or 32 = steps of 17 - 32 rows stream every weight matrix once (weights.py; read-only afterwards)

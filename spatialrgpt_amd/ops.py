@@ -536,6 +536,30 @@ def gemm_w8a8(a8, ascale, w8, wscale, bias=None, residual=None, out=None, out_f3
     return out
 
 
+def gemm_w4a8(a8, ascale, w4, wscale8, bias=None, residual=None, out=None, out_f32=False, ws=None):
+    """gemm_w8a8 with MXFP4 weights (W4A8): ((fp8(a8) @ dequant(w4, wscale8).T) * ascale[:,None] + bias) + residual on the
+    block-scaled fp8 x fp4 MFMA -- a8 uint8 [M,K] + ascale fp32 [M] as for gemm_w8a8, w4 uint8 [N,K/2] codes and wscale8 uint8
+    [N,K/32] E8M0 bytes as quantize_mxfp4_rows stores them; nothing is expanded.  bias / residual / out / ws: as for gemm_w8a8."""
+    _dev(a8, ascale, w4, wscale8, bias, residual)
+    if a8.dtype != torch.uint8 or ascale.dtype != torch.float32:
+        raise ValueError("gemm_w4a8: a8 must be uint8, ascale fp32")
+    _check_mxfp4("gemm_w4a8", w4, wscale8)
+    for name, t in (("bias", bias), ("residual", residual)):
+        if t is not None and t.dtype != torch.bfloat16:
+            raise ValueError(f"gemm_w4a8: {name} must be bf16")
+    M, K = a8.shape
+    N = w4.shape[0]
+    if w4.shape[1] * 2 != K:
+        raise ValueError(f"gemm_w4a8: a8 has K = {K}, the codes {w4.shape[1] * 2}")
+    assert a8.stride(1) == 1 and ascale.numel() == M
+    if out is None:
+        out = torch.empty((M, N), device=a8.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
+    ws, ws_bytes = _ws_arg(a8.device, M, N, ws=ws)
+    L.check(L.load().srgpt_gemm_w4a8(_p(a8), _p(ascale), _p(w4), _p(wscale8), _p(bias), _p(residual), _p(out), M, N, K,
+                                     a8.stride(0), out.stride(0), int(out_f32), ws, ws_bytes, _stream()))
+    return out
+
+
 def layernorm(x, w, b, eps, act=L.ACT_NONE, out=None):
     _dev(x, w, b)
     _same_dtype("layernorm", x, weight=w, bias=b, out=out)

@@ -68,6 +68,11 @@ class PreparedWeights:
         values (ops.quantize_mxfp4_rows; include/srgpt.h, srgpt_gemv_w4), a quarter of the bf16 bytes and the only copy in HBM;
         lm_head is held as under "fp8".  Decode streams the codes (srgpt_gemv_w4); prefill expands each matrix into a bf16 scratch
         just before its product.  Opt-in, it changes the numbers; its accuracy cost on a trained checkpoint is unmeasured.
+        "mxfp4_w4a8": the same codes and scales (`llm_weight_format` then reads "mxfp4" and `fp8_act` True, as "fp8_w8a8" reads
+        "fp8"); prefill, ragged prefill and append prefill quantise every GEMM input per token to e4m3 and multiply it with the
+        codes on the block-scaled fp8 x fp4 MFMA (srgpt_gemm_w4a8) -- no bf16 expansion at any row count and no expansion scratch in
+        the workspace; the decode steps are "mxfp4"'s.  Widths must be multiples of 128.  Changes the prefill's numbers once more
+        (quantised activations); the batched choice, "mxfp4" + mxfp4_prefill_direct being the batch-1 one.
         pack13 (bf16 engines, "native" only): also hold the PACK13_PRODUCTS as lossless 13-bit codes and bind them, so that the
         batch-1 decode step streams 0.8125 of their bytes and computes the same bits.  None: PACK13_DEFAULT; True / False: on /
         off.  On packs the matrices whose copy is smaller than the matrix (K % 2048 == 0).  "all" is for tests: q/k/v and
@@ -94,7 +99,7 @@ class PreparedWeights:
         if decode_pass_rows not in (16, 32) or isinstance(decode_pass_rows, bool):
             raise ValueError(f"decode_pass_rows must be 16 or 32, got {decode_pass_rows!r}")
         self._decode_pass_rows = int(decode_pass_rows)
-        if mxfp4_prefill_direct and llm_weight_format != "mxfp4":
+        if mxfp4_prefill_direct and llm_weight_format != "mxfp4":  # (under "mxfp4_w4a8" no product expands: it would do nothing)
             raise ValueError(f"mxfp4_prefill_direct needs llm_weight_format='mxfp4', got {llm_weight_format!r}")
         self._mxfp4_prefill_direct = bool(mxfp4_prefill_direct)
         self.cfg, self.device, self.dtype = cfg, torch.device(device), dtype
@@ -108,15 +113,16 @@ class PreparedWeights:
         self.vit = self.llm = None
         self.vocab = 0
         self.rope_len = 0
-        if llm_weight_format not in ("native", "fp8", "fp8_w8a8", "mxfp4"):
+        if llm_weight_format not in ("native", "fp8", "fp8_w8a8", "mxfp4", "mxfp4_w4a8"):
             raise ValueError(f"unknown llm_weight_format {llm_weight_format!r}")
         # "fp8_w8a8": the same fp8 weights; prefill additionally quantises every GEMM input per token to e4m3 and multiplies on
         # the fp8 matrix pipe (srgpt_gemm_w8a8) -- opt-in, it changes the numbers; decode stays W8A16
-        self.fp8_act = llm_weight_format == "fp8_w8a8"
+        # "mxfp4_w4a8": the same with the MXFP4 weights (srgpt_gemm_w4a8); decode stays W4A16
+        self.fp8_act = llm_weight_format in ("fp8_w8a8", "mxfp4_w4a8")
         if self.fp8_act:
-            llm_weight_format = "fp8"
             if cfg.hidden % 128 or cfg.inter % 128 or (cfg.heads * cfg.head_dim) % 128:
-                raise ValueError("fp8_w8a8 needs hidden, inter and heads * head_dim to be multiples of 128")
+                raise ValueError(f"{llm_weight_format} needs hidden, inter and heads * head_dim to be multiples of 128")
+            llm_weight_format = llm_weight_format.split("_")[0]
         if llm_weight_format == "fp8" and dtype != torch.bfloat16:
             raise ValueError("fp8 LLM weights need a bf16 engine")
         if llm_weight_format == "mxfp4":

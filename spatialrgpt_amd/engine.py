@@ -21,6 +21,7 @@ from . import _lib as L
 from . import ops
 from .config import SrgptConfig
 from .constants import IGNORE_INDEX, IMAGE_TOKEN_INDEX
+from .generation import StopJudge
 from .weights import PreparedWeights
 
 
@@ -119,17 +120,21 @@ class DecodeState:
         self.logits_proc.set(**proc)
         self.proc = self.logits_proc.ptr()
 
+    def _graph(self, key: str, create):
+        """the captured graph `key`; first use: create(stream, out) captures it"""
+        if key not in self.graphs:
+            g = L.vp()
+            L.check(create(ops._stream(), C.byref(g)))
+            self.graphs[key] = g
+        return self.graphs[key]
+
     def ensure_graph(self):
         key = "greedy" if not self.c.sampling else ("sample_full" if self.sampler == L.SAMPLER_FULL else "sample")
         if self.proc:
             key += "+proc"
-        if key not in self.graphs:
-            g = L.vp()
-            lib, w = L.load(), self._eng.w.llm
-            # proc = None goes as NULL: exactly the graph of the _ex form (same launches)
-            L.check(lib.srgpt_llm_decode_graph_create_proc(C.byref(w), C.byref(self.c), self.sampler, self.proc, ops._stream(), C.byref(g)))
-            self.graphs[key] = g
-        return self.graphs[key]
+        # proc = None goes as NULL: exactly the graph of the _ex form (same launches)
+        return self._graph(key, lambda stream, g: L.load().srgpt_llm_decode_graph_create_proc(
+            C.byref(self._eng.w.llm), C.byref(self.c), self.sampler, self.proc, stream, g))
 
     def ensure_lookup(self, K: int, max_ngram: int, prompt_ids: Optional[torch.Tensor]):
         """The lookup step's buffers (first use: workspace -- zeroed, it holds arrival tickets --, the [T, vocab] logits, the stats
@@ -210,12 +215,8 @@ class DecodeState:
 
     def ensure_lookup_batch_graph(self):
         """the captured batched lookup step (greedy)"""
-        if "lookup_batch" not in self.graphs:
-            g = L.vp()
-            L.check(L.load().srgpt_llm_lookup_graph_create_batch(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup_b["c"]),
-                                                                 ops._stream(), C.byref(g)))
-            self.graphs["lookup_batch"] = g
-        return self.graphs["lookup_batch"]
+        return self._graph("lookup_batch", lambda stream, g: L.load().srgpt_llm_lookup_graph_create_batch(
+            C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup_b["c"]), stream, g))
 
     def lookup_sample_ws(self):
         """device pointer of the running request's sampler workspace for the lookup step; None: a greedy request"""
@@ -224,12 +225,8 @@ class DecodeState:
     def ensure_lookup_graph(self):
         """the captured lookup step of the running request's pick: greedy, or sampled by the state's sampler kind"""
         key = "lookup" if not self.c.sampling else ("lookup+sample_full" if self.sampler == L.SAMPLER_FULL else "lookup+sample")
-        if key not in self.graphs:
-            g = L.vp()
-            L.check(L.load().srgpt_llm_lookup_graph_create_ex(C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup["c"]),
-                                                              self.sampler, self.lookup_sample_ws(), ops._stream(), C.byref(g)))
-            self.graphs[key] = g
-        return self.graphs[key]
+        return self._graph(key, lambda stream, g: L.load().srgpt_llm_lookup_graph_create_ex(
+            C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup["c"]), self.sampler, self.lookup_sample_ws(), stream, g))
 
     def __del__(self):
         try:
@@ -716,7 +713,7 @@ class SrgptEngine:
         Philox counter + t), the drafts are kept up to the first draw that differs -- generated id i is a draw from the model's
         distribution at counter c0 + i, as in the plain sampled loop.  self.last_lookup_stats = what it did.
         A state of 2+ rows (greedy, batch * (K + 1) <= 16; lookup also carries prompt_ids [B, P] and prompt_mask): batched lookup
-        steps (srgpt_llm_lookup_step_batch, _lookup_loop_batch) -- every row drafted from its own ids and advanced by its own
+        steps (srgpt_llm_lookup_step_batch) -- every row drafted from its own ids and advanced by its own
         accepted drafts; ids, padding and length as the plain batched loop's."""
         batched = lookup is not None and st.batch > 1  # the caller opted in (LlavaLlamaModel.lookup_batch; generation.plan_lookup)
         if lookup is not None and logits_proc is not None:
@@ -729,9 +726,7 @@ class SrgptEngine:
             st.set_sampling(sampling)
             st.set_logits_proc(logits_proc)
             try:
-                if batched:
-                    n_keep, eos, n_rows = self._lookup_loop_batch(st, max_new_tokens, eos_token_id, stopping_criteria, lookup)
-                elif lookup is not None:
+                if lookup is not None:
                     n_keep, eos, n_rows = self._lookup_loop(st, max_new_tokens, eos_token_id, stopping_criteria, lookup)
                 else:
                     n_keep, eos, n_rows = self._decode_loop(st, max_new_tokens, eos_token_id, stopping_criteria)
@@ -763,241 +758,80 @@ class SrgptEngine:
         return out
 
     def _decode_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria):
-        lib = L.load()
-        stream = ops._stream()
+        lib, stream = L.load(), ops._stream()
         L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))  # proc None: NULL
-        eos = None  # ordered list of EOS ids (HF accepts an int or a list; Llama-3 checkpoints list two)
-        if eos_token_id is not None:
-            eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
-            eos = eos or None
-        interactive = stopping_criteria is not None and len(stopping_criteria) > 0
+        judge = StopJudge(st.batch, eos_token_id, stopping_criteria, max_new_tokens)
         graph = st.ensure_graph() if self.use_graph and max_new_tokens > 1 else None
-        B = st.batch
-        finished = [False] * B
-        n_rows = [None] * B  # ids a row keeps: up to and including its first EOS
 
-        def launch(n):
+        def launch(n=1):
             if graph is not None:
                 L.check(lib.srgpt_graph_launch(graph, n, stream))
             else:
                 for _ in range(n):
                     L.check(lib.srgpt_llm_decode_step_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, st.proc, stream))
 
-        def judge(ids, lo, hi):
-            """host-side EOS / stopping-criteria scan of steps [lo, hi) of `ids` (CPU int64 [B, >= hi]); -> stop step or None."""
-            for s_ in range(lo, hi):
-                for b in range(B):
-                    if eos and not finished[b] and int(ids[b, s_]) in eos:
-                        finished[b] = True
-                        n_rows[b] = s_ + 1
-                if eos and all(finished):
-                    return s_ + 1
-                if interactive:
-                    # HF passes only the generated ids when generate() was fed inputs_embeds (SURVEY 9.11)
-                    full = ids[:, :s_ + 1]
-                    for crit in stopping_criteria:
-                        r = crit(full, None)
-                        if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
-                            return s_ + 1
-            return None
-
-        if interactive or eos:
+        if judge.can_stop:
             # anything that can end the request early is judged EVERY step, one step behind the device.  Round 3 scanned for EOS
             # every `check_every` = 8 steps: a request that ends in EOS -- the reference's real eval mode, eval_spatial.py:221-237,
             # answers of a few dozen tokens -- ran 3.5 steps (10 ms at 2.9 ms per token) past its end on average; the run-ahead
             # loop wastes at most ONE step and costs 1.6 % while it runs (profiles/r04_sampling.txt)
-            n_keep = self._decode_loop_run_ahead(st, max_new_tokens, launch, judge)
-            return n_keep, eos, [n_keep if n is None else n for n in n_rows]
+            n_keep = self._run_ahead(judge, launch, _ColumnSource(st, max_new_tokens))
+            return n_keep, judge.eos, judge.rows(n_keep)
         # nothing can stop the request early (the benchmark: EOS disabled): all steps are queued at once, no host work per token
         if max_new_tokens > 1:
             launch(max_new_tokens - 1)
-        return max_new_tokens, eos, [max_new_tokens] * B
+        return max_new_tokens, judge.eos, [max_new_tokens] * st.batch
 
     def _lookup_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria, lookup: dict):
-        """The run-ahead loop over lookup steps.  A step emits a number of tokens only the device knows, so every round reads the step
-        counter, the stats block and the ids row behind the previous step through the copy stream -- after the NEXT step went out --
-        and judges every new id in order (EOS ids, then the stopping criteria: the order HF sees them in).  The first stop, or
-        max_new_tokens ids, ends the request; what the device emitted behind that (the rest of an accepted run, the step that ran
-        ahead) lies beyond the kept ids and the live cache rows, exactly like the plain loop's one step ahead.  With nothing that can
-        stop the request the loop still reads the counter: how many steps max_new_tokens ids take is not known in advance."""
-        lib, stream = L.load(), ops._stream()
-        eos = None
-        if eos_token_id is not None:
-            eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
-            eos = eos or None
-        lk = st.ensure_lookup(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"))
+        """The run-ahead loop over lookup steps: srgpt_llm_lookup_step_ex for one sequence (greedy or sampled),
+        srgpt_llm_lookup_step_batch for B rows (greedy).  A step emits a number of tokens per row only the device knows, so every
+        round reads the per-row counts (st.step / lk["steps"]), the stats block and out_ids[:, :max_new_tokens] behind the previous
+        step (_PrefixSource) -- after the NEXT step went out -- and StopJudge judges them as the plain loop would: the same ids, stop
+        step and state.  What the device emitted behind the kept ids (the rest of an accepted run, the step that ran ahead, rows
+        that accepted more than the others) lies beyond them and the live cache rows, exactly like the plain loop's one step ahead:
+        truncate() rolls the device positions back.  A row at st.max_new ids is frozen on the device until the others arrive.
+        With nothing that can stop the request the loop still reads the counts: how many steps max_new_tokens ids take is not
+        known in advance."""
+        lib, stream, B = L.load(), ops._stream(), st.batch
+        judge = StopJudge(B, eos_token_id, stopping_criteria, max_new_tokens)
+        if B == 1:
+            lk = st.ensure_lookup(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"))
+        else:
+            lk = st.ensure_lookup_batch(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"), lookup.get("prompt_mask"))
         L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, None, stream))
-        graph = st.ensure_lookup_graph() if self.use_graph and max_new_tokens > 1 else None
+        if B > 1:
+            lk["steps"].fill_(1)  # every row has emitted its first id
+        graph = None
+        if self.use_graph and max_new_tokens > 1:
+            graph = st.ensure_lookup_graph() if B == 1 else st.ensure_lookup_batch_graph()
 
         def launch():
             if graph is not None:
                 L.check(lib.srgpt_graph_launch(graph, 1, stream))
-            else:
+            elif B == 1:
                 L.check(lib.srgpt_llm_lookup_step_ex(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), st.sampler,
                                                      st.lookup_sample_ws(), stream))
-
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-        host_ids = torch.empty((1, max_new_tokens), dtype=torch.int64).pin_memory()
-        host_cnt = torch.empty((4,), dtype=torch.int32).pin_memory()  # the step counter, then the stats block
-        dec = torch.cuda.current_stream(self.device)
-
-        def mark():
-            ev = torch.cuda.Event()
-            ev.record(dec)
-            return ev
-
-        def fetch(ev):
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(ev)
-                host_cnt[:1].copy_(st.step, non_blocking=True)
-                host_cnt[1:].copy_(lk["stats"], non_blocking=True)
-                host_ids[0].copy_(st.out_ids[0, :max_new_tokens], non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(self._copy_stream)
-            return done
-
-        def finish(n_keep, stop):
-            dec.wait_stream(self._copy_stream)
-            steps, drafted, accepted = (int(v) for v in host_cnt[1:].tolist())
-            self.last_lookup_stats = dict(steps=steps, tokens=n_keep, drafted=drafted, accepted=accepted)
-            return n_keep, eos, [n_keep]
-
-        interactive = stopping_criteria is not None and len(stopping_criteria) > 0
-        ev, judged = mark(), 0  # the first token (srgpt_llm_sample_first) is on the stream
-        for _ in range(max_new_tokens + 1):  # every step emits at least one id
-            ready = fetch(ev)
-            if max_new_tokens > 1:
-                launch()  # run ahead: the next step goes out before the ids behind `ev` are judged
-                ev = mark()
-            ready.synchronize()
-            have = min(int(host_cnt[0]), max_new_tokens)
-            for t in range(judged, have):
-                if eos and int(host_ids[0, t]) in eos:
-                    return finish(t + 1, True)
-                if interactive:
-                    full = host_ids[:, :t + 1]  # HF passes only the generated ids when generate() was fed inputs_embeds
-                    for crit in stopping_criteria:
-                        r = crit(full, None)
-                        if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
-                            return finish(t + 1, True)
-            judged = have
-            if judged >= max_new_tokens:
-                return finish(max_new_tokens, False)
-        raise RuntimeError("lookup decode loop: the device step counter did not advance")
-
-    def _lookup_loop_batch(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria, lookup: dict):
-        """_lookup_loop for B rows (srgpt_llm_lookup_step_batch): the same run-ahead shape, but every row emits its own number of ids
-        per step, so every round fetches the per-row counts `steps` [B], the stats block and out_ids[:, :max_new_tokens] behind the
-        previous step -- after the next step went out.  Judging reproduces the plain batched loop's: EOS per row over that row's new
-        ids in order (the first one sets the ids the row keeps); the stopping criteria per COLUMN, in column order, on the columns
-        every row has reached, with ids[:, :s + 1] -- the tensors the plain loop hands them, whose stop column they therefore name.
-        The request ends at the first criteria stop, at the column the last row finished in, or with max_new_tokens columns filled.
-        Rows that accepted more ran ahead of the kept columns; their device positions are rolled back by truncate() like the plain
-        loop's one step ahead, and a row at st.max_new ids is frozen on the device until the others arrive."""
-        lib, stream, B = L.load(), ops._stream(), st.batch
-        eos = None
-        if eos_token_id is not None:
-            eos = [int(e) for e in eos_token_id] if isinstance(eos_token_id, (list, tuple, set)) else [int(eos_token_id)]
-            eos = eos or None
-        lk = st.ensure_lookup_batch(lookup["K"], lookup["max_ngram"], lookup.get("prompt_ids"), lookup.get("prompt_mask"))
-        L.check(lib.srgpt_llm_sample_first_proc(C.byref(self.w.llm), C.byref(st.c), st.sampler, None, stream))
-        lk["steps"].fill_(1)  # every row has emitted its first id
-        graph = st.ensure_lookup_batch_graph() if self.use_graph and max_new_tokens > 1 else None
-
-        def launch():
-            if graph is not None:
-                L.check(lib.srgpt_graph_launch(graph, 1, stream))
             else:
                 L.check(lib.srgpt_llm_lookup_step_batch(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), stream))
 
-        if getattr(self, "_copy_stream", None) is None:
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-        # out_ids[:, :max_new_tokens] is strided when the state holds more ids per row: gathered into a contiguous device scratch on the
-        # copy stream, it leaves as one contiguous copy into pinned memory (the reason _decode_loop_run_ahead gives)
-        host_ids = torch.empty((B, max_new_tokens), dtype=torch.int64).pin_memory()
-        scratch = torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device)
-        host_cnt = torch.empty((B + 3,), dtype=torch.int32).pin_memory()  # the rows' counts, then the stats block
-        dec = torch.cuda.current_stream(self.device)
+        source = _PrefixSource(st, max_new_tokens, st.step if B == 1 else lk["steps"], lk["stats"])
+        n_keep = self._run_ahead(judge, launch, source)
+        rows = judge.rows(n_keep)
+        steps, drafted, accepted = source.stats()
+        self.last_lookup_stats = dict(steps=steps, tokens=sum(rows), drafted=drafted, accepted=accepted, **({"batch": B} if B > 1 else {}))
+        return n_keep, judge.eos, rows
 
-        def mark():
-            ev = torch.cuda.Event()
-            ev.record(dec)
-            return ev
-
-        def fetch(ev):
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(ev)
-                host_cnt[:B].copy_(lk["steps"], non_blocking=True)
-                host_cnt[B:].copy_(lk["stats"], non_blocking=True)
-                scratch.copy_(st.out_ids[:, :max_new_tokens])
-                host_ids.copy_(scratch, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(self._copy_stream)
-            return done
-
-        n_rows = [None] * B  # ids a row keeps: up to and including its first EOS
-
-        def finish(n_keep):
-            dec.wait_stream(self._copy_stream)
-            steps, drafted, accepted = (int(v) for v in host_cnt[B:].tolist())
-            rows = [n_keep if n is None else min(n, n_keep) for n in n_rows]
-            self.last_lookup_stats = dict(steps=steps, tokens=sum(rows), drafted=drafted, accepted=accepted, batch=B)
-            return n_keep, eos, rows
-
-        interactive = stopping_criteria is not None and len(stopping_criteria) > 0
-        ev = mark()  # the first token of every row (srgpt_llm_sample_first) is on the stream
-        seen, col = [0] * B, 0  # ids of row b scanned for EOS; columns judged by the criteria
-        for _ in range(max_new_tokens + 1):  # every step emits at least one id per live row
-            ready = fetch(ev)
-            if max_new_tokens > 1:
-                launch()  # run ahead: the next step goes out before the ids behind `ev` are judged
-                ev = mark()
-            ready.synchronize()
-            have = [min(int(v), max_new_tokens) for v in host_cnt[:B].tolist()]
-            if eos:
-                for b in range(B):
-                    for t in range(seen[b], have[b]):
-                        if n_rows[b] is None and int(host_ids[b, t]) in eos:
-                            n_rows[b] = t + 1
-            seen = have
-            reached = min(have)
-            # the column the last row finished in ends the request there (the plain loop judges a column's EOS ids before its criteria)
-            last = max(n_rows) if eos and all(n is not None for n in n_rows) else None
-            if interactive:
-                while col < reached:
-                    if last is not None and last == col + 1:
-                        return finish(last)
-                    full = host_ids[:, :col + 1]  # HF passes only the generated ids when generate() was fed inputs_embeds
-                    for crit in stopping_criteria:
-                        r = crit(full, None)
-                        if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
-                            return finish(col + 1)
-                    col += 1
-            elif last is not None:  # nothing judges the columns in between: every row's kept ids are known
-                return finish(last)
-            if reached >= max_new_tokens:
-                return finish(max_new_tokens)
-        raise RuntimeError("batched lookup decode loop: a row's device step counter did not advance")
-
-    def _decode_loop_run_ahead(self, st: DecodeState, max_new_tokens: int, launch, judge) -> int:
+    def _run_ahead(self, judge: StopJudge, launch, source) -> int:
         """A stopping criterion (the demo's KeywordsStoppingCriteria, gradio_web_server_multi.py:195-197; model_vqa.py's conv stop
         strings) is host Python over the ids so far: HF evaluates it after every token.  Round 3 did launch -> D2H -> Python ->
         launch, serialising the device behind the host every token.  Here step t + 1 is launched BEFORE step t is judged: the
         ids of step t travel on a side stream behind an event recorded after step t (so the copy does not wait for step t + 1),
-        the criteria run while step t + 1 computes, and a stop discards the one step that ran ahead (it only wrote cache rows
-        and ids beyond the kept prefix).  Same ids, same stop step as the serial loop."""
-        B = st.batch
+        the judge runs while step t + 1 computes, and a stop discards the one step that ran ahead (it only wrote cache rows
+        and ids beyond the kept prefix).  Same ids, same stop step as the serial loop.
+        `launch()` queues one step; `source` (_ColumnSource / _PrefixSource) queues the copies of what a step left and reads them
+        on the host.  -> the columns the request keeps."""
         if getattr(self, "_copy_stream", None) is None:
             self._copy_stream = torch.cuda.Stream(device=self.device)
-        # One step's ids are the COLUMN out_ids[:, t]: a strided source for B > 1, and torch serves a strided D2H through a pageable
-        # temporary plus a host-side copy that no event covers (ADVICE r4).  So the column is gathered into a contiguous device
-        # scratch on the copy stream and leaves as ONE contiguous copy into a pinned, step-major buffer: the `done` event covers
-        # everything the judge reads.
-        host_t = torch.empty((max_new_tokens, B), dtype=torch.int64).pin_memory()
-        host = host_t.t()  # [B, steps] view for the judge (HF criteria index ids[b, -n:])
-        scratch = torch.empty((B,), dtype=torch.int64, device=self.device)
-        assert host_t.is_pinned() and host_t[0].is_contiguous() and scratch.is_contiguous()
         dec = torch.cuda.current_stream(self.device)
 
         def mark():
@@ -1005,26 +839,85 @@ class SrgptEngine:
             ev.record(dec)
             return ev
 
-        def fetch(col, ev):
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(ev)
-                scratch.copy_(st.out_ids[:, col])                 # device gather (copy stream: ordered behind the previous D2H)
-                host_t[col].copy_(scratch, non_blocking=True)     # contiguous, pinned: truly asynchronous
-                done = torch.cuda.Event()
-                done.record(self._copy_stream)
-            return done
+        ev = mark()  # the first token of every row (srgpt_llm_sample_first) is on the stream
+        try:
+            for t in range(judge.max_new_tokens + 1):  # every step emits at least one id per live row
+                with torch.cuda.stream(self._copy_stream):
+                    self._copy_stream.wait_event(ev)
+                    source.queue(t)
+                    ready = torch.cuda.Event()
+                    ready.record(self._copy_stream)
+                if source.more(t):
+                    launch()  # run ahead: the next step goes out before the ids behind `ev` are judged
+                    ev = mark()
+                ready.synchronize()
+                n_keep = judge.feed(source.ids, source.have(t))
+                if n_keep is not None:
+                    return n_keep
+            raise RuntimeError("decode loop: a row's device step counter did not advance")
+        finally:
+            dec.wait_stream(self._copy_stream)
 
-        ev = mark()            # step 0 (srgpt_llm_sample_first) is on the stream
-        produced = 1
-        for t in range(max_new_tokens):
-            ready = fetch(t, ev)
-            if produced < max_new_tokens:  # run ahead: step t + 1 goes out before step t is judged
-                launch(1)
-                produced += 1
-                ev = mark()
-            ready.synchronize()
-            if judge(host, t, t + 1) is not None:
-                dec.wait_stream(self._copy_stream)
-                return t + 1
-        dec.wait_stream(self._copy_stream)
-        return max_new_tokens
+
+class _ColumnSource:
+    """What a PLAIN step leaves, for _run_ahead: after step t every row has t + 1 ids (the host knows without a read-back), so only
+    the column out_ids[:, t] travels, and the last step goes out in round max_new_tokens - 2."""
+
+    def __init__(self, st: DecodeState, max_new_tokens: int):
+        # One step's ids are the COLUMN out_ids[:, t]: a strided source for B > 1, and torch serves a strided D2H through a pageable
+        # temporary plus a host-side copy that no event covers (ADVICE r4).  So the column is gathered into a contiguous device
+        # scratch on the copy stream and leaves as ONE contiguous copy into a pinned, step-major buffer: the round's event covers
+        # everything the judge reads.
+        self.st, self.n = st, max_new_tokens
+        self.host_t = torch.empty((max_new_tokens, st.batch), dtype=torch.int64).pin_memory()
+        self.ids = self.host_t.t()  # [B, steps] view for the judge (HF criteria index ids[b, -n:])
+        self.scratch = torch.empty((st.batch,), dtype=torch.int64, device=st.out_ids.device)
+        assert self.host_t.is_pinned() and self.host_t[0].is_contiguous() and self.scratch.is_contiguous()
+
+    def more(self, t: int) -> bool:
+        return t + 1 < self.n
+
+    def queue(self, t: int):
+        self.scratch.copy_(self.st.out_ids[:, t])               # device gather (copy stream: ordered behind the previous D2H)
+        self.host_t[t].copy_(self.scratch, non_blocking=True)   # contiguous, pinned: truly asynchronous
+
+    def have(self, t: int) -> List[int]:
+        return [t + 1] * self.st.batch
+
+
+class _PrefixSource:
+    """What a LOOKUP step leaves, for _run_ahead: every row emitted a number of ids only the device knows, so the per-row counts
+    (`counts`, int32 [B]), the three-int stats block and out_ids[:, :max_new_tokens] travel every round, and a next step goes out
+    every round."""
+
+    def __init__(self, st: DecodeState, max_new_tokens: int, counts: torch.Tensor, stats: torch.Tensor):
+        B = st.batch
+        self.B, self.n, self.counts, self.stats_dev = B, max_new_tokens, counts, stats
+        self.ids = torch.empty((B, max_new_tokens), dtype=torch.int64).pin_memory()
+        self.cnt = torch.empty((B + 3,), dtype=torch.int32).pin_memory()  # the rows' counts, then the stats block
+        self.src, self.dst, self.scratch = st.out_ids[:, :max_new_tokens], self.ids, None
+        if B == 1:  # one row: contiguous as it lies, it leaves as it is
+            self.src, self.dst = self.src[0], self.dst[0]
+        else:
+            # out_ids[:, :max_new_tokens] is strided when the state holds more ids per row: gathered into a contiguous device scratch on
+            # the copy stream, it leaves as one contiguous copy into pinned memory (the reason _ColumnSource gives)
+            self.scratch = torch.empty((B, max_new_tokens), dtype=torch.int64, device=st.out_ids.device)
+
+    def more(self, t: int) -> bool:
+        return self.n > 1
+
+    def queue(self, t: int):
+        self.cnt[:self.B].copy_(self.counts, non_blocking=True)
+        self.cnt[self.B:].copy_(self.stats_dev, non_blocking=True)
+        if self.scratch is None:
+            self.dst.copy_(self.src, non_blocking=True)
+        else:
+            self.scratch.copy_(self.src)
+            self.dst.copy_(self.scratch, non_blocking=True)
+
+    def have(self, t: int) -> List[int]:
+        return [min(int(v), self.n) for v in self.cnt[:self.B].tolist()]
+
+    def stats(self):
+        """(steps, drafted, accepted) as last read"""
+        return tuple(int(v) for v in self.cnt[self.B:].tolist())

@@ -16,7 +16,8 @@ The reference decodes through `self.llm.generate(inputs_embeds=..., **generation
     `min_new_tokens` (the device kernel of csrc/logits_proc.hip; `ResolvedGeneration.logits_processors`).
 
 `resolve_generation` reproduces that resolution; `warp_logits` is the three warpers on plain torch tensors (pinned against HF's own
-`TemperatureLogitsWarper` / `TopKLogitsWarper` / `TopPLogitsWarper` on CPU by tests/test_host_generation.py).
+`TemperatureLogitsWarper` / `TopKLogitsWarper` / `TopPLogitsWarper` on CPU by tests/test_host_generation.py).  `StopJudge` is where
+a request ends -- EOS ids, stopping criteria, max_new_tokens -- for the engine's decode loops (tests/test_host_stop_judge.py).
 """
 from __future__ import annotations
 
@@ -194,6 +195,70 @@ def _plan_lookup_batch(g: "ResolvedGeneration", batch: int, processors: bool, he
         return None, f"batch {batch}: two rows per sequence exceed the {L.LOOKUP_ROWS_MAX}-row weight pass of a step"
     k = min(int(K), cap, rows)
     return k, f"K = {k} drafts per step, batch {batch}" + (f" (asked for {K})" if K > k else "")
+
+
+class StopJudge:
+    """Where a request of `batch` rows ends: the host's stop rule of every decode loop (engine._run_ahead), plain or lookup steps.
+    The loop hands over what the device has emitted so far -- `feed(ids, have)`: ids CPU int64 [B, >= max(have)], have[b] the ids
+    row b has (never decreasing between calls, capped at max_new_tokens) -- and gets back the columns the request keeps (n_keep)
+    once it ends there, else None.  A plain step adds one column to every row; a lookup step adds 1 .. K + 1 ids per row, rows
+    apart from each other.  The verdict is the serial HF loop's in both cases (after every whole column: EOS ids, "all rows
+    finished?", then the criteria):
+
+    1. EOS scan.  Each row's new ids are scanned in order for an EOS id; the first one fixes what the row keeps.  Later ids of
+       that row are never looked at for EOS.
+    2. Column order.  Columns are judged in order, each exactly once, and column c only once every row has reached it
+       (c < min(have)).
+    3. EOS closes a column before the criteria.  At column c, if every row has an EOS and the largest kept count is c + 1, the
+       request ends with c + 1 and the criteria are not called for column c.
+    4. Criteria.  Otherwise each criterion is called once, in list order, with (ids[:, :c + 1], None) -- HF passes only the
+       generated ids when generate() was fed inputs_embeds.  A truthy result (r.all() for a tensor) ends the request
+       with c + 1; later criteria in the list are not called.
+    5. No criteria.  The request ends with the largest kept count as soon as every row has an EOS, even when min(have) has not
+       reached that column yet: nothing judges the columns in between.
+    6. Length cap.  min(have) >= max_new_tokens ends the request with max_new_tokens.
+
+    Criteria may hold state (the demo's KeywordsStoppingCriteria), so the sequence of calls they receive is behaviour."""
+
+    def __init__(self, batch: int, eos_token_id, stopping_criteria, max_new_tokens: int):
+        self.batch, self.max_new_tokens = int(batch), int(max_new_tokens)
+        self.eos = _eos_list(eos_token_id)  # ordered list of EOS ids (HF accepts an int or a list; Llama-3 checkpoints list two)
+        self.criteria = list(stopping_criteria) if stopping_criteria is not None else []
+        self.can_stop = bool(self.eos or self.criteria)
+        self._kept = [None] * self.batch  # ids a row keeps: up to and including its first EOS (None: no EOS so far)
+        self._seen = [0] * self.batch     # ids of row b scanned for EOS
+        self._col = 0                     # columns judged
+
+    def feed(self, ids: torch.Tensor, have) -> Optional[int]:
+        kept = self._kept
+        if self.eos:
+            for b in range(self.batch):
+                if kept[b] is None:
+                    kept[b] = next((t + 1 for t in range(self._seen[b], have[b]) if int(ids[b, t]) in self.eos), None)
+        self._seen = list(have)
+        reached = min(have)
+        # the column the last row finished in ends the request there
+        last = max(kept) if self.eos and all(n is not None for n in kept) else None
+        if self.criteria:
+            while self._col < reached:
+                c = self._col
+                if last == c + 1:
+                    return last
+                self._col += 1
+                full = ids[:, :c + 1]
+                for crit in self.criteria:
+                    r = crit(full, None)
+                    if bool(r.all()) if isinstance(r, torch.Tensor) else bool(r):
+                        return c + 1
+        elif last is not None:
+            return last
+        if reached >= self.max_new_tokens:
+            return self.max_new_tokens
+        return None
+
+    def rows(self, n_keep: int) -> List[int]:
+        """ids each row keeps of a request that ended with n_keep columns: up to and including its first EOS, at most n_keep"""
+        return [n_keep if n is None else min(n, n_keep) for n in self._kept]
 
 
 def warp_logits(logits: torch.Tensor, temperature=None, top_k=None, top_p=None, min_tokens_to_keep: int = 1) -> torch.Tensor:

@@ -565,7 +565,7 @@ typedef struct {
   uint64_t seed;
   uint64_t counter;
   int* kept_out;       /* parity hook (device, may be NULL): int[batch][257] = the kept-set size, then its token ids best first
-                        * (srgpt_sample_rows and the sampled lookup step: int[rows][257]) */
+                        * (srgpt_sample_rows, srgpt_sample_seq_rows and the sampled lookup steps: int[rows][257]) */
 } srgpt_sampling;
 
 /* Stand-alone draw over fp32 logits [B, V] with the parameter block above (what the decode step runs after its lm_head):
@@ -603,6 +603,27 @@ int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out,
 int srgpt_sample_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int T, int V, srgpt_stream_t stream);
 int srgpt_sample_full_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int T, int V,
                            srgpt_stream_t stream);
+
+/* Rows are sequences x steps (additions under ABI 9).  The two samplers over logits [B * T, V] whose rows are B SEQUENCES x T SUCCESSIVE
+ * STEPS, row r = b * T + t -- what the batched sampled lookup step (srgpt_llm_lookup_step_batch_ex) draws behind its rows.  The
+ * sequences have emitted different numbers of ids, steps[b] (DEVICE int [B]; a negative entry counts as 0), and share ONE counter:
+ * with m = min over b of max(steps[b], 0), the column of the ids every sequence has filled, sp->counter names the draw of column m,
+ * and row (b, t) reads the Philox stream at (counter + (max(steps[b], 0) - m) + t, sequence b), the 64-bit sum carried into the high
+ * word.  Every block computes m from steps[0 .. B) itself.  With B = 1 that is the rows-are-steps address above, with T = 1 and equal
+ * steps the address of srgpt_sample / srgpt_sample_full; slices, selects, tie rules and the kept set are the samplers' (the same
+ * kernel templates, the addressing a compile-time mode).
+ *   Contract: tok_out[b * T + t] (and the kept set of that row: kept_out int[B * T][257], kept_mask [B * T][ceil(V / 32)]) equals
+ *   what srgpt_sample / srgpt_sample_full return in row b of a B-ROW call at counter + (max(steps[b], 0) - m) + t whose row b holds
+ *   these logits.
+ *   Both take sp as const and leave sp->counter UNCHANGED: how far the sequences advance is the accept's decision
+ *   (srgpt_llm_lookup_step_batch_ex adds the columns that filled up), not the sampler's.
+ * Workspaces: srgpt_sample_ws_bytes(B * T), srgpt_sample_full_ws_bytes(B * T, V).  The error word and srgpt_sample_status(ws, B * T,
+ * stream) behave as for srgpt_sample.  NULL pointers (kept_mask may be NULL), B < 1, T < 1, V < 1: SRGPT_ERR_ARG; V > 262144:
+ * SRGPT_ERR_UNSUPPORTED; both before any launch. */
+int srgpt_sample_seq_rows(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok_out, void* ws, int B, int T, int V,
+                          srgpt_stream_t stream);
+int srgpt_sample_full_seq_rows(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok_out, uint32_t* kept_mask,
+                               void* ws, int B, int T, int V, srgpt_stream_t stream);
 
 /* Logits processors (additions under ABI 9): the part of HF's `LogitsProcessorList` that `generate(repetition_penalty=...,
  * no_repeat_ngram_size=..., min_length=... / min_new_tokens=...)` builds, transformers 4.37.2 generation/logits_process.py, on the
@@ -936,7 +957,7 @@ int srgpt_llm_lookup_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state
 
 /* The lookup step for a BATCH (additions under ABI 9): B = st->batch sequences of T = K + 1 rows each ride through one pass over the
  * weights.  Every sequence is drafted from its OWN history, verified in the shared step and advanced by its OWN number of accepted
- * drafts; greedy only.  Row r = b * T + t of every step buffer is token t of sequence b, the [B, T, ...] layout of
+ * drafts; greedy here, sampled through the _ex forms at the end of this header.  Row r = b * T + t of every step buffer is token t of sequence b, the [B, T, ...] layout of
  * srgpt_decode_attention_multi.  B * T <= 16: the rows one pass of the decode products' MFMA kernel carries.  The entry points above
  * are unchanged and keep refusing a state of more than one sequence.
  *
@@ -991,6 +1012,28 @@ int srgpt_llm_lookup_graph_create_batch(const srgpt_llm_weights* w, srgpt_llm_st
                                         srgpt_stream_t stream, srgpt_graph** out);
 int srgpt_llm_lookup_sync_state_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk,
                                       srgpt_stream_t stream);
+
+/* The batched lookup step under SAMPLING (additions under ABI 9): the _ex forms of the three entries above, in the manner of
+ * srgpt_llm_lookup_step_ex.  With st->sampling == NULL they ARE the greedy batched step (same launches; sample_ws may be NULL).  With
+ * st->sampling set the step is the same through lm_head into lk->logits; then the sampler `sampler` (SRGPT_SAMPLER_*) runs in its
+ * sequences-x-steps mode over the B * T rows with lk->steps as its counts (srgpt_sample_seq_rows / srgpt_sample_full_seq_rows; its
+ * error bits go to the state's sticky error word), and the accept takes the draws for picks: every sequence by srgpt_lookup_accept_batch's
+ * rule, *st->step = min steps[b] and the stats as there, and sp->counter += m_after - m_before, m = min over b of max(steps[b], 0)
+ * before and after -- 0 when every sequence is frozen.  So sp->counter keeps naming the draw of the column every sequence has filled
+ * (behind srgpt_llm_sample_first_ex: counter = c0 + 1 with every steps[b] = 1), and generated id i of sequence b is drawn at
+ * (c0 + i, b) as in the plain sampled batched loop, however many drafts the steps accepted; a discarded row's random numbers
+ * influenced nothing that was kept.  It is exact as srgpt_llm_lookup_step_ex is: row t's draw is used only when rows 0 .. t - 1 of
+ * its sequence agreed with their drafts.  With one sequence it leaves the bits srgpt_llm_lookup_step_ex leaves.
+ *   sample_ws: srgpt_llm_lookup_batch_sample_ws_bytes(w, B, T, sampler) bytes = srgpt_sample_ws_bytes(B * T) /
+ *   srgpt_sample_full_ws_bytes(B * T, vocab) (-1: NULL weights, B < 1, T < 2, B * T > 16, unknown kind).  Unknown sampler kind, or
+ *   st->sampling set with sample_ws NULL: SRGPT_ERR_ARG; every refusal of srgpt_llm_lookup_step_batch but the greedy-only one applies;
+ *   all before any launch.  srgpt_llm_lookup_step_batch itself keeps refusing a sampling state.  A graph captured with st->sampling
+ *   set replays the sampled step of that kind.  srgpt_llm_lookup_sync_state_batch serves both steps. */
+int64_t srgpt_llm_lookup_batch_sample_ws_bytes(const srgpt_llm_weights* w, int B, int T, int sampler);
+int srgpt_llm_lookup_step_batch_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, int sampler,
+                                   void* sample_ws, srgpt_stream_t stream);
+int srgpt_llm_lookup_graph_create_batch_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, int sampler,
+                                           void* sample_ws, srgpt_stream_t stream, srgpt_graph** out);
 
 #ifdef __cplusplus
 }

@@ -186,6 +186,8 @@ _SIGNATURES = {
     "srgpt_sample_full": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
     "srgpt_sample_rows": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "srgpt_sample_full_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+    "srgpt_sample_seq_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "srgpt_sample_full_seq_rows": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "srgpt_logits_process": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, vp]),
     "srgpt_image_resize_normalize": (i32, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, i32, i32, vp]),
     "srgpt_mask_resize_nearest": (i32, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp]),
@@ -224,6 +226,10 @@ _SIGNATURES = {
     "srgpt_llm_lookup_step_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp]),
     "srgpt_llm_lookup_graph_create_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp, C.POINTER(vp)]),
     "srgpt_llm_lookup_sync_state_batch": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), vp]),
+    "srgpt_llm_lookup_batch_sample_ws_bytes": (i64, [C.POINTER(LlmWeights), i32, i32, i32]),
+    "srgpt_llm_lookup_step_batch_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), i32, vp, vp]),
+    "srgpt_llm_lookup_graph_create_batch_ex": (i32, [C.POINTER(LlmWeights), C.POINTER(LlmState), C.POINTER(LookupBatch), i32, vp, vp,
+                                                      C.POINTER(vp)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

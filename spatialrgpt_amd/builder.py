@@ -252,7 +252,8 @@ def load_model(model_path, device="cuda", dtype=torch.bfloat16, llm_weight_forma
 
 def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", dtype=torch.bfloat16, prefix_reuse=False, lookup_sampling=False,
-                          lookup_batch=False, mxfp4_packed=False, decode_pass_rows=16, mxfp4_prefill_direct=False, **kwargs):
+                          lookup_batch=False, mxfp4_packed=False, decode_pass_rows=16, mxfp4_prefill_direct=False,
+                          lookup_batch_sampling=False, **kwargs):
     if load_4bit:
         raise NotImplementedError("bitsandbytes 4-bit loading is out of scope (builder.py:40-60); the engine's own 4-bit option is "
                                   "llm_weight_format=\"mxfp4\" (INTEGRATION.md)")
@@ -272,6 +273,7 @@ def load_pretrained_model(model_path, model_name, model_base=None, load_8bit=Fal
     model.prefix_reuse = bool(prefix_reuse)  # opt-in: unchanged callers continue the last request's cache (spatialrgpt_amd/reuse.py)
     model.lookup_sampling = bool(lookup_sampling)  # opt-in: sampled requests with prompt_lookup_num_tokens run sampled lookup steps
     model.lookup_batch = bool(lookup_batch)  # opt-in: greedy batches with prompt_lookup_num_tokens run batched lookup steps
+    model.lookup_batch_sampling = bool(lookup_batch_sampling)  # opt-in on top of lookup_batch: sampled batches run them too
     lc = _read_json(os.path.join(model_path, "llm", "config.json"))
     context_len = _read_json(os.path.join(model_path, "config.json")).get("max_sequence_length", 2048) \
         if "max_sequence_length" in lc else 2048  # builder.py:207-211

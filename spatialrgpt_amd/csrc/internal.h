@@ -96,6 +96,12 @@ int srgpt_lookup_draft_batch_launch(const int64_t* prompt_ids, int ld_prompt, co
 int srgpt_lookup_accept_batch_launch(const int64_t* picks, const float* pv, const int* pi, const int64_t* draft, const int* n_draft, int B,
                                      int T, int64_t* tok, int64_t* out_ids, int* pos, int* steps, int* step, int max_new, int max_pos,
                                      int64_t* tok_emb, int* stats, hipStream_t s);
+// the accept of a SAMPLED batched step: the B * T rows' picks were drawn by a B-sequences-x-T-steps sampler launch below (where they
+// lie: as for srgpt_lookup_accept_sampled_launch); sp->counter += the columns of out_ids that filled up (draw_addr.h)
+int srgpt_lookup_accept_batch_sampled_launch(srgpt_sampling* sp, int select_drew, const int64_t* drawn, const float* pv, const int* pi,
+                                             const int64_t* draft, const int* n_draft, int B, int T, int64_t* tok, int64_t* out_ids,
+                                             int* pos, int* steps, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
+                                             hipStream_t s);
 
 // ---- sample.hip, for greedy_pick of model.hip: the samplers' launches without the bookkeeping (slices, partials, workspaces: pick.h) ----
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
@@ -108,6 +114,12 @@ int srgpt_sample_rows_launch(const float* logits, const srgpt_sampling* sp, int6
                              int V, hipStream_t s);
 int srgpt_sample_full_rows_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask,
                                   int T, int V, hipStream_t s);
+// ... and for the batched sampled lookup step: over the B * T rows of B sequences x T successive steps (row b * T + t draws at
+// draw_addr.h's address over the device counts steps [B]); pv / pi / tok / kept_mask hold B * T rows, the workspaces are sized for them
+int srgpt_sample_seq_rows_launch(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok, void* ws, float* pv, int* pi,
+                                 int* err, int B, int T, int V, hipStream_t s);
+int srgpt_sample_full_seq_rows_launch(const float* logits, const srgpt_sampling* sp, const int* steps, void* keys_thr, float* pv, int* pi,
+                                      unsigned* kept_mask, int B, int T, int V, hipStream_t s);
 
 // ---- logits_proc.hip, for greedy_pick of model.hip: the logits processors' launch (n_dev != NULL: the history length on the device) ----
 int srgpt_logits_proc_launch(float* scores, const srgpt_logits_proc* lp, const int64_t* ids, int ld, int n, const int* n_dev, int B, int V,

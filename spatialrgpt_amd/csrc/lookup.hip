@@ -5,7 +5,7 @@
 //     lookup_accept_sampled_kernel -- the same on picks that were DRAWN (a sampled request), and advances the Philox counter.
 // One block each, nothing allocated, no host round trip: both sit inside the captured step.  The batched step's pair
 // (lookup_draft_batch_kernel: one block per sequence, lookup_accept_batch_kernel: one thread per sequence) does the same for B
-// sequences.  Each rule is written once: draft_sequence and accept_sequence; the kernels find their sequence's words and call them.
+// sequences, lookup_accept_batch_sampled_kernel on draws (one Philox counter for all of them: draw_addr.h).  Each rule is written once: draft_sequence and accept_sequence; the kernels find their sequence's words and call them.
 #include "common.h"
 #include "internal.h"
 #include "pick.h"
@@ -182,11 +182,25 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_sampled_ke
   sp->counter += (unsigned long long)a.emitted;
 }
 
+// Thread 0 of a batched accept, behind the sequences' accepts (s_steps: their counts now): *step = min over b of steps[b], the columns
+// of out_ids every row has filled; stats += {1, the drafts, the accepted ones} of the rows that advanced, summed in row order.
+__device__ void book_batch_step(const int* s_steps, const Accepted* s_acc, int B, int* __restrict__ step, int* __restrict__ stats) {
+  int lo = INT_MAX, live = 0, nd = 0, n_acc = 0;
+  for (int b = 0; b < B; ++b) {
+    lo = min(lo, s_steps[b]);
+    if (s_acc[b].emitted) {
+      live = 1;
+      nd += s_acc[b].nd;
+      n_acc += s_acc[b].n_acc;
+    }
+  }
+  *step = lo;
+  if (live) count_step(stats, nd, n_acc);
+}
+
 // One wave per row gathers the B * T rows' picks (B * T <= LOOKUP_ROWS_MAX); then thread b accepts sequence b: its own steps[b], pos[b],
 // tok[b], tok_emb[b], out_ids[b, :], its T - 1 drafts and picks b * T .. .  A frozen sequence is neither written nor counted (the
-// run-ahead rule, per row -- a row that accepted more than the others gets there first and waits).  Then thread 0: *step = min over
-// b of steps[b], the columns of out_ids every row has filled; stats += {1 when a row advanced, the drafts, the accepted ones of the
-// rows that did}, summed in row order.
+// run-ahead rule, per row -- a row that accepted more than the others gets there first and waits).  Then thread 0: book_batch_step.
 __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_batch_kernel(
     const int64_t* __restrict__ picks, const float* __restrict__ pv, const int* __restrict__ pi, const int64_t* __restrict__ draft,
     const int* __restrict__ n_draft, int B, int T, int64_t* __restrict__ tok, int64_t* __restrict__ out_ids, int* __restrict__ pos,
@@ -203,17 +217,36 @@ __global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_batch_kern
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  int lo = INT_MAX, live = 0, nd = 0, n_acc = 0;
-  for (int b = 0; b < B; ++b) {
-    lo = min(lo, s_steps[b]);
-    if (s_acc[b].emitted) {
-      live = 1;
-      nd += s_acc[b].nd;
-      n_acc += s_acc[b].n_acc;
-    }
+  book_batch_step(s_steps, s_acc, B, step, stats);
+}
+
+// the SAMPLED batched step: the B * T rows' picks are DRAWS, row (b, t) at draw_addr.h's address -- sp->counter names the draw of
+// column m = min over b of max(steps[b], 0) of out_ids, and the row reads (counter + max(steps[b], 0) - m + t, b), the samplers'
+// PICK_ROWS_SEQ_STEPS mode.  Where the picks lie is read from the parameter block as lookup_accept_sampled_kernel reads it.  The
+// sequences' accepts and thread 0's book_batch_step are lookup_accept_batch_kernel's; then sp->counter += m after - m before, taken
+// from the steps[] values on both sides of the accepts, so the counter goes on naming column m: generated id i of sequence b was
+// drawn at (c0 + i, b) whatever the steps accepted, as in the plain sampled batched loop.  A frozen sequence is neither written nor
+// counted; when every one is frozen m stays, so the advance is 0 and the counter stays.
+__global__ __launch_bounds__(64 * LOOKUP_ROWS_MAX) void lookup_accept_batch_sampled_kernel(
+    srgpt_sampling* __restrict__ sp, int select_drew, const int64_t* __restrict__ drawn, const float* __restrict__ pv,
+    const int* __restrict__ pi, const int64_t* __restrict__ draft, const int* __restrict__ n_draft, int B, int T, int64_t* __restrict__ tok,
+    int64_t* __restrict__ out_ids, int* __restrict__ pos, int* __restrict__ steps, int* __restrict__ step, int max_new, int max_pos,
+    int64_t* __restrict__ tok_emb, int* __restrict__ stats) {
+  __shared__ int64_t picked[LOOKUP_ROWS_MAX];
+  __shared__ int s_before[LOOKUP_ROWS_MAX], s_steps[LOOKUP_ROWS_MAX];
+  __shared__ Accepted s_acc[LOOKUP_ROWS_MAX];  // per sequence
+  gather_picks(select_drew && sp->top_k > 0 ? drawn : nullptr, pv, pi, B * T, picked);
+  if ((int)threadIdx.x < B) {
+    const int b = threadIdx.x;
+    s_before[b] = steps[b];
+    s_acc[b] = accept_sequence(draft + (size_t)b * (T - 1), n_draft[b], picked + b * T, T, tok + b, out_ids + (size_t)b * max_new, pos + b,
+                               steps + b, max_new, max_pos, tok_emb ? tok_emb + b : nullptr);
+    s_steps[b] = steps[b];
   }
-  *step = lo;
-  if (live) count_step(stats, nd, n_acc);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  book_batch_step(s_steps, s_acc, B, step, stats);
+  sp->counter += draw_advance(draw_column(s_before, B), draw_column(s_steps, B));
 }
 
 int check_draft_args(int n_prompt, int max_new, int K, int max_ngram, int64_t vocab, const char* fn) {
@@ -253,6 +286,16 @@ int srgpt_lookup_accept_sampled_launch(srgpt_sampling* sp, int select_drew, cons
                                        int max_new, int max_pos, int64_t* tok_emb, int* stats, hipStream_t s) {
   hipLaunchKernelGGL(lookup_accept_sampled_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, sp, select_drew, drawn, pv, pi, draft,
                      n_draft, T, tok, out_ids, pos, step, max_new, max_pos, tok_emb, stats);
+  SRGPT_LAUNCH_CHECK();
+  return SRGPT_OK;
+}
+
+int srgpt_lookup_accept_batch_sampled_launch(srgpt_sampling* sp, int select_drew, const int64_t* drawn, const float* pv, const int* pi,
+                                             const int64_t* draft, const int* n_draft, int B, int T, int64_t* tok, int64_t* out_ids,
+                                             int* pos, int* steps, int* step, int max_new, int max_pos, int64_t* tok_emb, int* stats,
+                                             hipStream_t s) {
+  hipLaunchKernelGGL(lookup_accept_batch_sampled_kernel, dim3(1), dim3(64 * LOOKUP_ROWS_MAX), 0, s, sp, select_drew, drawn, pv, pi, draft,
+                     n_draft, B, T, tok, out_ids, pos, steps, step, max_new, max_pos, tok_emb, stats);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }

@@ -1002,16 +1002,18 @@ struct LookupReq {
   int ld_prompt;
   const int* n_prompt_dev;
   int* steps;
-  // single: the id count (a host int of the public struct), the sampler kind of a sampled step and its workspace
-  int n_prompt, sampler;
+  // single: the id count (a host int of the public struct)
+  int n_prompt;
+  // the sampler kind of a sampled step and its workspace (the _ex entries)
+  int sampler;
   void* sample_ws;
 };
 LookupReq lookup_req(const srgpt_lookup* lk, int sampler = SRGPT_SAMPLER_TOPK64, void* sample_ws = nullptr) {
   return LookupReq{1, lk->T, lk->max_ngram, lk->ws, lk->logits, lk->stats, lk->prompt_ids, 0, nullptr, nullptr, lk->n_prompt, sampler, sample_ws};
 }
-LookupReq lookup_req(const srgpt_lookup_batch* lk, int B) {
+LookupReq lookup_req(const srgpt_lookup_batch* lk, int B, int sampler = SRGPT_SAMPLER_TOPK64, void* sample_ws = nullptr) {
   return LookupReq{B, lk->T, lk->max_ngram, lk->ws, lk->logits, lk->stats, lk->prompt_ids, lk->ld_prompt, lk->n_prompt, lk->steps, 0,
-                   SRGPT_SAMPLER_TOPK64, nullptr};
+                   sampler, sample_ws};
 }
 
 }  // namespace
@@ -1071,11 +1073,12 @@ static int check_lookup_ex(const srgpt_llm_weights* w, const srgpt_llm_state* st
 }
 
 // every batched lookup entry point, on the host before any launch
-static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk, const char* fn) {
+static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk, const char* fn,
+                              bool greedy_only = true) {
   SRGPT_CHECK(lk, SRGPT_ERR_ARG, "%s: null lookup block", fn);
   SRGPT_TRY(check_llm(w, st));
   SRGPT_CHECK(lk->T >= 2, SRGPT_ERR_ARG, "%s: T=%d rows per sequence (the next token and at least one draft)", fn, lk->T);
-  SRGPT_CHECK(!st->sampling, SRGPT_ERR_UNSUPPORTED,
+  SRGPT_CHECK(!greedy_only || !st->sampling, SRGPT_ERR_UNSUPPORTED,
               "%s: greedy only (st->sampling is set: a sampled batch has one Philox counter, rows that emit different numbers of ids "
               "would need one each)", fn);
   SRGPT_CHECK((int64_t)st->batch * lk->T <= srgpt_lookup_rows_max(), SRGPT_ERR_UNSUPPORTED,
@@ -1090,6 +1093,22 @@ static int check_lookup_batch(const srgpt_llm_weights* w, const srgpt_llm_state*
   return llm_format(w, fn, &fmt);
 }
 
+// the batched _ex entry points' check, built like check_lookup_ex
+static int check_lookup_batch_ex(const srgpt_llm_weights* w, const srgpt_llm_state* st, const srgpt_lookup_batch* lk, int sampler,
+                                 const void* sample_ws, const char* fn) {
+  SRGPT_CHECK(sampler == SRGPT_SAMPLER_TOPK64 || sampler == SRGPT_SAMPLER_FULL, SRGPT_ERR_ARG, "%s: unknown sampler kind %d", fn, sampler);
+  SRGPT_TRY(check_lookup_batch(w, st, lk, fn, false));
+  SRGPT_CHECK(!st->sampling || sample_ws, SRGPT_ERR_ARG, "%s: st->sampling is set and sample_ws is null", fn);
+  return SRGPT_OK;
+}
+
+extern "C" int64_t srgpt_llm_lookup_batch_sample_ws_bytes(const srgpt_llm_weights* w, int B, int T, int sampler) {
+  if (!w || B < 1 || T < 2 || (int64_t)B * T > srgpt_lookup_rows_max()) return -1;
+  if (sampler == SRGPT_SAMPLER_TOPK64) return srgpt_sample_ws_bytes(B * T);
+  if (sampler == SRGPT_SAMPLER_FULL) return srgpt_sample_full_ws_bytes(B * T, w->vocab);
+  return -1;
+}
+
 extern "C" int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, int T, int sampler) {
   if (!w || T < 2 || T > srgpt_lookup_rows_max()) return -1;
   if (sampler == SRGPT_SAMPLER_TOPK64) return srgpt_sample_ws_bytes(T);
@@ -1101,10 +1120,10 @@ extern "C" int64_t srgpt_llm_lookup_sample_ws_bytes(const srgpt_llm_weights* w, 
 // sequences of T rows (no o_proj prefetch blocks: 2+ rows take the skinny kernel) -> the rows' picks -> accept.  The forms differ in
 // the first and the last launch only.  Draft: the batched kernel reads every row's id count from the device, the single one takes
 // the public struct's host int.  Accept: greedy (st->sampling == NULL) the rows' argmax partials, then the single or the batched
-// accept; sampled (single only: check_lookup_batch refuses it) the sampler q.sampler in its rows-are-steps mode over the T rows
-// (q.sample_ws: its own workspace, srgpt_llm_lookup_sample_ws_bytes; error bits go to the state's sticky word), then the accept
-// that advances the Philox counter.  The top-k-64 sampler's drawn ids go to the lookup workspace's row_ids, dead since the rows were
-// embedded.
+// accept; sampled the sampler q.sampler over the R rows -- in its rows-are-steps mode, or (batched) as B sequences x T steps over
+// q.steps (q.sample_ws: its own workspace, srgpt_llm_lookup_sample_ws_bytes / _batch_sample_ws_bytes; error bits go to the state's
+// sticky word) -- then the single or the batched accept that advances the Philox counter.  The top-k-64 sampler's drawn ids go to the
+// lookup workspace's row_ids, dead since the rows were embedded.
 static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, const LookupReq& q, srgpt_stream_t stream) {
   const bool batched = q.steps != nullptr;
   LlmFormat fmt;
@@ -1126,15 +1145,24 @@ static int lookup_step_impl(const srgpt_llm_weights* w, srgpt_llm_state* st, con
                                         w->head_dim, st->max_pos, dt, stream);
   }));
   if (st->sampling) {
-    if (q.sampler == SRGPT_SAMPLER_FULL) {
-      const SampleFullWs c = carve_sample_full_ws(q.sample_ws, T, w->vocab);
-      SRGPT_TRY(srgpt_sample_full_rows_launch(q.logits, st->sampling, q.sample_ws, c.pv, c.pi, nullptr, T, w->vocab, s));
-      return srgpt_lookup_accept_sampled_launch(st->sampling, 0, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
-                                                st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
+    const bool full = q.sampler == SRGPT_SAMPLER_FULL;
+    float* pv;
+    int* pi;
+    if (full) {
+      const SampleFullWs c = carve_sample_full_ws(q.sample_ws, R, w->vocab);
+      pv = c.pv, pi = c.pi;
+      SRGPT_TRY(batched ? srgpt_sample_full_seq_rows_launch(q.logits, st->sampling, q.steps, q.sample_ws, pv, pi, nullptr, B, T, w->vocab, s)
+                        : srgpt_sample_full_rows_launch(q.logits, st->sampling, q.sample_ws, pv, pi, nullptr, T, w->vocab, s));
+    } else {
+      const SampleWs c = carve_sample_ws(q.sample_ws, R);
+      pv = c.pv, pi = c.pi;
+      SRGPT_TRY(batched ? srgpt_sample_seq_rows_launch(q.logits, st->sampling, q.steps, l.row_ids, q.sample_ws, pv, pi, d.err, B, T, w->vocab, s)
+                        : srgpt_sample_rows_launch(q.logits, st->sampling, l.row_ids, q.sample_ws, pv, pi, d.err, T, w->vocab, s));
     }
-    const SampleWs c = carve_sample_ws(q.sample_ws, T);
-    SRGPT_TRY(srgpt_sample_rows_launch(q.logits, st->sampling, l.row_ids, q.sample_ws, c.pv, c.pi, d.err, T, w->vocab, s));
-    return srgpt_lookup_accept_sampled_launch(st->sampling, 1, l.row_ids, c.pv, c.pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
+    if (batched)
+      return srgpt_lookup_accept_batch_sampled_launch(st->sampling, !full, l.row_ids, pv, pi, l.draft, l.n_draft, B, T, st->tok, st->out_ids,
+                                                      st->pos, q.steps, st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
+    return srgpt_lookup_accept_sampled_launch(st->sampling, !full, l.row_ids, pv, pi, l.draft, l.n_draft, T, st->tok, st->out_ids, st->pos,
                                               st->step, st->max_new, st->max_pos, d.tok_emb, q.stats, s);
   }
   hipLaunchKernelGGL(argmax_partial_kernel, dim3(PICK_SLICES, R), dim3(256), 0, s, q.logits, l.amax_v, l.amax_i, w->vocab);
@@ -1161,6 +1189,12 @@ extern "C" int srgpt_llm_lookup_step_batch(const srgpt_llm_weights* w, srgpt_llm
                                            srgpt_stream_t stream) {
   SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_step_batch"));
   return lookup_step_impl(w, st, lookup_req(lk, st->batch), stream);
+}
+
+extern "C" int srgpt_llm_lookup_step_batch_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk, int sampler,
+                                              void* sample_ws, srgpt_stream_t stream) {
+  SRGPT_TRY(check_lookup_batch_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_step_batch_ex"));
+  return lookup_step_impl(w, st, lookup_req(lk, st->batch, sampler, sample_ws), stream);
 }
 
 // srgpt_llm_decode_sync_state for a state a lookup step ran on: the (B, T) lookup workspace's own arrival tickets first, then
@@ -1255,6 +1289,13 @@ extern "C" int srgpt_llm_lookup_graph_create_batch(const srgpt_llm_weights* w, s
   SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_batch: null out");
   SRGPT_TRY(check_lookup_batch(w, st, lk, "srgpt_llm_lookup_graph_create_batch"));
   return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lookup_req(lk, st->batch), stream); });
+}
+
+extern "C" int srgpt_llm_lookup_graph_create_batch_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, const srgpt_lookup_batch* lk,
+                                                      int sampler, void* sample_ws, srgpt_stream_t stream, srgpt_graph** out) {
+  SRGPT_CHECK(out, SRGPT_ERR_ARG, "srgpt_llm_lookup_graph_create_batch_ex: null out");
+  SRGPT_TRY(check_lookup_batch_ex(w, st, lk, sampler, sample_ws, "srgpt_llm_lookup_graph_create_batch_ex"));
+  return capture_graph(stream, out, [&] { return lookup_step_impl(w, st, lookup_req(lk, st->batch, sampler, sample_ws), stream); });
 }
 
 extern "C" int srgpt_llm_decode_graph_create_ex(const srgpt_llm_weights* w, srgpt_llm_state* st, int sampler, srgpt_stream_t stream,

@@ -6,6 +6,7 @@
 // header: pick_slice for the bounds, pick_gumbel_key for a draw, pick_store_slice to publish.
 #pragma once
 #include "common.h"
+#include "draw_addr.h"
 
 constexpr int PICK_SLICES = 128;                              // slices per row = blocks per row of a producer = partials per row
 constexpr int PICK_SLICE_MAX = 2048;                          // entries of a slice (sample_partial_kernel holds one in LDS)
@@ -127,16 +128,30 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1) {
   }
   return c;
 }
-// Where row b of a sampler launch reads that stream.  The rows are the sequences of ONE step (STEPS = false): (counter, b).  Or they
-// are successive steps of ONE sequence (STEPS = true, the lookup step's T rows): (counter + b, 0), the 64-bit sum carried into the
-// high word -- exactly what B = 1 calls at counter, counter + 1, ... read, so a row's draw does not depend on which launch made it
+// Where row b of a sampler launch reads that stream.  The rows are the sequences of ONE step (PICK_ROWS_SEQS): (counter, b).  Or they
+// are successive steps of ONE sequence (PICK_ROWS_STEPS, the lookup step's T rows): (counter + b, 0), the 64-bit sum carried into the
+// high word -- exactly what B = 1 calls at counter, counter + 1, ... read, so a row's draw does not depend on which launch made it.
+// Or they are B sequences x T successive steps (PICK_ROWS_SEQ_STEPS, the batched lookup step; row b * T + t): draw_addr.h's rule over
+// the sequences' emission counts, which a kernel of that mode takes as one more argument (PickSeqs) -- the other two take none.
+enum PickRows { PICK_ROWS_SEQS, PICK_ROWS_STEPS, PICK_ROWS_SEQ_STEPS };
 struct PickDraw {
   unsigned long long ctr;
   int seq;
 };
-template <bool STEPS>
+struct PickSeqs {
+  const int* steps;  // device int [B]: ids every sequence has emitted; every block reads all B and takes the minimum itself
+  int B, T;
+};
+template <PickRows MODE>
 __device__ __forceinline__ PickDraw pick_draw(unsigned long long counter, int b) {
-  return STEPS ? PickDraw{counter + (unsigned long long)b, 0} : PickDraw{counter, b};
+  static_assert(MODE != PICK_ROWS_SEQ_STEPS, "rows of several sequences are addressed over their counts");
+  return MODE == PICK_ROWS_STEPS ? PickDraw{counter + (unsigned long long)b, 0} : PickDraw{counter, b};
+}
+template <PickRows MODE>
+__device__ __forceinline__ PickDraw pick_draw(unsigned long long counter, int r, PickSeqs q) {
+  static_assert(MODE == PICK_ROWS_SEQ_STEPS, "only rows of several sequences carry counts");
+  const DrawAddr a = draw_addr(counter, q.steps, q.B, q.T, r);
+  return PickDraw{a.ctr, a.seq};
 }
 // Gumbel-max: argmax_i (score_i + g_i), g_i = -log(-log(u_i)), u_i in (0, 1), is a draw from softmax(score).  The key of entry i of
 // row b at step counter ctr (srgpt_sampling::counter / ::seed)

@@ -25,10 +25,13 @@
 //             indices first (CPU torch.sort's ascending order).
 //   launch 2  sample_full_draw_kernel       grid (128 slices, batch): masked Gumbel-max, per-slice (value, index) for the greedy
 //             merge (advance_kernel / sample_merge_kernel), Philox addressed like the top_k = 0 path.
-// ROWS ARE STEPS (template argument STEPS of the kernels that draw; srgpt_sample_rows / srgpt_sample_full_rows and the sampled lookup
-// step of model.hip): the rows of a launch are T successive steps of ONE sequence, row t reads the stream below at (step counter + t,
-// sequence 0) -- what a one-row call at that counter reads -- and nothing else differs.  The <false> instantiations are the kernels
-// as they were, instruction for instruction.
+// WHAT THE ROWS ARE (template argument MODE of the kernels that draw, PickRows of pick.h).  PICK_ROWS_SEQS: the sequences of one step.
+// PICK_ROWS_STEPS (srgpt_sample_rows / srgpt_sample_full_rows and the sampled lookup step of model.hip): T successive steps of ONE
+// sequence, row t reads the stream below at (step counter + t, sequence 0) -- what a one-row call at that counter reads.
+// PICK_ROWS_SEQ_STEPS (srgpt_sample_seq_rows / srgpt_sample_full_seq_rows and the batched sampled lookup step): B sequences x T
+// successive steps, row b * T + t at draw_addr.h's address over the sequences' emission counts, which these instantiations take as
+// one more kernel argument (PickSeqs); they leave the counter alone.  Nothing else differs between the three, and the first two are
+// the kernels as they were, instruction for instruction.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (step counter, sequence, vocabulary index | ~0): reproducible for
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
 // on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
@@ -99,12 +102,13 @@ __device__ unsigned block_select_kth(const unsigned* __restrict__ keys, int n, i
   return prefix;
 }
 
-// STEPS (every sampler kernel below): how row b addresses the Philox stream (PickDraw, pick.h) -- false: the rows are sequences of one
-// step, true: the rows are successive steps of ONE sequence (the lookup step's T rows).  Nothing else differs between the two.
-template <bool STEPS>
+// MODE (every sampler kernel below): how row b addresses the Philox stream (PickRows / pick_draw, pick.h) -- the rows are sequences of
+// one step, successive steps of ONE sequence (the lookup step's T rows), or B sequences x T steps (the batched lookup step's rows; only
+// then SEQS is one PickSeqs, otherwise the pack is empty and the kernel has the arguments it always had).  Nothing else differs.
+template <PickRows MODE, class... SEQS>
 __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __restrict__ logits, const srgpt_sampling* __restrict__ sp,
                                                              unsigned* __restrict__ cand_key, int* __restrict__ cand_idx,
-                                                             float* __restrict__ pv, int* __restrict__ pi, int V) {
+                                                             float* __restrict__ pv, int* __restrict__ pi, int V, SEQS... seqs) {
   __shared__ unsigned keys[PICK_SLICE_MAX];
   __shared__ SelectLds L;
   __shared__ unsigned cnt;
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
   const int topk = min(sp->top_k, SMP_K);
   if (topk <= 0) {
     // ---- Gumbel-max over logits / T: the slice's best key for the greedy merge ----
-    const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+    const PickDraw dr = pick_draw<MODE>(sp->counter, b, seqs...);
     const unsigned long long seed = sp->seed;
     float best = -INFINITY;
     int bi = PICK_NONE;
@@ -168,10 +172,10 @@ __global__ __launch_bounds__(256) void sample_partial_kernel(const float* __rest
   }
 }
 
-template <bool STEPS>
+template <PickRows MODE, class... SEQS>
 __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ cand_key,
                                                              const int* __restrict__ cand_idx, int64_t* __restrict__ tok, int nb,
-                                                             int* __restrict__ err) {
+                                                             int* __restrict__ err, SEQS... seqs) {
   constexpr int NC = PICK_SLICES * SMP_K;
   __shared__ unsigned keys[NC];
   __shared__ int idxs[NC];
@@ -251,7 +255,7 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_samplin
     }
     float Z2 = 0.f;
     for (int r = 0; r < n2; ++r) Z2 += __expf(ss[r] - m);
-    const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+    const PickDraw dr = pick_draw<MODE>(sp->counter, b, seqs...);
     const unsigned long long ctr = dr.ctr, seed = sp->seed;
     const U4 rr = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)dr.seq, 0xFFFFFFFFu}, (unsigned)seed, (unsigned)(seed >> 32));
     const float u = (float)(rr.x >> 8) * (1.0f / 16777216.0f);  // [0, 1)
@@ -277,17 +281,20 @@ __global__ __launch_bounds__(1024) void sample_select_kernel(const srgpt_samplin
 
 // the stand-alone ops only (the decode step's advance_kernel does both): merge the slices' maxima, one wave per row -- always (the full
 // sampler), or only in Gumbel mode (srgpt_sample: sample_select_kernel drew the token otherwise); every call advances the counter --
-// by one step, or (STEPS: the B rows were B steps) by B
-template <bool STEPS>
-__global__ void sample_merge_kernel(srgpt_sampling* sp, const float* __restrict__ pv, const int* __restrict__ pi, int64_t* __restrict__ tok,
-                                    int B, int always) {
+// by one step, or (PICK_ROWS_STEPS: the B rows were B steps) by B -- but for rows of several sequences (PICK_ROWS_SEQ_STEPS, SP =
+// const srgpt_sampling): how far those advance is their accept's decision, the block is only read
+template <PickRows MODE, class SP>
+__global__ void sample_merge_kernel(SP* sp, const float* __restrict__ pv, const int* __restrict__ pi, int64_t* __restrict__ tok, int B,
+                                    int always) {
   if (always || sp->top_k <= 0)
     for (int b = threadIdx.x >> 6; b < B; b += blockDim.x >> 6) {
       const int t = pick_merge_row(pv + (size_t)b * PICK_SLICES, pi + (size_t)b * PICK_SLICES, PICK_SLICES, threadIdx.x & 63);
       if ((threadIdx.x & 63) == 0) tok[b] = t;
     }
-  __syncthreads();
-  if (threadIdx.x == 0) sp->counter += STEPS ? (unsigned long long)B : 1ull;
+  if constexpr (MODE != PICK_ROWS_SEQ_STEPS) {
+    __syncthreads();
+    if (threadIdx.x == 0) sp->counter += MODE == PICK_ROWS_STEPS ? (unsigned long long)B : 1ull;
+  }
 }
 
 // ================================================================================================
@@ -504,15 +511,15 @@ __global__ __launch_bounds__(SFU_THREADS) void sample_full_threshold_kernel(cons
 // launch 2: masked Gumbel-max per vocabulary slice, grid (PICK_SLICES, batch) -> the per-slice (value, index) pairs the greedy merge
 // (advance_kernel, or sample_merge_kernel for the stand-alone op) consumes.  Same Philox addressing as the top_k = 0 path of
 // sample_partial_kernel.  kept_mask (optional): bit i % 32 of word i / 32 of the row = entry i kept.
-template <bool STEPS>
+template <PickRows MODE, class... SEQS>
 __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampling* __restrict__ sp, const unsigned* __restrict__ keys_ws,
                                                               const unsigned* __restrict__ thr, float* __restrict__ pv,
-                                                              int* __restrict__ pi, unsigned* __restrict__ kept_mask, int V) {
+                                                              int* __restrict__ pi, unsigned* __restrict__ kept_mask, int V, SEQS... seqs) {
   const int b = blockIdx.y, nb = gridDim.x, blk = blockIdx.x, tid = threadIdx.x;
   const PickSlice sl = pick_slice(V);
   const unsigned* keys = keys_ws + (size_t)b * V;
   const unsigned tkey = thr[(size_t)b * 4], tidx = thr[(size_t)b * 4 + 1];
-  const PickDraw dr = pick_draw<STEPS>(sp->counter, b);
+  const PickDraw dr = pick_draw<MODE>(sp->counter, b, seqs...);
   const unsigned long long seed = sp->seed;
   float best = -INFINITY;
   int bi = PICK_NONE;
@@ -546,16 +553,19 @@ __global__ __launch_bounds__(256) void sample_full_draw_kernel(const srgpt_sampl
 // the top-k-64 sampler's workspace (SampleWs, pick.h)
 extern "C" int64_t srgpt_sample_ws_bytes(int B) { return B <= 0 ? -1 : carve_sample_ws(nullptr, B).bytes; }
 
-// launches 1 and 2 of the top-k-64 sampler over B rows: sequences, or (STEPS) successive steps of one sequence
-template <bool STEPS>
+// launches 1 and 2 of the top-k-64 sampler over B rows: sequences, successive steps of one sequence, or (seqs: one PickSeqs) the
+// rows of seqs.B sequences x seqs.T steps
+template <PickRows MODE, class... SEQS>
 static int sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
-                         hipStream_t s) {
+                         hipStream_t s, SEQS... seqs) {
   SRGPT_CHECK(logits && sp && tok && ws && pv && pi && err, SRGPT_ERR_ARG, "srgpt_sample: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_UNSUPPORTED, "srgpt_sample: empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
   const SampleWs c = carve_sample_ws(ws, B);
-  hipLaunchKernelGGL((sample_partial_kernel<STEPS>), dim3(PICK_SLICES, B), dim3(256), 0, s, logits, sp, c.cand_key, c.cand_idx, pv, pi, V);
-  hipLaunchKernelGGL((sample_select_kernel<STEPS>), dim3(B), dim3(1024), 0, s, sp, c.cand_key, c.cand_idx, tok, PICK_SLICES, err);
+  hipLaunchKernelGGL((sample_partial_kernel<MODE, SEQS...>), dim3(PICK_SLICES, B), dim3(256), 0, s, logits, sp, c.cand_key, c.cand_idx, pv,
+                     pi, V, seqs...);
+  hipLaunchKernelGGL((sample_select_kernel<MODE, SEQS...>), dim3(B), dim3(1024), 0, s, sp, c.cand_key, c.cand_idx, tok, PICK_SLICES, err,
+                     seqs...);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -563,36 +573,57 @@ static int sample_launch(const float* logits, const srgpt_sampling* sp, int64_t*
 // internal (model.hip): launches 1 and 2; the caller books the token (advance_kernel) and advances the counter
 int srgpt_sample_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int B, int V,
                         hipStream_t s) {
-  return sample_launch<false>(logits, sp, tok, ws, pv, pi, err, B, V, s);
+  return sample_launch<PICK_ROWS_SEQS>(logits, sp, tok, ws, pv, pi, err, B, V, s);
 }
 
 // internal (model.hip, the sampled lookup step): the same over T rows that are successive steps of one sequence -- row t draws at
 // counter + t; the caller accepts (lookup.hip) and advances the counter by what it emitted
 int srgpt_sample_rows_launch(const float* logits, const srgpt_sampling* sp, int64_t* tok, void* ws, float* pv, int* pi, int* err, int T,
                              int V, hipStream_t s) {
-  return sample_launch<true>(logits, sp, tok, ws, pv, pi, err, T, V, s);
+  return sample_launch<PICK_ROWS_STEPS>(logits, sp, tok, ws, pv, pi, err, T, V, s);
 }
 
-// the stand-alone draw: clear the workspace's error word, launches 1 and 2, the Gumbel-mode merge and the counter
-template <bool STEPS>
-static int sample_op(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
+// internal (model.hip, the batched sampled lookup step): the same over the B * T rows of B sequences x T steps -- row b * T + t draws
+// at draw_addr.h's address over steps [B] (device); the caller accepts (lookup.hip) and moves the counter with the filled column
+int srgpt_sample_seq_rows_launch(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok, void* ws, float* pv, int* pi,
+                                 int* err, int B, int T, int V, hipStream_t s) {
+  SRGPT_CHECK(steps && B > 0 && T > 0, SRGPT_ERR_ARG, "srgpt_sample_seq_rows: null steps or empty shape");
+  return sample_launch<PICK_ROWS_SEQ_STEPS>(logits, sp, tok, ws, pv, pi, err, B * T, V, s, PickSeqs{steps, B, T});
+}
+
+// the stand-alone draw: clear the workspace's error word, launches 1 and 2, the Gumbel-mode merge and (SP not const) the counter
+template <PickRows MODE, class SP, class... SEQS>
+static int sample_op(const float* logits, SP* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream, SEQS... seqs) {
   SRGPT_CHECK(logits && sp && tok_out && ws && B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample: null pointer or empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample"));
   const SampleWs c = carve_sample_ws(ws, B);
   hipStream_t s = as_stream(stream);
   SRGPT_HIP_TRY(hipMemsetAsync(c.err, 0, sizeof(int), s), "srgpt_sample: clearing the error word");
-  SRGPT_TRY(sample_launch<STEPS>(logits, sp, tok_out, ws, c.pv, c.pi, c.err, B, V, s));
-  hipLaunchKernelGGL((sample_merge_kernel<STEPS>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 0);
+  SRGPT_TRY(sample_launch<MODE>(logits, sp, tok_out, ws, c.pv, c.pi, c.err, B, V, s, seqs...));
+  hipLaunchKernelGGL((sample_merge_kernel<MODE, SP>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 0);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int srgpt_sample(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int B, int V, srgpt_stream_t stream) {
-  return sample_op<false>(logits, sp, tok_out, ws, B, V, stream);
+  return sample_op<PICK_ROWS_SEQS>(logits, sp, tok_out, ws, B, V, stream);
 }
 
 extern "C" int srgpt_sample_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, void* ws, int T, int V, srgpt_stream_t stream) {
-  return sample_op<true>(logits, sp, tok_out, ws, T, V, stream);
+  return sample_op<PICK_ROWS_STEPS>(logits, sp, tok_out, ws, T, V, stream);
+}
+
+// both stand-alone entries over B sequences x T steps: the sizes, before anything else is looked at
+static int check_seq_rows(const int* steps, int B, int T, int V, const char* fn) {
+  SRGPT_CHECK(steps, SRGPT_ERR_ARG, "%s: null pointer", fn);
+  SRGPT_CHECK(B >= 1 && T >= 1 && V >= 1 && (int64_t)B * T <= INT_MAX, SRGPT_ERR_ARG, "%s: bad sizes B=%d T=%d V=%d", fn, B, T, V);
+  return SRGPT_OK;
+}
+
+extern "C" int srgpt_sample_seq_rows(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok_out, void* ws, int B,
+                                     int T, int V, srgpt_stream_t stream) {
+  SRGPT_TRY(check_seq_rows(steps, B, T, V, "srgpt_sample_seq_rows"));
+  return sample_op<PICK_ROWS_SEQ_STEPS>(logits, sp, tok_out, ws, B * T, V, stream, PickSeqs{steps, B, T});
 }
 
 // health of the last srgpt_sample call(s) on this workspace (synchronises `stream`): the sticky error word at the tail of ws
@@ -610,15 +641,16 @@ extern "C" int srgpt_sample_status(const void* ws, int B, srgpt_stream_t stream)
 // ---- the full sampler: its workspace is SampleFullWs (pick.h) ----
 extern "C" int64_t srgpt_sample_full_ws_bytes(int B, int V) { return B <= 0 || V <= 0 ? -1 : carve_sample_full_ws(nullptr, B, V).bytes; }
 
-template <bool STEPS>
+template <PickRows MODE, class... SEQS>
 static int sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
-                              int V, hipStream_t s) {
+                              int V, hipStream_t s, SEQS... seqs) {
   SRGPT_CHECK(logits && sp && keys_thr && pv && pi, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
   SRGPT_TRY(pick_check_vocab(V, "srgpt_sample_full"));
   const SampleFullWs c = carve_sample_full_ws(keys_thr, B, V);
   hipLaunchKernelGGL(sample_full_threshold_kernel, dim3(B), dim3(SFU_THREADS), 0, s, logits, sp, c.keys, c.thr, V);
-  hipLaunchKernelGGL((sample_full_draw_kernel<STEPS>), dim3(PICK_SLICES, B), dim3(256), 0, s, sp, c.keys, c.thr, pv, pi, kept_mask, V);
+  hipLaunchKernelGGL((sample_full_draw_kernel<MODE, SEQS...>), dim3(PICK_SLICES, B), dim3(256), 0, s, sp, c.keys, c.thr, pv, pi, kept_mask,
+                     V, seqs...);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
@@ -627,34 +659,47 @@ static int sample_full_launch(const float* logits, const srgpt_sampling* sp, voi
 // advances the counter.  keys_thr = the head (keys and thresholds) of a SampleFullWs.
 int srgpt_sample_full_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask, int B,
                              int V, hipStream_t s) {
-  return sample_full_launch<false>(logits, sp, keys_thr, pv, pi, kept_mask, B, V, s);
+  return sample_full_launch<PICK_ROWS_SEQS>(logits, sp, keys_thr, pv, pi, kept_mask, B, V, s);
 }
 
 // internal (model.hip, the sampled lookup step): the same over T rows that are successive steps of one sequence
 int srgpt_sample_full_rows_launch(const float* logits, const srgpt_sampling* sp, void* keys_thr, float* pv, int* pi, unsigned* kept_mask,
                                   int T, int V, hipStream_t s) {
-  return sample_full_launch<true>(logits, sp, keys_thr, pv, pi, kept_mask, T, V, s);
+  return sample_full_launch<PICK_ROWS_STEPS>(logits, sp, keys_thr, pv, pi, kept_mask, T, V, s);
 }
 
-template <bool STEPS>
-static int sample_full_op(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
-                          srgpt_stream_t stream) {
+// internal (model.hip, the batched sampled lookup step): the same over the B * T rows of B sequences x T steps (steps [B], device)
+int srgpt_sample_full_seq_rows_launch(const float* logits, const srgpt_sampling* sp, const int* steps, void* keys_thr, float* pv, int* pi,
+                                      unsigned* kept_mask, int B, int T, int V, hipStream_t s) {
+  SRGPT_CHECK(steps && B > 0 && T > 0, SRGPT_ERR_ARG, "srgpt_sample_full_seq_rows: null steps or empty shape");
+  return sample_full_launch<PICK_ROWS_SEQ_STEPS>(logits, sp, keys_thr, pv, pi, kept_mask, B * T, V, s, PickSeqs{steps, B, T});
+}
+
+template <PickRows MODE, class SP, class... SEQS>
+static int sample_full_op(const float* logits, SP* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V, srgpt_stream_t stream,
+                          SEQS... seqs) {
   SRGPT_CHECK(tok_out && ws, SRGPT_ERR_ARG, "srgpt_sample_full: null pointer");
   SRGPT_CHECK(B > 0 && V > 0, SRGPT_ERR_ARG, "srgpt_sample_full: empty shape");
   const SampleFullWs c = carve_sample_full_ws(ws, B, V);
   hipStream_t s = as_stream(stream);
-  SRGPT_TRY(sample_full_launch<STEPS>(logits, sp, ws, c.pv, c.pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s));
-  hipLaunchKernelGGL((sample_merge_kernel<STEPS>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 1);
+  SRGPT_TRY(sample_full_launch<MODE>(logits, sp, ws, c.pv, c.pi, reinterpret_cast<unsigned*>(kept_mask), B, V, s, seqs...));
+  hipLaunchKernelGGL((sample_merge_kernel<MODE, SP>), dim3(1), dim3(256), 0, s, sp, c.pv, c.pi, tok_out, B, 1);
   SRGPT_LAUNCH_CHECK();
   return SRGPT_OK;
 }
 
 extern "C" int srgpt_sample_full(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int B, int V,
                                  srgpt_stream_t stream) {
-  return sample_full_op<false>(logits, sp, tok_out, kept_mask, ws, B, V, stream);
+  return sample_full_op<PICK_ROWS_SEQS>(logits, sp, tok_out, kept_mask, ws, B, V, stream);
 }
 
 extern "C" int srgpt_sample_full_rows(const float* logits, srgpt_sampling* sp, int64_t* tok_out, uint32_t* kept_mask, void* ws, int T, int V,
                                       srgpt_stream_t stream) {
-  return sample_full_op<true>(logits, sp, tok_out, kept_mask, ws, T, V, stream);
+  return sample_full_op<PICK_ROWS_STEPS>(logits, sp, tok_out, kept_mask, ws, T, V, stream);
+}
+
+extern "C" int srgpt_sample_full_seq_rows(const float* logits, const srgpt_sampling* sp, const int* steps, int64_t* tok_out,
+                                          uint32_t* kept_mask, void* ws, int B, int T, int V, srgpt_stream_t stream) {
+  SRGPT_TRY(check_seq_rows(steps, B, T, V, "srgpt_sample_full_seq_rows"));
+  return sample_full_op<PICK_ROWS_SEQ_STEPS>(logits, sp, tok_out, kept_mask, ws, B * T, V, stream, PickSeqs{steps, B, T});
 }

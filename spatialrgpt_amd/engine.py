@@ -53,7 +53,7 @@ class DecodeState:
         self.c = st
         self.host_len = [0] * batch  # cached positions per row as known on the host (prefill lengths + steps taken)
         self.graphs = {}             # "greedy" / "sample" / "sample_full" (+ "+proc") -> captured decode step (the pick kernels differ);
-        #                              "lookup" (+ "+sample" / "+sample_full") -> captured lookup step; "lookup_batch" -> the batched one
+        #                              "lookup" (+ "+sample" / "+sample_full") -> captured lookup step; "lookup_batch" (+ the same) -> the batched one
         self.sampler = L.SAMPLER_TOPK64  # which device sampler draws while c.sampling is set (SRGPT_SAMPLER_*)
         self.sampling: Optional[ops.SamplingParams] = None  # device parameter block of the draw; ONE address for the state's lifetime
         self.logits_proc: Optional[ops.LogitsProcParams] = None  # device block of the logits processors; ONE address likewise
@@ -177,15 +177,16 @@ class DecodeState:
         the prompt rows [B, cap] and their lengths `n_prompt` [B] on the device.  prompt_ids int64 [B, P] (None: no prompt ids, the
         rows draft from their generated ids alone), prompt_mask [B, P] (None: every id is valid): every row contributes its valid
         ids in order, packed to the front, sentinels included (they never match).  The addresses are fixed, so one captured graph
-        serves every prompt."""
+        serves every prompt.  While the state samples the block also gets that sampler kind's workspace for the B * T rows, as
+        ensure_lookup's does."""
         eng, dev, B = self._eng, self._eng.device, self.batch
         T, n = int(K) + 1, 0 if prompt_ids is None else int(prompt_ids.shape[1])
         if prompt_ids is not None and (prompt_ids.dim() != 2 or prompt_ids.shape[0] != B):
             raise ValueError(f"ensure_lookup_batch: prompt_ids must be [{B}, P]")
         lk = self.lookup_b
         if lk is None or lk["T"] != T or lk["max_ngram"] != max_ngram or n > lk["cap"]:
-            if "lookup_batch" in self.graphs:
-                L.load().srgpt_graph_destroy(self.graphs.pop("lookup_batch"))
+            for key in [k for k in self.graphs if k.startswith("lookup_batch")]:
+                L.load().srgpt_graph_destroy(self.graphs.pop(key))
             nbytes = L.load().srgpt_llm_lookup_batch_ws_bytes(C.byref(eng.w.llm), B, T)
             if nbytes < 0:
                 raise RuntimeError("srgpt_llm_lookup_batch_ws_bytes failed")
@@ -194,7 +195,7 @@ class DecodeState:
                       logits=torch.empty((B * T, eng.w.vocab), device=dev, dtype=torch.float32),
                       stats=torch.zeros((3,), device=dev, dtype=torch.int32), steps=torch.zeros((B,), device=dev, dtype=torch.int32),
                       prompt=torch.full((B, cap), -1, device=dev, dtype=torch.int64),
-                      n_prompt=torch.zeros((B,), device=dev, dtype=torch.int32), c=L.LookupBatch())
+                      n_prompt=torch.zeros((B,), device=dev, dtype=torch.int32), c=L.LookupBatch(), sample_ws={})
             c = lk["c"]
             c.T, c.max_ngram, c.prompt_ids, c.ld_prompt, c.n_prompt = T, max_ngram, lk["prompt"].data_ptr(), cap, lk["n_prompt"].data_ptr()
             c.steps, c.ws, c.logits, c.stats = lk["steps"].data_ptr(), lk["ws"].data_ptr(), lk["logits"].data_ptr(), lk["stats"].data_ptr()
@@ -211,16 +212,27 @@ class DecodeState:
             lk["prompt"][:, :n].copy_(packed)
             lk["n_prompt"].copy_(lens.to(torch.int32))
         lk["stats"].zero_()
+        if self.c.sampling and self.sampler not in lk["sample_ws"]:
+            nbytes = L.load().srgpt_llm_lookup_batch_sample_ws_bytes(C.byref(eng.w.llm), B, T, self.sampler)
+            if nbytes < 0:
+                raise RuntimeError("srgpt_llm_lookup_batch_sample_ws_bytes failed")
+            lk["sample_ws"][self.sampler] = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
         return lk
 
     def ensure_lookup_batch_graph(self):
-        """the captured batched lookup step (greedy)"""
-        return self._graph("lookup_batch", lambda stream, g: L.load().srgpt_llm_lookup_graph_create_batch(
-            C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup_b["c"]), stream, g))
+        """the captured batched lookup step of the running request's pick: greedy, or sampled by the state's sampler kind (a graph
+        key of its own each)"""
+        key = "lookup_batch" + ("" if not self.c.sampling else ("+sample_full" if self.sampler == L.SAMPLER_FULL else "+sample"))
+        return self._graph(key, lambda stream, g: L.load().srgpt_llm_lookup_graph_create_batch_ex(
+            C.byref(self._eng.w.llm), C.byref(self.c), C.byref(self.lookup_b["c"]), self.sampler, self.lookup_sample_ws(True), stream, g))
 
-    def lookup_sample_ws(self):
-        """device pointer of the running request's sampler workspace for the lookup step; None: a greedy request"""
-        return self.lookup["sample_ws"][self.sampler].data_ptr() if self.c.sampling else None
+    def lookup_sample_ws(self, batched: Optional[bool] = None):
+        """device pointer of the running request's sampler workspace for the lookup step, sized for the state's B * T rows -- the
+        batch-1 block's, or (batched; default: a state of 2+ rows) the batched block's; None: a greedy request"""
+        if not self.c.sampling:
+            return None
+        batched = self.batch > 1 if batched is None else batched
+        return (self.lookup_b if batched else self.lookup)["sample_ws"][self.sampler].data_ptr()
 
     def ensure_lookup_graph(self):
         """the captured lookup step of the running request's pick: greedy, or sampled by the state's sampler kind"""
@@ -712,14 +724,15 @@ class SrgptEngine:
         tokens.  Greedy: the same ids, stop step and state as the plain loop.  With `sampling`: every row's token is DRAWN (row t at
         Philox counter + t), the drafts are kept up to the first draw that differs -- generated id i is a draw from the model's
         distribution at counter c0 + i, as in the plain sampled loop.  self.last_lookup_stats = what it did.
-        A state of 2+ rows (greedy, batch * (K + 1) <= 16; lookup also carries prompt_ids [B, P] and prompt_mask): batched lookup
-        steps (srgpt_llm_lookup_step_batch) -- every row drafted from its own ids and advanced by its own
-        accepted drafts; ids, padding and length as the plain batched loop's."""
+        A state of 2+ rows (batch * (K + 1) <= 16; lookup also carries prompt_ids [B, P] and prompt_mask): batched lookup
+        steps (srgpt_llm_lookup_step_batch_ex) -- every row drafted from its own ids and advanced by its own
+        accepted drafts; ids, padding and length as the plain batched loop's.  With `sampling` every one of the B * (K + 1) rows
+        is drawn, row t of sequence b at the Philox address the plain sampled batched loop reads for that id (csrc/draw_addr.h)."""
         batched = lookup is not None and st.batch > 1  # the caller opted in (LlavaLlamaModel.lookup_batch; generation.plan_lookup)
         if lookup is not None and logits_proc is not None:
             raise ValueError("greedy_decode(lookup=...) takes a batch-1 request without logits processors")
-        if batched and (sampling is not None or (st.batch * (lookup["K"] + 1)) > L.LOOKUP_ROWS_MAX):
-            raise ValueError(f"greedy_decode(lookup=...) on batch {st.batch}: a greedy request of batch * (K + 1) <= {L.LOOKUP_ROWS_MAX} rows")
+        if batched and st.batch * (lookup["K"] + 1) > L.LOOKUP_ROWS_MAX:
+            raise ValueError(f"greedy_decode(lookup=...) on batch {st.batch}: a request of batch * (K + 1) <= {L.LOOKUP_ROWS_MAX} rows")
         cur = torch.cuda.current_stream(self.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
@@ -783,8 +796,8 @@ class SrgptEngine:
         return max_new_tokens, judge.eos, [max_new_tokens] * st.batch
 
     def _lookup_loop(self, st: DecodeState, max_new_tokens: int, eos_token_id, stopping_criteria, lookup: dict):
-        """The run-ahead loop over lookup steps: srgpt_llm_lookup_step_ex for one sequence (greedy or sampled),
-        srgpt_llm_lookup_step_batch for B rows (greedy).  A step emits a number of tokens per row only the device knows, so every
+        """The run-ahead loop over lookup steps: srgpt_llm_lookup_step_ex for one sequence, srgpt_llm_lookup_step_batch_ex for B
+        rows (greedy or sampled, both).  A step emits a number of tokens per row only the device knows, so every
         round reads the per-row counts (st.step / lk["steps"]), the stats block and out_ids[:, :max_new_tokens] behind the previous
         step (_PrefixSource) -- after the NEXT step went out -- and StopJudge judges them as the plain loop would: the same ids, stop
         step and state.  What the device emitted behind the kept ids (the rest of an accepted run, the step that ran ahead, rows
@@ -812,7 +825,8 @@ class SrgptEngine:
                 L.check(lib.srgpt_llm_lookup_step_ex(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), st.sampler,
                                                      st.lookup_sample_ws(), stream))
             else:
-                L.check(lib.srgpt_llm_lookup_step_batch(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), stream))
+                L.check(lib.srgpt_llm_lookup_step_batch_ex(C.byref(self.w.llm), C.byref(st.c), C.byref(lk["c"]), st.sampler,
+                                                           st.lookup_sample_ws(), stream))
 
         source = _PrefixSource(st, max_new_tokens, st.step if B == 1 else lk["steps"], lk["stats"])
         n_keep = self._run_ahead(judge, launch, source)

@@ -135,7 +135,7 @@ def resolve_generation(stored: Optional[dict], **kwargs) -> ResolvedGeneration:
 
 
 def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sampling: bool, vocab: int, heads: int, kv_heads: int,
-                head_dim: int, bf16: bool, lookup_batch: bool = False):
+                head_dim: int, bf16: bool, lookup_batch_sampling: bool = False, lookup_batch: bool = False):
     """-> (drafts per step or None, why): does a request with `prompt_lookup_num_tokens=K` run lookup steps?  A pure function of
     the resolved generation settings `g` and the model's facts (the decision of LlavaLlamaModel._lookup_plan, as reuse.plan_reuse
     is PrefixReuse's).  Prompt-lookup decoding serves a batch-1 request without beams and logits processors: a greedy one always, a
@@ -145,7 +145,11 @@ def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sa
     head_dim-128 kernel, 16 rows otherwise).
     `lookup_batch` (the model's switch of that name, off by default): a GREEDY request of 2 .. 8 rows without beams and processors
     runs batched lookup steps -- every row drafted from its own history, batch * (K + 1) <= 16 rows in one weight pass, so K is
-    clamped to 16 // batch - 1 as well.  Beams, processors and sampled batches keep the plain loop; batch 1 takes the path above."""
+    clamped to 16 // batch - 1 as well.  Beams, processors and sampled batches keep the plain loop; batch 1 takes the path above.
+    `lookup_batch_sampling` (the third switch, off by default; it means something only with `lookup_batch` on): a SAMPLED request of
+    2 .. 8 rows gets the greedy batch's K -- the batched step draws its B * (K + 1) rows on the device, every row at the Philox
+    address the plain sampled batched loop reads (csrc/draw_addr.h) -- if a device sampler serves its settings.  `lookup_sampling`
+    stays the batch-1 switch and is not consulted for a batch.  Both batch switches are passed by keyword."""
     from . import _lib as L
     from .ops import SamplingParams
 
@@ -153,7 +157,7 @@ def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sa
     if not K:
         return None, "prompt_lookup_num_tokens not set"
     if batch != 1 and lookup_batch:
-        return _plan_lookup_batch(g, batch, processors, heads, kv_heads, head_dim, bf16)
+        return _plan_lookup_batch(g, batch, processors, heads, kv_heads, head_dim, bf16, lookup_batch_sampling, vocab)
     if batch != 1:
         return None, f"batch {batch}: the lookup step takes one sequence"
     if g.num_beams != 1:
@@ -173,16 +177,21 @@ def plan_lookup(g: "ResolvedGeneration", batch: int, processors: bool, lookup_sa
     return min(int(K), cap), f"K = {min(int(K), cap)} drafts per step" + (f" (asked for {K})" if K > cap else "")
 
 
-def _plan_lookup_batch(g: "ResolvedGeneration", batch: int, processors: bool, heads: int, kv_heads: int, head_dim: int, bf16: bool):
-    """plan_lookup for batch > 1 with the model's `lookup_batch` switch on"""
+def _plan_lookup_batch(g: "ResolvedGeneration", batch: int, processors: bool, heads: int, kv_heads: int, head_dim: int, bf16: bool,
+                       lookup_batch_sampling: bool = False, vocab: int = 0):
+    """plan_lookup for batch > 1 with the model's `lookup_batch` switch on; `lookup_batch_sampling`: a sampled batch is served too"""
     from . import _lib as L
+    from .ops import SamplingParams
 
     K = g.prompt_lookup_num_tokens
     if g.num_beams != 1:
         return None, "num_beams > 1"
     if g.do_sample and g.temperature is not None and g.temperature > 0:
-        return None, (f"do_sample: batch {batch} draws from one Philox counter, rows that emit different numbers of ids would need "
-                      "one each")
+        if not lookup_batch_sampling:
+            return None, (f"do_sample: batch {batch} draws from one Philox counter, rows that emit different numbers of ids would need "
+                          "one each")
+        if SamplingParams.sampler(g.temperature, g.top_k, g.top_p, vocab) is None:
+            return None, f"do_sample: no device sampler serves a vocabulary of {vocab}"
     if processors:
         return None, "logits processors are on"
     G = heads // kv_heads
@@ -194,7 +203,8 @@ def _plan_lookup_batch(g: "ResolvedGeneration", batch: int, processors: bool, he
     if rows < 1:
         return None, f"batch {batch}: two rows per sequence exceed the {L.LOOKUP_ROWS_MAX}-row weight pass of a step"
     k = min(int(K), cap, rows)
-    return k, f"K = {k} drafts per step, batch {batch}" + (f" (asked for {K})" if K > k else "")
+    sampled = bool(g.do_sample and g.temperature is not None and g.temperature > 0)  # then lookup_batch_sampling is on
+    return k, f"K = {k} drafts per step, batch {batch}" + (", sampled" if sampled else "") + (f" (asked for {K})" if K > k else "")
 
 
 class StopJudge:

@@ -185,7 +185,7 @@ class LlavaLlamaModel:
                  dtype=torch.bfloat16, tokenizer=None, image_processor=None, rope_positions: int = 0,
                  consume_state_dict: bool = False, llm_weight_format: str = "native", parts=None, prefix_reuse: bool = False,
                  lookup_sampling: bool = False, lookup_batch: bool = False, pack13=None, mxfp4_packed: bool = False,
-                 decode_pass_rows: int = 16, mxfp4_prefill_direct: bool = False, **hf_kwargs):
+                 decode_pass_rows: int = 16, mxfp4_prefill_direct: bool = False, lookup_batch_sampling: bool = False, **hf_kwargs):
         self.hf_config = None
         if isinstance(config, LlavaConfig):
             # the reference's construction path: config carries the checkpoint location
@@ -237,6 +237,10 @@ class LlavaLlamaModel:
         # ... for batches, opt-in: with the switch on a GREEDY request of 2 .. 8 rows with the keyword runs batched lookup steps (every
         # row drafted from its own history and advanced by its own accepted drafts, batch * (K + 1) <= 16 rows per step)
         self.lookup_batch = bool(lookup_batch)
+        # ... for SAMPLED batches, opt-in on top of lookup_batch (it means nothing alone): a sampled request of 2 .. 8 rows with the
+        # keyword runs batched lookup steps whose B * (K + 1) rows are drawn on the device, each at the Philox address the plain
+        # sampled batched loop reads for that id (csrc/draw_addr.h): exact as the batch-1 switch is.  Off: the plain sampled loop
+        self.lookup_batch_sampling = bool(lookup_batch_sampling)
 
     @property
     def decode_pass_rows(self) -> int:
@@ -629,7 +633,8 @@ class LlavaLlamaModel:
         attention kernel's columns hold), taken from `_prompt_ids` (the caller's input_ids row; none for llm.generate(inputs_embeds=))
         and the generated ids.  Every other request runs the plain loop, unchanged.  A greedy request's ids are the same either
         way; a sampled one draws every id from the same distribution at the same Philox counter (generation.plan_lookup decides;
-        `self.last_lookup` says which happened and why).  With `self.lookup_batch` on a greedy request of 2 .. 8 rows runs BATCHED
+        `self.last_lookup` says which happened and why).  With `self.lookup_batch` on a greedy request of 2 .. 8 rows (with
+        `self.lookup_batch_sampling` on as well: a sampled one too) runs BATCHED
         lookup steps: every row drafted from its own valid ids (`_prompt_ids` [B, P] with `_prompt_mask`, the caller's input_ids and
         attention_mask) and advanced by its own accepted drafts; ids, padding and length as without the keyword."""
         g = resolve_generation(self.generation_defaults(), do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
@@ -697,13 +702,13 @@ class LlavaLlamaModel:
                 # serves the demo's settings; the full sampler every other one (top_k > 64, top-p without top-k)
                 seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 sampling = dict(temperature=g.temperature, top_k=g.top_k, top_p=g.top_p, seed=seed, sampler=kind)
-                if lookup_k:  # the lookup_sampling switch is on (_lookup_plan): the same draws, T rows per step
+                if lookup_k:  # lookup_sampling (batch 1) or lookup_batch + lookup_batch_sampling is on (_lookup_plan): the same draws, T rows per sequence and step
                     from . import _lib as L
 
                     ids = self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
                                                     stopping_criteria=stopping_criteria, sampling=sampling,
                                                     lookup=dict(K=lookup_k, max_ngram=min(g.max_matching_ngram_size, L.LOOKUP_NGRAM_MAX),
-                                                                prompt_ids=_prompt_ids))
+                                                                prompt_ids=_prompt_ids, prompt_mask=_prompt_mask))
                     self.last_lookup = dict(mode="lookup", reason=why, **self.engine.last_lookup_stats)
                     return done(ids)
                 return done(self.engine.greedy_decode(st, max_new_tokens, eos_token_id=eos_ids, pad_token_id=g.pad_token_id,
@@ -731,7 +736,8 @@ class LlavaLlamaModel:
 
         c = self.engine.cfg
         return plan_lookup(g, batch, proc is not None, self.lookup_sampling, self.engine.w.vocab, c.heads, c.kv_heads, c.head_dim,
-                           self.engine.dtype == torch.bfloat16, lookup_batch=self.lookup_batch)
+                           self.engine.dtype == torch.bfloat16, lookup_batch=self.lookup_batch,
+                           lookup_batch_sampling=self.lookup_batch_sampling)
 
     def _beam_search(self, inputs_embeds, lens, num_beams, max_new_tokens, eos_ids, pad_token_id, stopping_criteria, sampling=None,
                      logits_proc=None):

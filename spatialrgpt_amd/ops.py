@@ -1087,7 +1087,17 @@ class SamplingParams:
         return self.buf.data_ptr()
 
 
-def _sample(entry: str, logits: torch.Tensor, params: SamplingParams, check: bool, out: Optional[torch.Tensor]) -> torch.Tensor:
+def _seq_rows(logits: torch.Tensor, steps: torch.Tensor, T: int):
+    """the (steps, B, T) of a `_seq_rows` call, checked: logits [B * T, V], steps int32 [B] on the device"""
+    _dev(steps)
+    B, T = int(steps.numel()), int(T)
+    if steps.dtype != torch.int32 or not steps.is_contiguous() or B < 1 or T < 1 or logits.ndim != 2 or logits.shape[0] != B * T:
+        raise ValueError("sample_seq_rows: steps must be int32 [B] and logits fp32 [B * T, V]")
+    return steps, B, T
+
+
+def _sample(entry: str, logits: torch.Tensor, params: SamplingParams, check: bool, out: Optional[torch.Tensor], seq=None) -> torch.Tensor:
+    """seq = (steps, B, T): an entry over B sequences x T steps, which takes the counts behind the block and (B, T) for the rows"""
     _dev(logits)
     if logits.dtype != torch.float32 or logits.ndim != 2:
         raise ValueError("sample: logits must be fp32 [B, V]")
@@ -1099,7 +1109,10 @@ def _sample(entry: str, logits: torch.Tensor, params: SamplingParams, check: boo
     else:
         _dev(out)
         assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == B
-    L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(ws), B, V, _stream()))
+    if seq is None:
+        L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(ws), B, V, _stream()))
+    else:
+        L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(seq[0]), _p(out), _p(ws), seq[1], seq[2], V, _stream()))
     if check:  # settings the device sampler does not serve raise instead of drawing from a clamped distribution
         L.check(lib.srgpt_sample_status(_p(ws), B, _stream()))
     return out
@@ -1117,6 +1130,15 @@ def sample_rows(logits: torch.Tensor, params: SamplingParams, check: bool = Fals
     return _sample("srgpt_sample_rows", logits, params, check, out)
 
 
+def sample_seq_rows(logits: torch.Tensor, params: SamplingParams, steps: torch.Tensor, T: int, check: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """srgpt_sample_seq_rows: the rows of fp32 logits [B * T, V] are B sequences x T successive steps (row b * T + t) that have emitted
+    steps[b] ids (int32 [B] on the device).  With m = min max(steps, 0), row (b, t) draws where row b of a B-row `sample` call at
+    params' counter + (max(steps[b], 0) - m) + t draws.  The counter is NOT advanced.  A kept-set hook must hold B * T rows.
+    -> int64 [B * T]"""
+    return _sample("srgpt_sample_seq_rows", logits, params, check, out, _seq_rows(logits, steps, T))
+
+
 def sample_full(logits: torch.Tensor, params: SamplingParams, kept_mask: bool = False):
     """one draw per row of fp32 logits [B, V] with the full device sampler (every temperature / top_k / top_p); advances params'
     counter.  -> int64 [B], or (ids, kept bool [B, V]) with kept_mask=True (the kept set, the parity hook)."""
@@ -1129,7 +1151,14 @@ def sample_full_rows(logits: torch.Tensor, params: SamplingParams, kept_mask: bo
     return _sample_full("srgpt_sample_full_rows", logits, params, kept_mask, out)
 
 
-def _sample_full(entry: str, logits: torch.Tensor, params: SamplingParams, kept_mask: bool, out: Optional[torch.Tensor]):
+def sample_full_seq_rows(logits: torch.Tensor, params: SamplingParams, steps: torch.Tensor, T: int, kept_mask: bool = False,
+                         out: Optional[torch.Tensor] = None):
+    """srgpt_sample_full_seq_rows: `sample_full` over rows that are B sequences x T successive steps, addressed as `sample_seq_rows`
+    addresses them; the counter is NOT advanced.  -> int64 [B * T], or (ids, kept bool [B * T, V])"""
+    return _sample_full("srgpt_sample_full_seq_rows", logits, params, kept_mask, out, _seq_rows(logits, steps, T))
+
+
+def _sample_full(entry: str, logits: torch.Tensor, params: SamplingParams, kept_mask: bool, out: Optional[torch.Tensor], seq=None):
     _dev(logits)
     if logits.dtype != torch.float32 or logits.ndim != 2:
         raise ValueError("sample_full: logits must be fp32 [B, V]")
@@ -1146,7 +1175,10 @@ def _sample_full(entry: str, logits: torch.Tensor, params: SamplingParams, kept_
         assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == B
     nw = (V + 31) // 32
     mask = torch.empty((B, nw), dtype=torch.int32, device=logits.device) if kept_mask else None
-    L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(mask), _p(ws), B, V, _stream()))
+    if seq is None:
+        L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(out), _p(mask), _p(ws), B, V, _stream()))
+    else:
+        L.check(getattr(lib, entry)(_p(_c(logits)), params.ptr(), _p(seq[0]), _p(out), _p(mask), _p(ws), seq[1], seq[2], V, _stream()))
     if not kept_mask:
         return out
     bits = torch.arange(32, device=logits.device, dtype=torch.int32)

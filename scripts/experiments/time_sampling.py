@@ -11,6 +11,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+from spatialrgpt_amd import _lib  # noqa: E402
+
+if os.environ.get("SRGPT_LIB"):  # another build of the library, as for scripts/sampling_full_timing.py
+    _lib.LIB_PATH = os.path.abspath(os.environ["SRGPT_LIB"])
 from spatialrgpt_amd.config import SrgptConfig  # noqa: E402
 from spatialrgpt_amd.model import LlavaLlamaModel  # noqa: E402
 from spatialrgpt_amd.weights import synth_state_dict  # noqa: E402

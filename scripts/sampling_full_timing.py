@@ -4,6 +4,8 @@ by routing the setting away from the device), and the top-k-64 sampler's (0.7, 5
 
   python scripts/sampling_full_timing.py             # tok/s table (best of --reps whole requests)
   python scripts/sampling_full_timing.py --trace     # decode only, full sampler at B = 1 and B = 8 (run under rocprofv3 --kernel-trace)
+  python scripts/sampling_full_timing.py --batch 1 4 --device-only   # the device samplers alone (no torch loop, no criterion), plus
+                                                     # the top-k-64 sampler's Gumbel path (0.7, 0): every rep's tok/s, for a spread
 SRGPT_LIB=<path of a libsrgpt_hip*.so build> selects the library, as for ubench_decode_step.py.
 """
 import argparse
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--max-new-tokens", type=int, default=128)
+    ap.add_argument("--batch", type=int, nargs="+", default=[1])
+    ap.add_argument("--device-only", action="store_true")
     args = ap.parse_args()
     cfg = bench.make_cfg("vila15_8b")
     G, dev, dt = args.max_new_tokens, torch.device("cuda"), torch.bfloat16
@@ -47,7 +51,12 @@ def main():
             torch.cuda.synchronize()
             print(f"traced: B = {B}, {len(SETTINGS) - 1} settings x {G} steps, full sampler", flush=True)
         return
-    ids, images, depths, masks = bench.synth_request(cfg, 8, 64, 1, dev, dt)
+    for batch in args.batch:
+        timed(args, cfg, model, batch, G, dev, dt)
+
+
+def timed(args, cfg, model, batch, G, dev, dt):
+    ids, images, depths, masks = bench.synth_request(cfg, 8, 64, batch, dev, dt)
     req = dict(input_ids=ids, images=images, depths=depths, masks=masks, max_new_tokens=G, eos_token_id=None, do_sample=True)
     never = [lambda ids_, scores: False]
     orig = ops.SamplingParams.sampler
@@ -56,23 +65,25 @@ def main():
         ops.SamplingParams.sampler = staticmethod(
             lambda *a: (None if orig(*a) == L.SAMPLER_FULL else orig(*a)) if torch_loop else orig(*a))
         try:
-            best = 1e9
+            times = []
             for _ in range(args.reps + 1):  # + 1 warm-up
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 out = model.generate(**req, temperature=T, top_k=k, top_p=p, stopping_criteria=crit)
                 torch.cuda.synchronize()
-                best = min(best, time.perf_counter() - t0)
+                times.append(time.perf_counter() - t0)
             assert out.shape[1] == G
-            return G / best
+            if args.device_only:
+                print(f"  B={batch} T={T} top_k={k} top_p={p} tok/s per rep after the warm-up: " + " ".join(f"{batch * G / t:.1f}" for t in times[1:]))
+            return batch * G / min(times)
         finally:
             ops.SamplingParams.sampler = staticmethod(orig)
 
     base = None
-    print(f"{os.path.basename(L.LIB_PATH)}: configs[1] geometry (vila15_8b, bf16, bs 1, 8 regions, prompt 64, {G} new tokens), whole request, best of {args.reps}")
-    for T, k, p in SETTINGS:
-        for crit in (None, never):
-            legs = [("device", False)] + ([("torch loop (before)", True)] if (k == 0 or k > 64) else [])
+    print(f"{os.path.basename(L.LIB_PATH)}: configs[1] geometry (vila15_8b, bf16, bs {batch}, 8 regions, prompt 64, {G} new tokens), whole request, best of {args.reps}")
+    for T, k, p in SETTINGS + ([(0.7, 0, None)] if args.device_only else []):
+        for crit in (None,) if args.device_only else (None, never):
+            legs = [("device", False)] + ([("torch loop (before)", True)] if (k == 0 or k > 64) and not args.device_only else [])
             for name, tl in legs:
                 r = run(T, k, p, crit, tl)
                 if base is None:

@@ -154,9 +154,12 @@ __device__ __forceinline__ PickDraw pick_draw(unsigned long long counter, int r,
   return PickDraw{a.ctr, a.seq};
 }
 // Gumbel-max: argmax_i (score_i + g_i), g_i = -log(-log(u_i)), u_i in (0, 1), is a draw from softmax(score).  The key of entry i of
-// row b at step counter ctr (srgpt_sampling::counter / ::seed)
+// row b at step counter ctr (srgpt_sampling::counter / ::seed).  u = (n + 0.5) * 2^-24 over the 24 bits n = x >> 8; for n >= 2^23 the
+// sum is no fp32 number and rounds half to even, and at n = 2^24 - 1 it rounds to 2^24: u = 1, g = +inf, the entry won whatever its
+// score (2^-24 per entry and draw, one pure-temperature draw in 130 over 128258 entries).  The minimum keeps that one u at the
+// largest fp32 below 1 and changes no other draw.  tests/draw_ref.py restates the key on the host, token for token.
 __device__ __forceinline__ float pick_gumbel_key(float score, unsigned long long ctr, unsigned long long seed, int b, int i) {
   const U4 r = philox4x32_10(U4{(unsigned)ctr, (unsigned)(ctr >> 32), (unsigned)b, (unsigned)i}, (unsigned)seed, (unsigned)(seed >> 32));
-  const float u = ((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u = fminf(((float)(r.x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   return score - logf(-logf(u));
 }

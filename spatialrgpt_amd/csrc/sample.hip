@@ -34,7 +34,9 @@
 // the kernels as they were, instruction for instruction.
 // Randomness: Philox4x32-10 keyed by the caller's seed, counter = (step counter, sequence, vocabulary index | ~0): reproducible for
 // a given seed, independent across steps / sequences / slices; torch's generator cannot be matched (HF itself draws differently
-// on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits) and the drawn DISTRIBUTION (chi-square).
+// on CPU and GPU) -- parity is the KEPT SET (bit-equal to HF's warpers on the same logits), the drawn DISTRIBUTION (chi-square) and
+// the TOKEN itself: tests/draw_ref.py restates the address, the inverse-CDF walk and the Gumbel key on the host, and every entry
+// below draws the token that restatement draws (tests/test_gpu_draw_exact.py).
 #include "common.h"
 #include "internal.h"
 #include "pick.h"

@@ -7,6 +7,7 @@ DISTRIBUTION by chi-square; plus determinism, graph replay == eager steps, and `
 import pytest
 import torch
 
+from tests.draw_ref import warp_stable as _warp_stable
 from tests.test_gpu_sampling import _chi2_crit, _logits, _peaked_model, _request
 
 pytestmark = pytest.mark.gpu
@@ -18,25 +19,6 @@ def _ops():
     from spatialrgpt_amd import ops
 
     return ops
-
-
-def _warp_stable(scores, top_k, top_p):
-    """warp_logits with a STABLE ascending sort (CPU torch.sort's order among ties: lower index first), and the oracle's
-    cumulative probability of every entry (nan where top-p is off).  -> (kept bool [B, V], cp [B, V])"""
-    V = scores.shape[-1]
-    if top_k is not None and top_k != 0:
-        k = min(max(int(top_k), 1), V)
-        kth = torch.topk(scores, k, dim=-1).values[..., -1, None]
-        scores = scores.masked_fill(scores < kth, float("-inf"))
-    cp_at = torch.full_like(scores, float("nan"))
-    if top_p is not None and top_p < 1.0:
-        sl, si = torch.sort(scores, descending=False, stable=True, dim=-1)
-        cp = sl.softmax(dim=-1).cumsum(dim=-1)
-        rm = cp <= (1 - top_p)
-        rm[..., -1:] = False
-        scores = scores.masked_fill(rm.scatter(-1, si, rm), float("-inf"))
-        cp_at = cp_at.scatter(-1, si, cp)
-    return scores > float("-inf"), cp_at
 
 
 def _check_kept(lg, temperature, top_k, top_p, seed=1, stable_oracle=False):
